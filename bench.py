@@ -14,15 +14,18 @@ LOCAL_RANK / WORLD_SIZE are in the environment) or ``bench.py --gpus N`` is run
 plainly, in which case it starts the N ranks itself (a child ``torch.distributed.run``,
 launched before this process touches the GPU) and relays rank 0's line.  Per-GPU work
 is fixed (``"scaling": "weak"``, ``--per-gpu-batch``, default 256) and ``value`` is the
-whole-job rate; the same run also times the strong-scaling reading of configs[3]
-(``--global-batch``, default 1024, split over the ranks) and reports it under
-``strong_scaling``.
+whole-job rate.
 
-Rank 0 prints ONE JSON line: metric/value/unit as the contract requires plus
-``roofline`` (conv + convT + BatchNorm kernels forward+backward against the HBM
-roofline), ``dist`` (backend, ranks seen, exposed all-reduce
-time per step) and, at N = 1, ``cpu_baseline`` (the CPU oracle timed on the host
-cores on a bounded sample of the same workload).
+Rank 0 prints ONE JSON line: metric/value/unit/ms_per_step as the contract requires plus
+``dist`` (backend, ranks seen).  A plain run does only what that line needs: set-up,
+warm-up, the K timed steps and, with ``--dump-outputs DIR``, the outputs of the last
+timed step (``dump_outputs``).  ``--full`` adds the other legs after that, each in the
+same line: ``roofline`` (conv + convT + BatchNorm kernels forward+backward against the
+HBM roofline), the exposed all-reduce time per step under
+``dist``, the strong-scaling reading of configs[3] (``--global-batch``, default 1024,
+split over the ranks) under ``strong_scaling`` and, at N = 1, ``loader_path``,
+``shotgun_path`` and ``cpu_baseline`` (the CPU oracle timed on the host cores on a
+bounded sample of the same workload).
 """
 import argparse
 import ctypes
@@ -57,6 +60,12 @@ def parse(argv=None):
     ap.add_argument("--dtype", choices=["f32", "bf16"], default="f32",
                     help="storage of the activations between the conv layers (configs[4]: bf16); arithmetic is fp32 either way")
     ap.add_argument("--pool", type=int, default=8, help="distinct device-resident batches")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run the roofline passes, the exposed-communication pass, the strong-scaling "
+                         "leg, the loader and shotgun paths and the CPU baseline (the --no-* options below skip single legs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (loss, gradients, parameters and BatchNorm statistics "
+                         "after Adam) to DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true", help="skip the two HIP-event passes")
     ap.add_argument("--no-loader-path", action="store_true", help="skip the PCIe-inclusive loader-path leg (N = 1 only)")
@@ -114,6 +123,48 @@ def one_step(model, x):
     model._forward_device(x, need_grad=True, accumulate=True)
     model._backward_device(x, defer_comm=True)       # data parallel: the Adam step consumes the gradient buckets one by one
     model.optimizer.step()
+
+
+DUMP_SAMPLE = 1 << 18          # a tensor with more entries is written as this many of them
+DUMP_SEED = 20240611
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(model, out_dir):
+    """Write what the last step handed its caller to ``out_dir/<name>.npy``: ``loss`` (the -ELBO summed over the batch that
+    ``VAE.forward`` returns, float64), ``grad.<p>`` (the gradient the backward left in ``p.grad``), ``param.<p>`` and
+    ``buffer.<b>`` (parameters and BatchNorm running statistics after Adam), float32, float64 for integer buffers.  A tensor
+    of more than DUMP_SAMPLE entries is written as the DUMP_SAMPLE flat entries at sorted indices drawn without
+    replacement by ``numpy.random.default_rng(DUMP_SEED)``: the same entries in every run and build.  Returns the bytes
+    written."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    if model.device.type == "cuda":
+        torch.cuda.synchronize()
+    arrays = {"loss": model._loss_buf[:1].double()}
+    for name, p in model.named_parameters():
+        arrays["grad." + name] = p.grad
+        arrays["param." + name] = p
+    for name, b in model.named_buffers():
+        arrays["buffer." + name] = b
+    samples = {}
+    total = 0
+    for name, t in arrays.items():
+        t = t.detach().reshape(-1)
+        if t.numel() > DUMP_SAMPLE:
+            n = t.numel()
+            if n not in samples:
+                idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_SAMPLE, replace=False))
+                samples[n] = torch.from_numpy(idx).to(t.device)
+            t = t[samples[n]]
+        a = t.cpu().numpy()
+        a = a.astype(np.float64 if a.dtype.itemsize == 8 else np.float32)
+        total += a.nbytes
+        if total > DUMP_MAX_BYTES:
+            raise ValueError("--dump-outputs: more than %d bytes" % DUMP_MAX_BYTES)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return total
 
 
 def loader_path(model, B, z_dim, shape):
@@ -382,6 +433,8 @@ def main():
     ms_per_step = 1e3 * dt / args.steps
     value = world * B * args.steps / dt
     elbo = float(model._loss_buf[0].item()) / B
+    if args.dump_outputs and rank == 0:
+        dump_outputs(model, args.dump_outputs)
 
     # ---- exposed communication: time the compute stream spends waiting for the gradient all-reduces --------------
     dist_info = {"backend": (torch.distributed.get_backend() if world > 1 else None), "world_size": world,
@@ -397,6 +450,7 @@ def main():
         t = torch.ones(1, device="cuda")
         torch.distributed.all_reduce(t)
         dist_info["ranks_seen"] = int(round(float(t.item())))
+    if world > 1 and args.full:
         model._comm_events = []
         n_comm = min(args.steps, 50)
         for i in range(n_comm):
@@ -411,7 +465,7 @@ def main():
 
     # ---- roofline leg: same K steps with HIP events on the launch stream -----------------------------------------
     roofline = None
-    if not args.no_roofline:
+    if args.full and not args.no_roofline:
         lib = _lib.load()
         ms = (ctypes.c_float * 16)()
         cnt = (ctypes.c_int * 16)()
@@ -478,7 +532,7 @@ def main():
 
     # ---- strong-scaling reading of configs[3]: a fixed global batch split over the ranks --------------------------
     strong = None
-    if args.global_batch and args.global_batch % world == 0 and args.global_batch // world != B:
+    if args.full and args.global_batch and args.global_batch % world == 0 and args.global_batch // world != B:
         Bs = args.global_batch // world
         del pool
         spool = make_pool(Bs)
@@ -511,7 +565,7 @@ def main():
         out["roofline"] = roofline
     if strong is not None:
         out["strong_scaling"] = strong
-    if world == 1 and not args.no_loader_path:
+    if args.full and world == 1 and not args.no_loader_path:
         model._ensure(B)
         out["loader_path"] = loader_path(model, B, args.z_dim, (H, W))
         if (H, W) == (128, 128):
@@ -519,7 +573,7 @@ def main():
                 out["shotgun_path"] = shotgun_path(model, B)
             except ValueError as e:           # a diverged posterior on the synthetic recordings must not cost the headline line
                 out["shotgun_path"] = {"error": str(e)}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(B, args.z_dim, args.cpu_protocol, (H, W))
     if rank == 0:
         print(json.dumps(out), flush=True)

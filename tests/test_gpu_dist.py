@@ -440,11 +440,12 @@ def test_two_ranks_over_rccl():
 def test_bench_gpus_2_starts_two_ranks_itself():
     """`python bench.py --gpus 2` with no launcher: bench.py starts the two ranks (a child torch.distributed.run) and
     rank 0 prints ONE line with n_gpus = 2.  The box has one GPU, so the hidden `--backend gloo` lets both ranks share
-    cuda:0; on a multi-GPU node the same command without that flag runs over RCCL."""
+    cuda:0; on a multi-GPU node the same command without that flag runs over RCCL.  `--full`: the exposed-communication,
+    roofline and strong-scaling legs are checked as well."""
     import json
     import subprocess
     res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--steps", "4",
-                          "--warmup", "2", "--per-gpu-batch", "16", "--global-batch", "64", "--no-cpu-baseline"],
+                          "--warmup", "2", "--per-gpu-batch", "16", "--global-batch", "64", "--no-cpu-baseline", "--full"],
                          capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert res.returncode == 0, res.stderr[-3000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]

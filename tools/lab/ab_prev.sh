@@ -12,7 +12,7 @@ AVA_HIP_LIB_TAG=prev timeout 300 python tools/conv_bench.py > $out/conv_prev.log
 timeout 300 python tools/conv_bench.py > $out/conv_new.log 2>&1
 paste <(cut -c1-40 $out/conv_prev.log) <(cut -c28-40 $out/conv_new.log) | head -n 46
 for i in 1 2; do
-  AVA_HIP_LIB_TAG=prev timeout 600 python bench.py --steps 50 --warmup 10 --no-cpu-baseline --no-loader-path --global-batch 0 > $out/bench_prev$i.json 2> $out/bench_prev$i.err
-  timeout 600 python bench.py --steps 50 --warmup 10 --no-cpu-baseline --no-loader-path --global-batch 0 > $out/bench_new$i.json 2> $out/bench_new$i.err
+  AVA_HIP_LIB_TAG=prev timeout 600 python bench.py --full --steps 50 --warmup 10 --no-cpu-baseline --no-loader-path --global-batch 0 > $out/bench_prev$i.json 2> $out/bench_prev$i.err
+  timeout 600 python bench.py --full --steps 50 --warmup 10 --no-cpu-baseline --no-loader-path --global-batch 0 > $out/bench_new$i.json 2> $out/bench_new$i.err
 done
 grep -o '"ms_per_step": [0-9.]*' $out/bench_prev1.json $out/bench_new1.json $out/bench_prev2.json $out/bench_new2.json

@@ -7,7 +7,7 @@ for v in 1 2; do
 done
 paste <(cut -c1-40 $out/conv_1.log) <(cut -c28-40 $out/conv_2.log)
 for i in 1 2; do for v in 1 2; do
-  AVA_CONV_LIMB=$v timeout 600 python bench.py --steps 50 --warmup 10 --no-cpu-baseline --no-loader-path --global-batch 0 > $out/bench_${v}_$i.json 2> $out/bench_${v}_$i.err
+  AVA_CONV_LIMB=$v timeout 600 python bench.py --full --steps 50 --warmup 10 --no-cpu-baseline --no-loader-path --global-batch 0 > $out/bench_${v}_$i.json 2> $out/bench_${v}_$i.err
   echo "AVA_CONV_LIMB=$v run $i: $(grep -o '"ms_per_step": [0-9.]*' $out/bench_${v}_$i.json)"
 done; done
 AVA_CONV_LIMB=2 timeout 1500 python -m pytest tests/test_gpu_step.py tests/test_gpu_callers.py -q > $out/pytest_2.log 2>&1

@@ -13,7 +13,7 @@ done
 cd /tmp && export TMPDIR=/tmp && cd - > /dev/null
 for v in 0 3; do
   export AVA_OVERLAP_DW=$v
-  timeout 400 rocprofv3 --kernel-trace --stats -d $out/prof -o bench --output-format csv -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-loader-path --global-batch 0 > $out/prof_$v.json 2> $out/prof_$v.err
+  timeout 400 rocprofv3 --kernel-trace --stats -d $out/prof -o bench --output-format csv -- python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-loader-path --global-batch 0 > $out/prof_$v.json 2> $out/prof_$v.err
   find $out/prof -name "*kernel_stats.csv" -exec cp {} $out/k_$v.csv \;
   rm -rf $out/prof
   echo "== kernel trace, overlap $v"; python3 tools/kstats.py $out/k_$v.csv 65 | grep -E "gemm_limb|skinny|fc_mid|24, 32, 0, 2|24, 24, 1, 1, 16|relu_mask|grouped|total" | cut -c1-150

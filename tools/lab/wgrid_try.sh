@@ -3,7 +3,7 @@
 out=gpurun_out/r03_wgrid; mkdir -p $out
 export AVA_HIP_LIB_TAG=lab
 for g in 512 384 256 128; do
-  AVA_WGRID=$g timeout 600 python bench.py --steps 50 --warmup 10 --no-cpu-baseline --no-loader-path --global-batch 0 > $out/bench_$g.json 2> $out/bench_$g.err
+  AVA_WGRID=$g timeout 600 python bench.py --full --steps 50 --warmup 10 --no-cpu-baseline --no-loader-path --global-batch 0 > $out/bench_$g.json 2> $out/bench_$g.err
   echo "AVA_WGRID=$g: $(grep -o '"ms_per_step": [0-9.]*' $out/bench_$g.json)"
 done
 for g in 256 128; do

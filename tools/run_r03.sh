@@ -13,21 +13,21 @@ case $pass in
       AVA_HIP_LIB_TAG=lab AVA_GEMM_LIMB_BN=$bn AVA_GEMM_LIMB_SPLITS=$sp timeout 300 python tools/gemm_bench.py 2>&1 | grep -E "fc1|fc8" > $out/gemm_bench_bn${bn}_s${sp}.log
     done
     AVA_HIP_LIB_TAG=lab AVA_GEMM_LIMB=0 timeout 300 python tools/gemm_bench.py 2>&1 | grep -E "fc1|fc8" > $out/gemm_bench_fp32.log
-    timeout 600 python bench.py --steps 20 --warmup 5 > $out/bench.json 2> $out/bench.err
+    timeout 600 python bench.py --full --steps 20 --warmup 5 > $out/bench.json 2> $out/bench.err
     ;;
   step)
     timeout 1500 python -m pytest tests/test_gpu_step.py tests/test_gpu_kernels.py tests/test_gpu_autograd_semantics.py -x -q > $out/pytest.log 2>&1; echo "pytest rc $?" >> $out/pytest.log
-    timeout 600 python bench.py --steps 20 --warmup 5 --no-cpu-baseline > $out/bench.json 2> $out/bench.err
+    timeout 600 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $out/bench.json 2> $out/bench.err
     tail -n 15 $out/pytest.log
     ;;
   full)
     timeout 2400 python -m pytest tests -m gpu -x -q > $out/pytest.log 2>&1; echo "pytest rc $?" >> $out/pytest.log
-    timeout 600 python bench.py --steps 20 --warmup 5 --no-cpu-baseline > $out/bench.json 2> $out/bench.err
+    timeout 600 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $out/bench.json 2> $out/bench.err
     tail -n 15 $out/pytest.log
     ;;
   prof)
     cd /tmp && export TMPDIR=/tmp && cd - > /dev/null
-    rocprofv3 --kernel-trace --stats -d $out/prof -o bench --output-format csv -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-loader-path --global-batch 0 > $out/bench_prof.json 2> $out/bench_prof.err
+    rocprofv3 --kernel-trace --stats -d $out/prof -o bench --output-format csv -- python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-loader-path --global-batch 0 > $out/bench_prof.json 2> $out/bench_prof.err
     find $out/prof -name "*kernel_stats.csv" -exec cp {} $out/kernel_stats.csv \;
     rm -rf $out/prof
     ;;
@@ -40,7 +40,7 @@ case $pass in
     # the round's evidence in one call: kernel stats, HBM traffic (two --pmc passes), SQ counters, the bench lines
     cd /tmp && export TMPDIR=/tmp && cd - > /dev/null
     R=$PWD
-    rocprofv3 --kernel-trace --stats -d $out/prof -o bench --output-format csv -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-loader-path --global-batch 0 > $out/bench_under_rocprof.json 2> $out/bench_under_rocprof.err
+    rocprofv3 --kernel-trace --stats -d $out/prof -o bench --output-format csv -- python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-loader-path --global-batch 0 > $out/bench_under_rocprof.json 2> $out/bench_under_rocprof.err
     find $out/prof -name "*kernel_stats.csv" -exec cp {} $out/final_kernel_stats.csv \;
     rm -rf $out/prof
     rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $out/pmc_fetch -o f -- python3 bench.py --steps 4 --warmup 2 --no-cpu-baseline --global-batch 0 --no-loader-path --no-roofline > $out/pmc_fetch.log 2>&1
@@ -50,11 +50,11 @@ case $pass in
     python3 tools/pmc_sq.py $(find $out/pmc_sq -name "*counter_collection.csv" | head -1) > $out/pmc_sq.json
     rm -rf $out/pmc_fetch $out/pmc_write $out/pmc_sq
     mkdir -p profiles/r03 && cp $out/pmc_traffic.json profiles/r03/pmc_traffic.json      # so that the bench below quotes this build's traffic
-    python3 bench.py > $out/bench_final.json 2> $out/bench_final.err
-    python3 bench.py --z-dim 64 --no-cpu-baseline --no-loader-path > $out/bench_z64.json 2> $out/bench_z64.err
-    python3 bench.py --per-gpu-batch 128 --global-batch 0 --no-cpu-baseline --no-loader-path > $out/bench_B128.json 2> $out/bench_B128.err
-    python3 bench.py --height 256 --width 256 --z-dim 128 --per-gpu-batch 64 --global-batch 0 --steps 50 --no-cpu-baseline --no-loader-path > $out/bench_256x256_z128_B64_fp32.json 2> $out/bench_256_fp32.err
-    python3 bench.py --height 256 --width 256 --z-dim 128 --per-gpu-batch 64 --global-batch 0 --steps 50 --dtype bf16 --no-cpu-baseline --no-loader-path > $out/bench_256x256_z128_B64_bf16act.json 2> $out/bench_256_bf16.err
+    python3 bench.py --full > $out/bench_final.json 2> $out/bench_final.err
+    python3 bench.py --full --z-dim 64 --no-cpu-baseline --no-loader-path > $out/bench_z64.json 2> $out/bench_z64.err
+    python3 bench.py --full --per-gpu-batch 128 --global-batch 0 --no-cpu-baseline --no-loader-path > $out/bench_B128.json 2> $out/bench_B128.err
+    python3 bench.py --full --height 256 --width 256 --z-dim 128 --per-gpu-batch 64 --global-batch 0 --steps 50 --no-cpu-baseline --no-loader-path > $out/bench_256x256_z128_B64_fp32.json 2> $out/bench_256_fp32.err
+    python3 bench.py --full --height 256 --width 256 --z-dim 128 --per-gpu-batch 64 --global-batch 0 --steps 50 --dtype bf16 --no-cpu-baseline --no-loader-path > $out/bench_256x256_z128_B64_bf16act.json 2> $out/bench_256_bf16.err
     tail -c 400 $out/bench_final.json
     ;;
   pair)
@@ -68,9 +68,9 @@ case $pass in
     done
     cat $out/ab.log
     timeout 1500 python -m pytest tests/test_gpu_step.py tests/test_gpu_graph.py tests/test_gpu_callers.py tests/test_gpu_autograd_semantics.py -x -q > $out/pytest.log 2>&1; echo "pytest rc $?" >> $out/pytest.log
-    timeout 600 python bench.py --steps 50 --warmup 10 --no-cpu-baseline --no-loader-path > $out/bench.json 2> $out/bench.err
-    AVA_HIP_LIB_TAG=lab AVA_WGRAD_PAIR=0 timeout 600 python bench.py --steps 50 --warmup 10 --no-cpu-baseline --no-loader-path > $out/bench_lab_off.json 2> $out/bench_lab_off.err
-    AVA_HIP_LIB_TAG=lab AVA_WGRAD_PAIR=1 timeout 600 python bench.py --steps 50 --warmup 10 --no-cpu-baseline --no-loader-path > $out/bench_lab_on.json 2> $out/bench_lab_on.err
+    timeout 600 python bench.py --full --steps 50 --warmup 10 --no-cpu-baseline --no-loader-path > $out/bench.json 2> $out/bench.err
+    AVA_HIP_LIB_TAG=lab AVA_WGRAD_PAIR=0 timeout 600 python bench.py --full --steps 50 --warmup 10 --no-cpu-baseline --no-loader-path > $out/bench_lab_off.json 2> $out/bench_lab_off.err
+    AVA_HIP_LIB_TAG=lab AVA_WGRAD_PAIR=1 timeout 600 python bench.py --full --steps 50 --warmup 10 --no-cpu-baseline --no-loader-path > $out/bench_lab_on.json 2> $out/bench_lab_on.err
     grep -o '"ms_per_step": [0-9.]*' $out/bench.json $out/bench_lab_off.json $out/bench_lab_on.json
     ;;
   gemmabl)
