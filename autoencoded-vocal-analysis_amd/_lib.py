@@ -104,6 +104,10 @@ SIGNATURES = {
     "ava_spec_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i, _i]),
     "ava_get_spec_batch": (_i, [_p, _i, _p, _p, _p, _p, _p, _p, _i, _i, _d, _i, _i, _p, _d, _p, _i, _i, _d, _d, _d, _i,
                                 _i, _i, _d, _p, _p, _p, _sz, _p]),
+    "ava_amp_workspace_bytes": (_sz, [_i64]),
+    "ava_amp_trace": (_i, [_p, _i, _p, _p, _p, _i, _i64, _i, _i, _p, _d, _i, _i, _d, _d, _i, _d, _p, _i, _i, _p, _p, _p,
+                           _sz, _p]),
+    "ava_amp_decide": (_i, [_p, _i, _p, _i, _i64, _d, _d, _d, _p, _p, _p, _p, _i64, _p]),
 }
 
 _lib = None

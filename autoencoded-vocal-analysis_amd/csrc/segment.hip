@@ -1,0 +1,352 @@
+// Amplitude segmentation on the device: the arithmetic of
+// ava/segmenting/amplitude_segmentation.py:get_onsets_offsets for every recording of a DeviceAudio at once.
+//
+//   scipy.signal.stft of the whole file (hann, zero boundary, zero padded to whole hops, 'spectrum' scaling, no detrend),
+//   bins [searchsorted(f, min_freq), searchsorted(f, max_freq)), clip((log(|X| + 1e-9) - min) / (max - min), 0, 1),
+//   per frame  sum v  or  sum v e / (sum e + 1e-9), e = exp(v / temperature)
+//                                          segmenting/utils.py:22-61, 400-404, amplitude_segmentation.py:63-66
+//                                                                     amp_stft_kernel     (workgroups stride over frames)
+//   gaussian_filter(amps, smoothing_timescale / dt), mode 'reflect' inside each file, cast to the reference's dtype
+//                                          amplitude_segmentation.py:67                  amp_smooth_kernel   (1 thread / frame)
+//   local maxima above th_3                amplitude_segmentation.py:70-73               amp_maxima_kernel   (1 thread / frame)
+//   nearest stop frame left and right of every maximum
+//                                          amplitude_segmentation.py:79-99               amp_stops_kernel    (1 wave / maximum)
+//
+// The host receives O(#maxima) integers and runs the greedy chain and the duration filter (ava_amd/segment.py).
+// The spectral arithmetic is fp64 (the radix-2 transform is that of spec.hip, duplicated so that f4 stays as proven);
+// the trace is stored in the dtype the reference holds it in (float32 for int16 / float32 audio, float64 otherwise), and
+// the decision kernels compare the values of THAT trace, promoted exactly to fp64, against thresholds the host has
+// already rounded the way numpy would (a Python float compared with a float32 array is a float32).
+#include "common.h"
+
+#define AVA_AMP_EPS 1e-9
+#define AVA_AMP_T 256
+
+enum { AMP_AUDIO_I16 = 0, AMP_AUDIO_I32 = 1, AMP_AUDIO_F32 = 2, AMP_AUDIO_F64 = 3 };
+
+struct AmpArgs {
+  const void* audio;
+  const long long* file_off;     // [files] first sample of each file in `audio`
+  const long long* file_len;     // [files] samples of each file
+  const long long* frame_off;    // [files + 1] first global frame of each file; frame_off[files] = frames
+  const double* window;          // [nperseg]
+  double* raw;                   // [frames] per-frame band value before smoothing (workspace)
+  double* spec;                  // [k1 - k0][frames] band spectrogram or null
+  double scale, spec_min, range, temperature;
+  long long frames;
+  int files, nperseg, nstep, k0, k1, softmax, dtype;
+};
+
+__device__ __forceinline__ double amp_audio_at(const void* base, int dtype, long long i) {
+  switch (dtype) {
+    case AMP_AUDIO_I16: return (double)reinterpret_cast<const short*>(base)[i];
+    case AMP_AUDIO_I32: return (double)reinterpret_cast<const int*>(base)[i];
+    case AMP_AUDIO_F32: return (double)reinterpret_cast<const float*>(base)[i];
+    default: return reinterpret_cast<const double*>(base)[i];
+  }
+}
+
+// file of global frame g: the f with frame_off[f] <= g < frame_off[f + 1] (files without frames are never returned)
+__device__ __forceinline__ int amp_file_of(const long long* frame_off, int files, long long g) {
+  int lo = 0, hi = files;
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (frame_off[mid] <= g) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+
+// One workgroup per frame, striding over all frames of all files: Hann window, N-point real transform as an N/2-point
+// complex FFT in LDS + the split step (spec_stft_kernel's arithmetic), the band reduction in a fixed order (thread
+// partial sums, then the waves' shuffles, then the four waves in order): deterministic.
+#define PD(i) ((i) + ((i) >> 3))
+template <int LOGN>
+__global__ __launch_bounds__(AVA_AMP_T) void amp_stft_kernel(const AmpArgs a) {
+  constexpr int N = 1 << LOGN, H = N / 2, LOGH = LOGN - 1;
+  __shared__ double re[H + H / 8 + 1], im[H + H / 8 + 1];
+  __shared__ double twr[H + H / 8 + 1], twi[H + H / 8 + 1];       // exp(-2 pi i k / N), k < N/2
+  __shared__ double red[2][AVA_AMP_T / 64];
+  const int t = threadIdx.x;
+  for (int k = t; k < H; k += AVA_AMP_T) {
+    double sn, cs;
+    sincospi(-2.0 * (double)k / (double)N, &sn, &cs);
+    twr[PD(k)] = cs;
+    twi[PD(k)] = sn;
+  }
+  constexpr int U = H / AVA_AMP_T > 0 ? H / AVA_AMP_T : 1;
+  double raw[U][2];
+  auto fetch = [&](long long g) {
+    const int f = amp_file_of(a.frame_off, a.files, g);
+    const long long j = g - a.frame_off[f], len = a.file_len[f], base = a.file_off[f];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int i = t + AVA_AMP_T * u;
+#pragma unroll
+      for (int e = 0; e < 2; ++e) {
+        const long long idx = j * a.nstep + 2 * i + e - N / 2;                  // position in the file (zeros outside)
+        const bool in = i < H && idx >= 0 && idx < len;
+        const double x = amp_audio_at(a.audio, a.dtype, base + (in ? idx : 0));   // clamped address
+        raw[u][e] = in ? x : 0.0;
+      }
+    }
+  };
+  if ((long long)blockIdx.x < a.frames) fetch(blockIdx.x);
+  for (long long g = blockIdx.x; g < a.frames; g += gridDim.x) {
+    __syncthreads();                                       // twiddles ready / previous frame's reads retired
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int i = t + AVA_AMP_T * u;
+      if (i < H) {
+        const int r = (int)(__brev((unsigned)i) >> (32 - LOGH));
+        re[PD(r)] = __dmul_rn(raw[u][0], a.window[2 * i]);
+        im[PD(r)] = __dmul_rn(raw[u][1], a.window[2 * i + 1]);
+      }
+    }
+    if (g + gridDim.x < a.frames) fetch(g + gridDim.x);   // in flight under this frame's butterflies
+    __syncthreads();
+    int st = 0;
+#pragma unroll 1
+    for (; st + 1 < LOGH; st += 2) {                        // two radix-2 stages per pass over LDS
+      const int h = 1 << st;
+      for (int b = t; b < H / 4; b += AVA_AMP_T) {
+        const int pos = b & (h - 1);
+        const int i0 = ((b >> st) << (st + 2)) + pos, i1 = i0 + h, i2 = i1 + h, i3 = i2 + h;
+        const int k1 = pos << (LOGN - 1 - st), k2 = pos << (LOGN - 2 - st);
+        const double w1r = twr[PD(k1)], w1i = twi[PD(k1)], w2r = twr[PD(k2)], w2i = twi[PD(k2)];
+        const double x1r = re[PD(i1)], x1i = im[PD(i1)], x3r = re[PD(i3)], x3i = im[PD(i3)];
+        const double p1r = w1r * x1r - w1i * x1i, p1i = w1r * x1i + w1i * x1r;
+        const double p3r = w1r * x3r - w1i * x3i, p3i = w1r * x3i + w1i * x3r;
+        const double u0r = re[PD(i0)], u0i = im[PD(i0)], u2r = re[PD(i2)], u2i = im[PD(i2)];
+        const double b0r = u0r + p1r, b0i = u0i + p1i, b1r = u0r - p1r, b1i = u0i - p1i;
+        const double b2r = u2r + p3r, b2i = u2i + p3i, b3r = u2r - p3r, b3i = u2i - p3i;
+        const double q2r = w2r * b2r - w2i * b2i, q2i = w2r * b2i + w2i * b2r;
+        const double w3r = twr[PD(k2 + H / 2)], w3i = twi[PD(k2 + H / 2)];
+        const double q3r = w3r * b3r - w3i * b3i, q3i = w3r * b3i + w3i * b3r;
+        re[PD(i0)] = b0r + q2r; im[PD(i0)] = b0i + q2i;
+        re[PD(i2)] = b0r - q2r; im[PD(i2)] = b0i - q2i;
+        re[PD(i1)] = b1r + q3r; im[PD(i1)] = b1i + q3i;
+        re[PD(i3)] = b1r - q3r; im[PD(i3)] = b1i - q3i;
+      }
+      __syncthreads();
+    }
+    if (st < LOGH) {
+      const int half = 1 << st;
+      for (int b = t; b < H / 2; b += AVA_AMP_T) {
+        const int pos = b & (half - 1);
+        const int i0 = ((b >> st) << (st + 1)) + pos, i1 = i0 + half;
+        const int tk = pos << (LOGN - 1 - st);
+        const double wr = twr[PD(tk)], wi = twi[PD(tk)];
+        const double xr = re[PD(i1)], xi = im[PD(i1)];
+        const double pr = wr * xr - wi * xi, pi = wr * xi + wi * xr;
+        const double ur = re[PD(i0)], ui = im[PD(i0)];
+        re[PD(i0)] = ur + pr; im[PD(i0)] = ui + pi;
+        re[PD(i1)] = ur - pr; im[PD(i1)] = ui - pi;
+      }
+      __syncthreads();
+    }
+    // split: X_k = E_k + W_N^k O_k for the kept bins k0 <= k < k1 (<= H), then the band value of each bin
+    double s0 = 0.0, s1 = 0.0;
+    for (int k = a.k0 + t; k < a.k1; k += AVA_AMP_T) {
+      const int ka = k & (H - 1), kb = (H - k) & (H - 1);
+      const double zr = re[PD(ka)], zi = im[PD(ka)], cr = re[PD(kb)], ci = -im[PD(kb)];
+      const double er = 0.5 * (zr + cr), ei = 0.5 * (zi + ci);
+      const double dr = 0.5 * (zr - cr), di = 0.5 * (zi - ci);
+      const double orr = di, oi = -dr;
+      const double wr = k == H ? -1.0 : twr[PD(k)], wi = k == H ? 0.0 : twi[PD(k)];
+      const double xr = er + (wr * orr - wi * oi), xi = ei + (wr * oi + wi * orr);
+      const double lg = log(__dadd_rn(__dmul_rn(sqrt(xr * xr + xi * xi), a.scale), AVA_AMP_EPS));
+      double v = __ddiv_rn(__dsub_rn(lg, a.spec_min), a.range);
+      v = v < 0.0 ? 0.0 : (v > 1.0 ? 1.0 : v);
+      if (a.spec != nullptr) a.spec[(size_t)(k - a.k0) * a.frames + g] = v;
+      if (a.softmax) {
+        const double e = exp(__ddiv_rn(v, a.temperature));
+        s0 = fma(v, e, s0);
+        s1 += e;
+      } else {
+        s0 += v;
+      }
+    }
+    s0 = wave_sum_d(s0);
+    s1 = wave_sum_d(s1);
+    if ((t & 63) == 0) { red[0][t >> 6] = s0; red[1][t >> 6] = s1; }
+    __syncthreads();
+    if (t == 0) {
+      double v0 = 0.0, v1 = 0.0;
+#pragma unroll
+      for (int w = 0; w < AVA_AMP_T / 64; ++w) { v0 += red[0][w]; v1 += red[1][w]; }
+      a.raw[g] = a.softmax ? __ddiv_rn(v0, __dadd_rn(v1, AVA_AMP_EPS)) : v0;
+    }
+  }
+}
+#undef PD
+
+// scipy.ndimage.gaussian_filter on each file's trace: correlation with the 2 radius + 1 host-computed weights, mode
+// 'reflect' (d c b a | a b c d | d c b a, repeated: period 2 T), fp64, then one rounding to the trace's dtype.
+template <typename V>
+__global__ __launch_bounds__(AVA_AMP_T) void amp_smooth_kernel(const double* raw, const long long* frame_off, int files,
+                                                               long long frames, const double* w, int radius, V* out) {
+  const long long g = (long long)blockIdx.x * AVA_AMP_T + threadIdx.x;
+  if (g >= frames) return;
+  const int f = amp_file_of(frame_off, files, g);
+  const long long b = frame_off[f], T = frame_off[f + 1] - b, i = g - b, P = 2 * T;
+  double s = 0.0;
+  for (int k = -radius; k <= radius; ++k) {
+    long long m = (i + k) % P;
+    if (m < 0) m += P;
+    if (m >= T) m = P - 1 - m;
+    s = fma(w[k + radius], raw[b + m], s);
+  }
+  out[g] = (V)s;
+}
+
+// amplitude_segmentation.py:83-98's stop test at frame j >= 1 of a file of T frames: a[j] < th_1, or a[j] < th_2 and
+// a[j] == min(a[j-1:j+2]) (the slice clipped at the file's end; a NaN in it makes the == false)
+template <typename V>
+__device__ __forceinline__ bool amp_is_stop(const V* a, long long b, long long T, long long j, double th1, double th2) {
+  const double x = (double)a[b + j];
+  if (x < th1) return true;
+  if (!(x < th2)) return false;
+  if (!((double)a[b + j - 1] >= x)) return false;
+  if (j + 1 < T && !((double)a[b + j + 1] >= x)) return false;
+  return true;
+}
+
+// amplitude_segmentation.py:70-73: 1 <= i <= T-2, a[i] > th_3, a[i] == max(a[i-1:i+2]).  The maxima of a wave are
+// appended with one atomic per wave (their order in the list is not deterministic; the host sorts them).
+template <typename V>
+__global__ __launch_bounds__(AVA_AMP_T) void amp_maxima_kernel(const V* a, const long long* frame_off, int files,
+                                                               long long frames, double th3,
+                                                               unsigned long long* count, long long* maxima) {
+  const long long g = (long long)blockIdx.x * AVA_AMP_T + threadIdx.x;
+  bool is_max = false;
+  if (g < frames) {
+    const int f = amp_file_of(frame_off, files, g);
+    const long long b = frame_off[f], T = frame_off[f + 1] - b, i = g - b;
+    if (i >= 1 && i <= T - 2) {
+      const double x = (double)a[g];
+      is_max = x > th3 && (double)a[g - 1] <= x && (double)a[g + 1] <= x;
+    }
+  }
+  const unsigned long long m = __ballot(is_max);
+  if (m == 0) return;
+  const int lane = threadIdx.x & 63;
+  unsigned long long base = 0;
+  if (lane == 0) base = atomicAdd(count, (unsigned long long)__popcll(m));
+  base = __shfl(base, 0, 64);
+  if (is_max) maxima[base + __popcll(m & ((1ull << lane) - 1ull))] = g;
+}
+
+// One wave per maximum: 64 candidate frames per step, the nearest stop is the lowest set lane of the ballot.
+// left[e] / right[e]: frame index inside the file, or -1 when the search ends without a stop.
+template <typename V>
+__global__ __launch_bounds__(AVA_AMP_T) void amp_stops_kernel(const V* a, const long long* frame_off, int files,
+                                                              double th1, double th2, const unsigned long long* count,
+                                                              const long long* maxima, long long* left, long long* right) {
+  const int lane = threadIdx.x & 63;
+  const long long waves = (long long)gridDim.x * (AVA_AMP_T / 64);
+  const long long n = (long long)*count;
+  for (long long e = (long long)blockIdx.x * (AVA_AMP_T / 64) + (threadIdx.x >> 6); e < n; e += waves) {
+    const long long g = maxima[e];
+    const int f = amp_file_of(frame_off, files, g);
+    const long long b = frame_off[f], T = frame_off[f + 1] - b, m = g - b;
+    long long l = -1, r = -1;
+    for (long long c = m - 1; c >= 1; c -= 64) {                // j = c, c-1, ..., down to 1
+      const long long j = c - lane;
+      const unsigned long long bal = __ballot(j >= 1 && amp_is_stop(a, b, T, j, th1, th2));
+      if (bal != 0) { l = c - __builtin_ctzll(bal); break; }
+    }
+    for (long long c = m + 1; c <= T - 1; c += 64) {            // j = c, c+1, ..., up to T-1
+      const long long j = c + lane;
+      const unsigned long long bal = __ballot(j <= T - 1 && amp_is_stop(a, b, T, j, th1, th2));
+      if (bal != 0) { r = c + __builtin_ctzll(bal); break; }
+    }
+    if (lane == 0) { left[e] = l; right[e] = r; }
+  }
+}
+
+extern "C" size_t ava_amp_workspace_bytes(int64_t frames) {
+  if (frames <= 0) return 0;
+  return 256 + (size_t)frames * sizeof(double);
+}
+
+extern "C" int ava_amp_trace(const void* audio, int audio_dtype, const int64_t* file_off, const int64_t* file_len,
+                             const int64_t* frame_off, int files, int64_t frames, int nperseg, int noverlap,
+                             const double* window, double scale, int k0, int k1, double spec_min, double spec_max,
+                             int softmax, double temperature, const double* gauss_w, int radius, int trace_f64,
+                             void* trace, double* spec, void* ws, size_t ws_bytes, ava_stream_t s) {
+  if (audio == nullptr || file_off == nullptr || file_len == nullptr || frame_off == nullptr || window == nullptr ||
+      gauss_w == nullptr || trace == nullptr)
+    return AVA_EINVAL;
+  if (files <= 0 || frames <= 0 || radius < 0) return AVA_EINVAL;
+  if (nperseg < 64 || nperseg > 2048 || (nperseg & (nperseg - 1)) != 0) return AVA_EINVAL;
+  if (noverlap < 0 || noverlap >= nperseg) return AVA_EINVAL;
+  if (k0 < 0 || k1 <= k0 || k1 > nperseg / 2 + 1) return AVA_EINVAL;             // empty band
+  if (audio_dtype < AMP_AUDIO_I16 || audio_dtype > AMP_AUDIO_F64) return AVA_EINVAL;
+  if (!(spec_max != spec_min) || (softmax && !(temperature != 0.0))) return AVA_EINVAL;
+  if (ws == nullptr || ws_bytes < ava_amp_workspace_bytes(frames)) return AVA_EINVAL;
+  AmpArgs a;
+  a.audio = audio;
+  a.file_off = reinterpret_cast<const long long*>(file_off);
+  a.file_len = reinterpret_cast<const long long*>(file_len);
+  a.frame_off = reinterpret_cast<const long long*>(frame_off);
+  a.window = window;
+  char* base = reinterpret_cast<char*>(ws);
+  base += (256 - (reinterpret_cast<uintptr_t>(base) & 255)) & 255;
+  a.raw = reinterpret_cast<double*>(base);
+  a.spec = spec;
+  a.scale = scale; a.spec_min = spec_min; a.range = spec_max - spec_min; a.temperature = temperature;
+  a.frames = frames; a.files = files; a.nperseg = nperseg; a.nstep = nperseg - noverlap;
+  a.k0 = k0; a.k1 = k1; a.softmax = softmax ? 1 : 0; a.dtype = audio_dtype;
+  hipStream_t st = to_stream(s);
+  const int grid = frames < 4096 ? (int)frames : 4096;      // workgroups stride over the frames
+  switch (nperseg) {
+    case 64: hipLaunchKernelGGL(amp_stft_kernel<6>, dim3(grid), dim3(AVA_AMP_T), 0, st, a); break;
+    case 128: hipLaunchKernelGGL(amp_stft_kernel<7>, dim3(grid), dim3(AVA_AMP_T), 0, st, a); break;
+    case 256: hipLaunchKernelGGL(amp_stft_kernel<8>, dim3(grid), dim3(AVA_AMP_T), 0, st, a); break;
+    case 512: hipLaunchKernelGGL(amp_stft_kernel<9>, dim3(grid), dim3(AVA_AMP_T), 0, st, a); break;
+    case 1024: hipLaunchKernelGGL(amp_stft_kernel<10>, dim3(grid), dim3(AVA_AMP_T), 0, st, a); break;
+    default: hipLaunchKernelGGL(amp_stft_kernel<11>, dim3(grid), dim3(AVA_AMP_T), 0, st, a); break;
+  }
+  AVA_CHECK_LAUNCH();
+  const dim3 sgrid((unsigned)ceil_div64(frames, AVA_AMP_T));
+  if (trace_f64)
+    hipLaunchKernelGGL(amp_smooth_kernel<double>, sgrid, dim3(AVA_AMP_T), 0, st, a.raw, a.frame_off, files, frames,
+                       gauss_w, radius, reinterpret_cast<double*>(trace));
+  else
+    hipLaunchKernelGGL(amp_smooth_kernel<float>, sgrid, dim3(AVA_AMP_T), 0, st, a.raw, a.frame_off, files, frames,
+                       gauss_w, radius, reinterpret_cast<float*>(trace));
+  AVA_CHECK_LAUNCH();
+  return AVA_OK;
+}
+
+extern "C" int ava_amp_decide(const void* trace, int trace_f64, const int64_t* frame_off, int files, int64_t frames,
+                              double th1, double th2, double th3, uint64_t* count, int64_t* maxima, int64_t* left,
+                              int64_t* right, int64_t capacity, ava_stream_t s) {
+  if (trace == nullptr || frame_off == nullptr || count == nullptr || maxima == nullptr || left == nullptr ||
+      right == nullptr)
+    return AVA_EINVAL;
+  if (files <= 0 || frames <= 0 || capacity < frames) return AVA_EINVAL;
+  hipStream_t st = to_stream(s);
+  if (hipMemsetAsync(count, 0, sizeof(uint64_t), st) != hipSuccess) return AVA_ELAUNCH;
+  const long long* fo = reinterpret_cast<const long long*>(frame_off);
+  unsigned long long* cnt = reinterpret_cast<unsigned long long*>(count);
+  long long* mx = reinterpret_cast<long long*>(maxima);
+  long long* lf = reinterpret_cast<long long*>(left);
+  long long* rt = reinterpret_cast<long long*>(right);
+  const dim3 mgrid((unsigned)ceil_div64(frames, AVA_AMP_T));
+  const long long want = ceil_div64(frames, AVA_AMP_T / 64);            // one wave per maximum at most
+  const dim3 wgrid((unsigned)(want < 2048 ? want : 2048));
+  if (trace_f64) {
+    const double* a = reinterpret_cast<const double*>(trace);
+    hipLaunchKernelGGL(amp_maxima_kernel<double>, mgrid, dim3(AVA_AMP_T), 0, st, a, fo, files, (long long)frames, th3, cnt, mx);
+    AVA_CHECK_LAUNCH();
+    hipLaunchKernelGGL(amp_stops_kernel<double>, wgrid, dim3(AVA_AMP_T), 0, st, a, fo, files, th1, th2, cnt, mx, lf, rt);
+  } else {
+    const float* a = reinterpret_cast<const float*>(trace);
+    hipLaunchKernelGGL(amp_maxima_kernel<float>, mgrid, dim3(AVA_AMP_T), 0, st, a, fo, files, (long long)frames, th3, cnt, mx);
+    AVA_CHECK_LAUNCH();
+    hipLaunchKernelGGL(amp_stops_kernel<float>, wgrid, dim3(AVA_AMP_T), 0, st, a, fo, files, th1, th2, cnt, mx, lf, rt);
+  }
+  AVA_CHECK_LAUNCH();
+  return AVA_OK;
+}

@@ -321,6 +321,49 @@ int ava_get_spec_batch(const void* audio, int audio_dtype, const int64_t* file_o
                        double fill_value, int remove_dc, int normalize, int q_lo, double q_gamma, float* out,
                        float* out_max, void* ws, size_t ws_bytes, ava_stream_t s);
 
+/* ---- amplitude segmentation on the device -------------------------------------------
+ * ava/segmenting/amplitude_segmentation.py:get_onsets_offsets for every file of a concatenated audio buffer at once.
+ * The host keeps the greedy onset / offset chain and the duration filter (O(#maxima) integers); every per-frame step
+ * runs here.
+ *
+ * ava_amp_workspace_bytes: scratch ava_amp_trace needs for `frames` frames in all (0 for frames <= 0).
+ *
+ * ava_amp_trace: the smoothed amplitude trace of every file.
+ *   audio / audio_dtype   concatenated samples; 0 = int16, 1 = int32, 2 = float32, 3 = float64
+ *   file_off, file_len    [files] first sample / number of samples of each file in `audio` (device)
+ *   frame_off             [files + 1] first frame of each file in the concatenated trace (device); a file of
+ *                         L >= nperseg samples has ceil(L / (nperseg - noverlap)) + 1 frames (scipy.signal.stft with
+ *                         boundary='zeros', padded=True), a shorter one 0; frame_off[files] = frames
+ *   nperseg, noverlap     a power of two in 64..2048, 0 <= noverlap < nperseg
+ *   window, scale         get_window('hann', nperseg) (device), 1 / sum(window): 'spectrum' scaling; no detrend
+ *   k0, k1                the kept bins [searchsorted(f, min_freq), searchsorted(f, max_freq)), 0 <= k0 < k1 <= nperseg/2+1
+ *   spec_min, spec_max    v = clip((log(|X| + 1e-9) - spec_min) / (spec_max - spec_min), 0, 1)  (segmenting/utils.py:52-57)
+ *   softmax, temperature  per frame sum v (softmax 0) or sum v e / (sum e + 1e-9), e = exp(v / temperature)
+ *   gauss_w, radius       [2 radius + 1] gaussian_filter weights (device, host-normalised); radius 0 with w = {1}:
+ *                         no smoothing.  Mode 'reflect' inside each file.
+ *   trace_f64, trace      [frames] output, float64 (trace_f64 != 0) or float32: the dtype the reference holds
+ *   spec                  [k1 - k0][frames] float64 band spectrogram (v) or NULL
+ * All spectral arithmetic is fp64.
+ *
+ * ava_amp_decide: the decisions on a trace of `frames` values (float64 or float32, as trace_f64 says) split into
+ * files by frame_off [files + 1] (device).  th1..th3 are compared against the trace values promoted to fp64: the caller
+ * rounds them as numpy would compare them with the trace.  Writes *count (device) maxima: maxima[e] the global frame of
+ * a local maximum (1 <= i <= T-2, a[i] > th3, a[i] == max(a[i-1:i+2])), left[e] / right[e] the nearest frame of its file
+ * (>= 1 on the left, <= T-1 on the right) with a[j] < th1, or a[j] < th2 and a[j] == min(a[j-1:j+2]); -1 for none.
+ * The order of the entries is not specified.  capacity >= frames.
+ *
+ * Both return AVA_EINVAL before any launch for null pointers, an unsupported nperseg, noverlap >= nperseg, an empty
+ * band or a workspace that is too small. */
+size_t ava_amp_workspace_bytes(int64_t frames);
+int ava_amp_trace(const void* audio, int audio_dtype, const int64_t* file_off, const int64_t* file_len,
+                  const int64_t* frame_off, int files, int64_t frames, int nperseg, int noverlap, const double* window,
+                  double scale, int k0, int k1, double spec_min, double spec_max, int softmax, double temperature,
+                  const double* gauss_w, int radius, int trace_f64, void* trace, double* spec, void* ws,
+                  size_t ws_bytes, ava_stream_t s);
+int ava_amp_decide(const void* trace, int trace_f64, const int64_t* frame_off, int files, int64_t frames, double th1,
+                   double th2, double th3, uint64_t* count, int64_t* maxima, int64_t* left, int64_t* right,
+                   int64_t capacity, ava_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif
