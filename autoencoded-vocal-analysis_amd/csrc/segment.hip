@@ -13,16 +13,14 @@
 //                                          amplitude_segmentation.py:79-99               amp_stops_kernel    (1 wave / maximum)
 //
 // The host receives O(#maxima) integers and runs the greedy chain and the duration filter (ava_amd/segment.py).
-// The spectral arithmetic is fp64 (the radix-2 transform is that of spec.hip, duplicated so that f4 stays as proven);
-// the trace is stored in the dtype the reference holds it in (float32 for int16 / float32 audio, float64 otherwise), and
-// the decision kernels compare the values of THAT trace, promoted exactly to fp64, against thresholds the host has
-// already rounded the way numpy would (a Python float compared with a float32 array is a float32).
-#include "common.h"
+// The spectral arithmetic is fp64 (the transform of stft.h, shared with spec.hip); the trace is stored in the dtype the
+// reference holds it in (float32 for int16 / float32 audio, float64 otherwise), and the decision kernels compare the
+// values of THAT trace, promoted exactly to fp64, against thresholds the host has already rounded the way numpy would
+// (a Python float compared with a float32 array is a float32).
+#include "stft.h"
 
 #define AVA_AMP_EPS 1e-9
 #define AVA_AMP_T 256
-
-enum { AMP_AUDIO_I16 = 0, AMP_AUDIO_I32 = 1, AMP_AUDIO_F32 = 2, AMP_AUDIO_F64 = 3 };
 
 struct AmpArgs {
   const void* audio;
@@ -37,15 +35,6 @@ struct AmpArgs {
   int files, nperseg, nstep, k0, k1, softmax, dtype;
 };
 
-__device__ __forceinline__ double amp_audio_at(const void* base, int dtype, long long i) {
-  switch (dtype) {
-    case AMP_AUDIO_I16: return (double)reinterpret_cast<const short*>(base)[i];
-    case AMP_AUDIO_I32: return (double)reinterpret_cast<const int*>(base)[i];
-    case AMP_AUDIO_F32: return (double)reinterpret_cast<const float*>(base)[i];
-    default: return reinterpret_cast<const double*>(base)[i];
-  }
-}
-
 // file of global frame g: the f with frame_off[f] <= g < frame_off[f + 1] (files without frames are never returned)
 __device__ __forceinline__ int amp_file_of(const long long* frame_off, int files, long long g) {
   int lo = 0, hi = files;
@@ -56,105 +45,36 @@ __device__ __forceinline__ int amp_file_of(const long long* frame_off, int files
   return lo;
 }
 
-// One workgroup per frame, striding over all frames of all files: Hann window, N-point real transform as an N/2-point
-// complex FFT in LDS + the split step (spec_stft_kernel's arithmetic), the band reduction in a fixed order (thread
-// partial sums, then the waves' shuffles, then the four waves in order): deterministic.
-#define PD(i) ((i) + ((i) >> 3))
+// One workgroup per frame, striding over all frames of all files: the shared transform of stft.h, then the band
+// reduction in a fixed order (thread partial sums, then the waves' shuffles, then the four waves in order):
+// deterministic.
 template <int LOGN>
 __global__ __launch_bounds__(AVA_AMP_T) void amp_stft_kernel(const AmpArgs a) {
-  constexpr int N = 1 << LOGN, H = N / 2, LOGH = LOGN - 1;
-  __shared__ double re[H + H / 8 + 1], im[H + H / 8 + 1];
-  __shared__ double twr[H + H / 8 + 1], twi[H + H / 8 + 1];       // exp(-2 pi i k / N), k < N/2
+  constexpr int N = 1 << LOGN, H = N / 2;
+  __shared__ double re[stft_lds(H)], im[stft_lds(H)];
+  __shared__ double twr[stft_lds(H)], twi[stft_lds(H)];       // exp(-2 pi i k / N), k < N/2
   __shared__ double red[2][AVA_AMP_T / 64];
   const int t = threadIdx.x;
   for (int k = t; k < H; k += AVA_AMP_T) {
     double sn, cs;
     sincospi(-2.0 * (double)k / (double)N, &sn, &cs);
-    twr[PD(k)] = cs;
-    twi[PD(k)] = sn;
+    twr[stft_pd(k)] = cs;
+    twi[stft_pd(k)] = sn;
   }
-  constexpr int U = H / AVA_AMP_T > 0 ? H / AVA_AMP_T : 1;
-  double raw[U][2];
-  auto fetch = [&](long long g) {
+  auto frame = [&](long long g) {                             // global frame g: a frame of its file
     const int f = amp_file_of(a.frame_off, a.files, g);
-    const long long j = g - a.frame_off[f], len = a.file_len[f], base = a.file_off[f];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const int i = t + AVA_AMP_T * u;
-#pragma unroll
-      for (int e = 0; e < 2; ++e) {
-        const long long idx = j * a.nstep + 2 * i + e - N / 2;                  // position in the file (zeros outside)
-        const bool in = i < H && idx >= 0 && idx < len;
-        const double x = amp_audio_at(a.audio, a.dtype, base + (in ? idx : 0));   // clamped address
-        raw[u][e] = in ? x : 0.0;
-      }
-    }
+    const long long c = (g - a.frame_off[f]) * a.nstep, len = a.file_len[f], base = a.file_off[f];
+    return [&a, c, len, base](long long p, bool live) {
+      const long long idx = c + p;
+      const bool in = live && idx >= 0 && idx < len;
+      const double x = audio_at(a.audio, a.dtype, base + (in ? idx : 0));
+      return in ? x : 0.0;
+    };
   };
-  if ((long long)blockIdx.x < a.frames) fetch(blockIdx.x);
-  for (long long g = blockIdx.x; g < a.frames; g += gridDim.x) {
-    __syncthreads();                                       // twiddles ready / previous frame's reads retired
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const int i = t + AVA_AMP_T * u;
-      if (i < H) {
-        const int r = (int)(__brev((unsigned)i) >> (32 - LOGH));
-        re[PD(r)] = __dmul_rn(raw[u][0], a.window[2 * i]);
-        im[PD(r)] = __dmul_rn(raw[u][1], a.window[2 * i + 1]);
-      }
-    }
-    if (g + gridDim.x < a.frames) fetch(g + gridDim.x);   // in flight under this frame's butterflies
-    __syncthreads();
-    int st = 0;
-#pragma unroll 1
-    for (; st + 1 < LOGH; st += 2) {                        // two radix-2 stages per pass over LDS
-      const int h = 1 << st;
-      for (int b = t; b < H / 4; b += AVA_AMP_T) {
-        const int pos = b & (h - 1);
-        const int i0 = ((b >> st) << (st + 2)) + pos, i1 = i0 + h, i2 = i1 + h, i3 = i2 + h;
-        const int k1 = pos << (LOGN - 1 - st), k2 = pos << (LOGN - 2 - st);
-        const double w1r = twr[PD(k1)], w1i = twi[PD(k1)], w2r = twr[PD(k2)], w2i = twi[PD(k2)];
-        const double x1r = re[PD(i1)], x1i = im[PD(i1)], x3r = re[PD(i3)], x3i = im[PD(i3)];
-        const double p1r = w1r * x1r - w1i * x1i, p1i = w1r * x1i + w1i * x1r;
-        const double p3r = w1r * x3r - w1i * x3i, p3i = w1r * x3i + w1i * x3r;
-        const double u0r = re[PD(i0)], u0i = im[PD(i0)], u2r = re[PD(i2)], u2i = im[PD(i2)];
-        const double b0r = u0r + p1r, b0i = u0i + p1i, b1r = u0r - p1r, b1i = u0i - p1i;
-        const double b2r = u2r + p3r, b2i = u2i + p3i, b3r = u2r - p3r, b3i = u2i - p3i;
-        const double q2r = w2r * b2r - w2i * b2i, q2i = w2r * b2i + w2i * b2r;
-        const double w3r = twr[PD(k2 + H / 2)], w3i = twi[PD(k2 + H / 2)];
-        const double q3r = w3r * b3r - w3i * b3i, q3i = w3r * b3i + w3i * b3r;
-        re[PD(i0)] = b0r + q2r; im[PD(i0)] = b0i + q2i;
-        re[PD(i2)] = b0r - q2r; im[PD(i2)] = b0i - q2i;
-        re[PD(i1)] = b1r + q3r; im[PD(i1)] = b1i + q3i;
-        re[PD(i3)] = b1r - q3r; im[PD(i3)] = b1i - q3i;
-      }
-      __syncthreads();
-    }
-    if (st < LOGH) {
-      const int half = 1 << st;
-      for (int b = t; b < H / 2; b += AVA_AMP_T) {
-        const int pos = b & (half - 1);
-        const int i0 = ((b >> st) << (st + 1)) + pos, i1 = i0 + half;
-        const int tk = pos << (LOGN - 1 - st);
-        const double wr = twr[PD(tk)], wi = twi[PD(tk)];
-        const double xr = re[PD(i1)], xi = im[PD(i1)];
-        const double pr = wr * xr - wi * xi, pi = wr * xi + wi * xr;
-        const double ur = re[PD(i0)], ui = im[PD(i0)];
-        re[PD(i0)] = ur + pr; im[PD(i0)] = ui + pi;
-        re[PD(i1)] = ur - pr; im[PD(i1)] = ui - pi;
-      }
-      __syncthreads();
-    }
-    // split: X_k = E_k + W_N^k O_k for the kept bins k0 <= k < k1 (<= H), then the band value of each bin
+  auto band = [&](long long g) {                              // the kept bins k0 <= k < k1 (<= H)
     double s0 = 0.0, s1 = 0.0;
     for (int k = a.k0 + t; k < a.k1; k += AVA_AMP_T) {
-      const int ka = k & (H - 1), kb = (H - k) & (H - 1);
-      const double zr = re[PD(ka)], zi = im[PD(ka)], cr = re[PD(kb)], ci = -im[PD(kb)];
-      const double er = 0.5 * (zr + cr), ei = 0.5 * (zi + ci);
-      const double dr = 0.5 * (zr - cr), di = 0.5 * (zi - ci);
-      const double orr = di, oi = -dr;
-      const double wr = k == H ? -1.0 : twr[PD(k)], wi = k == H ? 0.0 : twi[PD(k)];
-      const double xr = er + (wr * orr - wi * oi), xi = ei + (wr * oi + wi * orr);
-      const double lg = log(__dadd_rn(__dmul_rn(sqrt(xr * xr + xi * xi), a.scale), AVA_AMP_EPS));
+      const double lg = stft_logmag(stft_bin<LOGN>(k, re, im, twr, twi), a.scale, AVA_AMP_EPS);
       double v = __ddiv_rn(__dsub_rn(lg, a.spec_min), a.range);
       v = v < 0.0 ? 0.0 : (v > 1.0 ? 1.0 : v);
       if (a.spec != nullptr) a.spec[(size_t)(k - a.k0) * a.frames + g] = v;
@@ -176,9 +96,10 @@ __global__ __launch_bounds__(AVA_AMP_T) void amp_stft_kernel(const AmpArgs a) {
       for (int w = 0; w < AVA_AMP_T / 64; ++w) { v0 += red[0][w]; v1 += red[1][w]; }
       a.raw[g] = a.softmax ? __ddiv_rn(v0, __dadd_rn(v1, AVA_AMP_EPS)) : v0;
     }
-  }
+  };
+  stft_frames<LOGN, AVA_AMP_T>((long long)blockIdx.x, a.frames, (long long)gridDim.x, a.window, re, im, twr, twi, frame,
+                               band);
 }
-#undef PD
 
 // scipy.ndimage.gaussian_filter on each file's trace: correlation with the 2 radius + 1 host-computed weights, mode
 // 'reflect' (d c b a | a b c d | d c b a, repeated: period 2 T), fp64, then one rounding to the trace's dtype.
@@ -281,7 +202,7 @@ extern "C" int ava_amp_trace(const void* audio, int audio_dtype, const int64_t* 
   if (nperseg < 64 || nperseg > 2048 || (nperseg & (nperseg - 1)) != 0) return AVA_EINVAL;
   if (noverlap < 0 || noverlap >= nperseg) return AVA_EINVAL;
   if (k0 < 0 || k1 <= k0 || k1 > nperseg / 2 + 1) return AVA_EINVAL;             // empty band
-  if (audio_dtype < AMP_AUDIO_I16 || audio_dtype > AMP_AUDIO_F64) return AVA_EINVAL;
+  if (audio_dtype < AVA_AUDIO_I16 || audio_dtype > AVA_AUDIO_F64) return AVA_EINVAL;
   if (!(spec_max != spec_min) || (softmax && !(temperature != 0.0))) return AVA_EINVAL;
   if (ws == nullptr || ws_bytes < ava_amp_workspace_bytes(frames)) return AVA_EINVAL;
   AmpArgs a;
@@ -299,14 +220,9 @@ extern "C" int ava_amp_trace(const void* audio, int audio_dtype, const int64_t* 
   a.k0 = k0; a.k1 = k1; a.softmax = softmax ? 1 : 0; a.dtype = audio_dtype;
   hipStream_t st = to_stream(s);
   const int grid = frames < 4096 ? (int)frames : 4096;      // workgroups stride over the frames
-  switch (nperseg) {
-    case 64: hipLaunchKernelGGL(amp_stft_kernel<6>, dim3(grid), dim3(AVA_AMP_T), 0, st, a); break;
-    case 128: hipLaunchKernelGGL(amp_stft_kernel<7>, dim3(grid), dim3(AVA_AMP_T), 0, st, a); break;
-    case 256: hipLaunchKernelGGL(amp_stft_kernel<8>, dim3(grid), dim3(AVA_AMP_T), 0, st, a); break;
-    case 512: hipLaunchKernelGGL(amp_stft_kernel<9>, dim3(grid), dim3(AVA_AMP_T), 0, st, a); break;
-    case 1024: hipLaunchKernelGGL(amp_stft_kernel<10>, dim3(grid), dim3(AVA_AMP_T), 0, st, a); break;
-    default: hipLaunchKernelGGL(amp_stft_kernel<11>, dim3(grid), dim3(AVA_AMP_T), 0, st, a); break;
-  }
+  stft_dispatch(nperseg, [&](auto logn) {
+    hipLaunchKernelGGL(amp_stft_kernel<decltype(logn)::value>, dim3(grid), dim3(AVA_AMP_T), 0, st, a);
+  });
   AVA_CHECK_LAUNCH();
   const dim3 sgrid((unsigned)ceil_div64(frames, AVA_AMP_T));
   if (trace_f64)

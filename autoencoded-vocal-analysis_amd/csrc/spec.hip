@@ -15,11 +15,9 @@
 // FFTs, 0.3 to 2 GFLOP.  The frame times and bin frequencies are computed with the reference's own operation order
 // (scipy's arange / fs - (nperseg/2) / fs + max(0, t1); rfftfreq's k * (1 / (n d))) and without contraction, so that
 // the interval a target point falls into is decided by the same numbers.
-#include "common.h"
+#include "stft.h"
 
 #define AVA_SPEC_EPS 1e-12
-
-enum { AVA_AUDIO_I16 = 0, AVA_AUDIO_I32 = 1, AVA_AUDIO_F32 = 2, AVA_AUDIO_F64 = 3 };
 
 struct SpecMeta {        // one per window, written by spec_prep_kernel
   long long lo;          // first sample of the slice inside the concatenated audio buffer
@@ -53,15 +51,6 @@ struct SpecArgs {
   double fs, scale, spec_min, range, fill_value, fbin;    // fbin: rfftfreq's 1 / (nperseg * (1 / fs))
   int n, maxframes, nperseg, nstep, F, T, dtype, remove_dc;
 };
-
-__device__ __forceinline__ double audio_at(const void* base, int dtype, long long i) {
-  switch (dtype) {
-    case AVA_AUDIO_I16: return (double)reinterpret_cast<const short*>(base)[i];
-    case AVA_AUDIO_I32: return (double)reinterpret_cast<const int*>(base)[i];
-    case AVA_AUDIO_F32: return (double)reinterpret_cast<const float*>(base)[i];
-    default: return reinterpret_cast<const double*>(base)[i];
-  }
-}
 
 // frame time j of a window: scipy's  arange(nperseg/2, ..., hop) / fs - (nperseg/2) / fs, then utils.py:75's + max(0, t1)
 __device__ __forceinline__ double frame_time(int j, const SpecArgs& a, double t_shift) {
@@ -195,119 +184,37 @@ __global__ __launch_bounds__(AVA_SPEC_PREP_T) void spec_prep_kernel(const SpecAr
   }
 }
 
-// Frames of one window: Hann window, N-point transform of the real frame as an N/2-point complex FFT of the
-// even/odd-interleaved samples (radix-2 decimation in time in LDS) + the split step, log-magnitude of the one-sided
-// spectrum.  A workgroup walks the needed frames of its window with stride gridDim.x; the twiddle table is loaded once.
-#define PD(i) ((i) + ((i) >> 3))
+// Frames of one window (the shared transform of stft.h).  A workgroup walks the needed frames of its window with
+// stride gridDim.x; the twiddle table is loaded once.
 template <int LOGN>
 __global__ __launch_bounds__(256) void spec_stft_kernel(const SpecArgs a) {
-  constexpr int N = 1 << LOGN, H = N / 2, LOGH = LOGN - 1;
-  // every LDS array is indexed through PD(i) = i + i / 8: one pad double per eight spreads the power-of-two strides of
-  // the bit-reversed store, the butterflies and the twiddle look-ups over the banks (73 % of the LDS cycles of the
-  // unpadded kernel were bank conflicts)
-  __shared__ double re[H + H / 8 + 1], im[H + H / 8 + 1];
-  __shared__ double twr[H + H / 8 + 1], twi[H + H / 8 + 1];       // exp(-2 pi i k / N), k < N/2
+  constexpr int N = 1 << LOGN, H = N / 2;
+  __shared__ double re[stft_lds(H)], im[stft_lds(H)];
+  __shared__ double twr[stft_lds(H)], twi[stft_lds(H)];       // exp(-2 pi i k / N), k < N/2
   const int w = blockIdx.y, t = threadIdx.x;
   const SpecMeta m = a.meta[w];
   if (m.nframes <= 0 || m.j0 + (int)blockIdx.x > m.j1) return;
   for (int k = t; k < H; k += 256) {
-    twr[PD(k)] = a.twiddle[2 * k];
-    twi[PD(k)] = a.twiddle[2 * k + 1];
+    twr[stft_pd(k)] = a.twiddle[2 * k];
+    twi[stft_pd(k)] = a.twiddle[2 * k + 1];
   }
   const int k0 = a.krange[0], k1 = a.krange[1];             // bins outside are never read by the interpolation
-  // samples of a frame: thread t owns the pairs (2 i, 2 i + 1), i = t + 256 u; raw values are fetched one frame ahead
-  constexpr int U = H / 256 > 0 ? H / 256 : 1;
-  double raw[U][2];
-  auto fetch = [&](int j) {
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const int i = t + 256 * u;
-#pragma unroll
-      for (int e = 0; e < 2; ++e) {
-        const long long idx = (long long)j * a.nstep + 2 * i + e - N / 2;      // position in the slice (zeros outside)
-        const bool in = i < H && idx >= 0 && idx < m.n;
-        const double x = audio_at(a.audio, a.dtype, m.lo + (in ? idx : 0));      // unconditional load, clamped address
-        raw[u][e] = in ? x - m.mean : 0.0;                                       // zero boundary / padding
-      }
-    }
+  auto frame = [&](int j) {                                   // frame j of the slice minus its mean
+    const long long c = (long long)j * a.nstep;
+    return [&a, &m, c](long long p, bool live) {
+      const long long idx = c + p;
+      const bool in = live && idx >= 0 && idx < m.n;
+      const double x = audio_at(a.audio, a.dtype, m.lo + (in ? idx : 0));
+      return in ? x - m.mean : 0.0;
+    };
   };
-  fetch(m.j0 + blockIdx.x);
-  for (int j = m.j0 + blockIdx.x; j <= m.j1; j += gridDim.x) {
-    __syncthreads();                                       // twiddles ready / previous frame's reads retired
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const int i = t + 256 * u;
-      if (i < H) {
-        const double v0 = __dmul_rn(raw[u][0], a.window[2 * i]);
-        const double v1 = __dmul_rn(raw[u][1], a.window[2 * i + 1]);
-        const int r = (int)(__brev((unsigned)i) >> (32 - LOGH));
-        re[PD(r)] = v0;
-        im[PD(r)] = v1;
-      }
-    }
-    if (j + (int)gridDim.x <= m.j1) fetch(j + gridDim.x);  // in flight under this frame's butterflies
-    __syncthreads();
-    // Two radix-2 stages (half = h, then 2 h) per pass over LDS: the four points i0 + {0, h, 2h, 3h} of a group are
-    // combined in registers (same operations, same order as two separate stages; half the LDS traffic, which bounds
-    // this kernel).  An odd stage count ends with one plain radix-2 pass.
-    int st = 0;
-#pragma unroll 1
-    for (; st + 1 < LOGH; st += 2) {
-      const int h = 1 << st;
-      for (int b = t; b < H / 4; b += 256) {
-        const int pos = b & (h - 1);
-        const int i0 = ((b >> st) << (st + 2)) + pos, i1 = i0 + h, i2 = i1 + h, i3 = i2 + h;
-        const int k1 = pos << (LOGN - 1 - st), k2 = pos << (LOGN - 2 - st);
-        const double w1r = twr[PD(k1)], w1i = twi[PD(k1)], w2r = twr[PD(k2)], w2i = twi[PD(k2)];
-        const double x1r = re[PD(i1)], x1i = im[PD(i1)], x3r = re[PD(i3)], x3i = im[PD(i3)];
-        const double p1r = w1r * x1r - w1i * x1i, p1i = w1r * x1i + w1i * x1r;
-        const double p3r = w1r * x3r - w1i * x3i, p3i = w1r * x3i + w1i * x3r;
-        const double u0r = re[PD(i0)], u0i = im[PD(i0)], u2r = re[PD(i2)], u2i = im[PD(i2)];
-        const double b0r = u0r + p1r, b0i = u0i + p1i, b1r = u0r - p1r, b1i = u0i - p1i;     // stage st
-        const double b2r = u2r + p3r, b2i = u2i + p3i, b3r = u2r - p3r, b3i = u2i - p3i;
-        const double q2r = w2r * b2r - w2i * b2i, q2i = w2r * b2i + w2i * b2r;               // stage st + 1: W^pos
-        // twiddle of the pair (i1, i3) is W_{4h}^{pos + h} = exp(-2 pi i (pos + h) / (4 h)): entry k2 + N/4 of the table
-        const double w3r = twr[PD(k2 + H / 2)], w3i = twi[PD(k2 + H / 2)];
-        const double q3r = w3r * b3r - w3i * b3i, q3i = w3r * b3i + w3i * b3r;
-        re[PD(i0)] = b0r + q2r; im[PD(i0)] = b0i + q2i;
-        re[PD(i2)] = b0r - q2r; im[PD(i2)] = b0i - q2i;
-        re[PD(i1)] = b1r + q3r; im[PD(i1)] = b1i + q3i;
-        re[PD(i3)] = b1r - q3r; im[PD(i3)] = b1i - q3i;
-      }
-      __syncthreads();
-    }
-    if (st < LOGH) {
-      const int half = 1 << st;
-      for (int b = t; b < H / 2; b += 256) {
-        const int pos = b & (half - 1);
-        const int i0 = ((b >> st) << (st + 1)) + pos, i1 = i0 + half;
-        const int tk = pos << (LOGN - 1 - st);               // exp(-2 pi i pos / (2 half)) in units of the N table
-        const double wr = twr[PD(tk)], wi = twi[PD(tk)];
-        const double xr = re[PD(i1)], xi = im[PD(i1)];
-        const double pr = wr * xr - wi * xi, pi = wr * xi + wi * xr;
-        const double ur = re[PD(i0)], ui = im[PD(i0)];
-        re[PD(i0)] = ur + pr; im[PD(i0)] = ui + pi;
-        re[PD(i1)] = ur - pr; im[PD(i1)] = ui - pi;
-      }
-      __syncthreads();
-    }
-    // split: X_k = E_k + W_N^k O_k,  E_k = (Z_k + conj Z_{H-k}) / 2,  O_k = -i (Z_k - conj Z_{H-k}) / 2,  k = 0 .. H
+  auto logmag = [&](int j) {
     double* dst = a.logmag + ((size_t)w * a.maxframes + j) * (H + 1);
-    for (int k = k0 + t; k <= k1; k += 256) {
-      const int ka = k & (H - 1), kb = (H - k) & (H - 1);
-      const double zr = re[PD(ka)], zi = im[PD(ka)], cr = re[PD(kb)], ci = -im[PD(kb)];
-      const double er = 0.5 * (zr + cr), ei = 0.5 * (zi + ci);
-      const double dr = 0.5 * (zr - cr), di = 0.5 * (zi - ci);
-      const double orr = di, oi = -dr;                                  // -i (dr + i di)
-      const double wr = k == H ? -1.0 : twr[PD(k)], wi = k == H ? 0.0 : twi[PD(k)];
-      const double xr = er + (wr * orr - wi * oi), xi = ei + (wr * oi + wi * orr);
-      // |X|: no overflow / underflow guard needed at audio magnitudes (numpy's abs is hypot: same value to an ulp)
-      dst[k] = log(__dadd_rn(__dmul_rn(sqrt(xr * xr + xi * xi), a.scale), AVA_SPEC_EPS));
-    }
-  }
+    for (int k = k0 + t; k <= k1; k += 256)
+      dst[k] = stft_logmag(stft_bin<LOGN>(k, re, im, twr, twi), a.scale, AVA_SPEC_EPS);
+  };
+  stft_frames<LOGN, 256>(m.j0 + (int)blockIdx.x, m.j1 + 1, (int)gridDim.x, a.window, re, im, twr, twi, frame, logmag);
 }
-
-#undef PD
 
 // The same for a segment length that is NOT a power of two (the reference hands any nperseg to scipy.signal.stft,
 // ava/preprocessing/utils.py:66-68; scipy's pocketfft takes any length): the one-sided spectrum by direct summation in fp64,
@@ -348,7 +255,7 @@ __global__ __launch_bounds__(256) void spec_dft_kernel(const SpecArgs a) {
         q += k;
         if (q >= N) q -= N;
       }
-      dst[k] = log(__dadd_rn(__dmul_rn(sqrt(xr * xr + xi * xi), a.scale), AVA_SPEC_EPS));
+      dst[k] = stft_logmag({xr, xi}, a.scale, AVA_SPEC_EPS);
     }
   }
 }
@@ -582,14 +489,9 @@ extern "C" int ava_get_spec_batch(const void* audio, int audio_dtype, const int6
   AVA_CHECK_LAUNCH();
   const dim3 fgrid(a.maxframes < 24 ? a.maxframes : 24, n);      // a workgroup strides over its window's needed frames
   if ((nperseg & (nperseg - 1)) != 0) hipLaunchKernelGGL(spec_dft_kernel, fgrid, dim3(256), 0, st, a);
-  else switch (nperseg) {
-    case 64: hipLaunchKernelGGL(spec_stft_kernel<6>, fgrid, dim3(256), 0, st, a); break;
-    case 128: hipLaunchKernelGGL(spec_stft_kernel<7>, fgrid, dim3(256), 0, st, a); break;
-    case 256: hipLaunchKernelGGL(spec_stft_kernel<8>, fgrid, dim3(256), 0, st, a); break;
-    case 512: hipLaunchKernelGGL(spec_stft_kernel<9>, fgrid, dim3(256), 0, st, a); break;
-    case 1024: hipLaunchKernelGGL(spec_stft_kernel<10>, fgrid, dim3(256), 0, st, a); break;
-    default: hipLaunchKernelGGL(spec_stft_kernel<11>, fgrid, dim3(256), 0, st, a); break;
-  }
+  else stft_dispatch(nperseg, [&](auto logn) {
+    hipLaunchKernelGGL(spec_stft_kernel<decltype(logn)::value>, fgrid, dim3(256), 0, st, a);
+  });
   AVA_CHECK_LAUNCH();
   hipLaunchKernelGGL(spec_interp_kernel, dim3(ceil_div(F, AVA_SPEC_ROWS), n), dim3(256), 0, st, a);
   AVA_CHECK_LAUNCH();
