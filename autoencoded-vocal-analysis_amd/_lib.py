@@ -108,6 +108,10 @@ SIGNATURES = {
     "ava_amp_trace": (_i, [_p, _i, _p, _p, _p, _i, _i64, _i, _i, _p, _d, _i, _i, _d, _d, _i, _d, _p, _i, _i, _p, _p, _p,
                            _sz, _p]),
     "ava_amp_decide": (_i, [_p, _i, _p, _i, _i64, _d, _d, _d, _p, _p, _p, _p, _i64, _p]),
+    "ava_tpl_workspace_bytes": (_sz, [_i64]),
+    "ava_tpl_tile_lags": (_i, []),
+    "ava_tpl_spec": (_i, [_p, _i, _p, _p, _p, _i, _i64, _i, _i, _p, _d, _i, _i, _d, _d, _p, _p, _p]),
+    "ava_tpl_xcorr": (_i, [_p, _p, _i, _i64, _p, _p, _p, _i, _i64, _i64, _p, _i, _i, _p, _p, _sz, _p]),
 }
 
 _lib = None

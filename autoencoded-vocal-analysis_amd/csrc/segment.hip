@@ -35,16 +35,6 @@ struct AmpArgs {
   int files, nperseg, nstep, k0, k1, softmax, dtype;
 };
 
-// file of global frame g: the f with frame_off[f] <= g < frame_off[f + 1] (files without frames are never returned)
-__device__ __forceinline__ int amp_file_of(const long long* frame_off, int files, long long g) {
-  int lo = 0, hi = files;
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (frame_off[mid] <= g) lo = mid; else hi = mid;
-  }
-  return lo;
-}
-
 // One workgroup per frame, striding over all frames of all files: the shared transform of stft.h, then the band
 // reduction in a fixed order (thread partial sums, then the waves' shuffles, then the four waves in order):
 // deterministic.
@@ -62,7 +52,7 @@ __global__ __launch_bounds__(AVA_AMP_T) void amp_stft_kernel(const AmpArgs a) {
     twi[stft_pd(k)] = sn;
   }
   auto frame = [&](long long g) {                             // global frame g: a frame of its file
-    const int f = amp_file_of(a.frame_off, a.files, g);
+    const int f = stft_file_of(a.frame_off, a.files, g);
     const long long c = (g - a.frame_off[f]) * a.nstep, len = a.file_len[f], base = a.file_off[f];
     return [&a, c, len, base](long long p, bool live) {
       const long long idx = c + p;
@@ -108,7 +98,7 @@ __global__ __launch_bounds__(AVA_AMP_T) void amp_smooth_kernel(const double* raw
                                                                long long frames, const double* w, int radius, V* out) {
   const long long g = (long long)blockIdx.x * AVA_AMP_T + threadIdx.x;
   if (g >= frames) return;
-  const int f = amp_file_of(frame_off, files, g);
+  const int f = stft_file_of(frame_off, files, g);
   const long long b = frame_off[f], T = frame_off[f + 1] - b, i = g - b, P = 2 * T;
   double s = 0.0;
   for (int k = -radius; k <= radius; ++k) {
@@ -141,7 +131,7 @@ __global__ __launch_bounds__(AVA_AMP_T) void amp_maxima_kernel(const V* a, const
   const long long g = (long long)blockIdx.x * AVA_AMP_T + threadIdx.x;
   bool is_max = false;
   if (g < frames) {
-    const int f = amp_file_of(frame_off, files, g);
+    const int f = stft_file_of(frame_off, files, g);
     const long long b = frame_off[f], T = frame_off[f + 1] - b, i = g - b;
     if (i >= 1 && i <= T - 2) {
       const double x = (double)a[g];
@@ -168,7 +158,7 @@ __global__ __launch_bounds__(AVA_AMP_T) void amp_stops_kernel(const V* a, const 
   const long long n = (long long)*count;
   for (long long e = (long long)blockIdx.x * (AVA_AMP_T / 64) + (threadIdx.x >> 6); e < n; e += waves) {
     const long long g = maxima[e];
-    const int f = amp_file_of(frame_off, files, g);
+    const int f = stft_file_of(frame_off, files, g);
     const long long b = frame_off[f], T = frame_off[f + 1] - b, m = g - b;
     long long l = -1, r = -1;
     for (long long c = m - 1; c >= 1; c -= 64) {                // j = c, c-1, ..., down to 1

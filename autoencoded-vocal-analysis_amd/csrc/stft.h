@@ -1,8 +1,8 @@
-// The fp64 STFT frame shared by the shotgun spectrograms (spec.hip) and the amplitude
-// segmentation (segment.hip, row f5): scipy.signal.stft's Hann frames with zero boundary, the N-point transform of a
-// real frame as an N/2-point complex FFT of the even/odd-interleaved samples (radix-2 decimation in time in LDS) + the
-// split step, and the log-magnitude of the one-sided spectrum.  Each unit keeps its own twiddle source and its own use of
-// the bins.
+// The fp64 STFT frame shared by the shotgun spectrograms (spec.hip), the amplitude
+// segmentation (segment.hip, row f5) and the template segmentation (template_seg.hip, row f6): scipy.signal.stft's
+// Hann frames with zero boundary, the N-point transform of a real frame as an N/2-point complex FFT of the
+// even/odd-interleaved samples (radix-2 decimation in time in LDS) + the split step, and the log-magnitude of the
+// one-sided spectrum.  Each unit keeps its own twiddle source and its own use of the bins.
 //
 // The units are built with -ffp-contract=on, which fuses a product into an add only inside one source expression: the
 // bits depend on how the arithmetic below is cut into expressions, so it stays cut exactly as it is.
@@ -20,6 +20,17 @@ __device__ __forceinline__ double audio_at(const void* base, int dtype, long lon
     case AVA_AUDIO_F32: return (double)reinterpret_cast<const float*>(base)[i];
     default: return reinterpret_cast<const double*>(base)[i];
   }
+}
+
+// file of global frame g: the f with frame_off[f] <= g < frame_off[f + 1] (files without frames are never returned).
+// Any [files + 1] table of ascending offsets works the same way (template_seg.hip looks workgroups up in its tile table).
+__device__ __forceinline__ int stft_file_of(const long long* frame_off, int files, long long g) {
+  int lo = 0, hi = files;
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (frame_off[mid] <= g) lo = mid; else hi = mid;
+  }
+  return lo;
 }
 
 // Every LDS array of the transform is indexed through stft_pd(i) = i + i / 8: one pad double per eight spreads the

@@ -166,3 +166,72 @@ def recordings(n_files=3, fs=32000, seconds=2.0, salt=4004, dtype=np.int16, ampl
         edges = np.linspace(0.02, dur - 0.02, 2 * k)
         rois.append(np.stack([edges[0::2], edges[1::2]], axis=1))
     return audio, rois
+
+
+# ---- synthetic birdsong for the template segmentation ----------------------------------
+def _motif(n, fs, motif_seconds, stretch, shift):
+    """``n`` samples of one rendition of the motif: four harmonic syllables with frequency sweeps, played ``stretch``
+    times slower and ``shift`` times higher than the model (float64, peak about 1.75)"""
+    t = np.arange(n) / fs / stretch
+    x = np.zeros(n)
+    for s in range(4):
+        a = motif_seconds * (0.03 + 0.24 * s)
+        b = a + motif_seconds * (0.12 + 0.03 * s)
+        inside = (t >= a) & (t < b)
+        u = np.where(inside, (t - a) / (b - a), 0.0)
+        env = np.where(inside, np.sin(np.pi * u) ** 2, 0.0)
+        f = fs * (0.03 + 0.025 * s) * shift * (1.0 + 0.3 * np.sin(np.pi * (s + 1) * u))
+        phase = 2.0 * np.pi * np.cumsum(f) / fs
+        x += env * (np.sin(phase) + 0.5 * np.sin(2.0 * phase) + 0.25 * np.sin(3.0 * phase))
+    return x
+
+
+def _to_dtype(x, dtype):
+    if np.issubdtype(np.dtype(dtype), np.integer):
+        return np.clip(np.rint(x), np.iinfo(dtype).min, np.iinfo(dtype).max).astype(dtype)
+    return (x / 32768.0).astype(dtype)                        # float audio in [-1, 1), as recordings() scales it
+
+
+def songs(n_exemplars=4, n_songs=3, fs=32000, seconds=4.0, motif_seconds=0.5, renditions=4, salt=6006,
+          dtype=np.int16, amplitude=3000.0, noise=0.05):
+    """Synthetic song for the template segmentation: ``(exemplars, songs, onsets)``.
+
+    ``exemplars``: ``n_exemplars`` files that each hold one rendition of the motif (slightly stretched, shifted in pitch
+    and louder or quieter) in a little noise.  ``songs``: ``n_songs`` files of ``seconds`` (each a little longer than
+    the one before) in which ``renditions`` jittered renditions sit in noise of ``noise * amplitude``, with two
+    stretches of near silence (one hundredth of that noise).  ``onsets``: per song the true onsets of the renditions in
+    seconds.  Integer dtypes hold the samples, float dtypes the samples / 32768.  Pure numpy, hash-seeded: identical
+    wherever generated."""
+    def rendition(k):
+        g = gauss(3, salt + 31 * k)
+        stretch, shift, gain = 1.0 + 0.03 * np.tanh(g[0]), 1.0 + 0.02 * np.tanh(g[1]), 1.0 + 0.1 * np.tanh(g[2])
+        n = int(round(motif_seconds * stretch * fs))
+        return gain * _motif(n, fs, motif_seconds, stretch, shift)
+
+    exemplars = []
+    for e in range(n_exemplars):
+        m = rendition(e)
+        pad = int(0.01 * fs)
+        x = 0.01 * amplitude * gauss(len(m) + 2 * pad, salt + 1000 + e)
+        x[pad:pad + len(m)] += amplitude * m
+        exemplars.append(_to_dtype(x, dtype))
+    out, onsets = [], []
+    for s in range(n_songs):
+        n = int(fs * seconds * (1.0 + 0.07 * s))
+        x = noise * amplitude * gauss(n, salt + 2000 + s)
+        u = u01(2, salt + 3000 + s)
+        for q in range(2):                                    # near-silent stretches of 0.2 s
+            a = int((0.1 + 0.35 * q + 0.1 * u[q]) * n)
+            x[a:a + int(0.2 * fs)] *= 0.01
+        slots = np.linspace(0.05, 0.9, renditions + 1)[:-1] * n
+        jit = u01(renditions, salt + 4000 + s)
+        on = []
+        for r in range(renditions):
+            m = rendition(100 * (s + 1) + r)
+            a = int(slots[r] + jit[r] * 0.25 * fs)
+            a = min(a, n - len(m))
+            x[a:a + len(m)] += amplitude * m
+            on.append(a / fs)
+        out.append(_to_dtype(x, dtype))
+        onsets.append(np.array(on))
+    return exemplars, out, onsets

@@ -1,0 +1,342 @@
+"""Template segmentation computed on the device.
+
+Mirror of the computational surface of ava/segmenting/template_segmentation.py, the birdsong path:
+
+  ``get_template``             lines 37-84     same signature; exemplar spectrograms on the device
+  ``get_template_from_audio``  the same on arrays instead of files
+  ``segment_files``            lines 87-153    same dict, files and prints; files go through ``segment_batch`` in chunks
+  ``read_segment_decisions``   lines 156-191   the plain reader
+  ``_segment_file``            lines 194-264   drop-in, same return tuple
+  ``xcorr_batch``              the normalised cross-correlation trace of every file of a ``DeviceAudio``
+  ``segment_batch``            ``_segment_file``'s segments for every file of a ``DeviceAudio``
+  ``segments_from_trace``      the decisions (lines 246-264) on a given trace
+  ``install``                  points the reference module's ``get_template``, ``segment_files``, ``_segment_file`` here
+
+The band spectrogram of whole files (``_get_spec``, lines 758-790) and the correlation with the template run on the
+device in fp64 (``csrc/template_seg.hip``); the host receives the fp64 trace and runs the threshold, the maxima and
+``_clean_max_indices`` on it (O(lags) per file, vectorised numpy).  The template's smoothing, truncation, mean and
+normalisation are the reference's own numpy calls on a few F x L arrays.  Unlike the reference, this module imports
+without affinewarp, umap, h5py or bokeh.
+
+``nperseg`` must be a power of two in 64..2048; other lengths raise ``NotImplementedError``.  There is no CPU fallback.
+"""
+import bisect
+import os
+import warnings
+
+import numpy as np
+import torch
+
+from . import _lib
+from . import segment as _seg
+from .spec import DeviceAudio, _stft_constants
+
+__all__ = ["EPSILON", "get_template", "get_template_from_audio", "segment_files", "read_segment_decisions",
+           "xcorr_batch", "segment_batch", "segments_from_trace", "install"]
+
+EPSILON = 1e-9                       # template_segmentation.py:31
+DEFAULT_CHUNK_BYTES = 1 << 30        # audio bytes per batch of segment_files()
+
+
+def _check_shape(nperseg, noverlap):
+    if nperseg < 64 or nperseg > 2048 or nperseg & (nperseg - 1) or not 0 <= noverlap < nperseg:
+        raise NotImplementedError("device template segmentation needs nperseg a power of two in 64..2048 and "
+                                  "0 <= noverlap < nperseg (got %d, %d)" % (nperseg, noverlap))
+
+
+def _is_wav_file(filename):
+    return len(filename) > 4 and filename[-4:] == '.wav'
+
+
+def _read(filename, p):
+    from scipy.io import wavfile
+    from scipy.io.wavfile import WavFileWarning
+    with warnings.catch_warnings():
+        warnings.filterwarnings("ignore", category=WavFileWarning)
+        fs, audio = wavfile.read(filename)
+    assert fs == p['fs'], "Found samplerate=" + str(fs) + ", expected " + str(p['fs'])
+    return audio
+
+
+# ---- device stages --------------------------------------------------------------------------------------------------
+
+def _band(device_audio, p):
+    """(spec [F, frames] float64, frame sums [frames], frame_off device, frame_off host, frames per file) of every file;
+    spec is None when no file reaches nperseg samples"""
+    nperseg, noverlap = int(p['nperseg']), int(p['noverlap'])
+    _check_shape(nperseg, noverlap)
+    i1, i2, _ = _seg.band_indices(p)
+    if i2 <= i1:
+        raise ValueError("empty frequency band [%s, %s)" % (p['min_freq'], p['max_freq']))
+    if not np.isfinite(float(p['spec_max_val']) - float(p['spec_min_val'])) or p['spec_max_val'] == p['spec_min_val']:
+        raise ValueError("spec_max_val must differ from spec_min_val")
+    T = _seg.frame_count(device_audio.lengths, nperseg, noverlap)
+    frame_off = np.concatenate([[0], np.cumsum(T)]).astype(np.int64)
+    frames = int(frame_off[-1])
+    dev = device_audio.device
+    fo = torch.from_numpy(frame_off).to(dev)
+    if frames == 0:
+        return None, None, fo, frame_off, T
+    lib = _lib.load()
+    window, scale = _stft_constants(nperseg, dev)
+    spec = torch.empty((i2 - i1, frames), dtype=torch.float64, device=dev)
+    fsum = torch.empty(frames, dtype=torch.float64, device=dev)
+    rc = lib.ava_tpl_spec(device_audio.samples.data_ptr(), device_audio.code, device_audio.file_off.data_ptr(),
+                          device_audio.file_len.data_ptr(), fo.data_ptr(), len(device_audio), frames, nperseg,
+                          noverlap, window.data_ptr(), scale, i1, i2, float(p['spec_min_val']),
+                          float(p['spec_max_val']), spec.data_ptr(), fsum.data_ptr(), _lib.stream())
+    _lib.check(rc, "ava_tpl_spec")
+    return spec, fsum, fo, frame_off, T
+
+
+def _xcorr(band, template, keep):
+    """the device trace (host float64) of the files with keep[f], and the per-file lag offsets"""
+    spec, fsum, fo, frame_off, T = band
+    F, L = template.shape
+    n_lags = np.where(keep, T - L, 0).astype(np.int64)
+    lag_off = np.concatenate([[0], np.cumsum(n_lags)]).astype(np.int64)
+    lags = int(lag_off[-1])
+    if lags == 0:
+        return np.zeros(0), lag_off
+    lib = _lib.load()
+    dev = spec.device
+    tile = lib.ava_tpl_tile_lags()
+    tile_off = np.concatenate([[0], np.cumsum((n_lags + tile - 1) // tile)]).astype(np.int64)
+    offs = torch.from_numpy(np.stack([lag_off, tile_off])).to(dev)
+    tm = torch.from_numpy(np.ascontiguousarray(template, dtype=np.float64)).to(dev)
+    trace = torch.empty(lags, dtype=torch.float64, device=dev)
+    nbytes = lib.ava_tpl_workspace_bytes(lags)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    rc = lib.ava_tpl_xcorr(spec.data_ptr(), fsum.data_ptr(), spec.shape[0], spec.shape[1], fo.data_ptr(),
+                           offs[0].data_ptr(), offs[1].data_ptr(), len(T), lags, int(tile_off[-1]), tm.data_ptr(), F, L,
+                           trace.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream())
+    _lib.check(rc, "ava_tpl_xcorr")
+    return trace.cpu().numpy(), lag_off
+
+
+def _traces(device_audio, template, p, min_extra_time_bins, names):
+    """per file: the trace, or None where _segment_file returns early (with its warning)"""
+    template = np.asarray(template)
+    if template.ndim != 2:
+        raise ValueError("expected a template [F, L]")
+    band = _band(device_audio, p)
+    T = band[4]
+    dt = _seg.frame_step(p['fs'], int(p['nperseg']), int(p['noverlap']))
+    L = template.shape[1]
+    names = names if names is not None else ["<file %d>" % f for f in range(len(T))]
+    keep = np.zeros(len(T), dtype=bool)
+    for f in range(len(T)):
+        n = int(device_audio.lengths[f])
+        if n < p['nperseg']:                                            # template_segmentation.py:218-225
+            warnings.warn("Found an audio file that is too short to make a spectrogram: " + names[f] +
+                          "\nSamples: " + str(n) + "\np['nperseg']: " + str(p['nperseg']), UserWarning)
+        elif T[f] - L < min_extra_time_bins:                            # lines 229-237
+            d1, d2 = dt * L, dt * T[f]
+            warnings.warn("Found an audio file that is too short to extract segments from: " + names[f] +
+                          "\nTemplate duration: " + str(d1) + "\nFile duration: " + str(d2) +
+                          "\nConsider reducing the template duration.", UserWarning)
+        else:
+            keep[f] = True
+    if not keep.any():
+        return [None] * len(T), dt
+    F = band[0].shape[0]
+    if template.shape[0] != F:          # where the reference's np.dot(template, temp) fails on mismatched lengths
+        raise ValueError("template has %d frequency bins, the band has %d" % (template.shape[0], F))
+    trace, lag_off = _xcorr(band, template, keep)
+    return [trace[lag_off[f]:lag_off[f + 1]].copy() if keep[f] else None for f in range(len(T))], dt
+
+
+def xcorr_batch(device_audio, template, p, min_extra_time_bins=5):
+    """The normalised cross-correlation of ``_segment_file`` (template_segmentation.py:239-245) for every file of a
+    ``DeviceAudio``: a list of float64 arrays of n_f - L values, ``None`` where the reference skips the file."""
+    return _traces(device_audio, template, p, min_extra_time_bins, None)[0]
+
+
+def _clean_max_indices(old_indices, old_times, values, min_dt=0.05):
+    """template_segmentation.py:793-815 (remove maxima that are too close together), same output, ties included: the
+    maxima in ``np.argsort`` order of their values, each kept unless a kept one lies within ``min_dt``.  The kept times
+    stay sorted, so only the nearest kept time on either side is compared (|a - t| rounds monotonically in a)."""
+    if len(old_indices) <= 1:
+        return old_indices
+    old_indices = old_indices[np.argsort(values[old_indices])]
+    times = old_times[old_indices]
+    kept, acc = [0], [times[0]]
+    for i in range(1, len(old_indices)):
+        time = times[i]
+        pos = bisect.bisect_left(acc, time)
+        if pos > 0 and abs(acc[pos - 1] - time) < min_dt:
+            continue
+        if pos < len(acc) and abs(acc[pos] - time) < min_dt:
+            continue
+        acc.insert(pos, time)
+        kept.append(i)
+    indices = np.array(old_indices[kept])
+    indices.sort()
+    return indices
+
+
+def segments_from_trace(result, dt, spec_len, num_mad=2.0, min_dt=0.05):
+    """The decisions of _segment_file (template_segmentation.py:246-264) on a trace: ``[n, 2]`` (onset, offset)."""
+    result = np.asarray(result, dtype=np.float64)
+    median = np.median(result)
+    abs_devs = np.abs(result - median)
+    mad = np.median(abs_devs) + EPSILON
+    times = dt * np.arange(len(result))
+    indices = np.argwhere(result > median + num_mad * mad).flatten()[1:-1]
+    cand = indices[2:len(indices) - 1]                                  # range(2, len(indices) - 1)
+    is_max = np.maximum(result[cand - 1], result[cand + 1]) < result[cand]
+    max_indices = np.array(cand[is_max], dtype='int')
+    max_indices = _clean_max_indices(max_indices, times, result, min_dt=min_dt)
+    segments = np.zeros((len(max_indices), 2))
+    segments[:, 0] = dt * max_indices
+    segments[:, 1] = segments[:, 0] + spec_len * dt
+    return segments
+
+
+def segment_batch(device_audio, template, p, num_mad=2.0, min_dt=0.05, min_extra_time_bins=5, names=None):
+    """``_segment_file``'s segments for every file of a ``DeviceAudio``: one ``[n, 2]`` float64 array of (onset,
+    offset) in seconds per file, ``(0, 2)`` with the reference's warning where it skips the file.  ``names`` (optional)
+    name the files in those warnings."""
+    traces, dt = _traces(device_audio, template, p, min_extra_time_bins, names)
+    L = np.asarray(template).shape[1]
+    return [np.zeros((0, 2)) if tr is None else segments_from_trace(tr, dt, L, num_mad, min_dt) for tr in traces]
+
+
+# ---- templates ------------------------------------------------------------------------------------------------------
+
+def _exemplar_specs(audio_list, p):
+    """(_get_spec's spectrogram of each exemplar in the reference's dtype, dt), all from one device launch"""
+    audio_list = [np.asarray(a) for a in audio_list]
+    if not audio_list:
+        raise ValueError("no exemplars")
+    short = [len(a) for a in audio_list if len(a) < p['nperseg']]
+    if short:
+        raise ValueError("an exemplar of %d samples is shorter than nperseg = %d" % (short[0], p['nperseg']))
+    spec, _, _, frame_off, _ = _band(DeviceAudio(audio_list), p)
+    host = spec.cpu().numpy()
+    dt = _seg.frame_step(p['fs'], int(p['nperseg']), int(p['noverlap']))
+    return [host[:, frame_off[f]:frame_off[f + 1]].astype(_seg.trace_dtype(a.dtype))
+            for f, a in enumerate(audio_list)], dt
+
+
+def _template_from_specs(specs, smoothing_kernel):
+    """template_segmentation.py:73-80 on the exemplar spectrograms"""
+    from scipy.ndimage import gaussian_filter
+    specs = [gaussian_filter(spec, smoothing_kernel) for spec in specs]
+    min_time_bins = min(spec.shape[1] for spec in specs)
+    specs = np.array([i[:, :min_time_bins] for i in specs])
+    template = np.mean(specs, axis=0)
+    template -= np.mean(template)
+    template /= np.sum(np.power(template, 2)) + EPSILON
+    return template, min_time_bins
+
+
+def get_template_from_audio(audio_list, p, smoothing_kernel=(0.5, 0.5)):
+    """``get_template`` on a list of 1-D audio arrays (the samples ``scipy.io.wavfile.read`` returns)."""
+    specs, _ = _exemplar_specs(audio_list, p)
+    return _template_from_specs(specs, smoothing_kernel)[0]
+
+
+def get_template(feature_dir, p, smoothing_kernel=(0.5, 0.5), verbose=True):
+    """Drop-in for ``ava.segmenting.template_segmentation.get_template``: the template from every ``*.wav`` of
+    ``feature_dir`` (``os.listdir`` order), float32 for int16 / float32 exemplars, float64 otherwise."""
+    filenames = [os.path.join(feature_dir, i) for i in os.listdir(feature_dir) if _is_wav_file(i)]
+    audio = [_read(fn, p) for fn in filenames]
+    specs, dt = _exemplar_specs(audio, p)
+    template, min_time_bins = _template_from_specs(specs, smoothing_kernel)
+    if verbose:
+        duration = min_time_bins * dt
+        print("Made template from", len(filenames), "files. Duration:", duration)
+    return template
+
+
+# ---- files ----------------------------------------------------------------------------------------------------------
+
+def _segment_file(segment_dir, filename, template, p, num_mad=2.0, min_dt=0.05, min_extra_time_bins=5):
+    """Drop-in for ``ava.segmenting.template_segmentation._segment_file``: ``(segment_dir, filename, segments)``."""
+    audio = _read(filename, p)
+    if len(audio) < p['nperseg']:
+        warnings.warn("Found an audio file that is too short to make a spectrogram: " + filename + "\nSamples: " +
+                      str(len(audio)) + "\np['nperseg']: " + str(p['nperseg']), UserWarning)
+        return segment_dir, filename, np.zeros((0, 2))
+    segments = segment_batch(DeviceAudio([audio]), template, p, num_mad=num_mad, min_dt=min_dt,
+                             min_extra_time_bins=min_extra_time_bins, names=[filename])[0]
+    return segment_dir, filename, segments
+
+
+def segment_files(audio_dirs, segment_dirs, template, p, num_mad=2.0, min_dt=0.05, n_jobs=1, verbose=True,
+                  max_chunk_bytes=DEFAULT_CHUNK_BYTES, device="cuda"):
+    """Drop-in for ``ava.segmenting.template_segmentation.segment_files``: same dict, same ``.txt`` files and prints.
+    ``n_jobs`` is accepted and ignored: the files go through ``segment_batch`` in chunks of at most
+    ``max_chunk_bytes`` of audio (a larger file is a chunk of its own; dtypes are never mixed).  The output does not
+    depend on the chunking."""
+    all_audio_fns, all_seg_dirs = [], []
+    for audio_dir, segment_dir in zip(audio_dirs, segment_dirs):
+        if not os.path.exists(segment_dir):
+            os.makedirs(segment_dir)
+        audio_fns = [os.path.join(audio_dir, i) for i in os.listdir(audio_dir) if _is_wav_file(i)]
+        all_audio_fns = all_audio_fns + audio_fns
+        all_seg_dirs = all_seg_dirs + [segment_dir] * len(audio_fns)
+    if verbose:
+        print("Segmenting files. n =", len(all_audio_fns))
+    res = []
+    chunk, nbytes = [], 0
+
+    def flush():
+        segs = segment_batch(DeviceAudio([a for _, a in chunk], device), template, p, num_mad=num_mad, min_dt=min_dt,
+                             names=[all_audio_fns[i] for i, _ in chunk])
+        res.extend((all_seg_dirs[i], all_audio_fns[i], s) for (i, _), s in zip(chunk, segs))
+
+    for i, audio_fn in enumerate(all_audio_fns):
+        audio = _read(audio_fn, p)
+        if chunk and (nbytes + audio.nbytes > max_chunk_bytes or audio.dtype != chunk[0][1].dtype):
+            flush()
+            chunk, nbytes = [], 0
+        chunk.append((i, audio))
+        nbytes += audio.nbytes
+    if chunk:
+        flush()
+    result = {}
+    num_segments = 0
+    for segment_dir, audio_fn, segments in res:
+        result[audio_fn] = segments
+        segment_fn = os.path.split(audio_fn)[-1][:-4] + '.txt'
+        segment_fn = os.path.join(segment_dir, segment_fn)
+        np.savetxt(segment_fn, segments, fmt='%.5f')
+        num_segments += len(segments)
+    if verbose:
+        print("\tFound", num_segments, "segments.")
+        print("\tDone.")
+    return result
+
+
+def read_segment_decisions(audio_dirs, segment_dirs, verbose=True):
+    """Mirror of ``ava.segmenting.template_segmentation.read_segment_decisions``: the dict ``segment_files``
+    returned, read back from the ``.txt`` files."""
+    if verbose:
+        print("Reading segments...")
+    result = {}
+    n_segs = 0
+    for audio_dir, segment_dir in zip(audio_dirs, segment_dirs):
+        audio_fns = [os.path.join(audio_dir, i) for i in os.listdir(audio_dir) if _is_wav_file(i)]
+        for audio_fn in audio_fns:
+            segment_fn = os.path.split(audio_fn)[-1][:-4] + '.txt'
+            segment_fn = os.path.join(segment_dir, segment_fn)
+            segments = np.loadtxt(segment_fn).reshape(-1, 2)
+            result[audio_fn] = segments
+            n_segs += len(segments)
+    if verbose:
+        print("\tFound", n_segs, "segments.")
+        print("\tDone.")
+    return result
+
+
+def install(module=None):
+    """Point ``get_template``, ``segment_files`` and ``_segment_file`` of ``module`` (by default
+    ``ava.segmenting.template_segmentation``, imported after the reference package) at this module."""
+    if module is None:
+        import ava.segmenting.template_segmentation as module
+    module.get_template = get_template
+    module.segment_files = segment_files
+    module._segment_file = _segment_file
+    return module

@@ -364,6 +364,47 @@ int ava_amp_decide(const void* trace, int trace_f64, const int64_t* frame_off, i
                    double th2, double th3, uint64_t* count, int64_t* maxima, int64_t* left, int64_t* right,
                    int64_t capacity, ava_stream_t s);
 
+/* ---- template segmentation on the device --------------------------------------------
+ * The arithmetic core of ava/segmenting/template_segmentation.py:_segment_file for every file of a concatenated audio
+ * buffer at once: the band spectrogram of _get_spec and the normalised cross-correlation with a template.  The host
+ * keeps the threshold, the maxima and _clean_max_indices (O(lags) per file).
+ *
+ * ava_tpl_workspace_bytes: scratch ava_tpl_xcorr needs for `lags` lags in all (0 for lags <= 0).
+ * ava_tpl_tile_lags: lags per correlation tile; the caller sizes tile_off with it.
+ *
+ * ava_tpl_spec: the band spectrogram and its per-frame sums.
+ *   audio ... frame_off   as ava_amp_trace (0 = int16, 1 = int32, 2 = float32, 3 = float64; frame_off [files + 1])
+ *   nperseg, noverlap     a power of two in 64..2048, 0 <= noverlap < nperseg
+ *   window, scale         get_window('hann', nperseg) (device), 1 / sum(window): 'spectrum' scaling; no detrend
+ *   k0, k1                the kept bins [searchsorted(f, min_freq), searchsorted(f, max_freq)), 0 <= k0 < k1 <= nperseg/2+1
+ *   spec_min, spec_max    S = clip((log(|X| + 1e-9) - spec_min) / (spec_max - spec_min), 0, 1)  (template_segmentation.py:786-789)
+ *   spec                  [k1 - k0][frames] float64 output, frequency-major
+ *   frame_sum             [frames] float64 output: sum over the band of each frame, in a fixed order
+ *
+ * ava_tpl_xcorr: the trace [lags] float64 of every file.
+ *   spec, frame_sum, F    what ava_tpl_spec wrote (F = k1 - k0 rows of `frames` frames)
+ *   frame_off             [files + 1] as above (device)
+ *   lag_off               [files + 1] first lag of each file in the trace (device): n_f - L lags for a file of n_f frames
+ *                         that is segmented, 0 for one that is skipped; lag_off[files] = lags
+ *   tile_off              [files + 1] first workgroup of each file (device): file f has ceil(lags_f / ava_tpl_tile_lags())
+ *                         tiles; tile_off[files] = tiles
+ *   tmpl, template_F, L   the template [template_F][L] float64 (device); template_F must equal F
+ *   trace                 r_i = N_i / (Q_i + 1e-9), N_i = sum T[k,t] (S[k,i+t] - mu_i), Q_i = sum (S[k,i+t] - mu_i)^2,
+ *                         mu_i = the mean of S over frames i..i+L-1 (template_segmentation.py:240-245).  Every lag's
+ *                         sums run in one fixed order: the trace is bit-reproducible and does not depend on the other
+ *                         files of the launch.
+ * All arithmetic is fp64.  Both return AVA_EINVAL before any launch for null pointers, an unsupported nperseg,
+ * noverlap >= nperseg, an empty band, L <= 0, template_F != F or a workspace that is too small. */
+size_t ava_tpl_workspace_bytes(int64_t lags);
+int ava_tpl_tile_lags(void);
+int ava_tpl_spec(const void* audio, int audio_dtype, const int64_t* file_off, const int64_t* file_len,
+                 const int64_t* frame_off, int files, int64_t frames, int nperseg, int noverlap, const double* window,
+                 double scale, int k0, int k1, double spec_min, double spec_max, double* spec, double* frame_sum,
+                 ava_stream_t s);
+int ava_tpl_xcorr(const double* spec, const double* frame_sum, int F, int64_t frames, const int64_t* frame_off,
+                  const int64_t* lag_off, const int64_t* tile_off, int files, int64_t lags, int64_t tiles,
+                  const double* tmpl, int template_F, int L, double* trace, void* ws, size_t ws_bytes, ava_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif
