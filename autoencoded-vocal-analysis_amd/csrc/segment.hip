@@ -5,7 +5,7 @@
 //   bins [searchsorted(f, min_freq), searchsorted(f, max_freq)), clip((log(|X| + 1e-9) - min) / (max - min), 0, 1),
 //   per frame  sum v  or  sum v e / (sum e + 1e-9), e = exp(v / temperature)
 //                                          segmenting/utils.py:22-61, 400-404, amplitude_segmentation.py:63-66
-//                                                                     amp_stft_kernel     (workgroups stride over frames)
+//                                                                     band_stft_kernel    (workgroups stride over frames)
 //   gaussian_filter(amps, smoothing_timescale / dt), mode 'reflect' inside each file, cast to the reference's dtype
 //                                          amplitude_segmentation.py:67                  amp_smooth_kernel   (1 thread / frame)
 //   local maxima above th_3                amplitude_segmentation.py:70-73               amp_maxima_kernel   (1 thread / frame)
@@ -13,6 +13,8 @@
 //                                          amplitude_segmentation.py:79-99               amp_stops_kernel    (1 wave / maximum)
 //
 // The host receives O(#maxima) integers and runs the greedy chain and the duration filter (ava_amd/segment.py).
+// band_stft_kernel in sum mode, with the spectrogram, is also the band stage of the template segmentation (row f6):
+// ava_tpl_spec below; its correlation is template_seg.hip.
 // The spectral arithmetic is fp64 (the transform of stft.h, shared with spec.hip); the trace is stored in the dtype the
 // reference holds it in (float32 for int16 / float32 audio, float64 otherwise), and the decision kernels compare the
 // values of THAT trace, promoted exactly to fp64, against thresholds the host has already rounded the way numpy would
@@ -22,28 +24,29 @@
 #define AVA_AMP_EPS 1e-9
 #define AVA_AMP_T 256
 
-struct AmpArgs {
+struct BandArgs {
   const void* audio;
   const long long* file_off;     // [files] first sample of each file in `audio`
   const long long* file_len;     // [files] samples of each file
   const long long* frame_off;    // [files + 1] first global frame of each file; frame_off[files] = frames
   const double* window;          // [nperseg]
-  double* raw;                   // [frames] per-frame band value before smoothing (workspace)
+  double* raw;                   // [frames] per-frame band value: the sum, or the softmax-weighted value
   double* spec;                  // [k1 - k0][frames] band spectrogram or null
   double scale, spec_min, range, temperature;
   long long frames;
-  int files, nperseg, nstep, k0, k1, softmax, dtype;
+  int files, nperseg, nstep, k0, k1, dtype;
 };
 
 // One workgroup per frame, striding over all frames of all files: the shared transform of stft.h, then the band
 // reduction in a fixed order (thread partial sums, then the waves' shuffles, then the four waves in order):
-// deterministic.
-template <int LOGN>
-__global__ __launch_bounds__(AVA_AMP_T) void amp_stft_kernel(const AmpArgs a) {
+// deterministic.  SOFTMAX is a template parameter, not a flag: the sum-mode instances are spared the exp, the second
+// reduction and their registers.
+template <int LOGN, bool SOFTMAX>
+__global__ __launch_bounds__(AVA_AMP_T) void band_stft_kernel(const BandArgs a) {
   constexpr int N = 1 << LOGN, H = N / 2;
   __shared__ double re[stft_lds(H)], im[stft_lds(H)];
   __shared__ double twr[stft_lds(H)], twi[stft_lds(H)];       // exp(-2 pi i k / N), k < N/2
-  __shared__ double red[2][AVA_AMP_T / 64];
+  __shared__ double red[SOFTMAX ? 2 : 1][AVA_AMP_T / 64];
   const int t = threadIdx.x;
   for (int k = t; k < H; k += AVA_AMP_T) {
     double sn, cs;
@@ -68,7 +71,7 @@ __global__ __launch_bounds__(AVA_AMP_T) void amp_stft_kernel(const AmpArgs a) {
       double v = __ddiv_rn(__dsub_rn(lg, a.spec_min), a.range);
       v = v < 0.0 ? 0.0 : (v > 1.0 ? 1.0 : v);
       if (a.spec != nullptr) a.spec[(size_t)(k - a.k0) * a.frames + g] = v;
-      if (a.softmax) {
+      if constexpr (SOFTMAX) {
         const double e = exp(__ddiv_rn(v, a.temperature));
         s0 = fma(v, e, s0);
         s1 += e;
@@ -77,14 +80,14 @@ __global__ __launch_bounds__(AVA_AMP_T) void amp_stft_kernel(const AmpArgs a) {
       }
     }
     s0 = wave_sum_d(s0);
-    s1 = wave_sum_d(s1);
-    if ((t & 63) == 0) { red[0][t >> 6] = s0; red[1][t >> 6] = s1; }
+    if constexpr (SOFTMAX) s1 = wave_sum_d(s1);
+    if ((t & 63) == 0) { red[0][t >> 6] = s0; if constexpr (SOFTMAX) red[1][t >> 6] = s1; }
     __syncthreads();
     if (t == 0) {
       double v0 = 0.0, v1 = 0.0;
 #pragma unroll
-      for (int w = 0; w < AVA_AMP_T / 64; ++w) { v0 += red[0][w]; v1 += red[1][w]; }
-      a.raw[g] = a.softmax ? __ddiv_rn(v0, __dadd_rn(v1, AVA_AMP_EPS)) : v0;
+      for (int w = 0; w < AVA_AMP_T / 64; ++w) { v0 += red[0][w]; if constexpr (SOFTMAX) v1 += red[1][w]; }
+      a.raw[g] = SOFTMAX ? __ddiv_rn(v0, __dadd_rn(v1, AVA_AMP_EPS)) : v0;
     }
   };
   stft_frames<LOGN, AVA_AMP_T>((long long)blockIdx.x, a.frames, (long long)gridDim.x, a.window, re, im, twr, twi, frame,
@@ -175,6 +178,43 @@ __global__ __launch_bounds__(AVA_AMP_T) void amp_stops_kernel(const V* a, const 
   }
 }
 
+// The band stage of ava_amp_trace and ava_tpl_spec: AVA_EINVAL before any launch for a null pointer, no files or
+// frames, an unsupported nperseg, noverlap >= nperseg, an empty band, an unknown audio dtype or spec_min == spec_max;
+// otherwise band_stft_kernel writes raw (and spec, if not null) on stream st.
+static int band_stft(const void* audio, int audio_dtype, const int64_t* file_off, const int64_t* file_len,
+                     const int64_t* frame_off, int files, int64_t frames, int nperseg, int noverlap,
+                     const double* window, double scale, int k0, int k1, double spec_min, double spec_max, bool softmax,
+                     double temperature, double* raw, double* spec, hipStream_t st) {
+  if (audio == nullptr || file_off == nullptr || file_len == nullptr || frame_off == nullptr || window == nullptr ||
+      raw == nullptr)
+    return AVA_EINVAL;
+  if (files <= 0 || frames <= 0) return AVA_EINVAL;
+  if (nperseg < 64 || nperseg > 2048 || (nperseg & (nperseg - 1)) != 0) return AVA_EINVAL;
+  if (noverlap < 0 || noverlap >= nperseg) return AVA_EINVAL;
+  if (k0 < 0 || k1 <= k0 || k1 > nperseg / 2 + 1) return AVA_EINVAL;             // empty band
+  if (audio_dtype < AVA_AUDIO_I16 || audio_dtype > AVA_AUDIO_F64) return AVA_EINVAL;
+  if (!(spec_max != spec_min)) return AVA_EINVAL;
+  BandArgs a;
+  a.audio = audio;
+  a.file_off = reinterpret_cast<const long long*>(file_off);
+  a.file_len = reinterpret_cast<const long long*>(file_len);
+  a.frame_off = reinterpret_cast<const long long*>(frame_off);
+  a.window = window;
+  a.raw = raw;
+  a.spec = spec;
+  a.scale = scale; a.spec_min = spec_min; a.range = spec_max - spec_min; a.temperature = temperature;
+  a.frames = frames; a.files = files; a.nperseg = nperseg; a.nstep = nperseg - noverlap;
+  a.k0 = k0; a.k1 = k1; a.dtype = audio_dtype;
+  const int grid = frames < 4096 ? (int)frames : 4096;      // workgroups stride over the frames
+  stft_dispatch(nperseg, [&](auto logn) {
+    constexpr int LOGN = decltype(logn)::value;
+    hipLaunchKernelGGL((softmax ? band_stft_kernel<LOGN, true> : band_stft_kernel<LOGN, false>), dim3(grid),
+                       dim3(AVA_AMP_T), 0, st, a);
+  });
+  AVA_CHECK_LAUNCH();
+  return AVA_OK;
+}
+
 extern "C" size_t ava_amp_workspace_bytes(int64_t frames) {
   if (frames <= 0) return 0;
   return 256 + (size_t)frames * sizeof(double);
@@ -185,44 +225,36 @@ extern "C" int ava_amp_trace(const void* audio, int audio_dtype, const int64_t* 
                              const double* window, double scale, int k0, int k1, double spec_min, double spec_max,
                              int softmax, double temperature, const double* gauss_w, int radius, int trace_f64,
                              void* trace, double* spec, void* ws, size_t ws_bytes, ava_stream_t s) {
-  if (audio == nullptr || file_off == nullptr || file_len == nullptr || frame_off == nullptr || window == nullptr ||
-      gauss_w == nullptr || trace == nullptr)
-    return AVA_EINVAL;
-  if (files <= 0 || frames <= 0 || radius < 0) return AVA_EINVAL;
-  if (nperseg < 64 || nperseg > 2048 || (nperseg & (nperseg - 1)) != 0) return AVA_EINVAL;
-  if (noverlap < 0 || noverlap >= nperseg) return AVA_EINVAL;
-  if (k0 < 0 || k1 <= k0 || k1 > nperseg / 2 + 1) return AVA_EINVAL;             // empty band
-  if (audio_dtype < AVA_AUDIO_I16 || audio_dtype > AVA_AUDIO_F64) return AVA_EINVAL;
-  if (!(spec_max != spec_min) || (softmax && !(temperature != 0.0))) return AVA_EINVAL;
+  if (gauss_w == nullptr || trace == nullptr || radius < 0) return AVA_EINVAL;
+  if (softmax && !(temperature != 0.0)) return AVA_EINVAL;
   if (ws == nullptr || ws_bytes < ava_amp_workspace_bytes(frames)) return AVA_EINVAL;
-  AmpArgs a;
-  a.audio = audio;
-  a.file_off = reinterpret_cast<const long long*>(file_off);
-  a.file_len = reinterpret_cast<const long long*>(file_len);
-  a.frame_off = reinterpret_cast<const long long*>(frame_off);
-  a.window = window;
   char* base = reinterpret_cast<char*>(ws);
   base += (256 - (reinterpret_cast<uintptr_t>(base) & 255)) & 255;
-  a.raw = reinterpret_cast<double*>(base);
-  a.spec = spec;
-  a.scale = scale; a.spec_min = spec_min; a.range = spec_max - spec_min; a.temperature = temperature;
-  a.frames = frames; a.files = files; a.nperseg = nperseg; a.nstep = nperseg - noverlap;
-  a.k0 = k0; a.k1 = k1; a.softmax = softmax ? 1 : 0; a.dtype = audio_dtype;
+  double* raw = reinterpret_cast<double*>(base);
   hipStream_t st = to_stream(s);
-  const int grid = frames < 4096 ? (int)frames : 4096;      // workgroups stride over the frames
-  stft_dispatch(nperseg, [&](auto logn) {
-    hipLaunchKernelGGL(amp_stft_kernel<decltype(logn)::value>, dim3(grid), dim3(AVA_AMP_T), 0, st, a);
-  });
-  AVA_CHECK_LAUNCH();
+  const int rc = band_stft(audio, audio_dtype, file_off, file_len, frame_off, files, frames, nperseg, noverlap, window,
+                           scale, k0, k1, spec_min, spec_max, softmax != 0, temperature, raw, spec, st);
+  if (rc != AVA_OK) return rc;
+  const long long* fo = reinterpret_cast<const long long*>(frame_off);
   const dim3 sgrid((unsigned)ceil_div64(frames, AVA_AMP_T));
   if (trace_f64)
-    hipLaunchKernelGGL(amp_smooth_kernel<double>, sgrid, dim3(AVA_AMP_T), 0, st, a.raw, a.frame_off, files, frames,
-                       gauss_w, radius, reinterpret_cast<double*>(trace));
+    hipLaunchKernelGGL(amp_smooth_kernel<double>, sgrid, dim3(AVA_AMP_T), 0, st, raw, fo, files, frames, gauss_w,
+                       radius, reinterpret_cast<double*>(trace));
   else
-    hipLaunchKernelGGL(amp_smooth_kernel<float>, sgrid, dim3(AVA_AMP_T), 0, st, a.raw, a.frame_off, files, frames,
-                       gauss_w, radius, reinterpret_cast<float*>(trace));
+    hipLaunchKernelGGL(amp_smooth_kernel<float>, sgrid, dim3(AVA_AMP_T), 0, st, raw, fo, files, frames, gauss_w,
+                       radius, reinterpret_cast<float*>(trace));
   AVA_CHECK_LAUNCH();
   return AVA_OK;
+}
+
+// ava_amp_trace's band stage in sum mode, without smoothing: the spectrogram and the raw band sums
+extern "C" int ava_tpl_spec(const void* audio, int audio_dtype, const int64_t* file_off, const int64_t* file_len,
+                            const int64_t* frame_off, int files, int64_t frames, int nperseg, int noverlap,
+                            const double* window, double scale, int k0, int k1, double spec_min, double spec_max,
+                            double* spec, double* frame_sum, ava_stream_t s) {
+  if (spec == nullptr) return AVA_EINVAL;
+  return band_stft(audio, audio_dtype, file_off, file_len, frame_off, files, frames, nperseg, noverlap, window, scale,
+                   k0, k1, spec_min, spec_max, false, 1.0, frame_sum, spec, to_stream(s));
 }
 
 extern "C" int ava_amp_decide(const void* trace, int trace_f64, const int64_t* frame_off, int files, int64_t frames,

@@ -1,10 +1,8 @@
 // Template segmentation on the device: the arithmetic core of
 // ava/segmenting/template_segmentation.py:_segment_file for every recording of a DeviceAudio at once.
 //
-//   _get_spec (lines 758-790, = segmenting/utils.py:get_spec): scipy.signal.stft of the whole file (hann, zero boundary,
-//   zero padded to whole hops, 'spectrum' scaling), bins [searchsorted(f, min_freq), searchsorted(f, max_freq)),
-//   clip((log(|X| + 1e-9) - min) / (max - min), 0, 1); plus the sum of every frame over the band
-//                                                                   tpl_spec_kernel   (workgroups stride over frames)
+//   _get_spec (lines 758-790, = segmenting/utils.py:get_spec): the band spectrogram of the whole file and the sum of
+//   every frame over the band: the amplitude segmentation's band stage in sum mode (ava_tpl_spec, segment.hip)
 //   the normalised cross-correlation (lines 240-245) of file f at lags i = 0 .. n_f - L - 1:
 //     mu_i = sum_{t<L} framesum[i + t] / (F L)                      tpl_mean_kernel   (1 thread / lag)
 //     N_i  = sum_{k<F, t<L} T[k, t] (S[k, i + t] - mu_i),  Q_i = sum (S[k, i + t] - mu_i)^2,  r_i = N_i / (Q_i + 1e-9)
@@ -19,7 +17,7 @@
 #include "stft.h"
 
 #define AVA_TPL_EPS 1e-9
-#define AVA_TPL_T 256            // threads of the spectrogram and mean kernels
+#define AVA_TPL_T 256            // threads of the mean kernel
 
 // Correlation tiles.  A workgroup of XT threads owns TILE = XT * R consecutive lags of one
 // file; thread x owns lags R x .. R x + R - 1, so every spectrogram value it reads from LDS serves R lags (a sliding
@@ -35,67 +33,6 @@
 #define AVA_TPL_WR ((AVA_TPL_TILE + AVA_TPL_LC) / AVA_TPL_R + 4)
 static_assert(AVA_TPL_LC % AVA_TPL_R == 0, "frame chunks hold whole register windows");
 static_assert(AVA_TPL_WR % 16 == 4, "conflict-free staging stores");
-
-struct TplSpecArgs {
-  const void* audio;
-  const long long* file_off;     // [files] first sample of each file in `audio`
-  const long long* file_len;     // [files] samples of each file
-  const long long* frame_off;    // [files + 1] first global frame of each file; frame_off[files] = frames
-  const double* window;          // [nperseg]
-  double* spec;                  // [k1 - k0][frames] band spectrogram
-  double* frame_sum;             // [frames] sum of spec over the band
-  double scale, spec_min, range;
-  long long frames;
-  int files, nstep, k0, k1, dtype;
-};
-
-// One workgroup per frame, striding over all frames of all files: the shared transform of stft.h, the clipped band
-// values, and their sum in a fixed order (thread partial sums, the waves' shuffles, the four waves in order).
-template <int LOGN>
-__global__ __launch_bounds__(AVA_TPL_T) void tpl_spec_kernel(const TplSpecArgs a) {
-  constexpr int N = 1 << LOGN, H = N / 2;
-  __shared__ double re[stft_lds(H)], im[stft_lds(H)];
-  __shared__ double twr[stft_lds(H)], twi[stft_lds(H)];       // exp(-2 pi i k / N), k < N/2
-  __shared__ double red[AVA_TPL_T / 64];
-  const int t = threadIdx.x;
-  for (int k = t; k < H; k += AVA_TPL_T) {
-    double sn, cs;
-    sincospi(-2.0 * (double)k / (double)N, &sn, &cs);
-    twr[stft_pd(k)] = cs;
-    twi[stft_pd(k)] = sn;
-  }
-  auto frame = [&](long long g) {                             // global frame g: a frame of its file
-    const int f = stft_file_of(a.frame_off, a.files, g);
-    const long long c = (g - a.frame_off[f]) * a.nstep, len = a.file_len[f], base = a.file_off[f];
-    return [&a, c, len, base](long long p, bool live) {
-      const long long idx = c + p;
-      const bool in = live && idx >= 0 && idx < len;
-      const double x = audio_at(a.audio, a.dtype, base + (in ? idx : 0));
-      return in ? x : 0.0;
-    };
-  };
-  auto band = [&](long long g) {                              // the kept bins k0 <= k < k1 (<= H)
-    double s = 0.0;
-    for (int k = a.k0 + t; k < a.k1; k += AVA_TPL_T) {
-      const double lg = stft_logmag(stft_bin<LOGN>(k, re, im, twr, twi), a.scale, AVA_TPL_EPS);
-      double v = __ddiv_rn(__dsub_rn(lg, a.spec_min), a.range);
-      v = v < 0.0 ? 0.0 : (v > 1.0 ? 1.0 : v);
-      a.spec[(size_t)(k - a.k0) * a.frames + g] = v;
-      s += v;
-    }
-    s = wave_sum_d(s);
-    if ((t & 63) == 0) red[t >> 6] = s;
-    __syncthreads();
-    if (t == 0) {
-      double v = 0.0;
-#pragma unroll
-      for (int w = 0; w < AVA_TPL_T / 64; ++w) v += red[w];
-      a.frame_sum[g] = v;
-    }
-  };
-  stft_frames<LOGN, AVA_TPL_T>((long long)blockIdx.x, a.frames, (long long)gridDim.x, a.window, re, im, twr, twi, frame,
-                               band);
-}
 
 struct TplXcorrArgs {
   const double* spec;            // [F][frames]
@@ -197,38 +134,6 @@ extern "C" size_t ava_tpl_workspace_bytes(int64_t lags) {
 }
 
 extern "C" int ava_tpl_tile_lags(void) { return AVA_TPL_TILE; }
-
-extern "C" int ava_tpl_spec(const void* audio, int audio_dtype, const int64_t* file_off, const int64_t* file_len,
-                            const int64_t* frame_off, int files, int64_t frames, int nperseg, int noverlap,
-                            const double* window, double scale, int k0, int k1, double spec_min, double spec_max,
-                            double* spec, double* frame_sum, ava_stream_t s) {
-  if (audio == nullptr || file_off == nullptr || file_len == nullptr || frame_off == nullptr || window == nullptr ||
-      spec == nullptr || frame_sum == nullptr)
-    return AVA_EINVAL;
-  if (files <= 0 || frames <= 0) return AVA_EINVAL;
-  if (nperseg < 64 || nperseg > 2048 || (nperseg & (nperseg - 1)) != 0) return AVA_EINVAL;
-  if (noverlap < 0 || noverlap >= nperseg) return AVA_EINVAL;
-  if (k0 < 0 || k1 <= k0 || k1 > nperseg / 2 + 1) return AVA_EINVAL;             // empty band
-  if (audio_dtype < AVA_AUDIO_I16 || audio_dtype > AVA_AUDIO_F64) return AVA_EINVAL;
-  if (!(spec_max != spec_min)) return AVA_EINVAL;
-  TplSpecArgs a;
-  a.audio = audio;
-  a.file_off = reinterpret_cast<const long long*>(file_off);
-  a.file_len = reinterpret_cast<const long long*>(file_len);
-  a.frame_off = reinterpret_cast<const long long*>(frame_off);
-  a.window = window;
-  a.spec = spec;
-  a.frame_sum = frame_sum;
-  a.scale = scale; a.spec_min = spec_min; a.range = spec_max - spec_min;
-  a.frames = frames; a.files = files; a.nstep = nperseg - noverlap;
-  a.k0 = k0; a.k1 = k1; a.dtype = audio_dtype;
-  const int grid = frames < 4096 ? (int)frames : 4096;      // workgroups stride over the frames
-  stft_dispatch(nperseg, [&](auto logn) {
-    hipLaunchKernelGGL(tpl_spec_kernel<decltype(logn)::value>, dim3(grid), dim3(AVA_TPL_T), 0, to_stream(s), a);
-  });
-  AVA_CHECK_LAUNCH();
-  return AVA_OK;
-}
 
 extern "C" int ava_tpl_xcorr(const double* spec, const double* frame_sum, int F, int64_t frames,
                              const int64_t* frame_off, const int64_t* lag_off, const int64_t* tile_off, int files,

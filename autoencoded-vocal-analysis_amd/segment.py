@@ -40,7 +40,7 @@ DEFAULT_CHUNK_BYTES = 1 << 30        # audio bytes per batch of segment()
 
 def _check_shape(nperseg, noverlap):
     if nperseg < 64 or nperseg > 2048 or nperseg & (nperseg - 1) or not 0 <= noverlap < nperseg:
-        raise NotImplementedError("device amplitude segmentation needs nperseg a power of two in 64..2048 and "
+        raise NotImplementedError("device segmentation needs nperseg a power of two in 64..2048 and "
                                   "0 <= noverlap < nperseg (got %d, %d)" % (nperseg, noverlap))
 
 
@@ -63,6 +63,25 @@ def band_indices(p):
     """(i1, i2, f): the kept bins [i1, i2) of rfftfreq(nperseg, 1 / fs) (segmenting/utils.py:54-56)"""
     f = np.fft.rfftfreq(int(p['nperseg']), 1 / p['fs'])
     return int(np.searchsorted(f, p['min_freq'])), int(np.searchsorted(f, p['max_freq'])), f
+
+
+def _band_params(p):
+    """(nperseg, noverlap, i1, i2) of the band stage shared with template_segmentation, checked before any device
+    work: the shape, then the band, then spec_min_val != spec_max_val"""
+    nperseg, noverlap = int(p['nperseg']), int(p['noverlap'])
+    _check_shape(nperseg, noverlap)
+    i1, i2, _ = band_indices(p)
+    if i2 <= i1:
+        raise ValueError("empty frequency band [%s, %s)" % (p['min_freq'], p['max_freq']))
+    if not np.isfinite(float(p['spec_max_val']) - float(p['spec_min_val'])) or p['spec_max_val'] == p['spec_min_val']:
+        raise ValueError("spec_max_val must differ from spec_min_val")
+    return nperseg, noverlap, i1, i2
+
+
+def _frame_offsets(lengths, nperseg, noverlap):
+    """(frames of each file, frame_off [files + 1]: first global frame of each file) for files of these lengths"""
+    T = frame_count(lengths, nperseg, noverlap)
+    return T, np.concatenate([[0], np.cumsum(T)]).astype(np.int64)
 
 
 def gaussian_weights(sigma, truncate=4.0):
@@ -123,20 +142,14 @@ def duration_filter(onsets, offsets, dt, p):
 def _trace(audio, frame_off, p, dt, want_spec=False):
     """the smoothed trace [frames] (torch, reference dtype) of every file of ``audio`` and the band spectrogram
     [F, frames] (float64) with ``want_spec``"""
-    nperseg, noverlap = int(p['nperseg']), int(p['noverlap'])
-    _check_shape(nperseg, noverlap)
-    i1, i2, _ = band_indices(p)
-    if i2 <= i1:
-        raise ValueError("empty frequency band [%s, %s)" % (p['min_freq'], p['max_freq']))
-    lib, dev = _lib.load(), audio.device
-    frames = int(frame_off[-1])
-    window, scale = _stft_constants(nperseg, dev)
+    nperseg, noverlap, i1, i2 = _band_params(p)
     softmax = bool(p.get('softmax', False))
     temperature = float(p['temperature']) if softmax else 1.0
     if softmax and temperature == 0.0:
         raise ZeroDivisionError("softmax temperature 0")
-    if not np.isfinite(float(p['spec_max_val']) - float(p['spec_min_val'])) or p['spec_max_val'] == p['spec_min_val']:
-        raise ValueError("spec_max_val must differ from spec_min_val")
+    lib, dev = _lib.load(), audio.device
+    frames = int(frame_off[-1])
+    window, scale = _stft_constants(nperseg, dev)
     sigma = p['smoothing_timescale'] / dt if 'smoothing_timescale' in p else 0.0
     w, radius = gaussian_weights(sigma)
     tdt = trace_dtype(audio.dtype)
@@ -185,8 +198,7 @@ def get_onsets_offsets_batch(device_audio, p, return_traces=False):
     or ``(onsets, offsets, [amps])`` with ``return_traces`` (``([], [], None)`` for files shorter than nperseg)."""
     nperseg, noverlap = int(p['nperseg']), int(p['noverlap'])
     _check_shape(nperseg, noverlap)
-    T = frame_count(device_audio.lengths, nperseg, noverlap)
-    frame_off = np.concatenate([[0], np.cumsum(T)]).astype(np.int64)
+    T, frame_off = _frame_offsets(device_audio.lengths, nperseg, noverlap)
     dt = frame_step(p['fs'], nperseg, noverlap)
     results = [([], [], None) if return_traces else ([], []) for _ in range(len(T))]
     if frame_off[-1] == 0:
@@ -241,7 +253,7 @@ def get_spec(audio, p):
     assert len(audio) >= p['nperseg'], "len(audio): " + str(len(audio)) + ", nperseg: " + str(p['nperseg'])
     nperseg, noverlap = int(p['nperseg']), int(p['noverlap'])
     dev_audio = DeviceAudio([audio])
-    frame_off = np.array([0, int(frame_count(len(audio), nperseg, noverlap))], dtype=np.int64)
+    _, frame_off = _frame_offsets([len(audio)], nperseg, noverlap)
     dt = frame_step(p['fs'], nperseg, noverlap)
     q = {k: p[k] for k in ('fs', 'nperseg', 'noverlap', 'min_freq', 'max_freq', 'spec_min_val', 'spec_max_val')}
     _, _, spec = _trace(dev_audio, frame_off, q, dt, want_spec=True)
@@ -262,6 +274,29 @@ def _is_amplitude_segmentation(fn):
                                         and getattr(fn, '__name__', None) == 'get_onsets_offsets')
 
 
+def _read_wav(fn):
+    """``scipy.io.wavfile.read(fn)``: (fs, samples), its WavFileWarning silenced"""
+    from scipy.io import wavfile
+    from scipy.io.wavfile import WavFileWarning
+    with warnings.catch_warnings():
+        warnings.filterwarnings("ignore", category=WavFileWarning)
+        return wavfile.read(fn)
+
+
+def _chunks(files, max_bytes):
+    """groups of the (index, samples) pairs of ``files``, in order: a new group starts where the group would exceed
+    ``max_bytes`` of audio or the dtype changes (a larger file is a group of its own); no group is empty"""
+    chunk, nbytes = [], 0
+    for i, audio in files:
+        if chunk and (nbytes + audio.nbytes > max_bytes or audio.dtype != chunk[0][1].dtype):
+            yield chunk
+            chunk, nbytes = [], 0
+        chunk.append((i, audio))
+        nbytes += audio.nbytes
+    if chunk:
+        yield chunk
+
+
 def _write(audio_fn, seg_fn, onsets, offsets):
     combined = np.stack([onsets, offsets]).T
     header = "Onsets/offsets for " + audio_fn
@@ -275,40 +310,21 @@ def segment(audio_dir, seg_dir, p, verbose=True, max_chunk_bytes=DEFAULT_CHUNK_B
     function or this module's), the files go through ``get_onsets_offsets_batch`` in chunks of at most
     ``max_chunk_bytes`` of audio (a file larger than that is a chunk of its own; files of different dtypes are never
     mixed); otherwise ``p['algorithm']`` is called per file.  The output does not depend on the chunking."""
-    from scipy.io import wavfile
-    from scipy.io.wavfile import WavFileWarning
     if verbose:
         print("Segmenting audio in", audio_dir)
     if not os.path.exists(seg_dir):
         os.makedirs(seg_dir)
     num_sylls = 0
     audio_fns, seg_fns = _audio_seg_filenames(audio_dir, seg_dir)
-
-    def read(fn):
-        with warnings.catch_warnings():
-            warnings.filterwarnings("ignore", category=WavFileWarning)
-            return wavfile.read(fn)[1]
-
     if not _is_amplitude_segmentation(p['algorithm']):
         for audio_fn, seg_fn in zip(audio_fns, seg_fns):
-            onsets, offsets = p['algorithm'](read(audio_fn), p)
+            onsets, offsets = p['algorithm'](_read_wav(audio_fn)[1], p)
             num_sylls += _write(audio_fn, seg_fn, onsets, offsets)
     else:
-        chunk, nbytes = [], 0
-
-        def flush():
+        files = ((i, _read_wav(fn)[1]) for i, fn in enumerate(audio_fns))
+        for chunk in _chunks(files, max_chunk_bytes):
             res = get_onsets_offsets_batch(DeviceAudio([a for _, a in chunk], device), p)
-            return sum(_write(audio_fns[i], seg_fns[i], on, off) for (i, _), (on, off) in zip(chunk, res))
-
-        for i, audio_fn in enumerate(audio_fns):
-            audio = read(audio_fn)
-            if chunk and (nbytes + audio.nbytes > max_chunk_bytes or audio.dtype != chunk[0][1].dtype):
-                num_sylls += flush()
-                chunk, nbytes = [], 0
-            chunk.append((i, audio))
-            nbytes += audio.nbytes
-        if chunk:
-            num_sylls += flush()
+            num_sylls += sum(_write(audio_fns[i], seg_fns[i], on, off) for (i, _), (on, off) in zip(chunk, res))
     if verbose:
         print("\tFound", num_sylls, "segments in", audio_dir)
 

@@ -13,10 +13,10 @@ Mirror of the computational surface of ava/segmenting/template_segmentation.py, 
   ``install``                  points the reference module's ``get_template``, ``segment_files``, ``_segment_file`` here
 
 The band spectrogram of whole files (``_get_spec``, lines 758-790) and the correlation with the template run on the
-device in fp64 (``csrc/template_seg.hip``); the host receives the fp64 trace and runs the threshold, the maxima and
-``_clean_max_indices`` on it (O(lags) per file, vectorised numpy).  The template's smoothing, truncation, mean and
-normalisation are the reference's own numpy calls on a few F x L arrays.  Unlike the reference, this module imports
-without affinewarp, umap, h5py or bokeh.
+device in fp64 (the band kernel of ``csrc/segment.hip`` in sum mode, then ``csrc/template_seg.hip``); the host
+receives the fp64 trace and runs the threshold, the maxima and ``_clean_max_indices`` on it (O(lags) per file,
+vectorised numpy).  The template's smoothing, truncation, mean and normalisation are the reference's own numpy calls
+on a few F x L arrays.  Unlike the reference, this module imports without affinewarp, umap, h5py or bokeh.
 
 ``nperseg`` must be a power of two in 64..2048; other lengths raise ``NotImplementedError``.  There is no CPU fallback.
 """
@@ -38,22 +38,12 @@ EPSILON = 1e-9                       # template_segmentation.py:31
 DEFAULT_CHUNK_BYTES = 1 << 30        # audio bytes per batch of segment_files()
 
 
-def _check_shape(nperseg, noverlap):
-    if nperseg < 64 or nperseg > 2048 or nperseg & (nperseg - 1) or not 0 <= noverlap < nperseg:
-        raise NotImplementedError("device template segmentation needs nperseg a power of two in 64..2048 and "
-                                  "0 <= noverlap < nperseg (got %d, %d)" % (nperseg, noverlap))
-
-
 def _is_wav_file(filename):
     return len(filename) > 4 and filename[-4:] == '.wav'
 
 
 def _read(filename, p):
-    from scipy.io import wavfile
-    from scipy.io.wavfile import WavFileWarning
-    with warnings.catch_warnings():
-        warnings.filterwarnings("ignore", category=WavFileWarning)
-        fs, audio = wavfile.read(filename)
+    fs, audio = _seg._read_wav(filename)
     assert fs == p['fs'], "Found samplerate=" + str(fs) + ", expected " + str(p['fs'])
     return audio
 
@@ -63,15 +53,8 @@ def _read(filename, p):
 def _band(device_audio, p):
     """(spec [F, frames] float64, frame sums [frames], frame_off device, frame_off host, frames per file) of every file;
     spec is None when no file reaches nperseg samples"""
-    nperseg, noverlap = int(p['nperseg']), int(p['noverlap'])
-    _check_shape(nperseg, noverlap)
-    i1, i2, _ = _seg.band_indices(p)
-    if i2 <= i1:
-        raise ValueError("empty frequency band [%s, %s)" % (p['min_freq'], p['max_freq']))
-    if not np.isfinite(float(p['spec_max_val']) - float(p['spec_min_val'])) or p['spec_max_val'] == p['spec_min_val']:
-        raise ValueError("spec_max_val must differ from spec_min_val")
-    T = _seg.frame_count(device_audio.lengths, nperseg, noverlap)
-    frame_off = np.concatenate([[0], np.cumsum(T)]).astype(np.int64)
+    nperseg, noverlap, i1, i2 = _seg._band_params(p)
+    T, frame_off = _seg._frame_offsets(device_audio.lengths, nperseg, noverlap)
     frames = int(frame_off[-1])
     dev = device_audio.device
     fo = torch.from_numpy(frame_off).to(dev)
@@ -280,22 +263,11 @@ def segment_files(audio_dirs, segment_dirs, template, p, num_mad=2.0, min_dt=0.0
     if verbose:
         print("Segmenting files. n =", len(all_audio_fns))
     res = []
-    chunk, nbytes = [], 0
-
-    def flush():
+    files = ((i, _read(fn, p)) for i, fn in enumerate(all_audio_fns))
+    for chunk in _seg._chunks(files, max_chunk_bytes):
         segs = segment_batch(DeviceAudio([a for _, a in chunk], device), template, p, num_mad=num_mad, min_dt=min_dt,
                              names=[all_audio_fns[i] for i, _ in chunk])
         res.extend((all_seg_dirs[i], all_audio_fns[i], s) for (i, _), s in zip(chunk, segs))
-
-    for i, audio_fn in enumerate(all_audio_fns):
-        audio = _read(audio_fn, p)
-        if chunk and (nbytes + audio.nbytes > max_chunk_bytes or audio.dtype != chunk[0][1].dtype):
-            flush()
-            chunk, nbytes = [], 0
-        chunk.append((i, audio))
-        nbytes += audio.nbytes
-    if chunk:
-        flush()
     result = {}
     num_segments = 0
     for segment_dir, audio_fn, segments in res:

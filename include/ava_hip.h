@@ -372,7 +372,7 @@ int ava_amp_decide(const void* trace, int trace_f64, const int64_t* frame_off, i
  * ava_tpl_workspace_bytes: scratch ava_tpl_xcorr needs for `lags` lags in all (0 for lags <= 0).
  * ava_tpl_tile_lags: lags per correlation tile; the caller sizes tile_off with it.
  *
- * ava_tpl_spec: the band spectrogram and its per-frame sums.
+ * ava_tpl_spec: the band spectrogram and its per-frame sums: ava_amp_trace's band stage in sum mode, without smoothing.
  *   audio ... frame_off   as ava_amp_trace (0 = int16, 1 = int32, 2 = float32, 3 = float64; frame_off [files + 1])
  *   nperseg, noverlap     a power of two in 64..2048, 0 <= noverlap < nperseg
  *   window, scale         get_window('hann', nperseg) (device), 1 / sum(window): 'spectrum' scaling; no detrend

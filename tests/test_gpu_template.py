@@ -202,6 +202,28 @@ def test_sizes_without_golden_match_numpy(nperseg, L, full_band):
         assert F == nperseg // 2 + 1
 
 
+@pytest.mark.parametrize("dtype", [np.int16, np.float64])
+@pytest.mark.parametrize("nperseg", [256, 1024])
+def test_band_stage_is_the_amplitude_band_stage(dtype, nperseg):
+    # ava_tpl_spec is ava_amp_trace's band stage in sum mode: the same fp64 spectrogram, bit for bit.  Without
+    # smoothing_timescale the amplitude trace is the raw band sum (radius 0, weights {1}); for float64 audio it is
+    # stored unrounded, so it equals the template path's frame sums bit for bit too.
+    from ava_amd import synthetic as syn
+    shift = TC.LOG_INT16_SCALE if dtype == np.float64 else 0.0
+    p = dict(TC.FINCH, nperseg=nperseg, noverlap=nperseg // 3, spec_min_val=TC.FINCH['spec_min_val'] - shift,
+             spec_max_val=TC.FINCH['spec_max_val'] - shift)
+    _, songs, _ = syn.songs(n_songs=3, seconds=2.0, dtype=dtype)
+    dev = DeviceAudio(songs + [songs[0][:nperseg // 2]])                     # a file without frames among them
+    spec, fsum, _, frame_off, _ = TS._band(dev, p)
+    trace, _, aspec = S._trace(dev, frame_off, p, S.frame_step(p['fs'], nperseg, p['noverlap']), want_spec=True)
+    spec, aspec = spec.cpu().numpy(), aspec.cpu().numpy()
+    assert spec.shape == aspec.shape and spec.shape[1] == frame_off[-1] > 0
+    assert np.array_equal(spec, aspec)
+    if dtype == np.float64:
+        assert trace.dtype == torch.float64
+        assert np.array_equal(fsum.cpu().numpy(), trace.cpu().numpy())
+
+
 def test_template_band_mismatch_raises(golden):
     cases, _ = golden
     c = cases['songs_int16_512']

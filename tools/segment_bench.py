@@ -41,8 +41,7 @@ def main():
     torch.cuda.synchronize()
     upload = time.perf_counter() - t0
 
-    T = S.frame_count(dev.lengths, p['nperseg'], p['noverlap'])
-    frame_off = np.concatenate([[0], np.cumsum(T)]).astype(np.int64)
+    _, frame_off = S._frame_offsets(dev.lengths, p['nperseg'], p['noverlap'])
     frames = int(frame_off[-1])
     dt = S.frame_step(fs, p['nperseg'], p['noverlap'])
 
