@@ -115,22 +115,6 @@ int ava_conv3x3_thin(const ConvArgs& a, int grid, int Cin, int Cout, int mode, i
 int ava_conv3x3_wgrad_thin(const WgradArgs& a, int grid, int Cin, int Cout, int mode, int dy_pro, hipStream_t st);
 int ava_conv3x3_wgrad_thin_rows(const WgradArgs& a, int grid, int Cin, int Cout, int mode);
 
-#ifdef AVA_LAB
-// lab build: AVA_CONV_IMPL=valu forces the version-0 VALU kernels (lab/conv_valu.hip) everywhere
-int ava_conv3x3_valu(const ConvArgs& a, int grid, int Cin, int Cout, int mode, int pro, int epi, int tw, hipStream_t st);
-int ava_conv3x3_wgrad_valu(const WgradArgs& a, int grid, int Cin, int Cout, int mode, int dy_pro, int tw, hipStream_t st);
-static bool use_mfma() {
-  static int cached = -1;
-  if (cached < 0) {
-    const char* e = ava_env("AVA_CONV_IMPL");
-    cached = (e != nullptr && strcmp(e, "valu") == 0) ? 0 : 1;
-  }
-  return cached == 1;
-}
-#else
-static constexpr bool use_mfma() { return true; }
-#endif
-
 static int tile_w(int Wo) { return Wo >= 32 ? 32 : 16; }
 
 static int conv_geometry(int B, int Ho, int Wo, int* tiles_y, int* tiles_x) {
@@ -181,10 +165,6 @@ int ava_conv3x3_ex(const float* in, const float* in2, const float* pa, const flo
                    int Cout, int mode, int pro, int epi, int relu, float prec, int act_bf16, const ConvAcc* acc,
                    ava_stream_t s) {
   ConvArgs a;
-#ifdef AVA_LAB
-  a.stamps = nullptr;
-#endif
-  a.rc = acc != nullptr ? acc->rc : RecompArgs{};
   a.fold = acc != nullptr ? acc->fold : ThinFold{};
   a.act_bf16 = act_bf16;
   a.acc_out = acc != nullptr ? acc->acc_out : nullptr;
@@ -193,7 +173,6 @@ int ava_conv3x3_ex(const float* in, const float* in2, const float* pa, const flo
   a.in = in; a.in2 = in2; a.pa = pa; a.pb = pb; a.pc = pc; a.G = G; a.bias = bias; a.out = out; a.out2 = out2;
   a.epi_x = epi_x; a.epi_mean = epi_mean; a.epi_invstd = epi_invstd; a.partials = partials;
   a.B = B; a.Hi = Hi; a.Wi = Wi; a.relu = relu; a.prec = prec;
-  { static int dbg = -1; if (dbg < 0) { const char* e = ava_env("AVA_DBG"); dbg = e ? atoi(e) : 0; } a.dbg = dbg; }
   a.Ho = mode == MODE_S1 ? Hi : (mode == MODE_DOWN ? Hi / 2 : Hi * 2);
   a.Wo = mode == MODE_S1 ? Wi : (mode == MODE_DOWN ? Wi / 2 : Wi * 2);
   a.ntiles = conv_geometry(B, a.Ho, a.Wo, &a.tiles_y, &a.tiles_x);
@@ -202,22 +181,16 @@ int ava_conv3x3_ex(const float* in, const float* in2, const float* pa, const flo
   if (pro == PRO_BWD && in2 == nullptr) return AVA_EINVAL;
   const int grid = 2 * a.ntiles < 1024 ? 2 * a.ntiles : 1024;     // == ava_conv_grid
   a.part_rows = grid;
-  const int tw = tile_w(a.Wo);
   hipStream_t st = to_stream(s);
-  if (use_mfma() && epi != EPI_SSE) {
+  if (epi != EPI_SSE) {
     const int rc = ava_conv3x3_mfma(a, grid, Cin, Cout, mode, pro, epi, st);
     if (rc != AVA_EINVAL) return rc;       // AVA_EINVAL: no matrix-core instantiation for this shape
   }
-  if (use_mfma()) {                        // single-channel layers at 128x128: dedicated VALU kernels
+  {                                        // single-channel layers at 128x128: dedicated VALU kernels
     const int rc = ava_conv3x3_thin(a, grid, Cin, Cout, mode, pro, epi, st);
     if (rc != AVA_EINVAL) return rc;
   }
-#ifdef AVA_LAB
-  return ava_conv3x3_valu(a, grid, Cin, Cout, mode, pro, epi, tw, st);
-#else
-  (void)tw;
   return AVA_EINVAL;                       // no kernel for this (Cin, Cout, mode, size)
-#endif
 }
 
 int ava_conv3x3_wgrad_ex(const float* x, const float* xa, const float* xb, const float* dy, const float* dy2,
@@ -241,20 +214,10 @@ int ava_conv3x3_wgrad_ex(const float* x, const float* xa, const float* xb, const
   if (a.ntiles <= 0 || x == nullptr || dy == nullptr || partials == nullptr) return AVA_EINVAL;
   if (dy_pro == PRO_BWD && dy2 == nullptr) return AVA_EINVAL;
   const int grid = 2 * a.ntiles < 512 ? 2 * a.ntiles : 512;   // == ava_conv_wgrad_grid; the matrix-core kernels may launch fewer
-  const int tw = tile_w(a.Wo);
   hipStream_t st = to_stream(s);
-  if (use_mfma()) {
-    int rc = ava_conv3x3_wgrad_mfma(a, grid, Cin, Cout, mode, dy_pro, st);
-    if (rc != AVA_EINVAL) return rc;
-    rc = ava_conv3x3_wgrad_thin(a, grid, Cin, Cout, mode, dy_pro, st);
-    if (rc != AVA_EINVAL) return rc;
-  }
-#ifdef AVA_LAB
-  return ava_conv3x3_wgrad_valu(a, grid, Cin, Cout, mode, dy_pro, tw, st);
-#else
-  (void)tw;
-  return AVA_EINVAL;
-#endif
+  const int rc = ava_conv3x3_wgrad_mfma(a, grid, Cin, Cout, mode, dy_pro, st);
+  if (rc != AVA_EINVAL) return rc;
+  return ava_conv3x3_wgrad_thin(a, grid, Cin, Cout, mode, dy_pro, st);
 }
 
 // Two layers' weight gradients in one launch where a pair kernel exists (conv_mfma.hip: the 16 x 16 layers), otherwise
@@ -262,30 +225,27 @@ int ava_conv3x3_wgrad_ex(const float* x, const float* xa, const float* xb, const
 int ava_conv3x3_wgrad_mfma_pair(const WgradArgs& a, int grid_a, const WgradCall& ca, const WgradArgs& b, int grid_b,
                                 const WgradCall& cb, hipStream_t st);
 int ava_conv3x3_wgrad_pair(const WgradCall& p, const WgradCall& q, int B, int act_bf16, ava_stream_t s) {
-  static const bool on = [] { const char* e = ava_env("AVA_WGRAD_PAIR"); return e == nullptr || atoi(e) != 0; }();
-  if (on && use_mfma()) {
-    WgradArgs w[2];
-    int grid[2];
-    const WgradCall* c[2] = {&p, &q};
-    bool ok = true;
-    for (int i = 0; i < 2 && ok; ++i) {
-      WgradArgs& a = w[i];
-      a.act_bf16 = act_bf16;
-      a.x = c[i]->x; a.xa = c[i]->xa; a.xb = c[i]->xb; a.dy = c[i]->dy; a.dy2 = c[i]->dy2;
-      a.da = c[i]->da; a.db = c[i]->db; a.dc = c[i]->dc; a.partials = c[i]->partials;
-      a.B = B; a.Hi = c[i]->Hi; a.Wi = c[i]->Wi;
-      const int mode = c[i]->mode;
-      a.Ho = mode == MODE_S1 ? a.Hi : (mode == MODE_DOWN ? a.Hi / 2 : a.Hi * 2);
-      a.Wo = mode == MODE_S1 ? a.Wi : (mode == MODE_DOWN ? a.Wi / 2 : a.Wi * 2);
-      a.ntiles = conv_geometry(B, a.Ho, a.Wo, &a.tiles_y, &a.tiles_x);
-      ok = a.ntiles > 0 && a.x != nullptr && a.dy != nullptr && a.partials != nullptr &&
-           !(c[i]->dy_pro == PRO_BWD && a.dy2 == nullptr);
-      grid[i] = 2 * a.ntiles < 512 ? 2 * a.ntiles : 512;
-    }
-    if (ok) {
-      const int rc = ava_conv3x3_wgrad_mfma_pair(w[0], grid[0], p, w[1], grid[1], q, to_stream(s));
-      if (rc != AVA_EINVAL) return rc;
-    }
+  WgradArgs w[2];
+  int grid[2];
+  const WgradCall* c[2] = {&p, &q};
+  bool ok = true;
+  for (int i = 0; i < 2 && ok; ++i) {
+    WgradArgs& a = w[i];
+    a.act_bf16 = act_bf16;
+    a.x = c[i]->x; a.xa = c[i]->xa; a.xb = c[i]->xb; a.dy = c[i]->dy; a.dy2 = c[i]->dy2;
+    a.da = c[i]->da; a.db = c[i]->db; a.dc = c[i]->dc; a.partials = c[i]->partials;
+    a.B = B; a.Hi = c[i]->Hi; a.Wi = c[i]->Wi;
+    const int mode = c[i]->mode;
+    a.Ho = mode == MODE_S1 ? a.Hi : (mode == MODE_DOWN ? a.Hi / 2 : a.Hi * 2);
+    a.Wo = mode == MODE_S1 ? a.Wi : (mode == MODE_DOWN ? a.Wi / 2 : a.Wi * 2);
+    a.ntiles = conv_geometry(B, a.Ho, a.Wo, &a.tiles_y, &a.tiles_x);
+    ok = a.ntiles > 0 && a.x != nullptr && a.dy != nullptr && a.partials != nullptr &&
+         !(c[i]->dy_pro == PRO_BWD && a.dy2 == nullptr);
+    grid[i] = 2 * a.ntiles < 512 ? 2 * a.ntiles : 512;
+  }
+  if (ok) {
+    const int rc = ava_conv3x3_wgrad_mfma_pair(w[0], grid[0], p, w[1], grid[1], q, to_stream(s));
+    if (rc != AVA_EINVAL) return rc;
   }
   int rc = ava_conv3x3_wgrad_ex(p.x, p.xa, p.xb, p.dy, p.dy2, p.da, p.db, p.dc, p.partials, B, p.Hi, p.Wi, p.Cin, p.Cout,
                                 p.mode, p.dy_pro, act_bf16, s);
@@ -310,12 +270,10 @@ int ava_conv_wgrad_rows_ex(int B, int Hi, int Wi, int Cin, int Cout, int mode, i
   a.ntiles = conv_geometry(B, a.Ho, a.Wo, &a.tiles_y, &a.tiles_x);
   if (a.ntiles <= 0) return AVA_EINVAL;
   const int grid = 2 * a.ntiles < 512 ? 2 * a.ntiles : 512;
-  if (use_mfma()) {
-    const int rows = ava_conv3x3_wgrad_mfma(a, grid, Cin, Cout, mode, dy_pro, nullptr);   // partials == NULL: query
-    if (rows > 0) return rows;
-    const int trows = ava_conv3x3_wgrad_thin_rows(a, grid, Cin, Cout, mode);
-    if (trows > 0) return trows;
-  }
+  const int rows = ava_conv3x3_wgrad_mfma(a, grid, Cin, Cout, mode, dy_pro, nullptr);   // partials == NULL: query
+  if (rows > 0) return rows;
+  const int trows = ava_conv3x3_wgrad_thin_rows(a, grid, Cin, Cout, mode);
+  if (trows > 0) return trows;
   return grid;
 }
 

@@ -25,16 +25,9 @@ struct FusedArgs {
   RecompArgs rcd;        // rcd.G1 != null: `dy` is a 1-channel tensor and the 8-channel upstream gradient is its 3x3 gather with the
                          // weights G1 [9][1][8], formed in the staging waves (conv_recomp.h: convt7's data gradient inside convt6's backward)
   int skip_dx;           // thin 8 -> 1 backward: only the weight gradient + BatchNorm sums (its data gradient is formed by the consumer)
-  RecompArgs rc;         // rc.G1 != null: `x` is the raw spectrogram batch; the layer input y1 is recomputed from it (conv_recomp.h)
+  RecompArgs rc;         // rc.G1 != null: `x` is the raw spectrogram batch; the layer input y1 is recomputed from it (conv_thin_kernels.h: RECY)
   int sweep;             // thin kernels: workgroups sweep the tile list together instead of per-XCD chunks
-  int dbg;               // lab build: phase ablation bits of the wave-specialised kernel (AVA_FDBG; timing only)
-#ifdef AVA_LAB
-  unsigned long long* stamps;   // lab: 16 s_memrealtime stamps of this launch (workgroup 0), tools/lab/conv_stamps.py
-#endif
 };
-#ifdef AVA_LAB
-unsigned long long* ava_lab_next_stamps_f();
-#endif
 
 // 0 when (Cin, Cout, mode, size) has no fused instantiation
 int ava_conv_fused_grid_for(int B, int Hi, int Wi, int Cin, int Cout, int mode);

@@ -1,11 +1,11 @@
 // Fused backward of one conv / convT layer with BOTH products on the bf16 matrix cores (gfx950, v_mfma_f32_16x16x32_bf16),
 // fp32 operands as three bf16 limbs (x = x0 + x1 + x2 exactly; six limb products with i + j <= 2, fp32 accumulate: as close
 // to fp64 as the fp32 MFMA it replaces -- conv_common.h, gemm_limb.hip) at 6/16 of the fp32 MFMA's matrix time.
-// Same contract as conv3x3_bwd_fused_ws_kernel (conv_fused.hip): one staging of the dU window and of the layer-input window
-// feeds the data gradient (+ BatchNorm-backward sums) and the weight / bias gradient (reference: autograd's convolution
+// The fused backward described in conv_fused.hip: one staging of the dU window and of the layer-input window feeds the
+// data gradient (+ BatchNorm-backward sums) and the weight / bias gradient (reference: autograd's convolution
 // backward behind loss.backward(), ava/models/vae.py:352).
 //
-// What is different from the fp32 kernel:
+// What is different from the fp32-MFMA fused kernel it replaced:
 //  * LDS tiles are limb planes ([limb][channel octet][pixel][8] bf16, written by TileStagerL): a pixel's octet is one 16-byte
 //    slot.  The data-gradient phase reads them row-wise (ds_read_b128: 8 channels of one pixel = 8 consecutive k of the
 //    implicit GEMM, ClassFragL / PairFragL).  The weight-gradient phase sums over PIXELS (K = 32 consecutive dU pixels per
@@ -52,7 +52,7 @@ __device__ __forceinline__ f32x4 ava_limb_mfma6(const ava_bf16x8 (&a)[3], const 
 
 template <int LMODE, int TW, int TH>
 struct FGeomL {
-  // x window [XR x XC], dU window [DR x DC], dU interior at offset (DOFF, DOFF), dx region [OH x OW]  (= conv_fused.hip: FGeom)
+  // x window [XR x XC], dU window [DR x DC], dU interior at offset (DOFF, DOFF), dx region [OH x OW]
   static constexpr int XR = LMODE == MODE_S1 ? TH + 2 : (LMODE == MODE_DOWN ? 2 * TH + 1 : TH + 1);
   static constexpr int XC = LMODE == MODE_S1 ? TW + 2 : (LMODE == MODE_DOWN ? 2 * TW + 1 : TW + 1);
   static constexpr int DR = LMODE == MODE_S1 ? TH + 2 : (LMODE == MODE_DOWN ? TH + 1 : 2 * TH + 1);
@@ -64,24 +64,9 @@ struct FGeomL {
 
 template <int N> using ava_ic = std::integral_constant<int, N>;
 
-#ifndef AVA_FL_RAWPRE
-#define AVA_FL_RAWPRE 0                    // lab: unrolled group loops request the raw x of every group at the top of the tile
-#endif
-#ifndef AVA_FL_NTSTORE
-#define AVA_FL_NTSTORE 0                   // lab: dx written with non-temporal stores
-#endif
-#ifndef AVA_FL_W2L
-#define AVA_FL_W2L 1                       // third weight limb of the single-class data gradients in an LDS table: 1 always, 0 never, 2 where the raw-x ring still takes registers
-#endif
-#ifndef AVA_FL_DUNROLL
-#define AVA_FL_DUNROLL 1                   // unroll factor of the data-gradient waves' rolled pixel-group loop
-#endif
-#ifndef AVA_FL_RAWX
-#define AVA_FL_RAWX 1                      // lab: 0 = the data-gradient waves load the raw x of their dx pixels from global memory
-#endif
 // Dynamic LDS of one workgroup (kernel and launcher agree on it here).  RAWX: each tile buffer also holds the raw x of the dx
 // region as fp32 [OH][OW][CI] (TileStagerL::store_tight_raw) wherever the resident workgroups still fit the CU's 160 KB.
-template <int CI, int CO, int LMODE, int TW, int TH, int NS, int ND, int NWV, int WPS, typename ACT, bool DUREC, bool DEEP>
+template <int CI, int CO, int LMODE, int TW, int TH, int NS, int ND, int NWV, int WPS, typename ACT, bool DUREC>
 struct FLds {
   using FG = FGeomL<LMODE, TW, TH>;
   static constexpr int MT = (CI + 15) / 16;
@@ -91,26 +76,17 @@ struct FLds {
   static constexpr bool BF16M = std::is_same<ACT, ava_bf16>::value;
   static constexpr int NLX = BF16M ? 1 : 3;
   static constexpr int W2_ALL = (LMODE == MODE_DOWN || BF16M) ? 0 : (((PAIRL ? 12 : 9) * (CO / 8) + 3) / 4) * 1024 * MT;   // the third-limb table
-  static constexpr size_t planes = (size_t)16 * (NLX * (CI / 8) * ava_plane_pix(FG::XR * FG::XC) + 3 * (CO / 8) * ava_plane_pix(FG::DR * FG::DC));
+  static constexpr size_t planes = (size_t)16 * (NLX * (CI / 8) * FG::XR * FG::XC + 3 * (CO / 8) * FG::DR * FG::DC);
   static constexpr size_t raw = (size_t)FG::OH * FG::OW * CI * sizeof(float);
   static constexpr size_t rest = (192 + ND * 32 * MT + (DUREC ? DU1to8Stager<FG::DC, ACT>::LDS_FLOATS : 0)) * sizeof(float) + W2_ALL;
   static constexpr int WG_PER_CU = WPS * 4 / (NS + ND + NWV);
   // measured per layer (same box, us): conv2 78.3 -> 70.3, conv4 46.6 -> 40.7, convt3 43.5 -> 37.2, conv6 34.7 -> 31.9, convt5 61.2 -> 59.4,
   // convt4 / convt2 / convt6 +-1; the stride-1 layers with MORE output than input channels lose (conv3 53.5 -> 60.1, conv5 38.8 -> 45.2:
   // few x channels to fetch, and their staging waves are the longer role already)
-  static constexpr bool RAWX = AVA_FL_RAWX && (!DEEP || DUREC) && !(LMODE == MODE_S1 && CI < CO && AVA_FL_RAWX < 2) &&
-                               (2 * (planes + raw) + rest + 1024) * WG_PER_CU <= 160 * 1024;
+  static constexpr bool RAWX = !(LMODE == MODE_S1 && CI < CO) && (2 * (planes + raw) + rest + 1024) * WG_PER_CU <= 160 * 1024;
   static constexpr size_t buf = planes + (RAWX ? raw : 0);
   static constexpr size_t lds = 2 * buf + rest;
 };
-
-// lab: compile a wave role out (register-pressure / ablation experiments; results are wrong): 1 staging, 2 data gradient, 4 weight gradient
-#ifndef AVA_FL_DCUT
-#define AVA_FL_DCUT 0                      // lab, timing only: 1 no raw-x ring loads, 2 no dx stores, 4 no fragment reads / MFMAs
-#endif
-#ifndef AVA_FL_CUT
-#define AVA_FL_CUT 0
-#endif
 
 // number of M tiles (units) of the weight gradient over all tap classes
 template <int LMODE> __host__ __device__ constexpr int wl_units(int cin) { return wsplit_base<LMODE>(n_classes<LMODE>(), cin); }
@@ -122,14 +98,14 @@ template <int LMODE> __host__ __device__ constexpr int wl_units(int cin) { retur
 // DUREC (convt6's backward): the upstream gradient dy (8 channels, full resolution) does not exist in memory -- it is convt7's
 // data gradient, a 3x3 gather of the 1-channel seed a.dy, formed on the matrix cores by the (four) staging waves as they build
 // the dU tile (conv_recomp.h: DU1to8Stager; its limb-plane store below).
-// DEEP: the staging waves hold TWO tiles in registers (tile it+2 and it+3 in flight while tile it+1 is converted): per tile the
-// matrix-core waves have ~1 us of work, a tile's loads take 2-3 us under load, so one tile in flight leaves both roles waiting
+// The staging waves hold ONE tile in registers.  Two (tile it+2 and it+3 in flight while tile it+1 is converted) were measured
+// and LOST everywhere (same box, one -> two: conv3 61.1 -> 64.3 us, convt4 41.7 -> 45.3 without a spill; convt5 61.5 -> 91,
+// conv5 40.5 -> 62 with the spills the second register set causes).
 // The three roles stay INLINED in one kernel.  Compiled as three noinline functions (tools/lab/noinline_roles.patch) each role gets
 // its own register allocation and the in-loop spills disappear -- but every kernel then carries 156-256 B of scratch per lane (the
 // callee-saved registers of the roles), and on this stack a kernel's time grows with its scratch size: the 16 x 16 layers, spill-free
 // either way, went 24.0 -> 30.6 us, the whole family +90 us (profiles/r04/ab_roles_*.csv).
-template <int CI, int CO, int LMODE, int DYPRO, int TW, int TH, int NS, int ND, int NWV, int WPS, typename ACT, bool DUREC = false,
-          bool DEEP = false>
+template <int CI, int CO, int LMODE, int DYPRO, int TW, int TH, int NS, int ND, int NWV, int WPS, typename ACT, bool DUREC = false>
 __global__ __launch_bounds__(64 * (NS + ND + NWV), WPS) void conv3x3_bwd_fused_limb_kernel(const FusedArgs a) {
   using FG = FGeomL<LMODE, TW, TH>;
   constexpr int XR = FG::XR, XC = FG::XC, DR = FG::DR, DC = FG::DC, DOFF = FG::DOFF;
@@ -149,9 +125,9 @@ __global__ __launch_bounds__(64 * (NS + ND + NWV), WPS) void conv3x3_bwd_fused_l
   constexpr bool DSPLIT = MT == 2 && ND % 2 == 0 && !(BMODE == MODE_UP && ND == 4);
   constexpr int NDG = DSPLIT ? ND / 2 : ND;     // waves that share the pixel groups of a tile
   constexpr int MTD = DSPLIT ? 1 : MT;
-  constexpr int XNPIX = ava_plane_pix(XR * XC), DNPIX = ava_plane_pix(DR * DC);     // octet-plane strides (pixels) of the two limb images
+  constexpr int XNPIX = XR * XC, DNPIX = DR * DC;     // octet-plane strides (pixels) of the two limb images
   constexpr int XPLANE = (CI / 8) * XNPIX * 16, DPLANE = (CO / 8) * DNPIX * 16;      // bytes
-  using FL = FLds<CI, CO, LMODE, TW, TH, NS, ND, NWV, WPS, ACT, DUREC, DEEP>;
+  using FL = FLds<CI, CO, LMODE, TW, TH, NS, ND, NWV, WPS, ACT, DUREC>;
   constexpr bool RAWX = FL::RAWX;           // raw x of the dx region behind the planes of each tile buffer
   // bf16 arithmetic: one limb of the (rounded) layer input and of the (rounded) weights; three of the gradient.  Both products
   // are then three MFMAs instead of six, and they are the exact derivative of the forward that rounded the same operands
@@ -165,7 +141,7 @@ __global__ __launch_bounds__(64 * (NS + ND + NWV), WPS) void conv3x3_bwd_fused_l
   float* red = cd + 96;                                        // [ND][32 * MT]: per data-gradient wave {sum g [16 MT], sum g x [16 MT]}
   // the data-gradient weights' third limb as an LDS table (ClassFragL: W2L) where one wave holds ALL of a class's chunks
   // (single-class gathers): the role then fits 128 VGPRs with room to spare
-  constexpr bool W2L = !BF16M && BCLS == 1 && (AVA_FL_W2L == 1 || (AVA_FL_W2L == 2 && !RAWX));
+  constexpr bool W2L = !BF16M && BCLS == 1;
   constexpr int DKG = PAIR ? 12 * (CO / 8) : 9 * (CO / 8);     // k-groups of the (single) data-gradient class
   constexpr int W2_TILE = W2L ? ((DKG + 3) / 4) * 1024 : 0;    // bytes per dx channel tile
   constexpr int W2_ALL = W2_TILE * MT;
@@ -177,7 +153,6 @@ __global__ __launch_bounds__(64 * (NS + ND + NWV), WPS) void conv3x3_bwd_fused_l
 
   const int t = threadIdx.x, lane = t & 63;
   const int wave8 = __builtin_amdgcn_readfirstlane(t >> 6);
-  AVA_STAMP(0, t == 0);
   const bool stager = wave8 < NS;            // waves 0 .. NS-1 stage tiles, the next ND form the data gradient, the rest the weight gradient
   const int n = lane & 15, kg = lane >> 4;
 
@@ -214,31 +189,13 @@ __global__ __launch_bounds__(64 * (NS + ND + NWV), WPS) void conv3x3_bwd_fused_l
     d_origin(y0, x0, gy, gx);
     sd.load(a.dy, a.dy2, b, a.Ho, a.Wo, gy, gx);
   };
-  // (DUREC + DEEP: both register sets of the seed gather pass through the SAME private LDS window of their wave -- it is only
-  // live inside one store_limb call, and a wave's two stores follow each other)
-  decltype(sx) sx2;                                            // DEEP: the second register set (odd tiles)
-  decltype(sd) sd2;
-  auto sd2_store = [&](unsigned char* dst) __attribute__((always_inline)) {
-    if constexpr (DUREC) sd2.store_limb(dst, cd, xs); else sd2.store_tight(dst, cd);
-  };
-  auto prefetch2 = [&](int tl) {
-    if constexpr (DEEP) {
-      int b, y0, x0, gy, gx;
-      origin(tl, b, y0, x0);
-      x_origin(y0, x0, gy, gx);
-      sx2.load(a.x, nullptr, b, a.Hi, a.Wi, gy, gx);
-      d_origin(y0, x0, gy, gx);
-      sd2.load(a.dy, a.dy2, b, a.Ho, a.Wo, gy, gx);
-    }
-  };
   if (stager) {
     sx.init();
-    if constexpr (DEEP) { sx2.init(); if constexpr (DUREC) sd2.init(a.rcd, xs); else sd2.init(); }
     if constexpr (DUREC) sd.init(a.rcd, xs); else sd.init();
     if (walk.valid()) prefetch(walk.cur);    // tile 0 goes in flight BEFORE the coefficient prologue
   }
   // everything the prologue and the epilogue read from global memory is requested in front of the coefficient finalisation
-  // and its barrier (conv_fused.hip)
+  // and its barrier
   float cxv = 0.f;
   if (t < 96) {
     const int which = t >> 5, c = t & 31;
@@ -266,50 +223,21 @@ __global__ __launch_bounds__(64 * (NS + ND + NWV), WPS) void conv3x3_bwd_fused_l
   }
   __syncthreads();                           // cx / cd visible
   if (!stager) asm volatile("" ::"v"(wpf));
-  AVA_STAMP(1, t == 0);
 
-  if (stager && (AVA_FL_CUT & 1)) return;
   if (stager) {
     // ---------------- staging waves ----------------
-    __builtin_amdgcn_s_setprio(3);           // issue priority over the matrix-core waves of the same SIMD (conv_fused.hip)
+    // issue priority over the matrix-core waves of the same SIMD: their loads and LDS stores are the longer pipeline
+    // (DESIGN.md section 3, item 16); same-box A/B of the step with the fp32 kernel: 1.9141 / 1.9131 ms without,
+    // 1.9087 / 1.8979 ms with (the reverse, matrix-core waves first, costs +26 us)
+    __builtin_amdgcn_s_setprio(3);
     constexpr int XOFF = LMODE == MODE_UP ? 0 : 1;              // the dx region inside the x window
-    auto sx_store_of = [&](auto& stg, unsigned char* dst) __attribute__((always_inline)) {
-      if constexpr (RAWX) stg.template store_tight_raw<XOFF, XOFF, FG::OH, FG::OW>(dst, cx, reinterpret_cast<float*>(dst + RAWOFF));
-      else stg.store_tight(dst, cx);
+    auto sx_store = [&](unsigned char* dst) __attribute__((always_inline)) {
+      if constexpr (RAWX) sx.template store_tight_raw<XOFF, XOFF, FG::OH, FG::OW>(dst, cx, reinterpret_cast<float*>(dst + RAWOFF));
+      else sx.store_tight(dst, cx);
     };
-    if constexpr (DEEP) {
-      // tile k lives in register set k & 1 and goes to LDS buffer k & 1
-      auto tile_k = [&](int k) { return walk.cur + k * walk.step; };
-      if (walk.valid()) {
-        if (tile_k(1) < walk.end) prefetch2(tile_k(1));
-        sx_store_of(sx, smem_b);
-        sd_store(smem_b + XBYTES);
-        if (tile_k(2) < walk.end) prefetch(tile_k(2));
-      }
-      __syncthreads();                                          // (A) tile 0 ready
-      int it = 0;
-      for (; walk.valid(); walk.advance(), ++it) {              // (tile_k is relative to the advancing walk.cur)
-        if (walk.has_next()) {
-          if ((it & 1) == 0) {
-            sx_store_of(sx2, smem_b + BUF);
-            sd2_store(smem_b + BUF + XBYTES);
-            if (tile_k(3) < walk.end) prefetch2(tile_k(3));
-          } else {
-            sx_store_of(sx, smem_b);
-            sd_store(smem_b + XBYTES);
-            if (tile_k(3) < walk.end) prefetch(tile_k(3));
-          }
-        }
-        __syncthreads();                                        // (B)
-      }
-      __syncthreads();                                          // (E)
-      return;
-    }
-    auto sx_store = [&](unsigned char* dst) __attribute__((always_inline)) { sx_store_of(sx, dst); };
     if (walk.valid()) {
       sx_store(smem_b);
       sd_store(smem_b + XBYTES);
-      AVA_STAMP(2, t == 0);
       if (walk.has_next()) prefetch(walk.next());
     }
     __syncthreads();                                            // (A) tile 0 ready
@@ -328,7 +256,6 @@ __global__ __launch_bounds__(64 * (NS + ND + NWV), WPS) void conv3x3_bwd_fused_l
     return;
   }
 
-  if (wave8 < NS + ND && (AVA_FL_CUT & 2)) return;
   if (wave8 < NS + ND) {
     // ---------------- data-gradient waves ----------------
     // Stride-2 conv layers (dx gathered in four output-parity classes): with four data-gradient waves each wave takes ONE
@@ -407,15 +334,7 @@ __global__ __launch_bounds__(64 * (NS + ND + NWV), WPS) void conv3x3_bwd_fused_l
 #pragma unroll
         for (int gi = 0; gi < LA; ++gi) load_ex_group(xb, gi, ring[gi]);
       }
-      if (AVA_FL_DCUT & 1) {
-#pragma unroll
-        for (int gi = 0; gi < LA; ++gi)
-#pragma unroll
-          for (int mt = 0; mt < MTD; ++mt) ring[gi][mt] = (avaf4){1.f, 1.f, 1.f, 1.f};
-      }
-      AVA_STAMP(3, t == NST);
       __syncthreads();                                              // (A)
-      AVA_STAMP(4, t == NST);
       int it = 0;
       for (; walk.valid(); walk.advance(), ++it) {
         int b, y0, x0;
@@ -431,22 +350,10 @@ __global__ __launch_bounds__(64 * (NS + ND + NWV), WPS) void conv3x3_bwd_fused_l
           const int cb4 = 16 * (mtb + mt) + cq;                      // lanes beyond CI re-read slot 0 (their sums are dropped)
           return *reinterpret_cast<const avaf4*>(rawt + group_raw(group_of(gi)) + (cb4 < CI ? lane_raw + 16 * (mtb + mt) : lane_raw - 4 * kg));
         };
-        // unrolled group loop: the raw x of all of the tile's groups is requested in front of the first fragment read
-        constexpr bool RAWPRE = RAWX && !ROLLED && AVA_FL_RAWPRE;
-        avaf4 rawall[RAWPRE ? GPW : 1][MTD];
-        if constexpr (RAWPRE) {
-#pragma unroll
-          for (int gi = 0; gi < GPW; ++gi)
-#pragma unroll
-            for (int mt = 0; mt < MTD; ++mt) rawall[gi][mt] = raw_of(gi, mt);
-        }
         auto do_group = [&](int gi) __attribute__((always_inline)) {
           const int g = group_of(gi);
           avaf4 exv[MTD];
-          if constexpr (RAWPRE) {
-#pragma unroll
-            for (int mt = 0; mt < MTD; ++mt) exv[mt] = rawall[gi][mt];
-          } else if constexpr (RAWX) {
+          if constexpr (RAWX) {
 #pragma unroll
             for (int mt = 0; mt < MTD; ++mt) exv[mt] = raw_of(gi, mt);
           } else {
@@ -457,17 +364,14 @@ __global__ __launch_bounds__(64 * (NS + ND + NWV), WPS) void conv3x3_bwd_fused_l
 #pragma unroll
               for (int mt = 0; mt < MTD; ++mt) ring[k][mt] = ring[k + 1][mt];
             const int gn = gi + LA;                                  // the group LA ahead: of this tile or of the next one
-            if (!(AVA_FL_DCUT & 1)) load_ex_group(gn < GPW ? xcur : xnext, gn < GPW ? gn : gn - GPW, ring[LA - 1]);
+            load_ex_group(gn < GPW ? xcur : xnext, gn < GPW ? gn : gn - GPW, ring[LA - 1]);
           }
           f32x4 acc[2][MTD];
 #pragma unroll
           for (int h = 0; h < 2; ++h)
 #pragma unroll
             for (int mt = 0; mt < MTD; ++mt) acc[h][mt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-          if (AVA_FL_DCUT & 4) {
-#pragma unroll
-            for (int mt = 0; mt < MTD; ++mt) acc[0][mt] = (f32x4){exv[mt][0], exv[mt][1], exv[mt][2], exv[mt][3]};
-          } else if (BMODE == MODE_UP) {
+          if (BMODE == MODE_UP) {
             const int rest = g >> 2, r = rest / CB, cb = rest % CB;
             const unsigned char* px = dut + (r * DC + 16 * cb) * 16;
             if constexpr (CSPLIT) {
@@ -496,24 +400,19 @@ __global__ __launch_bounds__(64 * (NS + ND + NWV), WPS) void conv3x3_bwd_fused_l
                 s1[mt][r] += v[r];
                 s2[mt][r] = fmaf(v[r], xr[r], s2[mt][r]);          // raw x: centred after the loop
               }
-              if (!(AVA_FL_DCUT & 2)) {
-                if (AVA_FL_NTSTORE) __builtin_nontemporal_store((avaf4){v[0], v[1], v[2], v[3]}, reinterpret_cast<avaf4*>(obase + gout + 16 * (mtb + mt)));
-                else ava_st4_wt<float>(obase + gout + 16 * (mtb + mt), avaf4{v[0], v[1], v[2], v[3]});
-              }
+              ava_st4<float>(obase + gout + 16 * (mtb + mt), avaf4{v[0], v[1], v[2], v[3]});
             }
           }
         };
         if constexpr (ROLLED) {
-#pragma unroll AVA_FL_DUNROLL
+#pragma unroll 1
           for (int gi = 0; gi < GPW; ++gi) do_group(gi);
         } else {
 #pragma unroll
           for (int gi = 0; gi < GPW; ++gi) do_group(gi);
         }
-        AVA_STAMP(5 + (it < 4 ? it : 4), t == NST);
         __syncthreads();                                            // (B)
       }
-      AVA_STAMP(10, t == NST);
       // ---- BatchNorm-backward partial sums: over the 16 pixel lanes, then over the data-gradient waves (fixed order) ----
 #pragma unroll
       for (int mt = 0; mt < MTD; ++mt)
@@ -557,12 +456,10 @@ __global__ __launch_bounds__(64 * (NS + ND + NWV), WPS) void conv3x3_bwd_fused_l
       if (a.acc_out != nullptr) bn_acc_add(a.acc_out, which * 32 + ci, tot);
       else a.bn_partials[(size_t)blockIdx.x * 2 * CI + tc] = tot;
     }
-    AVA_STAMP(12, t == NST);
     return;
   }
 
   // ---------------- weight-gradient waves ----------------
-  if (AVA_FL_CUT & 4) return;
   // Units: the M tiles (16 rows of (tap, ci)) of every tap class, numbered class by class, plus the bias row as unit NU.
   // Unit u belongs to wave u % NWV, slot u / NWV.  K = 32 pixels per step: KW consecutive pixels of 32 / KW rows.
   constexpr int NU = wl_units<LMODE>(CI);
@@ -629,7 +526,6 @@ __global__ __launch_bounds__(64 * (NS + ND + NWV), WPS) void conv3x3_bwd_fused_l
       ones = __builtin_bit_cast(ava_bf16x8, vv);
     }
 
-    AVA_STAMP(13, t == 64 * (NS + ND));
     __syncthreads();                                              // (A)
     int it = 0;
     for (; walk.valid(); walk.advance(), ++it) {
@@ -727,153 +623,83 @@ __global__ __launch_bounds__(64 * (NS + ND + NWV), WPS) void conv3x3_bwd_fused_l
 }
 
 // ------------------------------------------------------------------------------------------------
-template <int CI, int CO, int LMODE, int DYPRO, int TW, int TH, int NS, int ND, int NWV, int WPS, typename ACT, bool DUREC = false,
-          bool DEEP = false>
+template <int CI, int CO, int LMODE, int DYPRO, int TW, int TH, int NS, int ND, int NWV, int WPS, typename ACT, bool DUREC = false>
 static int launch_fused_limb_t(const FusedArgs& a, int grid, hipStream_t st) {
-  using FL = FLds<CI, CO, LMODE, TW, TH, NS, ND, NWV, WPS, ACT, DUREC, DEEP>;
+  using FL = FLds<CI, CO, LMODE, TW, TH, NS, ND, NWV, WPS, ACT, DUREC>;
   constexpr size_t lds = FL::lds;
   constexpr int WG_PER_CU = FL::WG_PER_CU;
   static_assert(WG_PER_CU >= 1 && (lds + 1024) * WG_PER_CU <= 160 * 1024, "the resident workgroups' tile buffers must fit 160 KB of LDS");
-  const void* kfn = reinterpret_cast<const void*>(&conv3x3_bwd_fused_limb_kernel<CI, CO, LMODE, DYPRO, TW, TH, NS, ND, NWV, WPS, ACT, DUREC, DEEP>);
+  const void* kfn = reinterpret_cast<const void*>(&conv3x3_bwd_fused_limb_kernel<CI, CO, LMODE, DYPRO, TW, TH, NS, ND, NWV, WPS, ACT, DUREC>);
   // (the kernel also carries < 1 KB of static LDS -- accvals, ems: the same allowance as the static_assert above; one attempt
   // per instantiation, thread-safe, its result remembered)
   static const bool attr_ok = (lds + 1024 <= 64 * 1024) ||
                               hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess;
   if (!attr_ok) return AVA_ELAUNCH;
   FusedArgs b = a;
-#ifdef AVA_LAB
-  b.stamps = ava_lab_next_stamps_f();
-#endif
   const int hl = LMODE == MODE_DOWN ? a.Ho : a.Hi, wl = LMODE == MODE_DOWN ? a.Wo : a.Wi;   // low-resolution side
   if (hl % TH != 0 || wl % TW != 0) return AVA_EINVAL;
   b.tiles_y = hl / TH;
   b.tiles_x = wl / TW;
   b.ntiles = a.B * b.tiles_y * b.tiles_x;
   if (grid < 1 || grid > b.ntiles) return AVA_EINVAL;
-  hipLaunchKernelGGL((conv3x3_bwd_fused_limb_kernel<CI, CO, LMODE, DYPRO, TW, TH, NS, ND, NWV, WPS, ACT, DUREC, DEEP>), dim3(grid), dim3(64 * (NS + ND + NWV)), lds, st, b);
+  hipLaunchKernelGGL((conv3x3_bwd_fused_limb_kernel<CI, CO, LMODE, DYPRO, TW, TH, NS, ND, NWV, WPS, ACT, DUREC>), dim3(grid), dim3(64 * (NS + ND + NWV)), lds, st, b);
   AVA_CHECK_LAUNCH();
   return AVA_OK;
 }
 
-#ifndef AVA_FL_DEEP_MIN_NS
-#define AVA_FL_DEEP_MIN_NS 99         // measured: two tiles in flight LOSE everywhere (same box, one -> two: conv3 61.1 -> 64.3 us,
-                                      // convt4 41.7 -> 45.3 without a spill; convt5 61.5 -> 91, conv5 40.5 -> 62 with the spills the
-                                      // second register set causes); lab: -DAVA_FL_DEEP_MIN_NS=8 builds it for the 8-stager shapes
-#endif
-#ifndef AVA_FL_T6_DEEP
-#define AVA_FL_T6_DEEP 0              // convt6's backward (seed gather in the staging waves): two tiles in the staging registers
-#endif
 template <int CI, int CO, int LMODE, int TW, int TH, int NS, int ND, int NWV, int WPS>
 static int launch_fused_limb(const FusedArgs& a, int grid, int dy_pro, hipStream_t st) {
-  constexpr bool DEEP = NS >= AVA_FL_DEEP_MIN_NS;
   if constexpr (CI == 8 && CO == 8 && LMODE == MODE_UP && TH == 4 && NS == 4) {
     if (a.rcd.G1 != nullptr) {            // convt6's backward with convt7's data gradient formed in the staging waves
       if (dy_pro != PRO_BWD) return AVA_EINVAL;
-      if (a.act_bf16) return launch_fused_limb_t<CI, CO, LMODE, PRO_BWD, TW, TH, NS, ND, NWV, WPS, ava_bf16, true, AVA_FL_T6_DEEP != 0>(a, grid, st);
-      return launch_fused_limb_t<CI, CO, LMODE, PRO_BWD, TW, TH, NS, ND, NWV, WPS, float, true, AVA_FL_T6_DEEP != 0>(a, grid, st);
+      if (a.act_bf16) return launch_fused_limb_t<CI, CO, LMODE, PRO_BWD, TW, TH, NS, ND, NWV, WPS, ava_bf16, true>(a, grid, st);
+      return launch_fused_limb_t<CI, CO, LMODE, PRO_BWD, TW, TH, NS, ND, NWV, WPS, float, true>(a, grid, st);
     }
   }
   if (a.rcd.G1 != nullptr) return AVA_EINVAL;
   if (dy_pro == PRO_BWD) {
-    if (a.act_bf16) return launch_fused_limb_t<CI, CO, LMODE, PRO_BWD, TW, TH, NS, ND, NWV, WPS, ava_bf16, false, DEEP>(a, grid, st);
-    return launch_fused_limb_t<CI, CO, LMODE, PRO_BWD, TW, TH, NS, ND, NWV, WPS, float, false, DEEP>(a, grid, st);
+    if (a.act_bf16) return launch_fused_limb_t<CI, CO, LMODE, PRO_BWD, TW, TH, NS, ND, NWV, WPS, ava_bf16>(a, grid, st);
+    return launch_fused_limb_t<CI, CO, LMODE, PRO_BWD, TW, TH, NS, ND, NWV, WPS, float>(a, grid, st);
   }
   if (dy_pro == PRO_ID) {
-    if (a.act_bf16) return launch_fused_limb_t<CI, CO, LMODE, PRO_ID, TW, TH, NS, ND, NWV, WPS, ava_bf16, false, DEEP>(a, grid, st);
-    return launch_fused_limb_t<CI, CO, LMODE, PRO_ID, TW, TH, NS, ND, NWV, WPS, float, false, DEEP>(a, grid, st);
+    if (a.act_bf16) return launch_fused_limb_t<CI, CO, LMODE, PRO_ID, TW, TH, NS, ND, NWV, WPS, ava_bf16>(a, grid, st);
+    return launch_fused_limb_t<CI, CO, LMODE, PRO_ID, TW, TH, NS, ND, NWV, WPS, float>(a, grid, st);
   }
   return AVA_EINVAL;
 }
 
-// Shapes with a limb instantiation: (cin, cout, mode) -> low-resolution tile, staging / data-gradient / weight-gradient waves,
-// waves per SIMD.  Measured in the step at batch 256 (tools/run_r04.sh variants; fp32 kernel -> this one):
+// Shapes with a limb instantiation: (cin, cout, mode) -> low-resolution tile (tw, th), staging / data-gradient /
+// weight-gradient waves (ns, nd, nwv), waves per SIMD (wps).  Measured in the step at batch 256 (fp32 kernel -> this one):
 //   conv3  8 -> 16 S1   82.5 -> 52.4 us   1024 threads, 32 x 8 tiles (32 x 4: 59.3; the halo rows are 33 % instead of 59 % extra)
 //   convt5 16 -> 8 S1   92.3 -> 62.4 us   768 threads (168 VGPRs), 32 x 8 tiles (1024 threads, 32 x 4: 68.6)
 //   conv5  16 -> 24 S1  65.7 -> 43.8 us   768 threads: the data-gradient waves hold 84 VGPRs of limb weights
 //   convt3 24 -> 16 S1  63.8 -> 46.2 us   the two dx channel tiles dealt to odd / even data-gradient waves
 //   convt4 16 -> 16 UP  43.8 -> 41.3 us
 //   conv4  16 -> 16 DOWN 49.4 -> 45.5 us  (16 x 4 tiles; each data-gradient wave owns one output-parity class)
-//   conv2 / convt6: below
-// (lab experiments: -DAVA_FL_CFG="th, ns, nd, nwv, wps" overrides conv3's row: tools/lab/build_variant.sh)
-#ifndef AVA_FL_CFG
-#define AVA_FL_CFG 32, 8, 8, 4, 4, 4          // conv3
-#endif
-#ifndef AVA_FL_CFG2
-#define AVA_FL_CFG2 32, 8, 8, 4, 4, 4         // convt5
-#endif
-#ifndef AVA_FL_T3
-#define AVA_FL_T3 32, 4, 8, 4, 4, 4           // convt3
-#endif
-#ifndef AVA_FL_T4
-#define AVA_FL_T4 16, 4, 10, 4, 2, 4          // convt4 (8+4+4: 41.3 us, 10+4+2: 38.6 us)
-#endif
-#ifndef AVA_FL_T6
-#define AVA_FL_T6 16, 4, 4, 2, 2, 4           // convt6
-#endif
-#ifndef AVA_FL_C2
-#define AVA_FL_C2 16, 4, 3, 4, 1, 4           // conv2: one dx parity class per data-gradient wave (99.8 -> 78.3 us; 2+4+2: 80.1)
-#endif
-#ifndef AVA_FL_C4
-#define AVA_FL_C4 16, 4, 8, 4, 4, 4           // conv4
-#endif
-#ifndef AVA_FL_C5
-#define AVA_FL_C5 32, 4, 9, 4, 3, 4           // conv5 (8+4+4: 39.7 us, 9+4+3: 38.5 us)
-#endif
 // The four layers at 16 x 16 (conv6, conv7, convt1, convt2; until round 4 a data-gradient launch plus half a weight-gradient
 // pair launch each).  With 24 / 32 channels on both sides the three roles together spilled 100-350 registers at 128 or 168
-// VGPRs although each role fits alone (-DAVA_FL_CUT), and a spill reload inside these latency-bound loops is a dependent
+// VGPRs although each role fits alone, and a spill reload inside these latency-bound loops is a dependent
 // memory round trip: fused, they LOST (same box, fused against data-gradient launch + half a pair launch: conv7 34.4 vs 33.9 us,
 // convt1 30.9 vs 33.6, conv6 74.3 vs 45.5, convt2 51.5 vs 45.4 at 768 threads; 33.7 / 41.5 / 84.4 / 65.3 at 1024).  ONE
 // 512-thread workgroup per CU (4 staging + 2 + 2 matrix-core waves, 256 VGPRs, no spill) wins: conv6 34.6, convt2 28.8,
 // conv7 24.6, convt1 23.8 us -- 111.8 us for the four against 158.4, and six launches fewer.
-#ifndef AVA_FL_C7
-#define AVA_FL_C7 16, 8, 4, 2, 2, 2
-#endif
-#ifndef AVA_FL_T1
-#define AVA_FL_T1 16, 8, 4, 2, 2, 2
-#endif
-#ifndef AVA_FL_C6
-#define AVA_FL_C6 16, 4, 4, 2, 2, 2
-#endif
-#ifndef AVA_FL_T2
-#define AVA_FL_T2 16, 4, 4, 2, 2, 2
-#endif
-#define AVA_FL_ROW(X, ci, co, md, ...) X(ci, co, md, __VA_ARGS__)
-#ifndef AVA_FL_NO16
-#define AVA_FL_16(X) AVA_FL_ROW(X, 24, 32, MODE_S1, AVA_FL_C7) AVA_FL_ROW(X, 32, 24, MODE_S1, AVA_FL_T1) AVA_FL_ROW(X, 24, 24, MODE_DOWN, AVA_FL_C6) AVA_FL_ROW(X, 24, 24, MODE_UP, AVA_FL_T2)
-#else
-#define AVA_FL_16(X)
-#endif
 // The 8 <-> 8 stride-2 layers at full resolution (conv2, and convt6 with convt7's data gradient gathered in its staging
 // waves) run 512-thread workgroups, two per CU like the fp32 kernel they replace (4 staging + 2 + 2 matrix-core waves: every
 // role fits 128 VGPRs there): same box conv2 106.0 -> 99.5 us, convt6 90.1 -> 87.1 us.  As ONE workgroup per CU they lost
 // (1024 threads: 112 .. 124 / 105 us; 768 threads: 99 / 124 us): a CU then has one small tile in flight instead of two.
-#define AVA_FL_88(X) AVA_FL_ROW(X, 8, 8, MODE_UP, AVA_FL_T6) AVA_FL_ROW(X, 8, 8, MODE_DOWN, AVA_FL_C2)
-#ifdef AVA_FL_ONLY16                            // lab: only the four 16 x 16 layers
-#define AVA_FUSED_LIMB_SHAPES(X)                \
-  AVA_FL_ROW(X, 24, 32, MODE_S1, AVA_FL_C7)     \
-  AVA_FL_ROW(X, 32, 24, MODE_S1, AVA_FL_T1)     \
-  AVA_FL_ROW(X, 24, 24, MODE_DOWN, AVA_FL_C6)   \
-  AVA_FL_ROW(X, 24, 24, MODE_UP, AVA_FL_T2)
-#elif defined(AVA_FL_EXP_ONLY)                  // lab: only the rows under experiment (fast variant builds)
-#ifdef AVA_FL_NONE
-#define AVA_FUSED_LIMB_SHAPES(X)
-#else
-#define AVA_FUSED_LIMB_SHAPES(X)                \
-  AVA_FL_ROW(X, 8, 8, MODE_UP, AVA_FL_T6)       \
-  AVA_FL_ROW(X, 8, 8, MODE_DOWN, AVA_FL_C2)
-#endif
-#else
-#define AVA_FUSED_LIMB_SHAPES(X)                \
-  AVA_FL_ROW(X, 8, 16, MODE_S1, AVA_FL_CFG)     \
-  AVA_FL_ROW(X, 16, 8, MODE_S1, AVA_FL_CFG2)    \
-  AVA_FL_ROW(X, 16, 16, MODE_UP, AVA_FL_T4)     \
-  AVA_FL_ROW(X, 24, 16, MODE_S1, AVA_FL_T3)     \
-  AVA_FL_ROW(X, 16, 24, MODE_S1, AVA_FL_C5)     \
-  AVA_FL_ROW(X, 16, 16, MODE_DOWN, AVA_FL_C4)   \
-  AVA_FL_16(X)                                  \
-  AVA_FL_88(X)
-#endif
+#define AVA_FUSED_LIMB_SHAPES(X)                                                                              \
+  X(8, 16, MODE_S1, 32, 8, 8, 4, 4, 4)        /* conv3 */                                                     \
+  X(16, 8, MODE_S1, 32, 8, 8, 4, 4, 4)        /* convt5 */                                                    \
+  X(16, 16, MODE_UP, 16, 4, 10, 4, 2, 4)      /* convt4 (8+4+4: 41.3 us, 10+4+2: 38.6 us) */                  \
+  X(24, 16, MODE_S1, 32, 4, 8, 4, 4, 4)       /* convt3 */                                                    \
+  X(16, 24, MODE_S1, 32, 4, 9, 4, 3, 4)       /* conv5 (8+4+4: 39.7 us, 9+4+3: 38.5 us) */                    \
+  X(16, 16, MODE_DOWN, 16, 4, 8, 4, 4, 4)     /* conv4 */                                                     \
+  X(24, 32, MODE_S1, 16, 8, 4, 2, 2, 2)       /* conv7 */                                                     \
+  X(32, 24, MODE_S1, 16, 8, 4, 2, 2, 2)       /* convt1 */                                                    \
+  X(24, 24, MODE_DOWN, 16, 4, 4, 2, 2, 2)     /* conv6 */                                                     \
+  X(24, 24, MODE_UP, 16, 4, 4, 2, 2, 2)       /* convt2 */                                                    \
+  X(8, 8, MODE_UP, 16, 4, 4, 2, 2, 4)         /* convt6 */                                                    \
+  X(8, 8, MODE_DOWN, 16, 4, 3, 4, 1, 4)       /* conv2: one dx parity class per data-gradient wave (99.8 -> 78.3 us; 2+4+2: 80.1) */
 
 bool ava_conv_fused_limb_has(int Cin, int Cout, int mode) {
 #define X(ci, co, md, tww, thh, ns, nd, nwv, wps) if (Cin == ci && Cout == co && mode == md) return true;
@@ -892,7 +718,7 @@ int ava_conv_fused_limb_cap(int Cin, int Cout, int mode, int* tw, int* th) {
   return 0;
 }
 
-// AVA_EINVAL when the shape has no limb instantiation (the caller then runs the fp32 kernel)
+// AVA_EINVAL when the shape has no limb instantiation
 int ava_conv3x3_bwd_fused_limb_launch(const FusedArgs& a, int grid, int Cin, int Cout, int mode, int dy_pro, hipStream_t st) {
   if (a.rc.G1 != nullptr || a.dx == nullptr) return AVA_EINVAL;
 #define X(ci, co, md, tww, thh, ns, nd, nwv, wps) \

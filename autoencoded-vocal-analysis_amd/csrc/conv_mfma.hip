@@ -98,7 +98,7 @@ __global__ __launch_bounds__(256, (MSPLIT ? 2 : 1)) void conv3x3_mfma_kernel(con
         exn[gi * MT + mt] = ava_ld4<ACT>(xb + group_out(group_of(gi)) + (cb < COUT ? lane_out + 16 * (mtb + mt) : lane_out - 4 * kg));
       }
   };
-  TileStager<CIN, PRO, IR, IC, false, 256, TIN, ACT> stg;
+  TileStager<CIN, PRO, IR, IC, 256, TIN, ACT> stg;
   stg.init();
   TileWalk walk(a.ntiles);
   if (walk.valid()) {
@@ -110,7 +110,7 @@ __global__ __launch_bounds__(256, (MSPLIT ? 2 : 1)) void conv3x3_mfma_kernel(con
   // Weights and epilogue constants are fetched AFTER the first tile's loads were issued: both round trips to
   // memory overlap instead of following each other at the start of every workgroup.
   constexpr bool BF16M = std::is_same<ACT, ava_bf16>::value;     // bf16 arithmetic: weights rounded to bfloat16 (TileStager rounds the BatchNorm output)
-  if (!AVA_DBG_BIT(a, 8)) f0.init(a.G, lane, SP * n * CIN, mtb, BF16M);
+  f0.init(a.G, lane, SP * n * CIN, mtb, BF16M);
   if (NCLS > 1) { f1.init(a.G, lane, n * CIN, mtb, BF16M); f2.init(a.G, lane, n * CIN, mtb, BF16M); f3.init(a.G, lane, n * CIN, mtb, BF16M); }
   // epilogue constants for this lane's 4 output channels per cout tile
   float bias[MT][4];
@@ -130,7 +130,7 @@ __global__ __launch_bounds__(256, (MSPLIT ? 2 : 1)) void conv3x3_mfma_kernel(con
     int b, oy0, ox0, gy0, gx0;
     origin(walk.cur, b, oy0, ox0, gy0, gx0);
     __syncthreads();                       // previous tile fully consumed (and coef[] visible on the first pass)
-    if (!AVA_DBG_BIT(a, 2)) stg.store(tile, coef);                 // s_waitcnt vmcnt(0): retires the prefetch (and exn) of this tile
+    stg.store(tile, coef);                 // s_waitcnt vmcnt(0): retires the prefetch (and exn) of this tile
     if (EPI == EPI_BWD) ava_wait_vm0(exn);
     __syncthreads();
     // uniform (scalar) part of the addresses of this tile
@@ -143,7 +143,7 @@ __global__ __launch_bounds__(256, (MSPLIT ? 2 : 1)) void conv3x3_mfma_kernel(con
 #pragma unroll
       for (int i = 0; i < GPW * MT; ++i) ex[i] = exn[i];
     }
-    if (walk.has_next() && !AVA_DBG_BIT(a, 2)) {  // next tile's loads stay in flight during the MFMAs below
+    if (walk.has_next()) {  // next tile's loads stay in flight during the MFMAs below
       int nb, noy0, nox0, ngy0, ngx0;
       origin(walk.next(), nb, noy0, nox0, ngy0, ngx0);
       stg.load(a.in, a.in2, nb, a.Hi, a.Wi, ngy0, ngx0);
@@ -158,8 +158,7 @@ __global__ __launch_bounds__(256, (MSPLIT ? 2 : 1)) void conv3x3_mfma_kernel(con
       for (int h = 0; h < 2; ++h)
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) acc[h][mt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-      if (AVA_DBG_BIT(a, 1)) {
-      } else if (MODE == MODE_UP) {
+      if (MODE == MODE_UP) {
         const int cls = gi & 3, r = g >> 2;       // == g & 3 (both group mappings keep the class in the low bits of gi)
         const float* px = tile + r * IC * CIN;
         if (cls == 0) f0.run(px, acc);
@@ -195,7 +194,7 @@ __global__ __launch_bounds__(256, (MSPLIT ? 2 : 1)) void conv3x3_mfma_kernel(con
               s2[mt][r] = fmaf(v[r], xv[r], s2[mt][r]);      // raw x: centred after the loop
             }
           }
-          if (obase != nullptr && !AVA_DBG_BIT(a, 4))
+          if (obase != nullptr)
             *reinterpret_cast<float4*>(obase + gout + 16 * (mtb + mt)) = make_float4(v[0], v[1], v[2], v[3]);
           if (EPI == EPI_FWD && MODE == MODE_S1 && !PAIR && a.out2 != nullptr) {
             // second copy in NCHW order (the flatten order of the fully connected layer that follows, vae.py:224):
@@ -211,7 +210,6 @@ __global__ __launch_bounds__(256, (MSPLIT ? 2 : 1)) void conv3x3_mfma_kernel(con
     }
   }
 
-  if (AVA_DBG_BIT(a, 16)) return;
   // ---- per-workgroup partial statistics: reduce over the 16 pixel lanes, then over the 4 waves ----
   __syncthreads();
   if (MSPLIT) {                              // a wave only fills its own cout tile: the other slots must read as 0
@@ -277,7 +275,6 @@ static int launch_mfma_t(const ConvArgs& a, int grid, hipStream_t st) {
   b.part_rows = grid;
   if (grid > b.ntiles) grid = b.ntiles;
   if (grid > ava_scale_grid(resident)) grid = ava_scale_grid(resident);
-  { const char* e = ava_env("AVA_GRID"); if (e) grid = atoi(e); if (grid > b.ntiles) grid = b.ntiles; if (grid > b.part_rows) grid = b.part_rows; }
   hipLaunchKernelGGL((conv3x3_mfma_kernel<CIN, COUT, MODE, PRO, EPI, TW, TH, MSPLIT, PAIR, ACT>), dim3(grid), dim3(256), lds, st, b);
   AVA_CHECK_LAUNCH();
   return AVA_OK;
@@ -293,16 +290,6 @@ static int launch_mfma(const ConvArgs& a, int grid, hipStream_t st) {
   return launch_mfma_t<CIN, COUT, MODE, PRO, EPI, TW, TH, float>(a, grid, st);
 }
 
-#ifdef AVA_LAB
-template <int CIN, int COUT, int MODE, int TW, int TH>
-static int launch_mfma_pe(const ConvArgs& a, int grid, int pro, int epi, hipStream_t st) {
-  if (pro == PRO_BN && epi == EPI_FWD) return launch_mfma<CIN, COUT, MODE, PRO_BN, EPI_FWD, TW, TH>(a, grid, st);
-  if (pro == PRO_BWD && epi == EPI_BWD) return launch_mfma<CIN, COUT, MODE, PRO_BWD, EPI_BWD, TW, TH>(a, grid, st);
-  if (pro == PRO_ID && epi == EPI_BWD) return launch_mfma<CIN, COUT, MODE, PRO_ID, EPI_BWD, TW, TH>(a, grid, st);
-  return AVA_EINVAL;
-}
-#endif
-
 // returns AVA_EINVAL when the shape has no matrix-core instantiation (caller falls back to the VALU kernel)
 // `grid` = number of workgroups = number of partial rows (the caller's ava_conv_grid value)
 int ava_conv3x3_mfma_ws(const ConvArgs& a, int grid, int Cin, int Cout, int mode, int pro, int epi, hipStream_t st);   // conv_ws.hip
@@ -315,37 +302,16 @@ int ava_conv3x3_mfma(const ConvArgs& a, int grid, int Cin, int Cout, int mode, i
     const int rc = ava_conv3x3_up88_direct(a, grid, Cin, Cout, mode, pro, epi, st);
     if (rc != AVA_EINVAL) return rc;
   }
-  // forward layers run the wave-specialised kernel (conv_ws.hip; -27 us/step); AVA_CONV_WS=0 selects the plain one
-  static const bool ws = [] { const char* e = ava_env("AVA_CONV_WS"); return e == nullptr || atoi(e) != 0; }();
-  static const bool ws_bwd = [] { const char* e = ava_env("AVA_CONV_WS_BWD"); return e == nullptr || atoi(e) != 0; }();
-  if (ws && a.out2 == nullptr && (epi == EPI_FWD || (epi == EPI_BWD && ws_bwd))) {
+  // forward layers and data gradients run the wave-specialised kernel (conv_ws.hip; -27 us/step)
+  if (a.out2 == nullptr && (epi == EPI_FWD || epi == EPI_BWD)) {
     const int rc = ava_conv3x3_mfma_ws(a, grid, Cin, Cout, mode, pro, epi, st);
     if (rc != AVA_EINVAL) return rc;
   }
-#ifndef AVA_LAB
   // Everything else runs the wave-specialised kernel above.  The plain 256-thread kernel is compiled for the one
   // launch that needs its second output: conv7's forward, which also writes the NCHW-flatten copy fc1 reads.
   if (a.out2 != nullptr && Cin == 24 && Cout == 32 && mode == MODE_S1 && a.Wo % 16 == 0 && a.Ho % 8 == 0 && pro == PRO_BN && epi == EPI_FWD)
     return launch_mfma<24, 32, MODE_S1, PRO_BN, EPI_FWD, 16, 8>(a, grid, st);
   return AVA_EINVAL;
-#else
-#define AVA_MFMA_CASE(ci, co, md, tww, thh) \
-  if (Cin == ci && Cout == co && mode == md && a.Wo % tww == 0 && a.Ho % thh == 0) return launch_mfma_pe<ci, co, md, tww, thh>(a, grid, pro, epi, st);
-  AVA_MFMA_CASE(8, 8, MODE_DOWN, 32, 4)
-  AVA_MFMA_CASE(8, 16, MODE_S1, 32, 8)
-  AVA_MFMA_CASE(16, 16, MODE_DOWN, 32, 4)
-  AVA_MFMA_CASE(16, 24, MODE_S1, 32, 4)
-  AVA_MFMA_CASE(24, 24, MODE_DOWN, 16, 4)
-  AVA_MFMA_CASE(24, 32, MODE_S1, 16, 8)
-  AVA_MFMA_CASE(32, 24, MODE_S1, 16, 8)
-  AVA_MFMA_CASE(24, 24, MODE_UP, 32, 8)
-  AVA_MFMA_CASE(24, 16, MODE_S1, 32, 4)
-  AVA_MFMA_CASE(16, 16, MODE_UP, 32, 8)
-  AVA_MFMA_CASE(16, 8, MODE_S1, 32, 8)
-  AVA_MFMA_CASE(8, 8, MODE_UP, 32, 8)
-#undef AVA_MFMA_CASE
-  return AVA_EINVAL;
-#endif
 }
 
 // ================================================================================================
@@ -399,8 +365,8 @@ __global__ __launch_bounds__(256) void conv3x3_wgrad_mfma_kernel(const WgradArgs
     else if (MODE == MODE_DOWN) { gy0 = 2 * oy0 - 1; gx0 = 2 * ox0 - 1; }
     else { gy0 = oy0 / 2; gx0 = ox0 / 2; }
   };
-  TileStager<CIN, PRO_BN, IR, IC, false, 256, ACT, ACT> sx;       // x: activation
-  TileStager<COUT, DYPRO, TH, TW, false, 256, float, ACT> sd;      // dy: fp32 gradient, dy2: saved activation
+  TileStager<CIN, PRO_BN, IR, IC, 256, ACT, ACT> sx;       // x: activation
+  TileStager<COUT, DYPRO, TH, TW, 256, float, ACT> sd;      // dy: fp32 gradient, dy2: saved activation
   sx.init();
   sd.init();
   TileWalk walk(a.ntiles);
@@ -525,8 +491,8 @@ __device__ __forceinline__ void wgrad_split_body(const WgradArgs& a, const int w
     else if (MODE == MODE_DOWN) { gy0 = 2 * oy0 - 1; gx0 = 2 * ox0 - 1; }
     else { gy0 = oy0 / 2; gx0 = ox0 / 2; }
   };
-  TileStager<CIN, PRO_BN, IR, IC, false, 256, ACT, ACT> sx;       // x: activation
-  TileStager<COUT, DYPRO, TH, TW, false, 256, float, ACT> sd;      // dy: fp32 gradient, dy2: saved activation
+  TileStager<CIN, PRO_BN, IR, IC, 256, ACT, ACT> sx;       // x: activation
+  TileStager<COUT, DYPRO, TH, TW, 256, float, ACT> sd;      // dy: fp32 gradient, dy2: saved activation
   sx.init();
   sd.init();
   TileWalk walk(a.ntiles, true, wg, nwg);
@@ -660,7 +626,6 @@ static int wgrad_plan(const WgradArgs& a, int grid, WgradArgs* b, size_t* lds_ou
   // which at one or two tiles per workgroup costs more than the tiles (same-box A/B of the step: 512 -> 256 workgroups
   // -13 us, 384 +-0, 128 +13 us)
   if (SPLIT && grid > ava_scale_grid(256)) grid = ava_scale_grid(256);
-  { const char* e = ava_env("AVA_WGRID"); if (e && atoi(e) > 0 && atoi(e) < grid) grid = atoi(e); }
   return grid;
 }
 

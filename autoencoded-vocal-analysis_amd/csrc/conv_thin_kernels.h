@@ -21,9 +21,6 @@ __device__ __forceinline__ float thin_sum_waves(F f) {
   if constexpr (NW == 4) return (f(0) + f(1)) + (f(2) + f(3));
   else return ((f(0) + f(1)) + (f(2) + f(3))) + ((f(4) + f(5)) + (f(6) + f(7)));
 }
-#ifndef THIN_PLANES
-#define THIN_PLANES 0     // 1: two [10][130][4] channel planes instead of [10][130][8]
-#endif
 
 // sum N per-thread values over the workgroup: wave shuffles, then one LDS exchange (lds: [NW][N] floats);
 // result i is written to out[i] by thread i.  Fixed order -> deterministic.
@@ -249,7 +246,7 @@ __global__ __launch_bounds__(2 * W, W == 128 ? 4 : 2) void thin_1to8_kernel(cons
         s2[0] = __builtin_elementwise_fma(v0, xh0, s2[0]);
         s2[1] = __builtin_elementwise_fma(v1, xh1, s2[1]);
       }
-      if (a.out != nullptr) ava_st4_wt<TOUT>(ava_as<TOUT>(a.out) + off, avaf4{v0[0], v0[1], v1[0], v1[1]});
+      if (a.out != nullptr) ava_st4<TOUT>(ava_as<TOUT>(a.out) + off, avaf4{v0[0], v0[1], v1[0], v1[1]});
     }
   }
   if (EPI == EPI_NONE) return;
@@ -296,7 +293,7 @@ __global__ __launch_bounds__(2 * W, W == 128 ? 2 : 1) void thin_8to1_kernel(cons
   const float bias0 = EPI == EPI_SSE ? ava_uniform(a.bias[0]) : 0.f;
   const float em0 = EPI == EPI_BWD ? ava_uniform(a.epi_mean[0]) : 0.f, ei0 = EPI == EPI_BWD ? ava_uniform(a.epi_invstd[0]) : 0.f;
   float s1 = 0.f, s2 = 0.f;
-  TileStager<8, PRO, THIN_IR, THIN_IC, (THIN_PLANES != 0), THIN_NT> stg;
+  TileStager<8, PRO, THIN_IR, THIN_IC, THIN_NT> stg;
   stg.init();
   const int tiles_y = a.Ho / THIN_TH;
   for (TileWalk walk(a.ntiles); walk.valid(); walk.advance()) {
@@ -313,9 +310,9 @@ __global__ __launch_bounds__(2 * W, W == 128 ? 2 : 1) void thin_8to1_kernel(cons
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int j = 0; j < 6; ++j) {
-        const float* px = tile + ((ty0 + j) * THIN_IC + x + kx) * (THIN_PLANES ? 4 : 8);
+        const float* px = tile + ((ty0 + j) * THIN_IC + x + kx) * 8;
         const float4 u = *reinterpret_cast<const float4*>(px);
-        const float4 w4 = *reinterpret_cast<const float4*>(px + (THIN_PLANES ? THIN_IR * THIN_IC * 4 : 4));
+        const float4 w4 = *reinterpret_cast<const float4*>(px + 4);
         const float in[8] = {u.x, u.y, u.z, u.w, w4.x, w4.y, w4.z, w4.w};
 #pragma unroll
         for (int ky = 0; ky < 3; ++ky) {
@@ -357,127 +354,6 @@ __global__ __launch_bounds__(2 * W, W == 128 ? 2 : 1) void thin_8to1_kernel(cons
   thin_zero_rows<2>(a.partials, a.part_rows);
 }
 
-#ifdef AVA_LAB
-#define W 128   /* lab-only kernels: 128-wide images only */
-// Wave-specialised variant (512 threads, one workgroup per CU): waves 0-3 stage tile k+1 (global -> registers ->
-// prologue -> LDS buffer (k+1)&1) while waves 4-7 multiply tile k out of buffer k&1; one barrier per tile.  At the
-// barrier of tile k the staging waves have filled buffer k&1 and the compute waves have left buffer (k-1)&1, which
-// is the one the staging waves write next.  The next window's loads are issued right after the LDS writes, so they
-// are in flight for the whole period of a tile instead of being waited for back to back.
-template <int PRO, int EPI, int NS>
-__global__ __launch_bounds__(NS + 256) void thin_8to1_ws_kernel(const ConvArgs a) {
-  extern __shared__ __align__(16) float smem[];
-  constexpr int TILE_F = THIN_IR * THIN_IC * 8;
-  float* coef = smem + 2 * TILE_F;                      // [3][32]
-  float* red = coef + 96;                               // [4][2]
-  const int t = threadIdx.x;
-  if (t < 96) {
-    const int which = t >> 5, c = t & 31;
-    const float* src = which == 0 ? a.pa : (which == 1 ? a.pb : a.pc);
-    coef[t] = (src != nullptr && c < 8) ? src[c] : 0.f;
-  }
-  const int tiles_y = a.Ho / THIN_TH;
-  float s1 = 0.f, s2 = 0.f;
-  if (t < NS) {
-    // ---- staging waves ----
-    TileStager<8, PRO, THIN_IR, THIN_IC, false, NS> stg;
-    stg.init(t);
-    TileWalk walk(a.ntiles);
-    if (walk.valid()) {
-      const int b = walk.cur / tiles_y, oy0 = (walk.cur - b * tiles_y) * THIN_TH;
-      stg.load(a.in, a.in2, b, a.Hi, a.Wi, oy0 - 1, -1);
-    }
-    __syncthreads();                                    // coefficients visible
-    for (int k = 0; walk.valid(); walk.advance(), k ^= 1) {
-      stg.store(smem + k * TILE_F, coef);
-      if (walk.has_next()) {
-        const int tn = walk.next();
-        const int b = tn / tiles_y, oy0 = (tn - b * tiles_y) * THIN_TH;
-        stg.load(a.in, a.in2, b, a.Hi, a.Wi, oy0 - 1, -1);
-      }
-      __syncthreads();                                  // buffer k full
-    }
-  } else {
-    // ---- compute waves ----
-    const int tc = t - NS, ty0 = (tc >> 7) * 4, x = tc & 127;
-    const ThinPairWeights Wp(a.G);                       // [9][8][1] as channel pairs
-    const float bias0 = EPI == EPI_SSE ? ava_uniform(a.bias[0]) : 0.f;
-    const float em0 = EPI == EPI_BWD ? ava_uniform(a.epi_mean[0]) : 0.f, ei0 = EPI == EPI_BWD ? ava_uniform(a.epi_invstd[0]) : 0.f;
-    __syncthreads();
-    int k = 0;
-    for (TileWalk walk(a.ntiles); walk.valid(); walk.advance(), k ^= 1) {
-      const int tl = walk.cur;
-      const int b = tl / tiles_y, oy0 = (tl - b * tiles_y) * THIN_TH;
-      const size_t opix0 = ((size_t)b * a.Ho + oy0 + ty0) * W + x;
-      float ex[4] = {0.f, 0.f, 0.f, 0.f};               // epilogue operand, requested before the wait for the tile
-      if (a.epi_x != nullptr) {
-#pragma unroll
-        for (int p = 0; p < 4; ++p) ex[p] = a.epi_x[opix0 + (size_t)p * W];
-      }
-      __syncthreads();                                  // buffer k full
-      const float* tile = smem + k * TILE_F;
-      avaf2 acc2[4];                                    // even / odd input channels of the 4 output pixels
-#pragma unroll
-      for (int p = 0; p < 4; ++p) acc2[p] = avaf2{0.f, 0.f};
-#pragma unroll
-      for (int kx = 0; kx < 3; ++kx) {
-        __builtin_amdgcn_sched_barrier(0);              // one tap column at a time (register pressure)
-#pragma unroll
-        for (int j = 0; j < 6; ++j) {
-          const float* px = tile + ((ty0 + j) * THIN_IC + x + kx) * 8;
-          const avaf4 u = *reinterpret_cast<const avaf4*>(px);
-          const avaf4 v = *reinterpret_cast<const avaf4*>(px + 4);
-          const avaf2 in2[4] = {avaf2{u[0], u[1]}, avaf2{u[2], u[3]}, avaf2{v[0], v[1]}, avaf2{v[2], v[3]}};
-#pragma unroll
-          for (int ky = 0; ky < 3; ++ky) {
-            const int p = j - ky;                       // output row fed by input row j through tap ky
-            if (p >= 0 && p < 4) {
-#pragma unroll
-              for (int q = 0; q < 4; ++q) acc2[p] = __builtin_elementwise_fma(in2[q], Wp.w[ky * 3 + kx][q], acc2[p]);
-            }
-          }
-        }
-      }
-      float acc[4];
-#pragma unroll
-      for (int p = 0; p < 4; ++p) acc[p] = acc2[p][0] + acc2[p][1];
-      if (EPI == EPI_SSE) {
-#pragma unroll
-        for (int p = 0; p < 4; ++p) {
-          const size_t opix = opix0 + (size_t)p * W;
-          const float v = acc[p] + bias0;
-          if (a.epi_x != nullptr) {
-            const float r = v - ex[p];
-            a.out2[opix] = a.prec * r;
-            s1 = fmaf(r, r, s1);
-          }
-          if (a.out != nullptr) a.out[opix] = v;
-        }
-      } else {
-#pragma unroll
-        for (int p = 0; p < 4; ++p) {
-          const size_t opix = opix0 + (size_t)p * W;
-          s1 += acc[p];
-          s2 = fmaf(acc[p], (ex[p] - em0) * ei0, s2);
-          if (a.out != nullptr) a.out[opix] = acc[p];
-        }
-      }
-    }
-  }
-  // ---- workgroup sums (compute waves 4..7 hold them), fixed order ----
-  __syncthreads();
-  const int lane = t & 63, wave = t >> 6;
-  const float r1 = wave_sum(s1), r2 = wave_sum(s2);
-  constexpr int W0 = NS / 64;                            // first compute wave
-  if (wave >= W0 && lane == 0) { red[(wave - W0) * 2] = r1; red[(wave - W0) * 2 + 1] = r2; }
-  __syncthreads();
-  if (t < 2 && a.partials != nullptr)
-    a.partials[(size_t)blockIdx.x * 2 + t] = (red[t] + red[2 + t]) + (red[4 + t] + red[6 + t]);
-  thin_zero_rows<2>(a.partials, a.part_rows);
-}
-
-#undef W
-#endif  // AVA_LAB
 
 // "Direct" form of the 8 -> 1 forward (convt7 + SSE epilogue): the 8-channel input needs no LDS window.  Thread (x, h)
 // of a lane pair reads channels 4h..4h+3 of its pixel column straight from global memory (10 rows: the 8 rows of the
@@ -824,7 +700,7 @@ __global__ __launch_bounds__(2 * W, W == 128 ? 2 : 1) void thin_wgrad_8to1_kerne
   for (int k = 0; k < 9; ++k)
 #pragma unroll
     for (int ci = 0; ci < 8; ++ci) acc[k][ci] = 0.f;
-  TileStager<8, PRO_BN, THIN_IR, THIN_IC, (THIN_PLANES != 0), THIN_NT> stg;
+  TileStager<8, PRO_BN, THIN_IR, THIN_IC, THIN_NT> stg;
   stg.init();
   const int tiles_y = a.Ho / THIN_TH;
   for (TileWalk walk(a.ntiles); walk.valid(); walk.advance()) {
@@ -846,9 +722,9 @@ __global__ __launch_bounds__(2 * W, W == 128 ? 2 : 1) void thin_wgrad_8to1_kerne
     for (int kx = 0; kx < 3; ++kx)
 #pragma unroll
       for (int j = 0; j < 6; ++j) {
-        const float* px = tile + ((ty0 + j) * THIN_IC + x + kx) * (THIN_PLANES ? 4 : 8);
+        const float* px = tile + ((ty0 + j) * THIN_IC + x + kx) * 8;
         const float4 u = *reinterpret_cast<const float4*>(px);
-        const float4 w4 = *reinterpret_cast<const float4*>(px + (THIN_PLANES ? THIN_IR * THIN_IC * 4 : 4));
+        const float4 w4 = *reinterpret_cast<const float4*>(px + 4);
         const float in[8] = {u.x, u.y, u.z, u.w, w4.x, w4.y, w4.z, w4.w};
 #pragma unroll
         for (int ky = 0; ky < 3; ++ky) {
@@ -1108,128 +984,6 @@ __global__ __launch_bounds__(2 * W) void thin_bwd_fused_1to8_kernel(const FusedA
 // (S[tap] = sum of dU over the pixels whose tap lands inside the image), so the data-gradient kernel
 // (thin_1to8_kernel<.., EPI_NONE>) only has to write dx and never reads x; this kernel reads x once.
 // ---------------------------------------------------------------------------------------------------------
-#ifdef AVA_LAB
-#define W 128   /* lab-only kernels: 128-wide images only */   // the LDS-staged form of this kernel (AVA_THIN_STATS_DIRECT=0); the library runs the direct form below
-template <int DYPRO>
-__global__ __launch_bounds__(256, 2) void thin_wgrad_stats_8to1_kernel(const FusedArgs a) {
-  extern __shared__ __align__(16) float smem[];
-  float* tile = smem;                                   // [10][130][8] xhat0
-  float* coef = smem + THIN_IR * THIN_IC * 8;           // [3][32]
-  float* aux = coef + 96;                               // [4] row sums per wave, [4] column sums, [4] corners
-  const int t = threadIdx.x, ty0 = (t >> 7) * 4, x = t & 127, wave = t >> 6, lane = t & 63;
-  if (t < 96) {
-    const int which = t >> 5, c = t & 31;
-    float v = 0.f;
-    if (c < 8) v = which == 0 ? a.invstd[c] : (which == 1 ? -a.mean[c] * a.invstd[c] : 0.f);
-    coef[t] = v;
-  }
-  const float da = DYPRO == PRO_BWD ? a.da[0] : 0.f, db = DYPRO == PRO_BWD ? a.db[0] : 0.f,
-              dc = DYPRO == PRO_BWD ? a.dc[0] : 0.f;
-  avaf2 acc2[9][4];                                     // channel pairs: the 288 FMAs per tile issue as 144 v_pk_fma_f32
-  float T = 0.f, R = 0.f, Cc = 0.f, K = 0.f;
-#pragma unroll
-  for (int k = 0; k < 9; ++k)
-#pragma unroll
-    for (int q = 0; q < 4; ++q) acc2[k][q] = avaf2{0.f, 0.f};
-  const bool edge_col = x == 0 || x == W - 1;
-  TileStager<8, PRO_BN, THIN_IR, THIN_IC, (THIN_PLANES != 0)> stg;
-  stg.init();
-  const int tiles_y = a.Ho / THIN_TH;
-  for (TileWalk walk(a.ntiles); walk.valid(); walk.advance()) {
-    const int tl = walk.cur;
-    const int b = tl / tiles_y, oy0 = (tl - b * tiles_y) * THIN_TH;
-    __syncthreads();
-    stg.load(a.x, nullptr, b, a.Hi, a.Wi, oy0 - 1, -1);
-    stg.store(tile, coef);
-    __syncthreads();
-    const size_t opix0 = ((size_t)b * a.Ho + oy0 + ty0) * W + x;
-    float du[4];
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-      const size_t opix = opix0 + (size_t)p * W;
-      du[p] = prologue<DYPRO>(a.dy[opix], DYPRO == PRO_BWD ? a.dy2[opix] : 0.f, da, db, dc);
-    }
-    const float strip = (du[0] + du[1]) + (du[2] + du[3]);
-    T += strip;
-    // border sums; a thread's role is fixed by (ty0, x) -- see thin_bwd_fused_1to8_kernel
-    const bool top = oy0 + ty0 == 0, bottom = oy0 + ty0 + 3 == a.Ho - 1;
-    if (top || bottom) {
-      const float v = top ? du[0] : du[3];
-      R += v;
-      K += edge_col ? v : 0.f;
-    }
-    Cc += edge_col ? strip : 0.f;
-    avaf2 dd[4];
-#pragma unroll
-    for (int p = 0; p < 4; ++p) { const float dp = ava_pin<4>(du[p]); dd[p] = avaf2{dp, dp}; }
-#pragma unroll
-    for (int kx = 0; kx < 3; ++kx)
-#pragma unroll
-      for (int j = 0; j < 6; ++j) {
-        const float* px = tile + ((ty0 + j) * THIN_IC + x + kx) * (THIN_PLANES ? 4 : 8);
-        const avaf4 u = *reinterpret_cast<const avaf4*>(px);
-        const avaf4 v = *reinterpret_cast<const avaf4*>(px + (THIN_PLANES ? THIN_IR * THIN_IC * 4 : 4));
-        const avaf2 in2[4] = {avaf2{u[0], u[1]}, avaf2{u[2], u[3]}, avaf2{v[0], v[1]}, avaf2{v[2], v[3]}};
-#pragma unroll
-        for (int ky = 0; ky < 3; ++ky) {
-          const int p = j - ky;
-          if (p >= 0 && p < 4) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-              acc2[ky * 3 + kx][q] = __builtin_elementwise_fma(in2[q], dd[p], acc2[ky * 3 + kx][q]);
-          }
-        }
-      }
-  }
-  float sv[73];
-#pragma unroll
-  for (int k = 0; k < 9; ++k)
-#pragma unroll
-    for (int ci = 0; ci < 8; ++ci) sv[k * 8 + ci] = acc2[k][ci >> 1][ci & 1];
-  sv[72] = T;
-  float* tot = smem + 4 * 73;                           // [73] behind the reduction scratch (tiles are dead)
-  thin_block_reduce<73, 4>(sv, smem, tot);
-  const float rw = wave_sum(R);
-  if (lane == 0) aux[wave] = rw;                        // waves 0,1: image row 0;  waves 2,3: image row H-1
-  if (edge_col) {
-    const int role = (t >> 7) * 2 + (x == 0 ? 0 : 1);   // 0: x=0 top half, 1: x=127 top half, 2: x=0 bottom, 3: x=127 bottom
-    aux[4 + role] = Cc;
-    aux[8 + role] = K;
-  }
-  __syncthreads();
-  float* scratch = smem + 512;                          // [2][72]
-  if (t < 72) {
-    const int tap = t >> 3, ci = t & 7, ky = tap / 3, kx = tap - 3 * ky;
-    float S = tot[72];
-    if (ky == 0) S -= aux[0] + aux[1];
-    if (ky == 2) S -= aux[2] + aux[3];
-    if (kx == 0) S -= aux[4] + aux[6];
-    if (kx == 2) S -= aux[5] + aux[7];
-    if (ky == 0 && kx == 0) S += aux[8];
-    if (ky == 0 && kx == 2) S += aux[9];
-    if (ky == 2 && kx == 0) S += aux[10];
-    if (ky == 2 && kx == 2) S += aux[11];
-    const float xa = a.xa[ci], xb = a.xb[ci], mean = a.mean[ci], invstd = a.invstd[ci];
-    const float gamma = xa / invstd, beta = fmaf(mean, xa, xb);
-    const float dgp = tot[t];
-    a.wg_partials[(size_t)blockIdx.x * 73 + t] = fmaf(gamma, dgp, beta * S);
-    const float w = a.Gb[(8 - tap) * 8 + ci];            // forward gather weight G[tap][ci] out of the backward pack
-    scratch[t] = w * S;
-    scratch[72 + t] = w * dgp;
-  } else if (t == 72) {
-    a.wg_partials[(size_t)blockIdx.x * 73 + 72] = tot[72];                    // bias gradient = T
-  }
-  __syncthreads();
-  if (t < 16) {
-    const int which = t >> 3, ci = t & 7;
-    float s = 0.f;
-    for (int tap = 0; tap < 9; ++tap) s += scratch[72 * which + tap * 8 + ci];
-    a.bn_partials[(size_t)blockIdx.x * 16 + t] = s;
-  }
-}
-
-#undef W
-#endif  // AVA_LAB
 
 // "Direct" form of thin_wgrad_stats_8to1_kernel: the same correlation, indexed by the INPUT pixel q instead of the
 // output pixel p,   dG'[tap][ci] = sum_q xhat[q][ci] * dU[q - tap]   (dU zero outside the image),
@@ -1467,7 +1221,7 @@ __global__ __launch_bounds__(256, 3) void up88_direct_kernel(const ConvArgs a) {
       s1[0] += v0; s1[1] += v1;
       s2[0] = __builtin_elementwise_fma(v0, v0, s2[0]);
       s2[1] = __builtin_elementwise_fma(v1, v1, s2[1]);
-      ava_st4_wt<ACT>(ava_as<ACT>(a.out) + o0 + (size_t)j * a.Wo * 8, avaf4{v0[0], v0[1], v1[0], v1[1]});
+      ava_st4<ACT>(ava_as<ACT>(a.out) + o0 + (size_t)j * a.Wo * 8, avaf4{v0[0], v0[1], v1[0], v1[1]});
     }
   }
   // ---- per-channel sums: lanes of equal parity hold the same 4 channels; waves, then workgroup, fixed order ----

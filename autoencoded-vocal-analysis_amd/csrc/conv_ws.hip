@@ -1,5 +1,5 @@
-// Wave-specialised forward convolution (default for the forward layers; AVA_CONV_WS=0 falls back to
-// conv3x3_mfma_kernel).  512 threads per workgroup: waves 0-3 only stage
+// Wave-specialised convolution: every forward layer and data gradient ava_conv3x3_mfma serves, except conv7's forward
+// (its second, NCHW output needs conv3x3_mfma_kernel).  512 threads per workgroup: waves 0-3 only stage
 // tiles (global -> registers -> BatchNorm prologue -> LDS), waves 4-7 only multiply (weights in registers, MFMA,
 // bias/ReLU/statistics epilogue), on two LDS tile buffers.  Every SIMD then hosts one staging wave and one matrix-core
 // wave of the workgroup, so the VALU/LDS-write work of tile k+1 runs beside the MFMAs of tile k instead of before them.
@@ -8,9 +8,8 @@
 #include <stdlib.h>
 #include <type_traits>
 #include "conv_mfma.h"
-#include "conv_recomp.h"
 
-// Which shapes run the limb form: every forward-type launch with 16 or more input channels (conv4..conv6, convt1..convt5
+// Which shapes run the limb form (launch_mfma_ws): every forward-type launch with 16 or more input channels (conv4..conv6, convt1..convt5
 // forward and the four 16 x 16 layers' data gradients) and, since the staging waves' prologue lost its serialised LDS reads
 // (conv_common.h: TileStager::coef_of) and has room for the split, the forward of conv2 and conv3 (8 input channels:
 // isolated 42.2 -> 35.2 and 40.1 -> 32.5 us, step -7 us; whole -m gpu suite unchanged).  Measured earlier on every shape (profiles/r03/limb_conv_forward.txt,
@@ -24,56 +23,13 @@
 // of them by a flip ({conv5, convt5}: golden B8 z64; forward-only sets: six-step trajectory; 16-channel forward set: the
 // callers' second-epoch loss at 4.9x the reference's own run-to-run noise against an allowance of 4x).  The mask-imposed
 // fp64-oracle gradient tests pass for all of them.
-// Lab build: AVA_CONV_LIMB=0 (off), 1 (this table), 2 (every shape with CIN % 8 == 0), 3-9 (the other sets measured).
-// lab build: phase ablation of the wave-specialised kernel (AVA_DBG bits: 1 no MFMA, 2 no prologue / limb split / LDS write,
-// 4 no global loads, 8 no output stores); timing only
-#ifdef AVA_LAB
-#define AVA_ABL(bit) ((a.dbg & (bit)) != 0)
-#else
-#define AVA_ABL(bit) false
-#endif
-
-#ifdef AVA_LAB
-// lab: time stamps of the wave-specialised forward kernels (tools/lab/conv_stamps.py): launch i of a step writes 16 stamps at
-// base + 16 i; ava_lab_conv_stamps(base, n) arms it (n launches), the counter restarts with every call
-static unsigned long long* g_ws_stamps = nullptr;
-static int g_ws_stamp_n = 0, g_ws_stamp_i = 0;
-extern "C" int ava_lab_conv_stamps(unsigned long long* base, int n) { g_ws_stamps = base; g_ws_stamp_n = n; g_ws_stamp_i = 0; return 0; }
-unsigned long long* ava_lab_next_stamps_f() {     // the fused backward kernels' slots: behind the forward kernels' (conv_fused_limb.hip)
-  if (g_ws_stamps == nullptr || g_ws_stamp_i >= g_ws_stamp_n) return nullptr;
-  return g_ws_stamps + 16 * (g_ws_stamp_i++);
-}
-static unsigned long long* ava_lab_next_stamps() {
-  if (g_ws_stamps == nullptr || g_ws_stamp_i >= g_ws_stamp_n) return nullptr;
-  return g_ws_stamps + 16 * (g_ws_stamp_i++);
-}
-#endif
-
-
-static bool conv_limb_on(int Cin, int Cout, int mode, int pro) {
-  static const int sel = [] { const char* e = ava_env("AVA_CONV_LIMB"); return e ? atoi(e) : 1; }();
-  if (sel == 0) return false;
-  if (sel == 2) return true;
-  if (sel == 3) return Cin == 16 && Cout == 8 && mode == MODE_S1 && pro == PRO_BN;     // convt5 only
-  if (sel == 4) return Cin == 16 && Cout == 24 && mode == MODE_S1 && pro == PRO_BN;    // conv5 only
-  if (sel == 5) return Cin >= 16;                                                      // every layer with >= 16 input channels
-  if (sel == 6) return Cin >= 16 && !(mode == MODE_DOWN && pro == PRO_BN);             // ... except the stride-2 forward layers
-  if (sel == 7) return Cin >= 16 && mode != MODE_DOWN && pro == PRO_BN;                // forward layers only, not stride 2
-  if (sel == 8) return Cin == 16 && pro == PRO_BN;                                     // the 16-channel forward layers
-  if (sel == 9) return Cin == 16 && mode == MODE_S1 && pro == PRO_BN;                  // conv5 + convt5
-  if (sel == 10) return Cin >= 16;                                                     // the table before conv2 / conv3 joined
-  return Cin >= 16 || pro == PRO_BN;
-}
 
 // ACT: storage type of the activations this launch touches -- the input of a forward layer (PRO_BN), the saved
 // activation in2 of the ReLU/BatchNorm-backward prologue (PRO_BWD), the raw x of the BatchNorm-backward sums (EPI_BWD)
 // and the output of a forward layer (EPI_FWD).  Gradients (PRO_BWD / PRO_ID inputs, EPI_BWD outputs) are always fp32.
-// RECOMP (conv2's forward): the 8-channel input y1 = relu(conv1(bn1 x)) is not in memory; the staging waves build its
-// window from the x window (conv_recomp.h), a.in is x.
 // LIMB: the products run on v_mfma_f32_16x16x32_bf16 with fp32 operands split into three bf16 limbs (six limb products,
 // fp32-faithful; conv_common.h / conv_mfma.h): the staging waves write limb planes, the matrix-core waves hold limb weights.
-template <int CIN, int COUT, int MODE, int PRO, int EPI, int TW, int TH, bool MSPLIT, bool PAIR, typename ACT, bool RECOMP = false,
-          bool LIMB = false>
+template <int CIN, int COUT, int MODE, int PRO, int EPI, int TW, int TH, bool MSPLIT, bool PAIR, typename ACT, bool LIMB = false>
 __global__ __launch_bounds__(512) void conv3x3_mfma_ws_kernel(const ConvArgs a) {
   using G = Geom<MODE, TW, TH>;
   using TIN = typename std::conditional<PRO == PRO_BN, ACT, float>::type;
@@ -84,26 +40,23 @@ __global__ __launch_bounds__(512) void conv3x3_mfma_ws_kernel(const ConvArgs a) 
   static_assert(!MSPLIT || MTA == 2, "MSPLIT deals exactly two cout tiles to the wave pairs");
   static_assert(!PAIR || (MODE == MODE_S1 && COUT == 8 && !MSPLIT && TH % 2 == 0), "PAIR: stride 1, 8 output channels");
   constexpr int NCLS = n_classes<MODE>();
-  static_assert(!LIMB || (!RECOMP && CIN % 8 == 0), "limb planes are made of channel octets");
+  static_assert(!LIMB || CIN % 8 == 0, "limb planes are made of channel octets");
   // bf16 arithmetic (act_dtype = bfloat16: BASELINE configs[4] "bf16 conv"): weights rounded to bfloat16 (one limb), and in a
   // forward launch the rounded BatchNorm outputs are one plane (TileStager::BF16_MATH) -- one product instead of six; a
   // data-gradient launch keeps its fp32 gradient in three planes (three products)
   constexpr bool BF16M = std::is_same<ACT, ava_bf16>::value;
   constexpr int NLW = BF16M ? 1 : 3, NLB = ava_stager_limbs<TIN, PRO>();
-  constexpr int NPIXP = ava_plane_pix(IR * IC);                               // octet-plane stride of the limb image (pixels)
+  constexpr int NPIXP = IR * IC;                               // octet-plane stride of the limb image (pixels)
   constexpr int TILE_F = LIMB ? NPIXP * CIN * NLB / 2 : IR * IC * CIN;        // floats; LIMB: NLB bf16 planes
   extern __shared__ __align__(16) float smem[];
   float* tile0 = smem;                      // two tile buffers
   float* coef = smem + 2 * TILE_F;          // [3][32]
   float* red = coef + 96;                   // [4][2*16*MTA]
-  float* xs = red + 4 * 32 * MTA;           // RECOMP: the staging waves' private x windows
-  static_assert(!RECOMP || (CIN == 8 && PRO == PRO_BN && IR == 9), "conv1 is recomputed in front of conv2's forward only (9-row windows)");
   __shared__ double accvals[64];            // consumer prologue scratch (bn_coef_from_acc)
 
   const int t = threadIdx.x, lane = t & 63, wave8 = t >> 6;
   const bool stager = wave8 < 4;
   const int wave = wave8 & 3;
-  AVA_STAMP(0, t == 0);
   const int n = lane & 15, kg = lane >> 4;
   auto origin = [&](int tl, int& b, int& oy0, int& ox0, int& gy0, int& gx0) {
     b = tl / (a.tiles_y * a.tiles_x);
@@ -115,33 +68,30 @@ __global__ __launch_bounds__(512) void conv3x3_mfma_ws_kernel(const ConvArgs a) 
     else { gy0 = oy0 / 2; gx0 = ox0 / 2; }
   };
   TileWalk walk(a.ntiles);
-  typename std::conditional<RECOMP, Y1MfmaStager<IC, ACT>,
-                            typename std::conditional<LIMB, TileStagerL<CIN, PRO, IR, IC, 256, TIN, ACT>,
-                                                      TileStager<CIN, PRO, IR, IC, false, 256, TIN, ACT>>::type>::type stg;   // staging waves only (threadIdx.x 0..255)
+  typename std::conditional<LIMB, TileStagerL<CIN, PRO, IR, IC, 256, TIN, ACT>,
+                            TileStager<CIN, PRO, IR, IC, 256, TIN, ACT>>::type stg;   // staging waves only (threadIdx.x 0..255)
   // DEEP: the limb tiles of the stride-2 layers with >= 16 channels fill the LDS of a CU with ONE workgroup (two buffers of
   // 56 / 43 KB), so one tile in flight per workgroup is all the memory-level parallelism the CU has: the staging waves hold
   // TWO tiles in registers (the workgroup's 8 waves may use 256 VGPRs each) and request tile it+3 while tile it+1 is converted
   // (two register sets of NPF float4 -- twice that with the saved activation of PRO_BWD -- must leave room: <= 128 VGPRs)
   constexpr int STG_NPF = (IR * IC * (CIN / 4) + 255) / 256;
-  constexpr bool DEEP = LIMB && !RECOMP && (size_t)2 * TILE_F * sizeof(float) > 80 * 1024 &&
+  constexpr bool DEEP = LIMB && (size_t)2 * TILE_F * sizeof(float) > 80 * 1024 &&
                         STG_NPF * (PRO == PRO_BWD ? 2 : 1) * 8 <= 128;
   decltype(stg) stg2;
   auto stg_store = [&](float* tile) __attribute__((always_inline)) {
-    if (AVA_ABL(2)) return;
-    if constexpr (RECOMP) stg.store(tile, coef, xs);
-    else if constexpr (LIMB) stg.store(reinterpret_cast<unsigned char*>(tile), coef);
+    if constexpr (LIMB) stg.store(reinterpret_cast<unsigned char*>(tile), coef);
     else stg.store(tile, coef);
   };
   // stride-2 gathers hold the most staging registers: keeping their first tile in flight across the prologue raised
   // conv2's forward from 70 to 112 VGPRs (3 -> 2 resident workgroups per CU, 42 -> 50 us); they load after it instead
   constexpr bool HOIST = MODE != MODE_DOWN || DEEP;
   if (stager) {
-    if constexpr (RECOMP) stg.init(a.rc, xs); else stg.init();
+    stg.init();
     if constexpr (DEEP) stg2.init();
     if (HOIST && walk.valid()) {                                // tile 0 goes in flight BEFORE the coefficient prologue
       int b, oy0, ox0, gy0, gx0;
       origin(walk.cur, b, oy0, ox0, gy0, gx0);
-      if (!AVA_ABL(4)) stg.load(a.in, a.in2, b, a.Hi, a.Wi, gy0, gx0);
+      stg.load(a.in, a.in2, b, a.Hi, a.Wi, gy0, gx0);
     }
   }
   // The matrix-core waves touch the packed weights now: their fragment loads come after the coefficient barrier, where a
@@ -172,7 +122,6 @@ __global__ __launch_bounds__(512) void conv3x3_mfma_ws_kernel(const ConvArgs a) 
   }
   __syncthreads();                          // coef[] visible
   if (!stager) asm volatile("" ::"v"(wpf));
-  AVA_STAMP(1, t == 0);
 
   if (stager) {
     // ---------------- staging waves ----------------
@@ -210,13 +159,12 @@ __global__ __launch_bounds__(512) void conv3x3_mfma_ws_kernel(const ConvArgs a) 
     if (walk.valid()) {
       if (!HOIST) {
         origin(walk.cur, b, oy0, ox0, gy0, gx0);
-        if (!AVA_ABL(4)) stg.load(a.in, a.in2, b, a.Hi, a.Wi, gy0, gx0);
+        stg.load(a.in, a.in2, b, a.Hi, a.Wi, gy0, gx0);
       }
       stg_store(tile0);                                         // tile 0 -> buffer 0
-      AVA_STAMP(2, t == 0);
       if (walk.has_next()) {
         origin(walk.next(), b, oy0, ox0, gy0, gx0);
-        if (!AVA_ABL(4)) stg.load(a.in, a.in2, b, a.Hi, a.Wi, gy0, gx0);         // tile 1 in flight
+        stg.load(a.in, a.in2, b, a.Hi, a.Wi, gy0, gx0);         // tile 1 in flight
       }
     }
     __syncthreads();                                            // (A) tile 0 ready
@@ -228,7 +176,7 @@ __global__ __launch_bounds__(512) void conv3x3_mfma_ws_kernel(const ConvArgs a) 
         const int nn = walk.next() + walk.step;
         if (nn < walk.end) {
           origin(nn, b, oy0, ox0, gy0, gx0);
-          if (!AVA_ABL(4)) stg.load(a.in, a.in2, b, a.Hi, a.Wi, gy0, gx0);
+          stg.load(a.in, a.in2, b, a.Hi, a.Wi, gy0, gx0);
         }
       }
       __syncthreads();                                          // (B) tile it consumed, tile it+1 ready
@@ -303,9 +251,7 @@ __global__ __launch_bounds__(512) void conv3x3_mfma_ws_kernel(const ConvArgs a) 
       }
   };
   if (EPI == EPI_BWD && walk.valid()) load_ex(walk.cur);
-  AVA_STAMP(3, t == 256);
   __syncthreads();                                              // (A)
-  AVA_STAMP(4, t == 256);
   int it = 0;
   for (; walk.valid(); walk.advance(), ++it) {
     int b, oy0, ox0, gy0, gx0;
@@ -327,8 +273,7 @@ __global__ __launch_bounds__(512) void conv3x3_mfma_ws_kernel(const ConvArgs a) 
       for (int h = 0; h < 2; ++h)
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) acc[h][mt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-      if (AVA_ABL(1)) {
-      } else if (MODE == MODE_UP) {
+      if (MODE == MODE_UP) {
         const int cls = gi & 3, r = g >> 2;
         const auto px = pxp(tile, r * IC);
         if (cls == 0) f0.run(px, acc);
@@ -363,14 +308,12 @@ __global__ __launch_bounds__(512) void conv3x3_mfma_ws_kernel(const ConvArgs a) 
               s2[mt][r] = fmaf(v[r], xr[r], s2[mt][r]);      // raw x: centred after the loop
             }
           }
-          if (obase != nullptr && !AVA_ABL(8)) ava_st4_wt<TOUT>(obase + gout + 16 * (mtb + mt), avaf4{v[0], v[1], v[2], v[3]});
+          if (obase != nullptr) ava_st4<TOUT>(obase + gout + 16 * (mtb + mt), avaf4{v[0], v[1], v[2], v[3]});
         }
       }
     }
-    AVA_STAMP(5 + (it < 4 ? it : 4), t == 256);
     __syncthreads();                                            // (B)
   }
-  AVA_STAMP(10, t == 256);
   // ---- per-workgroup partial statistics (matrix-core waves only) ----
   if (MSPLIT) {                              // a wave only fills its own cout tile: the other slots must read as 0
     const int tz = t - 256;
@@ -410,72 +353,52 @@ __global__ __launch_bounds__(512) void conv3x3_mfma_ws_kernel(const ConvArgs a) 
         (red[idx] + red[32 * MTA + idx]) + (red[64 * MTA + idx] + red[96 * MTA + idx]);
     for (int r = gridDim.x + blockIdx.x; r < a.part_rows; r += gridDim.x) a.partials[(size_t)r * 2 * COUT + tc] = 0.f;
   }
-  AVA_STAMP(11, t == 256);
   __syncthreads();
-  AVA_STAMP(12, t == 256);
 }
 
-template <int CIN, int COUT, int MODE, int PRO, int EPI, int TW, int TH, typename ACT, bool RECOMP = false, bool LIMB = false>
+template <int CIN, int COUT, int MODE, int PRO, int EPI, int TW, int TH, typename ACT, bool LIMB = false>
 int launch_mfma_ws_t(const ConvArgs& a, int grid, hipStream_t st) {
   using G = Geom<MODE, TW, TH>;
   constexpr int MT = (COUT + 15) / 16;
   constexpr bool MSPLIT = MT == 2 && CIN >= 16;     // same rules as launch_mfma
   constexpr bool PAIR = MODE == MODE_S1 && COUT == 8;
-  constexpr int XS_F = RECOMP ? Y1MfmaStager<G::IC, ACT>::LDS_FLOATS : 0;
   using TIN = typename std::conditional<PRO == PRO_BN, ACT, float>::type;
   constexpr int NLB = ava_stager_limbs<TIN, PRO>();                 // limb planes of the staged operand (kernel: TILE_F)
-  const size_t lds = (size_t)(2 * (LIMB ? ava_plane_pix(G::IR * G::IC) * CIN * NLB / 2 : G::IR * G::IC * CIN) + 96 + 4 * 32 * MT + XS_F) * sizeof(float);
+  const size_t lds = (size_t)(2 * (LIMB ? (G::IR * G::IC) * CIN * NLB / 2 : G::IR * G::IC * CIN) + 96 + 4 * 32 * MT) * sizeof(float);
   static bool attr_set = false;
   if (!attr_set && lds > 64 * 1024) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_mfma_ws_kernel<CIN, COUT, MODE, PRO, EPI, TW, TH, MSPLIT, PAIR, ACT, RECOMP, LIMB>),
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_mfma_ws_kernel<CIN, COUT, MODE, PRO, EPI, TW, TH, MSPLIT, PAIR, ACT, LIMB>),
                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
       return AVA_ELAUNCH;
     attr_set = true;
   }
   ConvArgs b = a;
-#ifdef AVA_LAB
-  b.stamps = ava_lab_next_stamps();
-#endif
   b.tiles_y = a.Ho / TH;
   b.tiles_x = a.Wo / TW;
   b.ntiles = a.B * b.tiles_y * b.tiles_x;
   int per_cu = 1;
   static int resident = 0;
   if (resident == 0) {
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(&conv3x3_mfma_ws_kernel<CIN, COUT, MODE, PRO, EPI, TW, TH, MSPLIT, PAIR, ACT, RECOMP, LIMB>), 512, lds) != hipSuccess || per_cu < 1) per_cu = 1;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(&conv3x3_mfma_ws_kernel<CIN, COUT, MODE, PRO, EPI, TW, TH, MSPLIT, PAIR, ACT, LIMB>), 512, lds) != hipSuccess || per_cu < 1) per_cu = 1;
     resident = per_cu * 256;
   }
   b.part_rows = grid;
   if (grid > b.ntiles) grid = b.ntiles;
   if (grid > ava_scale_grid(resident)) grid = ava_scale_grid(resident);
-  { const char* e = ava_env("AVA_GRID"); if (e) grid = atoi(e); if (grid > b.ntiles) grid = b.ntiles; if (grid > b.part_rows) grid = b.part_rows; }
-  hipLaunchKernelGGL((conv3x3_mfma_ws_kernel<CIN, COUT, MODE, PRO, EPI, TW, TH, MSPLIT, PAIR, ACT, RECOMP, LIMB>), dim3(grid), dim3(512), lds, st, b);
+  hipLaunchKernelGGL((conv3x3_mfma_ws_kernel<CIN, COUT, MODE, PRO, EPI, TW, TH, MSPLIT, PAIR, ACT, LIMB>), dim3(grid), dim3(512), lds, st, b);
   AVA_CHECK_LAUNCH();
   return AVA_OK;
 }
 
 template <int CIN, int COUT, int MODE, int PRO, int EPI, int TW, int TH>
 int launch_mfma_ws(const ConvArgs& a, int grid, hipStream_t st) {
-  if constexpr (CIN == 8 && COUT == 8 && MODE == MODE_DOWN && PRO == PRO_BN && EPI == EPI_FWD) {
-    if (a.rc.G1 != nullptr) {             // conv2's forward on a recomputed y1 (a.in = x)
-      if (a.act_bf16) return launch_mfma_ws_t<CIN, COUT, MODE, PRO, EPI, TW, TH, ava_bf16, true>(a, grid, st);
-      return launch_mfma_ws_t<CIN, COUT, MODE, PRO, EPI, TW, TH, float, true>(a, grid, st);
-    }
+  if constexpr (CIN % 8 == 0 && (CIN >= 16 || PRO == PRO_BN)) {     // the limb form: see the table at the top
+    if (a.act_bf16) return launch_mfma_ws_t<CIN, COUT, MODE, PRO, EPI, TW, TH, ava_bf16, true>(a, grid, st);
+    return launch_mfma_ws_t<CIN, COUT, MODE, PRO, EPI, TW, TH, float, true>(a, grid, st);
+  } else {
+    if (a.act_bf16) return launch_mfma_ws_t<CIN, COUT, MODE, PRO, EPI, TW, TH, ava_bf16>(a, grid, st);
+    return launch_mfma_ws_t<CIN, COUT, MODE, PRO, EPI, TW, TH, float>(a, grid, st);
   }
-  if (a.rc.G1 != nullptr) return AVA_EINVAL;
-#ifdef AVA_LAB
-  constexpr bool kLimbBuilt = CIN % 8 == 0;
-#else
-  constexpr bool kLimbBuilt = CIN % 8 == 0 && (CIN >= 16 || PRO == PRO_BN);
-#endif
-  if constexpr (kLimbBuilt) {
-    if (conv_limb_on(CIN, COUT, MODE, PRO)) {
-      if (a.act_bf16) return launch_mfma_ws_t<CIN, COUT, MODE, PRO, EPI, TW, TH, ava_bf16, false, true>(a, grid, st);
-      return launch_mfma_ws_t<CIN, COUT, MODE, PRO, EPI, TW, TH, float, false, true>(a, grid, st);
-    }
-  }
-  if (a.act_bf16) return launch_mfma_ws_t<CIN, COUT, MODE, PRO, EPI, TW, TH, ava_bf16>(a, grid, st);
-  return launch_mfma_ws_t<CIN, COUT, MODE, PRO, EPI, TW, TH, float>(a, grid, st);
 }
 
 template <int CIN, int COUT, int MODE, int TW, int TH>

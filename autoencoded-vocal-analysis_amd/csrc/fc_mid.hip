@@ -93,17 +93,7 @@ struct FcMidFwdArgs {
   float *mu, *u, *logd, *d, *z, *lat_sums, *h5, *h6;
   int* status;
   int B, zdim;
-  unsigned long long* stamps;            // lab only
 };
-
-// lab: stage time stamps (s_memrealtime, 100 MHz) of workgroup 0 / wave 0, written to a caller-given buffer (tools/lab/fc_mid_probe.py)
-#ifdef AVA_LAB
-static unsigned long long* g_fm_stamps = nullptr;
-extern "C" int ava_fc_mid_debug_stamps(unsigned long long* p) { g_fm_stamps = p; return 0; }
-#define FM_STAMP(i) do { if (a.stamps != nullptr && blockIdx.x == 0 && t == 0) a.stamps[i] = __builtin_amdgcn_s_memrealtime(); } while (0)
-#else
-#define FM_STAMP(i) do { } while (0)
-#endif
 
 #define FM_LD(n) ((((n) + 15) & ~15) + 4)          // padded row length: rows 4 banks apart, 16-byte aligned
 #define FM_THREADS 1024                            // 16 waves: every stage is ONE pass of <= 16 column tiles, one row per wave
@@ -120,7 +110,6 @@ __global__ __launch_bounds__(FM_THREADS) void fc_mid_fwd_kernel(const FcMidFwdAr
   constexpr int L3 = FM_LD(192), LZ = FM_LD(128), L5 = FM_LD(64);
   const int ztiles = (z + 15) >> 4;
 
-  FM_STAMP(0);
   // the heads' weights (24 KB) and fc6's (64 KB: the largest, needed last) are requested before anything else
   FmWTile<64> w4;
   const int hh = wave / ztiles, hnt = wave - hh * ztiles;                 // head and column tile of this wave (wave < 3 ztiles)
@@ -131,8 +120,6 @@ __global__ __launch_bounds__(FM_THREADS) void fc_mid_fwd_kernel(const FcMidFwdAr
   fm_load_rows(s_h3, L3, a.h3, 192, r0, B, 192, t, FM_THREADS);
   for (int e = t; e < 16 * LZ; e += FM_THREADS) s_z[e] = 0.f;            // k padding of fc5's operand
   __syncthreads();
-  FM_STAMP(1);
-  FM_STAMP(2);
 
   // ---- heads: mu | u | log d = h3[:, 64 h : 64 h + 64] W4h^T + b4h; fc5's weights and the noise are requested first ----
   FmWTile<128> w5;
@@ -181,7 +168,6 @@ __global__ __launch_bounds__(FM_THREADS) void fc_mid_fwd_kernel(const FcMidFwdAr
     }
   }
   __syncthreads();
-  FM_STAMP(3);
 
   // ---- rsample + entropy (misc.hip: latent_fwd_kernel, same operations in the same order): one row per wave ----
   if (brow < B) {                                                          // wave-uniform
@@ -216,7 +202,6 @@ __global__ __launch_bounds__(FM_THREADS) void fc_mid_fwd_kernel(const FcMidFwdAr
     }
   }
   __syncthreads();
-  FM_STAMP(4);
 
   // ---- h5 = relu(z W5^T + b5): 4 column tiles ----
   if (wave < 4) {
@@ -232,7 +217,6 @@ __global__ __launch_bounds__(FM_THREADS) void fc_mid_fwd_kernel(const FcMidFwdAr
     }
   }
   __syncthreads();
-  FM_STAMP(5);
 
   // ---- h6 = relu(h5 W6^T + b6): 16 column tiles ----
   {
@@ -245,7 +229,6 @@ __global__ __launch_bounds__(FM_THREADS) void fc_mid_fwd_kernel(const FcMidFwdAr
       if (r0 + row < B) a.h6[(size_t)(r0 + row) * 256 + n] = fmaxf(acc[r] + bias, 0.f);
     }
   }
-  FM_STAMP(6);
 }
 
 struct FcMidBwdArgs {
@@ -256,7 +239,6 @@ struct FcMidBwdArgs {
   const float* scale;                    // d(result)/d(loss) (null: 1), see latent_bwd_kernel
   float *dh5, *dz, *dmu, *du, *dlogd, *dh3, *dh2;
   int B, zdim;
-  unsigned long long* stamps;            // lab only
 };
 
 __global__ __launch_bounds__(FM_THREADS) void fc_mid_bwd_kernel(const FcMidBwdArgs a) {
@@ -366,21 +348,13 @@ __global__ __launch_bounds__(FM_THREADS) void fc_mid_bwd_kernel(const FcMidBwdAr
   }
 }
 
-int ava_fc_mid_fwd(const FcMidFwdArgs& a_, hipStream_t st) {
-  FcMidFwdArgs a = a_;
+int ava_fc_mid_fwd(const FcMidFwdArgs& a, hipStream_t st) {
   if (a.B < 1 || a.zdim < 1 || a.zdim > 128) return AVA_EINVAL;
-#ifdef AVA_LAB
-  a.stamps = g_fm_stamps;
-#else
-  a.stamps = nullptr;
-#endif
   hipLaunchKernelGGL(fc_mid_fwd_kernel, dim3((a.B + 15) / 16), dim3(FM_THREADS), 0, st, a);
   AVA_CHECK_LAUNCH();
   return AVA_OK;
 }
-int ava_fc_mid_bwd(const FcMidBwdArgs& a_, hipStream_t st) {
-  FcMidBwdArgs a = a_;
-  a.stamps = nullptr;
+int ava_fc_mid_bwd(const FcMidBwdArgs& a, hipStream_t st) {
   if (a.B < 1 || a.zdim < 1 || a.zdim > 128) return AVA_EINVAL;
   hipLaunchKernelGGL(fc_mid_bwd_kernel, dim3((a.B + 15) / 16), dim3(FM_THREADS), 0, st, a);
   AVA_CHECK_LAUNCH();

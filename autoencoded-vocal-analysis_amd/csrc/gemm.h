@@ -18,7 +18,6 @@ struct GemmArgs {
   int splits;
   int act;
   int vec_a, vec_b;  // 16-byte loads legal
-  int dbg;           // lab build only: ablation bits of the limb kernel (1 no MFMA, 2 no split / LDS write, 4 no global loads, 8 no output)
 };
 
 #ifdef __HIPCC__

@@ -418,11 +418,8 @@ __global__ __launch_bounds__(512) void gemm_skinny_kernel(const GemmArgs g) {
 
 // products the skinny kernel takes: small output, A k-major, 16-byte alignable operands, no bias-gradient column sums
 static bool skinny_ok(const GemmArgs& g, int a_kmajor, int b_kmajor) {
-  static const bool on = [] { const char* e = ava_env("AVA_GEMM_SKINNY"); return e == nullptr || atoi(e) != 0; }();
-  static const int kmax = [] { const char* e = ava_env("AVA_GEMM_SKINNY_KMAX"); return e ? atoi(e) : 2048; }();
-  if (!on) return false;
   if (g.colsum != nullptr && a_kmajor) return false;         // column sums are taken from an m-major A
-  if ((size_t)g.M * g.N > 262144 || g.K > kmax) return false;
+  if ((size_t)g.M * g.N > 262144 || g.K > 2048) return false;
   if (a_kmajor && (g.K % 4 != 0 || g.lda % 4 != 0 || (reinterpret_cast<uintptr_t>(g.A) & 15) != 0)) return false;
   if (b_kmajor && (g.K % 4 != 0 || g.ldb % 4 != 0 || (reinterpret_cast<uintptr_t>(g.B) & 15) != 0)) return false;
   return true;
@@ -450,7 +447,6 @@ static void plan(int M, int N, int K, int* bm, int* splits, int* klen) {
   // of slabs instead of 32)
   const bool deep = M <= 256 && K >= 4096 && (size_t)M * N <= 262144;
   if (wide || deep) *bm = 64;
-  { const char* e = ava_env("AVA_GEMM_BM"); if (e && M <= 256) *bm = atoi(e); }      // lab: tile size for the M = batch shapes
   const int tiles = ceil_div(M, *bm) * ceil_div(N, *bm);
   int s = 1;
   if (tiles < 384) {
@@ -460,7 +456,6 @@ static void plan(int M, int N, int K, int* bm, int* splits, int* klen) {
     if (s > max_s) s = max_s;
     if (s < 1) s = 1;
   }
-  { const char* e = ava_env("AVA_GEMM_SPLITS"); if (e && tiles < 384) { s = atoi(e); if (s > K / 16) s = K / 16; if (s < 1) s = 1; } }
   int kl = ceil_div(ceil_div(K, s), 16) * 16;
   s = ceil_div(K, kl);
   *splits = s;
@@ -515,7 +510,6 @@ static int gemm_impl(const float* A, int lda, const float* B, int ldb, const flo
   plan(M, N, K, &bm, &splits, &klen);
   if (splits > 1 && (ws == nullptr || ws_bytes < ava_gemm_workspace_bytes(M, N, K))) return AVA_EWORKSPACE;
   GemmArgs g;
-  g.dbg = 0;
   g.A = A; g.B = B; g.bias = bias; g.colsum = colsum; g.mask = mask;
   g.C = splits > 1 ? reinterpret_cast<float*>(ws) : C;
   g.M = M; g.N = N; g.K = K;
@@ -565,16 +559,14 @@ static int gemm_impl(const float* A, int lda, const float* B, int ldb, const flo
     return AVA_OK;
   }
   dim3 grid(ceil_div(N, bm), ceil_div(M, bm), splits);
-  static int bk32 = -1;
-  if (bk32 < 0) { const char* e = ava_env("AVA_GEMM_BK"); bk32 = (e && atoi(e) == 16) ? 0 : 1; }
   if (!vec) {
     if (bm == 128) launch_gemm<128, 16, false>(g, a_kmajor, b_kmajor, grid, st);
     else launch_gemm<64, 16, false>(g, a_kmajor, b_kmajor, grid, st);
   } else if (bm == 128) {
-    if (bk32 && klen % 32 == 0) launch_gemm<128, 32, true>(g, a_kmajor, b_kmajor, grid, st);
+    if (klen % 32 == 0) launch_gemm<128, 32, true>(g, a_kmajor, b_kmajor, grid, st);
     else launch_gemm<128, 16, true>(g, a_kmajor, b_kmajor, grid, st);
   } else {
-    if (bk32 && klen % 32 == 0 && klen >= 512) launch_gemm<64, 32, true>(g, a_kmajor, b_kmajor, grid, st);   // the long-K 64-tile shapes
+    if (klen % 32 == 0 && klen >= 512) launch_gemm<64, 32, true>(g, a_kmajor, b_kmajor, grid, st);   // the long-K 64-tile shapes
     else launch_gemm<64, 16, true>(g, a_kmajor, b_kmajor, grid, st);
   }
   AVA_CHECK_LAUNCH();
@@ -608,7 +600,7 @@ int ava_gemm_grouped(const AvaGemmProblem* p, int n, int a_kmajor, int b_kmajor,
     g.lda = p[i].lda > 0 ? p[i].lda : (a_kmajor ? g.K : g.M);
     g.ldb = p[i].ldb > 0 ? p[i].ldb : (b_kmajor ? g.K : g.N);
     g.ldc = p[i].ldc > 0 ? p[i].ldc : g.N;
-    g.klen = ceil_div(g.K, 16) * 16; g.splits = 1; g.act = p[i].act; g.dbg = 0;
+    g.klen = ceil_div(g.K, 16) * 16; g.splits = 1; g.act = p[i].act;
     g.vec_a = (g.lda % 4 == 0) && ((reinterpret_cast<uintptr_t>(g.A) & 15) == 0) &&
               (a_kmajor ? g.K % 4 == 0 && g.K >= 4 : g.M % 4 == 0 && g.M >= 4);
     g.vec_b = (g.ldb % 4 == 0) && ((reinterpret_cast<uintptr_t>(g.B) & 15) == 0) &&

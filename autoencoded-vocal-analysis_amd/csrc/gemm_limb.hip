@@ -222,11 +222,11 @@ struct LimbItem { int m0, n0, split, kbeg, kend, bx; };
 // RING: operand tiles the staging waves keep in registers (loads RING - 1 steps ahead).  MINW: waves per SIMD the
 // register allocation must allow (4 = two 512-thread workgroups per CU: the staging waves of one workgroup then run
 // beside the matrix-core waves of the other, which matters because a staging wave alone is stalled half of the time).
-// NSW: staging waves (4, or 8: the split is the long pole of a K step, section 3 item 17 of DESIGN.md -- two staging waves
-// per SIMD share it beside one matrix-core wave); the workgroup has NSW + 4 waves.
-template <int BN, bool A_KMAJ, bool B_KMAJ, int RING, int MINW, int NSW = 4>
-__global__ __launch_bounds__(64 * (NSW + 4), MINW) void gemm_limb_kernel(const GemmArgs g, const int tiles_m, const int tiles_n,
-                                                                          const int nitems) {
+// The workgroup has NSW = 4 staging waves and 4 matrix-core waves.
+template <int BN, bool A_KMAJ, bool B_KMAJ, int RING, int MINW>
+__global__ __launch_bounds__(512, MINW) void gemm_limb_kernel(const GemmArgs g, const int tiles_m, const int tiles_n,
+                                                              const int nitems) {
+  constexpr int NSW = 4;
   constexpr int BM = 128, T = 64 * NSW, WM = BM / 2, WN = BN / 2, TM = WM / 16, TN = WN / 16;
   constexpr int A_BYTES = 3 * BM * 64, B_BYTES = 3 * BN * 64, BUF = A_BYTES + B_BYTES;
   __shared__ __align__(16) unsigned char smem[2 * BUF];
@@ -272,10 +272,8 @@ __global__ __launch_bounds__(64 * (NSW + 4), MINW) void gemm_limb_kernel(const G
     auto load_step = [&](auto slot) __attribute__((always_inline)) {
       constexpr int SLOT = decltype(slot)::value;
       if (l_k == li.kbeg) { la.init(li.m0, g.M, g.lda); lb.init(li.n0, g.N, g.ldb); }
-      if (!AVA_DBG_BIT(g, 4)) {
-        la.template load<SLOT>(g.A, g.lda, l_k, li.kend, g.K);
-        lb.template load<SLOT>(g.B, g.ldb, l_k, li.kend, g.K);
-      }
+      la.template load<SLOT>(g.A, g.lda, l_k, li.kend, g.K);
+      lb.template load<SLOT>(g.B, g.ldb, l_k, li.kend, g.K);
       l_k += LBK;
       if (l_k >= li.kend) {
         l_it += it_step;
@@ -285,10 +283,8 @@ __global__ __launch_bounds__(64 * (NSW + 4), MINW) void gemm_limb_kernel(const G
     auto store_step = [&](auto slot, int buf) __attribute__((always_inline)) {
       constexpr int SLOT = decltype(slot)::value;
       unsigned char* S_ = smem + buf * BUF;
-      if (!AVA_DBG_BIT(g, 2)) {
-        la.template store<SLOT, !A_KMAJ>(S_);
-        lb.template store<SLOT, false>(S_ + A_BYTES);
-      }
+      la.template store<SLOT, !A_KMAJ>(S_);
+      lb.template store<SLOT, false>(S_ + A_BYTES);
       s_k += LBK;
       if (s_k >= si.kend) {             // last step of an item: its column sums (bias gradient) are complete
         if constexpr (!A_KMAJ) {
@@ -371,7 +367,6 @@ __global__ __launch_bounds__(64 * (NSW + 4), MINW) void gemm_limb_kernel(const G
       for (int i = 0; i < TM; ++i)
 #pragma unroll
         for (int l = 0; l < 3; ++l) af[i][l] = *reinterpret_cast<const bf16x8*>(As + l * BM * 64 + i * 1024);
-      if (!AVA_DBG_BIT(g, 1))
 #pragma unroll
       for (int j = 0; j < TN; ++j) {
         bf16x8 bf[3];
@@ -400,7 +395,7 @@ __global__ __launch_bounds__(64 * (NSW + 4), MINW) void gemm_limb_kernel(const G
     // dW products and split-K slabs: nothing to add or mask -- keep the per-element activation switch out of the store loop
     const bool plain = !fin || (g.bias == nullptr && g.mask == nullptr && g.act == ACT_NONE);
     const bool relu = g.act == ACT_RELU;         // (ava_gemm_limb_ok admits ACT_NONE and ACT_RELU only)
-    if (!AVA_DBG_BIT(g, 8) && plain) {
+    if (plain) {
 #pragma unroll
       for (int i = 0; i < TM; ++i) {
         const int gm = ci.m0 + wm * WM + i * 16 + fr;
@@ -412,7 +407,7 @@ __global__ __launch_bounds__(64 * (NSW + 4), MINW) void gemm_limb_kernel(const G
           *reinterpret_cast<f32x4*>(obase + (size_t)gm * ldo + gn) = acc[i][j];
         }
       }
-    } else if (!AVA_DBG_BIT(g, 8)) {
+    } else {
       // row tiles outermost: consecutive store instructions of a wave then write neighbouring 64-byte pieces of the SAME
       // 16 output rows (4 kg quads x 16 bytes per row and instruction), which the L2 merges into full lines
       float4 bq[TN];
@@ -457,8 +452,7 @@ static bool limb_shape(int M, int N, int K) {
 }
 
 bool ava_gemm_limb_ok(const GemmArgs& g, int a_kmajor, int b_kmajor) {
-  static const bool on = [] { const char* e = ava_env("AVA_GEMM_LIMB"); return e == nullptr || atoi(e) != 0; }();
-  if (!on || !limb_shape(g.M, g.N, g.K) || !g.vec_a || !g.vec_b) return false;
+  if (!limb_shape(g.M, g.N, g.K) || !g.vec_a || !g.vec_b) return false;
   if ((a_kmajor || b_kmajor) && g.K % 8 != 0) return false;
   if (!a_kmajor && g.M % 4 != 0) return false;
   if (!b_kmajor && g.N % 4 != 0) return false;
@@ -476,8 +470,7 @@ void ava_gemm_limb_plan(int M, int N, int K, int a_kmajor, int* bn, int* splits,
   // 512-thread workgroups per CU, so 512 work items fill the chip once.  dW products (both operands K-strided: their
   // in-register transposition needs more registers than that occupancy leaves): 128 x 128 tiles, one workgroup per CU.
   // K is split until the chip is full (fp32 slabs + fixed-order reduce kernel), at least two K steps per item.
-  int b = a_kmajor ? 64 : 128;
-  { const char* e = ava_env("AVA_GEMM_LIMB_BN"); if (e && a_kmajor) b = atoi(e) == 128 ? 128 : 64; }
+  const int b = a_kmajor ? 64 : 128;
   const int tiles = ceil_div(M, 128) * ceil_div(N, b);
   const int want = b == 64 ? 512 : 256;
   int s = 1;
@@ -486,24 +479,12 @@ void ava_gemm_limb_plan(int M, int N, int K, int a_kmajor, int* bn, int* splits,
     const int max_s = K / 64 > 0 ? K / 64 : 1;
     if (s > max_s) s = max_s;
   }
-  { const char* e = ava_env("AVA_GEMM_LIMB_SPLITS"); if (e) { s = atoi(e); if (s < 1) s = 1; if (s > ceil_div(K, LBK)) s = ceil_div(K, LBK); } }
   int kl = ceil_div(ceil_div(K, s), LBK) * LBK;
   s = ceil_div(K, kl);
   *bn = b; *splits = s; *klen = kl;
 }
 
-template <int BN, int RING, int MINW, int NSW = 4>
-static void launch_limb(const GemmArgs& g, int a_k, int b_k, int tm, int tn, int nitems, int grid, hipStream_t st) {
-  const dim3 blk(64 * (NSW + 4));
-  if (a_k && b_k) hipLaunchKernelGGL((gemm_limb_kernel<BN, true, true, RING, MINW, NSW>), dim3(grid), blk, 0, st, g, tm, tn, nitems);
-  else if (a_k && !b_k) hipLaunchKernelGGL((gemm_limb_kernel<BN, true, false, RING, MINW, NSW>), dim3(grid), blk, 0, st, g, tm, tn, nitems);
-  else if (!a_k && b_k) hipLaunchKernelGGL((gemm_limb_kernel<BN, false, true, RING, MINW, NSW>), dim3(grid), blk, 0, st, g, tm, tn, nitems);
-  else hipLaunchKernelGGL((gemm_limb_kernel<BN, false, false, RING, MINW, NSW>), dim3(grid), blk, 0, st, g, tm, tn, nitems);
-}
-
-int ava_gemm_limb_launch(const GemmArgs& g0, int a_kmajor, int b_kmajor, int bn, hipStream_t st) {
-  GemmArgs g = g0;
-  { const char* e = ava_env("AVA_GEMM_LIMB_DBG"); g.dbg = e ? atoi(e) : 0; }
+int ava_gemm_limb_launch(const GemmArgs& g, int a_kmajor, int b_kmajor, int bn, hipStream_t st) {
   const int tm = ceil_div(g.M, 128), tn = ceil_div(g.N, bn), nitems = tm * tn * g.splits;
   static int cus = 0;
   if (cus == 0) {
@@ -514,11 +495,6 @@ int ava_gemm_limb_launch(const GemmArgs& g0, int a_kmajor, int b_kmajor, int bn,
   }
   const int resident = ava_scale_grid((bn == 64 ? 2 : 1) * cus);     // persistent workgroups: one resident wave of them
   int grid = nitems < resident ? nitems : resident;
-  { const char* e = ava_env("AVA_GEMM_LIMB_GRID"); if (e) { grid = atoi(e); if (grid > nitems) grid = nitems; if (grid < 1) grid = 1; } }
-#ifdef AVA_LAB
-  { static const int nsw = [] { const char* e = ava_env("AVA_GEMM_LIMB_NSW"); return e ? atoi(e) : 4; }();
-    if (nsw == 8 && bn == 128) { launch_limb<128, 4, 3, 8>(g, a_kmajor, b_kmajor, tm, tn, nitems, grid, st); AVA_CHECK_LAUNCH(); return AVA_OK; } }
-#endif
   if (bn == 64 && a_kmajor) {
     if (b_kmajor) hipLaunchKernelGGL((gemm_limb_kernel<64, true, true, 3, 4>), dim3(grid), dim3(512), 0, st, g, tm, tn, nitems);
     else hipLaunchKernelGGL((gemm_limb_kernel<64, true, false, 3, 4>), dim3(grid), dim3(512), 0, st, g, tm, tn, nitems);
@@ -526,9 +502,6 @@ int ava_gemm_limb_launch(const GemmArgs& g0, int a_kmajor, int b_kmajor, int bn,
     if (b_kmajor) hipLaunchKernelGGL((gemm_limb_kernel<128, false, true, 4, 2>), dim3(grid), dim3(512), 0, st, g, tm, tn, nitems);
     else hipLaunchKernelGGL((gemm_limb_kernel<128, false, false, 4, 2>), dim3(grid), dim3(512), 0, st, g, tm, tn, nitems);
   }
-#ifdef AVA_LAB
-  else if (bn == 128) launch_limb<128, 4, 2>(g, a_kmajor, b_kmajor, tm, tn, nitems, grid, st);
-#endif
   else return AVA_EINVAL;
   AVA_CHECK_LAUNCH();
   return AVA_OK;

@@ -33,9 +33,6 @@ int ava_bn_bwd_apply_to_nchw(const float* g, const float* f8, const float* A, co
 int ava_bn_finalize_bwd_ex(const float* partials, int nparts, int64_t n, int C, const float* gamma, const float* mean,
                            const float* invstd, float* dgamma, float* dbeta, float* A, float* Bc, float* Cc, int eval,
                            hipStream_t st);
-int ava_latent_bwd_scaled(const float* z, const float* dz_dec, const float* u, const float* d, const float* eps_w,
-                          const float* eps_d, float* dmu, float* du, float* dlogd, int B, int zdim, const float* scale,
-                          hipStream_t st);
 int ava_scale_backward_roots(float* seed, int64_t n, float* wg, int64_t nwg, long long* slot, const float* scale, hipStream_t st);
 int ava_adam_flat_guarded(float* p, const float* g, float* m, float* v, int64_t n, double lr, double beta1, double beta2,
                           double eps, int step, const int* skip_if_set, hipStream_t st);
@@ -54,7 +51,6 @@ struct FcMidFwdArgs {
   float *h3, *mu, *u, *logd, *d, *z, *lat_sums, *h5, *h6;
   int* status;
   int B, zdim;
-  unsigned long long* stamps;
 };
 struct FcMidBwdArgs {
   const float* dh6;
@@ -64,7 +60,6 @@ struct FcMidBwdArgs {
   const float* scale;
   float *dh5, *dz, *dmu, *du, *dlogd, *dh3, *dh2;
   int B, zdim;
-  unsigned long long* stamps;
 };
 int ava_fc_mid_fwd(const FcMidFwdArgs& a, hipStream_t st);
 int ava_fc_mid_bwd(const FcMidBwdArgs& a, hipStream_t st);
@@ -604,7 +599,6 @@ __global__ __launch_bounds__(256) void pack_stats_kernel(const PackTable tab, co
   }
 }
 
-static bool acc_enabled(bool bwd);
 static long long* acc_slot(ava_model* m, int slot);
 // x_stats != nullptr: also the bn1 input statistics of x_stats[n] (training forward); *nstats_out = partial rows written
 struct NoiseGen { float* eps; int64_t n; uint64_t seed, offset; };   // eps == nullptr: no noise to generate
@@ -628,8 +622,7 @@ static int pack_weights(ava_model* m, bool with_bwd, hipStream_t st, const float
   tab.keep0 = tab.keep1 = 0; tab.in_acc = nullptr;
   m->acc0_used = -1;
   mark(m, -1, st);
-  static const bool fuse = [] { const char* e = ava_env("AVA_PACK_STATS"); return e == nullptr || atoi(e) != 0; }();
-  if (x_stats != nullptr && nstats_out != nullptr && fuse && (reinterpret_cast<uintptr_t>(x_stats) & 15) == 0) {
+  if (x_stats != nullptr && nstats_out != nullptr && (reinterpret_cast<uintptr_t>(x_stats) & 15) == 0) {
     int64_t work = n / 4;                                  // same grid rule as ava_bn_stats (C = 1)
     int nstats = (int)((work + 256 * 8 - 1) / (256 * 8));
     if (nstats < 1) nstats = 1;
@@ -641,7 +634,7 @@ static int pack_weights(ava_model* m, bool with_bwd, hipStream_t st, const float
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     const bool capturing = hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone;
     if (capturing) m->acc0_slot = -1;
-    if (acc_enabled(false) && m->acc0_slot >= 0) {      // bn1's sums into the slot the previous pack launch zeroed
+    if (m->acc0_slot >= 0) {      // bn1's sums into the slot the previous pack launch zeroed
       tab.in_acc = acc_slot(m, m->acc0_slot);
       tab.keep0 = m->acc0_slot * AVA_ACC_SLOT_LL; tab.keep1 = tab.keep0 + AVA_ACC_SLOT_LL;
       m->acc0_used = m->acc0_slot;
@@ -672,18 +665,6 @@ static int pack_weights(ava_model* m, bool with_bwd, hipStream_t st, const float
   return AVA_OK;
 }
 
-#ifdef AVA_LAB
-// what-if probe (results are WRONG): AVA_SKIP_BN_FIN=1 drops the BatchNorm finalisation launches (the coefficient
-// buffers keep the values of the last full step), bounding what removing them from the critical path can gain
-static bool lab_skip_bn_fin() {
-  static const int v = [] { const char* e = ava_env("AVA_SKIP_BN_FIN"); return e ? atoi(e) : 0; }();
-  static int calls = 0;
-  return v != 0 && ++calls > 28 * 30;            // the first 30 steps run normally (finite coefficients)
-}
-#else
-static constexpr bool lab_skip_bn_fin() { return false; }
-#endif
-
 // ---- BatchNorm sums accumulated in the producing kernel and finalised in the consumer's prologue (bn_acc.h) ----------
 // Forward: BatchNorm j (input of layer j) when layer j runs the wave-specialised / plain matrix-core forward kernel (the
 // consumer side) and its input comes from such a kernel, from conv1's packed-FMA kernel (j = 1) or from the
@@ -692,33 +673,13 @@ static constexpr bool lab_skip_bn_fin() { return false; }
 // backward, or to the data-gradient kernel, of layer j-1 (j = 7: to bn8's layout kernel; j = 1: to conv1's packed-FMA backward;
 // j = 0: to the weight-gradient reduction that ends the pass): j = 13 .. 0.  Forward bn1's sums come from the pack launch,
 // which also zeroes the accumulators: two slots (0 and 28) alternate, the launch adds to the one its predecessor zeroed.
-static bool acc_enabled(bool bwd) {
-#ifdef AVA_LAB
-  static const int on = [] {
-    const char* e = ava_env("AVA_BN_ACC");
-    if (e != nullptr) return atoi(e);
-    // any kernel-selection switch may route a layer to a kernel without the accumulator hooks: finalisation launches then
-    static const char* const sel[] = {"AVA_CONV_FUSED", "AVA_FUSED_WS", "AVA_CONV_IMPL", "AVA_CONV_WS", "AVA_CONV_WS_BWD",
-                                      "AVA_THIN_WS", "AVA_THIN_FWD_DIRECT", "AVA_THIN_STATS_DIRECT", "AVA_UP88_DIRECT",
-                                      "AVA_PACK_STATS"};
-    for (const char* n : sel)
-      if (ava_env(n) != nullptr) return 0;
-    return 1;
-  }();
-  (void)bwd;
-  return on != 0;
-#else
-  (void)bwd;
-  return true;
-#endif
-}
 static bool acc_pair_fwd(const ava_model* m, int j) {
   (void)m;
-  return acc_enabled(false) && ((j >= 1 && j <= 6) || (j >= 7 && j <= 13));
+  return j >= 1 && j <= 13;
 }
 static bool acc_pair_bwd(const ava_model* m, int j) {
   (void)m;
-  return acc_enabled(true) && (j >= 0 && j <= 13);
+  return j >= 0 && j <= 13;
 }
 static long long* acc_slot(ava_model* m, int slot) { return m->bn_acc + (size_t)slot * AVA_ACC_SLOT_LL; }
 static BnFin fin_none() { BnFin f = {}; f.acc = nullptr; return f; }
@@ -749,7 +710,6 @@ static BnFin fin_bwd(ava_model* m, int j, int B) {
 }
 
 static int finalize_fwd(ava_model* m, int l, int nparts, int64_t n, hipStream_t st) {
-  if (lab_skip_bn_fin()) return AVA_OK;
   const ConvLayer& L = kLayers[l];
   const int rc = ava_bn_finalize(m->bn_part, nparts, n, L.cin, PP(m, L.pg), PP(m, L.pbeta), m->bn_running + l * 32,
                                  m->bn_running + (NCONV + l) * 32, m->bn_batches + l, 1, bn_mean(m, l), bn_invstd(m, l),
@@ -758,7 +718,6 @@ static int finalize_fwd(ava_model* m, int l, int nparts, int64_t n, hipStream_t 
   return rc;
 }
 static int finalize_bwd(ava_model* m, int l, int nparts, int64_t n, hipStream_t st) {
-  if (lab_skip_bn_fin()) return AVA_OK;
   const ConvLayer& L = kLayers[l];
   // a forward in eval mode normalised with the running statistics: they are constants, so dx = gamma*invstd*g
   // (no batch-statistic terms); dgamma / dbeta keep their forms with xhat built from the running statistics
@@ -804,48 +763,20 @@ static int gemm_group(ava_model* m, const AvaGemmProblem* p, int n, int ak, int 
 enum { FC1 = 28, FC2 = 30, FC31 = 32, FC32 = 34, FC33 = 36, FC41 = 38, FC42 = 40, FC43 = 42, FC5 = 44, FC6 = 46,
        FC7 = 48, FC8 = 50 };
 
-// the version-0 (VALU) conv kernels have no NCHW second output: keep the transpose launch for them
-static bool conv7_writes_nchw() {
-  static const bool on = [] { const char* e = ava_env("AVA_CONV_IMPL"); return !(e != nullptr && strcmp(e, "valu") == 0); }();
-  return on;
-}
-
-// y1 recomputed instead of stored (conv_recomp.h).  Measured (profiles/r03): correct (bit-identical y1, all step tests
-// green) but SLOWER in this VALU form -- conv2's forward 44 -> 67 us (the staging waves' 9-tap recomputation costs ~40 us of
-// vector issue chip-wide) and the store-free conv1 pass takes the 36 us of the storing one (that kernel is bound by its
-// LDS-staged compute chain, not by its 128 MiB of stores).  Lab switch only (AVA_RECOMP_Y1=1); the product stores y1.
-static bool recomp_y1() {
-  static const bool on = [] { const char* e = ava_env("AVA_RECOMP_Y1"); return e != nullptr && atoi(e) != 0; }();
-  return on;
-}
 static RecompArgs recomp_args(ava_model* m) {
   RecompArgs rc;
   rc.G1 = m->Gf[0]; rc.bias1 = PP(m, kLayers[0].pb); rc.pa1 = bn_scale(m, 0); rc.pb1 = bn_shift(m, 0);
   return rc;
 }
-// Writes y1 into its workspace slot with the kernel (and therefore the arithmetic) whose store-free form took its
-// statistics: for debugging / the tests' mask read-back, and for backward kernels that still read the tensor.
-static int materialize_y1(ava_model* m, const float* x, int B, hipStream_t st) {
-  const ConvLayer& L = kLayers[0];
-  const LayerDims& D = m->lay[0];
-  ConvAcc acc;
-  acc.fin = fin_none(); acc.acc_out = nullptr;
-  TRY(ava_conv3x3_ex(x, nullptr, bn_scale(m, 0), bn_shift(m, 0), nullptr, m->Gf[0], PP(m, L.pb), m->X[1], nullptr, nullptr,
-                     nullptr, nullptr, m->bn_part, B, D.hi, D.wi, L.cin, L.cout, L.mode, PRO_BN, EPI_FWD, 1, 0.f, m->act_bf16,
-                     &acc, reinterpret_cast<ava_stream_t>(st)));
-  mark(m, CAT_CONV_FWD, st);
-  return AVA_OK;
-}
+// y1 is stored by conv1's forward.  Recomputing it in conv2's forward from x instead was measured (profiles/r03): correct
+// (bit-identical y1, all step tests green) but SLOWER -- conv2's forward 44 -> 67 us (the staging waves' 9-tap
+// recomputation costs ~40 us of vector issue chip-wide) and the store-free conv1 pass takes the 36 us of the storing one
+// (that kernel is bound by its LDS-staged compute chain, not by its 128 MiB of stores).  y1 is therefore always in its
+// workspace slot and there is nothing to materialise.
 extern "C" int ava_debug_materialize(ava_model* m, const float* x, int B, ava_stream_t s) {
+  (void)s;
   if (m == nullptr || x == nullptr || B < 1 || B > m->maxB) return AVA_EINVAL;
-  if (!recomp_y1()) return AVA_OK;
-  return materialize_y1(m, x, B, to_stream(s));
-}
-
-// the small fully connected middle as one launch per direction (fc_mid.hip); lab: AVA_FC_MID=0 keeps the separate launches
-static bool fc_mid_on() {
-  static const bool on = [] { const char* e = ava_env("AVA_FC_MID"); return e == nullptr || atoi(e) != 0; }();
-  return on;
+  return AVA_OK;
 }
 
 // stop_at_fc2 (historic name): stop behind fc31|32|33, the caller continues with the fused middle (forward_impl)
@@ -862,22 +793,17 @@ static int encoder_forward(ava_model* m, const float* x, int B, int train, float
   } else {
     TRY(bn_eval_all(m, st));       // all 14 layers from the running statistics (also serves the decoder)
   }
-  const bool rc1 = recomp_y1();
   for (int l = 0; l < 7; ++l) {
     const ConvLayer& L = kLayers[l];
     const LayerDims& D = m->lay[l];
-    // y1 = relu(conv1(bn1 x)) is never stored (conv_recomp.h): conv1's launch only takes bn2's batch statistics
-    // (training; nothing at all on running statistics) and conv2's kernel recomputes its y1 window from x
-    if (rc1 && l == 0 && !train) continue;
-    const float* in = (l == 0 || (rc1 && l == 1)) ? x : m->X[l];
-    float* out = l == 6 ? m->y7 : ((rc1 && l == 0) ? nullptr : m->X[l + 1]);
+    const float* in = l == 0 ? x : m->X[l];
+    float* out = l == 6 ? m->y7 : m->X[l + 1];
     // conv7's matrix-core kernel also writes the NCHW-flatten copy fc1 reads (saves the transpose launch)
-    float* nchw = (l == 6 && conv7_writes_nchw()) ? m->y7t : nullptr;
+    float* nchw = l == 6 ? m->y7t : nullptr;
     ConvAcc acc;
     acc.fin = (train && acc_pair_fwd(m, l)) ? fin_fwd(m, l, B) : fin_none();                 // BatchNorm l: finalised in this kernel
     if (train && l == 0 && m->acc0_used >= 0) { acc.fin = fin_fwd(m, 0, B); acc.fin.acc = acc_slot(m, m->acc0_used); }
     acc.acc_out = (train && l < 6 && acc_pair_fwd(m, l + 1)) ? acc_slot(m, l + 1) : nullptr;    // BatchNorm l+1: summed by this kernel
-    if (rc1 && l == 1) acc.rc = recomp_args(m);
     TRY(ava_conv3x3_ex(in, nullptr, bn_scale(m, l), bn_shift(m, l), nullptr, m->Gf[l], PP(m, L.pb), out, nchw,
                        nullptr, nullptr, nullptr, m->bn_part, B, D.hi, D.wi, L.cin, L.cout, L.mode, PRO_BN, EPI_FWD, 1,
                        0.f, m->act_bf16, &acc, reinterpret_cast<ava_stream_t>(st)));
@@ -885,7 +811,6 @@ static int encoder_forward(ava_model* m, const float* x, int B, int train, float
     if (train && l < 6 && acc.acc_out == nullptr)
       TRY(finalize_fwd(m, l + 1, ava_conv_grid(B, D.ho, D.wo, L.mode), (int64_t)B * D.ho * D.wo, st));
   }
-  if (!conv7_writes_nchw()) TRY(ava_nhwc_to_nchw(m->y7, m->y7t, B, m->P8, st));
   mark(m, CAT_LAYOUT, st);
   TRY(gemm(m, m->y7t, 0, PP(m, FC1), 0, PP(m, FC1 + 1), m->h1, 0, nullptr, nullptr, B, 1024, m->F, 1, 1, ACT_RELU, st));
   TRY(gemm(m, m->h1, 0, PP(m, FC2), 0, PP(m, FC2 + 1), m->h2, 0, nullptr, nullptr, B, 256, 1024, 1, 1, ACT_RELU, st));
@@ -905,10 +830,9 @@ static int encoder_forward(ava_model* m, const float* x, int B, int train, float
 static bool dd6_fused(const ava_model* m);
 static bool acc_pair_bwd(const ava_model* m, int j);
 // convt7's TRAINING forward also forms its weight-gradient partials and the BatchNorm-backward sums of its input
-// (conv_thin_kernels.h: FOLD).  Lab build: AVA_FOLD13=0 keeps the separate kernel in the backward.
+// (conv_thin_kernels.h: FOLD).
 static bool fold13_on(const ava_model* m) {
-  static const bool on = [] { const char* e = ava_env("AVA_FOLD13"); return e == nullptr || atoi(e) != 0; }();
-  return on && m->G != nullptr && acc_pair_bwd(m, 13) && m->lay[13].hi % 8 == 0;
+  return m->G != nullptr && acc_pair_bwd(m, 13) && m->lay[13].hi % 8 == 0;
 }
 
 // `fold`: the caller is a training forward a backward may follow (forward_impl)
@@ -970,28 +894,23 @@ static int forward_impl(ava_model* m, const float* x, int B, const float* eps_w,
   const int z = m->z;
   int pre = 0;
   TRY(pack_weights(m, true, st, bn_train ? x : nullptr, (int64_t)B * m->H * m->W, &pre, ng));
-  const bool mid = fc_mid_on();
-  TRY(encoder_forward(m, x, B, bn_train, m->mu, m->u, m->logd, ACT_NONE, st, pre, mid));
+  TRY(encoder_forward(m, x, B, bn_train, m->mu, m->u, m->logd, ACT_NONE, st, pre, true));
   mark(m, CAT_LAYOUT, st);
-  if (mid) {
-    // the three heads, rsample + entropy, fc5 and fc6: one launch (16 batch rows per workgroup, fc_mid.hip)
-    FcMidFwdArgs fa;
-    fa.h3_in = nullptr; fa.W3 = nullptr; fa.b3 = nullptr;
-    fa.W41 = PP(m, FC41); fa.b41 = PP(m, FC41 + 1); fa.W42 = PP(m, FC42); fa.b42 = PP(m, FC42 + 1);
-    fa.W43 = PP(m, FC43); fa.b43 = PP(m, FC43 + 1);
-    fa.W5 = PP(m, FC5); fa.b5 = PP(m, FC5 + 1); fa.W6 = PP(m, FC6); fa.b6 = PP(m, FC6 + 1);
-    fa.eps_w = eps_w; fa.eps_d = eps_d;
-    fa.h3 = m->h3; fa.mu = m->mu; fa.u = m->u; fa.logd = m->logd; fa.d = m->d; fa.z = m->zs; fa.lat_sums = m->lat_sums;
-    fa.h5 = m->h5; fa.h6 = m->h6; fa.status = status_out; fa.B = B; fa.zdim = z;
-    TRY(ava_fc_mid_fwd(fa, st));
-  } else {
-    TRY(ava_latent_fwd(m->mu, m->u, m->logd, eps_w, eps_d, m->d, m->zs, m->lat_sums, status_out, B, z, st));
-  }
+  // the three heads, rsample + entropy, fc5 and fc6: one launch (16 batch rows per workgroup, fc_mid.hip)
+  FcMidFwdArgs fa;
+  fa.h3_in = nullptr; fa.W3 = nullptr; fa.b3 = nullptr;
+  fa.W41 = PP(m, FC41); fa.b41 = PP(m, FC41 + 1); fa.W42 = PP(m, FC42); fa.b42 = PP(m, FC42 + 1);
+  fa.W43 = PP(m, FC43); fa.b43 = PP(m, FC43 + 1);
+  fa.W5 = PP(m, FC5); fa.b5 = PP(m, FC5 + 1); fa.W6 = PP(m, FC6); fa.b6 = PP(m, FC6 + 1);
+  fa.eps_w = eps_w; fa.eps_d = eps_d;
+  fa.h3 = m->h3; fa.mu = m->mu; fa.u = m->u; fa.logd = m->logd; fa.d = m->d; fa.z = m->zs; fa.lat_sums = m->lat_sums;
+  fa.h5 = m->h5; fa.h6 = m->h6; fa.status = status_out; fa.B = B; fa.zdim = z;
+  TRY(ava_fc_mid_fwd(fa, st));
   m->eps_w_last = eps_w;          // backward reads the same noise: the caller keeps it alive until then
   m->eps_d_last = eps_d;
   mark(m, CAT_LATENT_LOSS, st);
   m->fold13 = 0;
-  TRY(decoder_forward(m, m->zs, x, B, bn_train, m->xrec, st, mid, true));
+  TRY(decoder_forward(m, m->zs, x, B, bn_train, m->xrec, st, true, true));
   TRY(ava_elbo_finalize_strided(m->lat_sums, B, m->bn_part, m->sse_parts, 2, z, m->prec, m->H * m->W,
                                 loss_out != nullptr ? loss_out : m->loss_dev, loss_accum, st));
   mark(m, CAT_LATENT_LOSS, st);
@@ -1042,17 +961,14 @@ extern "C" int ava_decode(ava_model* m, const float* z, int B, int bn_train, flo
 // ---- all 14 weight-gradient reductions are issued per layer (partials buffer is shared) --------------
 // workgroups (= partial rows) of layer l's fused backward kernel; 0: the layer runs the separate kernels
 static int fused_grid(const ava_model* m, int l, int B) {
-  static const bool on = [] { const char* e = ava_env("AVA_CONV_FUSED"); return e == nullptr || atoi(e) != 0; }();
-  if (!on) return 0;
   const ConvLayer& L = kLayers[l];
   return ava_conv_fused_grid_for(B, m->lay[l].hi, m->lay[l].wi, L.cin, L.cout, L.mode);
 }
 
 // convt7's data gradient formed inside convt6's fused backward (the shape that kernel is instantiated for: W = 128 tiles of
-// 32 x 4 low-resolution pixels).  Lab build: AVA_DD6_FUSED=0 restores the separate data-gradient launch.
+// 32 x 4 low-resolution pixels).
 static bool dd6_fused(const ava_model* m) {
-  static const bool on = [] { const char* e = ava_env("AVA_DD6_FUSED"); return e == nullptr || atoi(e) != 0; }();
-  return on && fused_grid(m, 12, m->lastB > 0 ? m->lastB : 1) > 0 && m->lay[12].wi % 32 == 0 && m->lay[12].hi % 4 == 0;
+  return fused_grid(m, 12, m->lastB > 0 ? m->lastB : 1) > 0 && m->lay[12].wi % 32 == 0 && m->lay[12].hi % 4 == 0;
 }
 
 int ava_conv3x3_wgrad_pair(const WgradCall& p, const WgradCall& q, int B, int act_bf16, ava_stream_t s);
@@ -1217,7 +1133,6 @@ static int backward_part0(ava_model* m, const float* x, int B, hipStream_t st, b
   mark(m, -1, st);
   if (m->bwd_scale != nullptr) {       // d(result)/d(loss) may differ from 1: scale the roots of the backward (here and latent_bwd)
     const bool folded = m->fold13 && dd6_fused(m);          // ... and what convt7's forward left behind for this backward
-    // (a lab build without the fused gather reruns the separate kernel on the scaled seed instead: conv_layer_backward)
     TRY(ava_scale_backward_roots(m->seed, (int64_t)B * m->H * m->W, folded ? m->wg_part[13] : nullptr,
                                  folded ? (int64_t)m->wg13_rows * 73 : 0, folded ? acc_slot(m, 14 + 13) : nullptr, m->bwd_scale, st));
     mark(m, CAT_LAYOUT, st);
@@ -1255,32 +1170,16 @@ static int backward_part1(ava_model* m, const float* x, int B, hipStream_t st) {
   // issued in place and the eight small ones are collected into ONE grouped launch at the end. ----
   TRY(gemm(m, m->dF8, 0, PP(m, FC8), 0, nullptr, m->dh7, 0, m->h7, nullptr, B, 1024, m->F, 1, 0, ACT_NONE, st));
   TRY(gemm(m, m->dh7, 0, PP(m, FC7), 0, nullptr, m->dh6, 0, m->h6, nullptr, B, 256, 1024, 1, 0, ACT_NONE, st));
-  if (fc_mid_on()) {
-    // dh6 -> dh5 -> dz -> latent backward -> dh3 in one launch (fc_mid.hip); fc31|32|33's data gradient stays a launch
-    FcMidBwdArgs ba;
-    ba.dh6 = m->dh6; ba.W6 = PP(m, FC6); ba.W5 = PP(m, FC5); ba.W41 = PP(m, FC41); ba.W42 = PP(m, FC42); ba.W43 = PP(m, FC43);
-    ba.W3 = PP(m, FC31); ba.h5 = m->h5; ba.h3 = m->h3; ba.h2 = m->h2;
-    ba.z = m->zs; ba.u = m->u; ba.d = m->d; ba.eps_w = m->eps_w_last; ba.eps_d = m->eps_d_last; ba.scale = m->bwd_scale;
-    ba.dh5 = m->dh5; ba.dz = m->dz; ba.dmu = m->dmu; ba.du = m->du; ba.dlogd = m->dlogd; ba.dh3 = m->dh3; ba.dh2 = m->dh2;
-    ba.B = B; ba.zdim = z;
-    TRY(ava_fc_mid_bwd(ba, st));
-    mark(m, CAT_LATENT_LOSS, st);
-    TRY(gemm(m, m->dh3, 0, PP(m, FC31), 0, nullptr, m->dh2, 0, m->h2, nullptr, B, 256, 192, 1, 0, ACT_NONE, st));
-  } else {
-  TRY(gemm(m, m->dh6, 0, PP(m, FC6), 0, nullptr, m->dh5, 0, m->h5, nullptr, B, 64, 256, 1, 0, ACT_NONE, st));
-  TRY(gemm(m, m->dh5, 0, PP(m, FC5), 0, nullptr, m->dz, 0, nullptr, nullptr, B, z, 64, 1, 0, ACT_NONE, st));
-  // ---- latent block ----
-  TRY(ava_latent_bwd_scaled(m->zs, m->dz, m->u, m->d, m->eps_w_last, m->eps_d_last, m->dmu, m->du, m->dlogd, B, z,
-                            m->bwd_scale, st));
+  // dh6 -> dh5 -> dz -> latent backward -> dh3 in one launch (fc_mid.hip); fc31|32|33's data gradient stays a launch
+  FcMidBwdArgs ba;
+  ba.dh6 = m->dh6; ba.W6 = PP(m, FC6); ba.W5 = PP(m, FC5); ba.W41 = PP(m, FC41); ba.W42 = PP(m, FC42); ba.W43 = PP(m, FC43);
+  ba.W3 = PP(m, FC31); ba.h5 = m->h5; ba.h3 = m->h3; ba.h2 = m->h2;
+  ba.z = m->zs; ba.u = m->u; ba.d = m->d; ba.eps_w = m->eps_w_last; ba.eps_d = m->eps_d_last; ba.scale = m->bwd_scale;
+  ba.dh5 = m->dh5; ba.dz = m->dz; ba.dmu = m->dmu; ba.du = m->du; ba.dlogd = m->dlogd; ba.dh3 = m->dh3; ba.dh2 = m->dh2;
+  ba.B = B; ba.zdim = z;
+  TRY(ava_fc_mid_bwd(ba, st));
   mark(m, CAT_LATENT_LOSS, st);
-  // ---- heads: dX of fc41/42/43 into the three 64-wide slices of dh3 (masked by h3's ReLU), one launch ----
-  const AvaGemmProblem hdx[3] = {
-      {m->dmu, 0, PP(m, FC41), 0, nullptr, m->dh3 + 0, 192, m->h3 + 0, nullptr, B, 64, z, ACT_NONE},
-      {m->du, 0, PP(m, FC42), 0, nullptr, m->dh3 + 64, 192, m->h3 + 64, nullptr, B, 64, z, ACT_NONE},
-      {m->dlogd, 0, PP(m, FC43), 0, nullptr, m->dh3 + 128, 192, m->h3 + 128, nullptr, B, 64, z, ACT_NONE}};
-  TRY(gemm_group(m, hdx, 3, 1, 0, st));
   TRY(gemm(m, m->dh3, 0, PP(m, FC31), 0, nullptr, m->dh2, 0, m->h2, nullptr, B, 256, 192, 1, 0, ACT_NONE, st));
-  }
   TRY(gemm(m, m->dh2, 0, PP(m, FC2), 0, nullptr, m->dh1, 0, m->h1, nullptr, B, 1024, 256, 1, 0, ACT_NONE, st));
   // fc1's weight gradient (its bias gradient -- the column sums -- is written by the same launch but belongs to bucket 2:
   // nothing reads it before part 2 is complete)
@@ -1318,7 +1217,6 @@ static int backward_part2(ava_model* m, const float* x, int B, hipStream_t st, b
   float* gcur = m->gA;
   float* gnext = m->gB;
   mark(m, -1, st);
-  if (recomp_y1()) TRY(materialize_y1(m, x, B, st));       // TEMPORARY: until conv2's / conv1's backward recompute y1 themselves
   if (m->dy7_slabs == 2) {
     const float* s0 = reinterpret_cast<const float*>(m->dy7_ws);
     TRY(ava_relu_mask_to_nhwc(s0, s0 + (size_t)B * m->F, m->y7, gcur, B, m->P8, st));

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""A/B of one lab switch on the gradients of a fixed step: run once per value, then diff the dumps.
-    AVA_HIP_LIB_TAG=lab AVA_X=0 python tools/ab_grads.py dump /tmp/a.npz ; AVA_X=1 ... dump /tmp/b.npz ; python tools/ab_grads.py diff /tmp/a.npz /tmp/b.npz"""
+"""A/B of two builds of the library on the gradients of a fixed step: run once per build, then diff the dumps.
+    AVA_HIP_LIB_TAG=prev python tools/ab_grads.py dump /tmp/a.npz ; python tools/ab_grads.py dump /tmp/b.npz ; python tools/ab_grads.py diff /tmp/a.npz /tmp/b.npz"""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))

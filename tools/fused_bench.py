@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Time the fused backward kernel of every layer that has one (B=256) through the C ABI, next to the separate
-backward-data + weight-gradient kernels.  AVA_FUSED_VAR=n selects tile variant n (conv_fused.hip)."""
+backward-data + weight-gradient kernels."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))

@@ -77,8 +77,7 @@ def worker(rank, q, parts, barrier, lock=None):
     reg = {nm: (o, n) for o, n, nm in regions}
     wg13 = reg["wg13"][0]                              # convt7's weight-gradient partial rows (model.hip: debug buffer "wg13", round 6)
     slot27 = reg["bn_bwd"][0] + reg["bn_bwd"][1] + 27 * 3200      # bn_acc slot 27 (1600 int64): what the fold adds bn14's backward sums to
-    fold_on = os.environ.get("AVA_FOLD13", "1") != "0"       # (lab build: with the fold off the forward leaves these regions unwritten)
-    for r in range(1, len(ws) if fold_on else 0):
+    for r in range(1, len(ws)):
         a = ws[0][0].view(torch.float32); b = ws[r][0].view(torch.float32)
         wa = a[wg13:wg13 + 128 * 73].view(128, 73); wb = b[wg13:wg13 + 128 * 73].view(128, 73)
         if not torch.equal(wa, wb):
