@@ -405,6 +405,33 @@ int ava_tpl_xcorr(const double* spec, const double* frame_sum, int F, int64_t fr
                   const int64_t* lag_off, const int64_t* tile_off, int files, int64_t lags, int64_t tiles,
                   const double* tmpl, int template_F, int L, double* trace, void* ws, size_t ws_bytes, ava_stream_t s);
 
+/* ---- exact 1-nearest-neighbour search ------------------------------------------------
+ * The searches of ava/plotting/shotgun_movie.py:shotgun_movie_DC: NearestNeighbors(n_neighbors=1,
+ * metric='correlation') over spectrograms (:148-158) and argmin of scipy's euclidean over latent means (:126-133).
+ *
+ * ava_nn_workspace_bytes: device scratch ava_nn_argmin needs (0 for an unsupported shape or metric).
+ *
+ * ava_nn_argmin: for each of nq query rows the nearest of nr reference rows.
+ *   queries, q_dtype      [nq][d] row-major on the device; 0 = float32, 1 = float64
+ *   refs, r_dtype         [nr][d] likewise
+ *   metric                0 = correlation, 1 - (q - mean q).(r - mean r) / (|q - mean q| |r - mean r|), the cosine
+ *                         clipped to [-1, 1] as scipy clips it; 1 = euclidean, sqrt(sum (q - r)^2)
+ *   out_idx, out_dist     [nq] int64 index of the nearest reference and its distance (float64), device
+ * nq, nr >= 1, 1 <= d <= 65536.  All arithmetic is fp64.  Equal distances resolve to the lowest index.  Correlation: a
+ * zero-variance row gives NaN distances, NaN loses to any number, and a query whose distances are all NaN gets index
+ * 0 and NaN.  Euclidean: NaN wins and the first NaN is taken (np.argmin).  The results are bit-reproducible.
+ *
+ * ava_nn_merge: fold the result of a later chunk of references into a running result: (idx[q] + offset, dist[q])
+ * replaces (best_idx[q], best_dist[q]) when it is better under the same order, so the earlier chunk wins ties.
+ *
+ * Both return AVA_EINVAL before any launch for null pointers, an unknown dtype or metric or an unsupported shape;
+ * ava_nn_argmin returns AVA_EWORKSPACE for a workspace that is too small. */
+size_t ava_nn_workspace_bytes(int nq, int nr, int d, int metric);
+int ava_nn_argmin(const void* queries, int q_dtype, int nq, const void* refs, int r_dtype, int nr, int d, int metric,
+                  int64_t* out_idx, double* out_dist, void* ws, size_t ws_bytes, ava_stream_t s);
+int ava_nn_merge(int64_t* best_idx, double* best_dist, const int64_t* idx, const double* dist, int nq, int64_t offset,
+                 int metric, ava_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif
