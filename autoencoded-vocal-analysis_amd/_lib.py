@@ -115,6 +115,12 @@ SIGNATURES = {
     "ava_nn_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "ava_nn_argmin": (_i, [_p, _i, _i, _p, _i, _i, _i, _i, _p, _p, _p, _sz, _p]),
     "ava_nn_merge": (_i, [_p, _p, _p, _p, _i, _i64, _i, _p]),
+    "ava_pj_knn": (_i, [_p, _i, _i, _i, _i, _i, _i, _p, _p, _p]),
+    "ava_pj_smooth": (_i, [_p, _p, _i, _i, _d, _p, _p, _p, _p, _p]),
+    "ava_pj_layout": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i64, _i, _i, _i, _d, _d, _d, _d, C.c_uint64, _p, _p]),
+    "ava_pj_gram_workspace_bytes": (_sz, [_i, _i]),
+    "ava_pj_gram": (_i, [_p, _i, _i, _i, _p, _p, _sz, _p]),
+    "ava_pj_project": (_i, [_p, _i, _i, _i, _p, _p, _i, _p, _p]),
 }
 
 _lib = None

@@ -1,0 +1,462 @@
+// UMAP and PCA projections of latent means (DataContainer's 'latent_mean_umap' / 'latent_mean_pca' fields,
+// ava/data/data_container.py:514-551).  All arithmetic is fp64; no kernel uses atomics and every reduction runs in one
+// fixed order, so every result is bit-reproducible and independent of the launch shape.
+//
+// kNN       exact euclidean k-nearest neighbours of every row among all rows.  A workgroup owns 64 query rows and walks
+//           the references in 64-row tiles (direct differences sum_c (x_c - y_c)^2 in one fixed order over c, as
+//           neighbors.hip); each query keeps a running top-(k-1) list in LDS ordered by (distance, index), the query
+//           itself excluded.  Column 0 of the output is the row itself at distance 0.
+// smooth    umap's smooth_knn_dist + compute_membership_strengths, one row per thread.
+// layout    one synchronous, gather-only SGD epoch per launch over the symmetric CSR graph (rows = heads): a thread
+//           per vertex sums, in CSR order, the attractive moves of its active edges and their negative samples, all
+//           read from the previous epoch's positions, and advances the edges' sample counters.
+// PCA       column sums and X^T X as the Gram matrix of [X, 1] (chunks of rows, chunks summed in order), and the
+//           projection X V^T - mu V^T.
+#include "common.h"
+
+#define PJ_T 64          // kNN tile: queries = references
+#define PJ_KC 32         // columns per LDS stage
+#define PJ_LD 33         // staging row stride (doubles)
+#define PJ_DLD 65        // distance tile row stride (doubles)
+#define PJ_MAX_K 64
+#define PJ_MAX_NEG 16
+#define PJ_GT 32         // Gram tile
+#define PJ_GR 64         // rows per Gram LDS stage
+#define PJ_MAX_PCA_DIM 512
+
+// (d1, i1) before (d2, i2); an empty slot (i2 < 0) comes after everything
+__device__ __forceinline__ bool pj_before(double d1, int i1, double d2, int i2) {
+  if (i2 < 0) return true;
+  return d1 < d2 || (d1 == d2 && i1 < i2);
+}
+
+// rows [q0, q0 + nq) of the kNN table; dynamic LDS holds the running lists: slot s of local query t at [s * 64 + t]
+template <typename T>
+__global__ __launch_bounds__(256) void pj_knn_kernel(const T* __restrict__ X, int n, int d, int k, int q0, int nq,
+                                                     int64_t* __restrict__ out_idx, double* __restrict__ out_dist) {
+  __shared__ double stage[2 * PJ_T * PJ_LD];        // xs | ys while staging, then the 64 x 64 distance tile
+  extern __shared__ double lists[];                 // (k - 1) x 64 distances, then (k - 1) x 64 int indices
+  double* xs = stage;
+  double* ys = stage + PJ_T * PJ_LD;
+  double* dt = stage;
+  const int m = k - 1;
+  double* ld = lists;
+  int* li = reinterpret_cast<int*>(lists + (size_t)m * PJ_T);
+  const int t = threadIdx.x, ty = t >> 4, tx = t & 15;
+  const int qb = q0 + blockIdx.x * PJ_T;             // first query row of this workgroup
+  const int qe = q0 + nq;
+  const int sc = t & 31, sr = t >> 5;
+  for (int s = t; s < m * PJ_T; s += 256) {
+    ld[s] = 0.0;
+    li[s] = -1;
+  }
+  for (int r0 = 0; r0 < n; r0 += PJ_T) {
+    double acc[4][4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) acc[i][j] = 0.0;
+    for (int k0 = 0; k0 < d; k0 += PJ_KC) {
+      const int c = k0 + sc;
+      __syncthreads();                               // previous stage / distance tile consumed
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const int r = sr + 8 * j;
+        xs[r * PJ_LD + sc] = (c < d && qb + r < qe) ? (double)X[(size_t)(qb + r) * d + c] : 0.0;
+        ys[r * PJ_LD + sc] = (c < d && r0 + r < n) ? (double)X[(size_t)(r0 + r) * d + c] : 0.0;
+      }
+      __syncthreads();
+      const int kn = d - k0 < PJ_KC ? d - k0 : PJ_KC;
+      for (int kk = 0; kk < kn; ++kk) {
+        double x[4], y[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) x[i] = xs[(ty + 16 * i) * PJ_LD + kk];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) y[j] = ys[(tx + 16 * j) * PJ_LD + kk];
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            const double df = x[i] - y[j];
+            acc[i][j] = fma(df, df, acc[i][j]);
+          }
+      }
+    }
+    __syncthreads();                                 // staging reads done: the tile reuses the buffer
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) dt[(ty + 16 * i) * PJ_DLD + tx + 16 * j] = sqrt(acc[i][j]);
+    __syncthreads();
+    // one thread per query folds the tile's candidates into its list, in reference order
+    if (t < PJ_T && qb + t < qe && m > 0) {
+      const int q = qb + t;
+      const int cn = n - r0 < PJ_T ? n - r0 : PJ_T;
+      double wd = ld[(m - 1) * PJ_T + t];
+      int wi = li[(m - 1) * PJ_T + t];
+      for (int c = 0; c < cn; ++c) {
+        const int r = r0 + c;
+        const double dd = dt[t * PJ_DLD + c];
+        if (r == q || !pj_before(dd, r, wd, wi)) continue;
+        int s = m - 1;
+        while (s > 0 && pj_before(dd, r, ld[(s - 1) * PJ_T + t], li[(s - 1) * PJ_T + t])) {
+          ld[s * PJ_T + t] = ld[(s - 1) * PJ_T + t];
+          li[s * PJ_T + t] = li[(s - 1) * PJ_T + t];
+          --s;
+        }
+        ld[s * PJ_T + t] = dd;
+        li[s * PJ_T + t] = r;
+        wd = ld[(m - 1) * PJ_T + t];
+        wi = li[(m - 1) * PJ_T + t];
+      }
+    }
+  }
+  __syncthreads();
+  if (t < PJ_T && qb + t < qe) {
+    const size_t o = (size_t)(qb + t - q0) * k;
+    out_idx[o] = qb + t;
+    out_dist[o] = 0.0;
+    for (int s = 0; s < m; ++s) {
+      out_idx[o + 1 + s] = li[s * PJ_T + t];
+      out_dist[o + 1 + s] = ld[s * PJ_T + t];
+    }
+  }
+}
+
+// mean of the whole [n][k] distance table: thread t sums rows t, t + 256, ... (each row left to right), then a fixed tree
+__global__ __launch_bounds__(256) void pj_mean_kernel(const double* __restrict__ dist, int n, int k,
+                                                      double* __restrict__ mean) {
+  __shared__ double red[256];
+  const int t = threadIdx.x;
+  double s = 0.0;
+  for (int r = t; r < n; r += 256) {
+    double rs = 0.0;
+    for (int j = 0; j < k; ++j) rs += dist[(size_t)r * k + j];
+    s += rs;
+  }
+  red[t] = s;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (t < o) red[t] += red[t + o];
+    __syncthreads();
+  }
+  if (t == 0) mean[0] = red[0] / ((double)n * (double)k);
+}
+
+// smooth_knn_dist (n_iter 64, bandwidth 1) and compute_membership_strengths of one row per thread
+__global__ __launch_bounds__(256) void pj_smooth_kernel(const double* __restrict__ dist, const int64_t* __restrict__ idx,
+                                                        int n, int k, double local_connectivity,
+                                                        const double* __restrict__ mean_all,
+                                                        double* __restrict__ sigma, double* __restrict__ rho,
+                                                        double* __restrict__ w) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const double* row = dist + (size_t)i * k;
+  const double target = log2((double)k);
+  // rho: the local_connectivity-th nonzero distance (interpolated), else the largest nonzero one
+  int nz = 0;
+  double maxnz = 0.0, rowsum = 0.0;
+  for (int j = 0; j < k; ++j) {
+    rowsum += row[j];
+    if (row[j] > 0.0) {
+      ++nz;
+      maxnz = fmax(maxnz, row[j]);
+    }
+  }
+  double r = 0.0;
+  if ((double)nz >= local_connectivity) {
+    const int index = (int)floor(local_connectivity);
+    const double interp = local_connectivity - index;
+    double prev = 0.0, at = 0.0;                     // nonzero distances index - 1 and index
+    int seen = 0;
+    for (int j = 0; j < k; ++j) {
+      if (row[j] > 0.0) {
+        if (seen == index - 1) prev = row[j];
+        if (seen == index) at = row[j];
+        ++seen;
+      }
+    }
+    if (index > 0) {
+      r = prev;
+      if (interp > 1e-5) r += interp * (at - prev);
+    } else {
+      double first = 0.0;
+      for (int j = k - 1; j >= 0; --j)
+        if (row[j] > 0.0) first = row[j];
+      r = interp * first;
+    }
+  } else if (nz > 0) {
+    r = maxnz;
+  }
+  double lo = 0.0, hi = INFINITY, mid = 1.0;
+  for (int it = 0; it < 64; ++it) {
+    double psum = 0.0;
+    for (int j = 1; j < k; ++j) {
+      const double dd = row[j] - r;
+      psum += dd > 0.0 ? exp(-(dd / mid)) : 1.0;
+    }
+    if (fabs(psum - target) < 1e-5) break;
+    if (psum > target) {
+      hi = mid;
+      mid = (lo + hi) / 2.0;
+    } else {
+      lo = mid;
+      mid = hi == INFINITY ? mid * 2.0 : (lo + hi) / 2.0;
+    }
+  }
+  const double floor_scale = 1e-3 * (r > 0.0 ? rowsum / (double)k : mean_all[0]);
+  if (mid < floor_scale) mid = floor_scale;
+  sigma[i] = mid;
+  rho[i] = r;
+  for (int j = 0; j < k; ++j) {
+    double v;
+    if (idx[(size_t)i * k + j] == i) v = 0.0;
+    else if (row[j] - r <= 0.0 || mid == 0.0) v = 1.0;
+    else v = exp(-((row[j] - r) / mid));
+    w[(size_t)i * k + j] = v;
+  }
+}
+
+__device__ __forceinline__ double pj_clip(double v) { return v > 4.0 ? 4.0 : (v < -4.0 ? -4.0 : v); }
+
+// one layout epoch: y_out[v] = y_in[v] + the moves of v's active edges and their negative samples
+__global__ __launch_bounds__(64) void pj_layout_kernel(const double* __restrict__ y_in, double* __restrict__ y_out,
+                                                        const int64_t* __restrict__ indptr,
+                                                        const int* __restrict__ col, const double* __restrict__ eps,
+                                                        const double* __restrict__ epn, double* __restrict__ next_s,
+                                                        double* __restrict__ next_n, int n, int64_t nnz, int epoch,
+                                                        double alpha, double a, double b, double gamma, uint64_t salt,
+                                                        int* __restrict__ flag) {
+  // every product and sum rounded on its own (no fused multiply-add): the layout is chaotic where negative samples
+  // meet close pairs, and contraction alone would part it from an unfused restatement within a few epochs
+#pragma clang fp contract(off)
+  const int v = blockIdx.x * 64 + threadIdx.x;
+  if (v >= n) return;
+  const double y0 = y_in[2 * (size_t)v], y1 = y_in[2 * (size_t)v + 1];
+  double m0 = 0.0, m1 = 0.0;
+  const double ep = (double)epoch;
+  for (int64_t e = indptr[v]; e < indptr[v + 1]; ++e) {
+    if (!(next_s[e] <= ep)) continue;
+    const int j = col[e];
+    double d0 = y0 - y_in[2 * (size_t)j], d1 = y1 - y_in[2 * (size_t)j + 1];
+    double d2 = d0 * d0 + d1 * d1;
+    double g = 0.0;
+    if (d2 > 0.0) g = -2.0 * a * b * pow(d2, b - 1.0) / (a * pow(d2, b) + 1.0);
+    m0 += 2.0 * alpha * pj_clip(g * d0);
+    m1 += 2.0 * alpha * pj_clip(g * d1);
+    next_s[e] += eps[e];
+    int nneg = (int)((ep - next_n[e]) / epn[e]);
+    if (nneg > PJ_MAX_NEG) {
+      flag[0] = 1;
+      nneg = PJ_MAX_NEG;
+    }
+    for (int p = 0; p < nneg; ++p) {
+      const uint64_t ctr = ((uint64_t)epoch * (uint64_t)nnz + (uint64_t)e) * PJ_MAX_NEG + (uint64_t)p;
+      int64_t kk = (int64_t)floor(ava_u01_hash(ctr, salt) * (double)n);
+      if (kk > n - 1) kk = n - 1;
+      if (kk == v) continue;
+      d0 = y0 - y_in[2 * (size_t)kk];
+      d1 = y1 - y_in[2 * (size_t)kk + 1];
+      d2 = d0 * d0 + d1 * d1;
+      if (d2 > 0.0) {
+        const double c = 2.0 * gamma * b / ((0.001 + d2) * (a * pow(d2, b) + 1.0));
+        if (c > 0.0) {
+          m0 += alpha * pj_clip(c * d0);
+          m1 += alpha * pj_clip(c * d1);
+        }
+      }
+    }
+    next_n[e] += nneg * epn[e];
+  }
+  y_out[2 * (size_t)v] = y0 + m0;
+  y_out[2 * (size_t)v + 1] = y1 + m1;
+}
+
+// partial Gram matrices of [X, 1] (D = d + 1 columns): part[chunk][i][j] = sum over the chunk's rows, in row order
+template <typename T>
+__global__ __launch_bounds__(256) void pj_gram_kernel(const T* __restrict__ X, int n, int d, int rows_per_chunk,
+                                                      int tiles, double* __restrict__ part) {
+  __shared__ double xi[PJ_GR][PJ_GT + 1];
+  __shared__ double xj[PJ_GR][PJ_GT + 1];
+  const int D = d + 1;
+  const int t = threadIdx.x;
+  const int i0 = (blockIdx.x / tiles) * PJ_GT, j0 = (blockIdx.x % tiles) * PJ_GT;
+  const int rb = blockIdx.y * rows_per_chunk;
+  const int re = rb + rows_per_chunk < n ? rb + rows_per_chunk : n;
+  const int ti = (t >> 4) * 2, tj = (t & 15) * 2;
+  double acc[2][2] = {{0.0, 0.0}, {0.0, 0.0}};
+  for (int r0 = rb; r0 < re; r0 += PJ_GR) {
+    __syncthreads();
+    for (int e = t; e < PJ_GR * PJ_GT; e += 256) {
+      const int r = e / PJ_GT, c = e % PJ_GT, gr = r0 + r;
+      const int ci = i0 + c, cj = j0 + c;
+      double vi = 0.0, vj = 0.0;
+      if (gr < re) {
+        vi = ci < d ? (double)X[(size_t)gr * d + ci] : (ci == d ? 1.0 : 0.0);
+        vj = cj < d ? (double)X[(size_t)gr * d + cj] : (cj == d ? 1.0 : 0.0);
+      }
+      xi[r][c] = vi;
+      xj[r][c] = vj;
+    }
+    __syncthreads();
+    for (int r = 0; r < PJ_GR; ++r) {
+      const double a0 = xi[r][ti], a1 = xi[r][ti + 1], b0 = xj[r][tj], b1 = xj[r][tj + 1];
+      acc[0][0] = fma(a0, b0, acc[0][0]);
+      acc[0][1] = fma(a0, b1, acc[0][1]);
+      acc[1][0] = fma(a1, b0, acc[1][0]);
+      acc[1][1] = fma(a1, b1, acc[1][1]);
+    }
+  }
+  double* out = part + (size_t)blockIdx.y * D * D;
+#pragma unroll
+  for (int a = 0; a < 2; ++a)
+#pragma unroll
+    for (int b = 0; b < 2; ++b) {
+      const int i = i0 + ti + a, j = j0 + tj + b;
+      if (i < D && j < D) out[(size_t)i * D + j] = acc[a][b];
+    }
+}
+
+__global__ __launch_bounds__(256) void pj_gram_reduce_kernel(const double* __restrict__ part, int chunks, int DD,
+                                                             double* __restrict__ gram) {
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e >= DD) return;
+  double s = 0.0;
+  for (int c = 0; c < chunks; ++c) s += part[(size_t)c * DD + e];
+  gram[e] = s;
+}
+
+// out[r][c] = sum_j X[r][j] V[c][j] - muv[c]
+template <typename T>
+__global__ __launch_bounds__(256) void pj_project_kernel(const T* __restrict__ X, int n, int d,
+                                                         const double* __restrict__ V, const double* __restrict__ muv,
+                                                         int nc, double* __restrict__ out) {
+  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= (int64_t)n * nc) return;
+  const int64_t r = e / nc;
+  const int c = (int)(e % nc);
+  const T* row = X + (size_t)r * d;
+  const double* vc = V + (size_t)c * d;
+  double s = 0.0;
+  for (int j = 0; j < d; ++j) s = fma((double)row[j], vc[j], s);
+  out[e] = s - muv[c];
+}
+
+static bool pj_knn_ok(int n, int d, int k, int q0, int nq) {
+  return n >= 1 && d >= 1 && d <= 65536 && k >= 1 && k <= PJ_MAX_K && k <= n && q0 >= 0 && nq >= 1 &&
+         (int64_t)q0 + nq <= n;
+}
+
+template <typename T>
+static int pj_knn_launch(const void* x, int n, int d, int k, int q0, int nq, int64_t* idx, double* dist,
+                         hipStream_t st) {
+  const size_t lds = (size_t)(k - 1) * PJ_T * (sizeof(double) + sizeof(int));
+  hipLaunchKernelGGL(pj_knn_kernel<T>, dim3(ceil_div(nq, PJ_T)), dim3(256), lds, st, reinterpret_cast<const T*>(x), n,
+                     d, k, q0, nq, idx, dist);
+  AVA_CHECK_LAUNCH();
+  return AVA_OK;
+}
+
+extern "C" int ava_pj_knn(const void* x, int dtype, int n, int d, int k, int q0, int nq, int64_t* out_idx,
+                          double* out_dist, ava_stream_t s) {
+  if (x == nullptr || out_idx == nullptr || out_dist == nullptr || (dtype != 0 && dtype != 1) ||
+      !pj_knn_ok(n, d, k, q0, nq))
+    return AVA_EINVAL;
+  if (dtype == 0) return pj_knn_launch<float>(x, n, d, k, q0, nq, out_idx, out_dist, to_stream(s));
+  return pj_knn_launch<double>(x, n, d, k, q0, nq, out_idx, out_dist, to_stream(s));
+}
+
+extern "C" int ava_pj_smooth(const double* dist, const int64_t* idx, int n, int k, double local_connectivity,
+                             double* mean_all, double* sigma, double* rho, double* w, ava_stream_t s) {
+  if (dist == nullptr || idx == nullptr || mean_all == nullptr || sigma == nullptr || rho == nullptr ||
+      w == nullptr || n < 1 || k < 1 || k > PJ_MAX_K || !(local_connectivity >= 0.0))
+    return AVA_EINVAL;
+  hipStream_t st = to_stream(s);
+  hipLaunchKernelGGL(pj_mean_kernel, dim3(1), dim3(256), 0, st, dist, n, k, mean_all);
+  AVA_CHECK_LAUNCH();
+  hipLaunchKernelGGL(pj_smooth_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, st, dist, idx, n, k, local_connectivity,
+                     mean_all, sigma, rho, w);
+  AVA_CHECK_LAUNCH();
+  return AVA_OK;
+}
+
+extern "C" int ava_pj_layout(double* y, double* y_tmp, const int64_t* indptr, const int* col, const double* eps,
+                             const double* epn, double* next_s, double* next_n, int n, int64_t nnz, int e0, int e1,
+                             int n_epochs, double learning_rate, double a, double b, double gamma, uint64_t salt,
+                             int* flag, ava_stream_t s) {
+  if (y == nullptr || y_tmp == nullptr || indptr == nullptr || flag == nullptr || n < 1 || nnz < 0 || e0 < 0 ||
+      e1 < e0 || e1 > n_epochs || (nnz > 0 && (col == nullptr || eps == nullptr || epn == nullptr ||
+                                               next_s == nullptr || next_n == nullptr)))
+    return AVA_EINVAL;
+  hipStream_t st = to_stream(s);
+  double* cur = y;
+  double* nxt = y_tmp;
+  for (int ep = e0; ep < e1; ++ep) {
+    const double alpha = ep == 0 ? learning_rate : learning_rate * (1.0 - (double)(ep - 1) / (double)n_epochs);
+    // one-wave workgroups: the thread per vertex is latency-bound on its gathers, so spread the vertices over all CUs
+    hipLaunchKernelGGL(pj_layout_kernel, dim3(ceil_div(n, 64)), dim3(64), 0, st, cur, nxt, indptr, col, eps, epn,
+                       next_s, next_n, n, nnz, ep, alpha, a, b, gamma, salt, flag);
+    AVA_CHECK_LAUNCH();
+    double* tmp = cur;
+    cur = nxt;
+    nxt = tmp;
+  }
+  if (cur != y && hipMemcpyAsync(y, cur, 2 * (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, st) != hipSuccess)
+    return AVA_ELAUNCH;
+  return AVA_OK;
+}
+
+static int pj_gram_rows(int n) {
+  const int r = ceil_div(n, 256);
+  return r < 2048 ? 2048 : ceil_div(r, PJ_GR) * PJ_GR;
+}
+
+extern "C" size_t ava_pj_gram_workspace_bytes(int n, int d) {
+  if (n < 1 || d < 1 || d > PJ_MAX_PCA_DIM) return 0;
+  const size_t D = (size_t)d + 1;
+  return (size_t)ceil_div(n, pj_gram_rows(n)) * D * D * sizeof(double);
+}
+
+template <typename T>
+static void pj_gram_launch(const void* x, int n, int d, double* part, hipStream_t st) {
+  const int tiles = ceil_div(d + 1, PJ_GT), rows = pj_gram_rows(n);
+  hipLaunchKernelGGL(pj_gram_kernel<T>, dim3(tiles * tiles, ceil_div(n, rows)), dim3(256), 0, st,
+                     reinterpret_cast<const T*>(x), n, d, rows, tiles, part);
+}
+
+extern "C" int ava_pj_gram(const void* x, int dtype, int n, int d, double* gram, void* ws, size_t ws_bytes,
+                           ava_stream_t s) {
+  if (x == nullptr || gram == nullptr || ws == nullptr || (dtype != 0 && dtype != 1) || n < 1 || d < 1 ||
+      d > PJ_MAX_PCA_DIM)
+    return AVA_EINVAL;
+  if (ws_bytes < ava_pj_gram_workspace_bytes(n, d)) return AVA_EWORKSPACE;
+  hipStream_t st = to_stream(s);
+  double* part = reinterpret_cast<double*>(ws);
+  if (dtype == 0) pj_gram_launch<float>(x, n, d, part, st);
+  else pj_gram_launch<double>(x, n, d, part, st);
+  AVA_CHECK_LAUNCH();
+  const int DD = (d + 1) * (d + 1);
+  hipLaunchKernelGGL(pj_gram_reduce_kernel, dim3(ceil_div(DD, 256)), dim3(256), 0, st, part,
+                     ceil_div(n, pj_gram_rows(n)), DD, gram);
+  AVA_CHECK_LAUNCH();
+  return AVA_OK;
+}
+
+extern "C" int ava_pj_project(const void* x, int dtype, int n, int d, const double* V, const double* muv, int nc,
+                              double* out, ava_stream_t s) {
+  if (x == nullptr || V == nullptr || muv == nullptr || out == nullptr || (dtype != 0 && dtype != 1) || n < 1 ||
+      d < 1 || nc < 1 || nc > d)
+    return AVA_EINVAL;
+  const int64_t total = (int64_t)n * nc;
+  const int64_t blocks = ceil_div64(total, 256);
+  if (blocks > 0x7fffffff) return AVA_EINVAL;
+  hipStream_t st = to_stream(s);
+  if (dtype == 0)
+    hipLaunchKernelGGL(pj_project_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, st,
+                       reinterpret_cast<const float*>(x), n, d, V, muv, nc, out);
+  else
+    hipLaunchKernelGGL(pj_project_kernel<double>, dim3((unsigned)blocks), dim3(256), 0, st,
+                       reinterpret_cast<const double*>(x), n, d, V, muv, nc, out);
+  AVA_CHECK_LAUNCH();
+  return AVA_OK;
+}

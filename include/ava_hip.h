@@ -432,6 +432,45 @@ int ava_nn_argmin(const void* queries, int q_dtype, int nq, const void* refs, in
 int ava_nn_merge(int64_t* best_idx, double* best_dist, const int64_t* idx, const double* dist, int nq, int64_t offset,
                  int metric, ava_stream_t s);
 
+/* ---- UMAP and PCA projections of latent means (DataContainer 'latent_mean_umap' / 'latent_mean_pca') --------------
+ * ava/data/data_container.py:514-551.  All arithmetic is fp64, nothing uses atomics, and every result is
+ * bit-reproducible and independent of the launch shape.  x / dtype: [n][d] row-major on the device, 0 = float32,
+ * 1 = float64.
+ *
+ * ava_pj_knn: rows [q0, q0 + nq) of the exact euclidean k-nearest-neighbour table of x among its own rows:
+ *   out_idx [nq][k] int64, out_dist [nq][k] float64 (device).  Column 0 is the row itself at distance 0; columns
+ *   1 .. k-1 are the nearest other rows ordered by (distance, index).  1 <= k <= min(64, n), 1 <= d <= 65536.
+ *
+ * ava_pj_smooth: umap's smooth_knn_dist (64 bisection steps, tolerance 1e-5, floor 1e-3 x mean distance) and
+ *   compute_membership_strengths on a [n][k] kNN table: sigma [n], rho [n], w [n][k] (0 for the row itself);
+ *   mean_all [1] receives the mean of the whole distance table.
+ *
+ * ava_pj_layout: epochs [e0, e1) of n_epochs of the synchronous SGD layout of y [n][2] (in / out; y_tmp the same size)
+ *   over the symmetric CSR graph indptr [n + 1] int64, col [nnz] int32 with per-edge eps (epochs per sample), epn
+ *   (epochs per negative sample) and the two counters next_s / next_n (in / out).  The learning rate of epoch e is
+ *   learning_rate for e = 0 and learning_rate (1 - (e - 1) / n_epochs) after; negative samples come from the
+ *   splitmix64 hash of ((e nnz + edge) 16 + p, salt).  flag [1] int is set to 1 if an edge needed more than 16
+ *   negative samples in one epoch (they are clamped to 16).  All epochs are enqueued without a host synchronisation.
+ *
+ * ava_pj_gram_workspace_bytes / ava_pj_gram: gram [(d+1)][(d+1)] = [x, 1]^T [x, 1] (so gram[i][d] is the sum of column
+ *   i and gram[d][d] = n), summed over fixed row chunks in order.  1 <= d <= 512.
+ *
+ * ava_pj_project: out [n][nc] = x V^T - muv, V [nc][d], muv [nc] (device, float64).
+ *
+ * All return AVA_EINVAL before any launch for null pointers, an unknown dtype or an unsupported shape;
+ * ava_pj_gram returns AVA_EWORKSPACE for a workspace that is too small. */
+int ava_pj_knn(const void* x, int dtype, int n, int d, int k, int q0, int nq, int64_t* out_idx, double* out_dist,
+               ava_stream_t s);
+int ava_pj_smooth(const double* dist, const int64_t* idx, int n, int k, double local_connectivity, double* mean_all,
+                  double* sigma, double* rho, double* w, ava_stream_t s);
+int ava_pj_layout(double* y, double* y_tmp, const int64_t* indptr, const int* col, const double* eps,
+                  const double* epn, double* next_s, double* next_n, int n, int64_t nnz, int e0, int e1, int n_epochs,
+                  double learning_rate, double a, double b, double gamma, uint64_t salt, int* flag, ava_stream_t s);
+size_t ava_pj_gram_workspace_bytes(int n, int d);
+int ava_pj_gram(const void* x, int dtype, int n, int d, double* gram, void* ws, size_t ws_bytes, ava_stream_t s);
+int ava_pj_project(const void* x, int dtype, int n, int d, const double* V, const double* muv, int nc, double* out,
+                   ava_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif
