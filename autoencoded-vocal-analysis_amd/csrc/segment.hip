@@ -179,11 +179,12 @@ __global__ __launch_bounds__(AVA_AMP_T) void amp_stops_kernel(const V* a, const 
 }
 
 // The band stage of ava_amp_trace and ava_tpl_spec: AVA_EINVAL before any launch for a null pointer, no files or
-// frames, an unsupported nperseg, noverlap >= nperseg, an empty band, an unknown audio dtype or spec_min == spec_max;
-// otherwise band_stft_kernel writes raw (and spec, if not null) on stream st.
+// frames, an unsupported nperseg, noverlap >= nperseg, an empty band, an unknown audio dtype or a divisor `range` of 0
+// (spec_min == spec_max for the segmenters, whose divisor is spec_max - spec_min); otherwise band_stft_kernel writes raw
+// (and spec, if not null) on stream st.
 static int band_stft(const void* audio, int audio_dtype, const int64_t* file_off, const int64_t* file_len,
                      const int64_t* frame_off, int files, int64_t frames, int nperseg, int noverlap,
-                     const double* window, double scale, int k0, int k1, double spec_min, double spec_max, bool softmax,
+                     const double* window, double scale, int k0, int k1, double spec_min, double range, bool softmax,
                      double temperature, double* raw, double* spec, hipStream_t st) {
   if (audio == nullptr || file_off == nullptr || file_len == nullptr || frame_off == nullptr || window == nullptr ||
       raw == nullptr)
@@ -193,7 +194,7 @@ static int band_stft(const void* audio, int audio_dtype, const int64_t* file_off
   if (noverlap < 0 || noverlap >= nperseg) return AVA_EINVAL;
   if (k0 < 0 || k1 <= k0 || k1 > nperseg / 2 + 1) return AVA_EINVAL;             // empty band
   if (audio_dtype < AVA_AUDIO_I16 || audio_dtype > AVA_AUDIO_F64) return AVA_EINVAL;
-  if (!(spec_max != spec_min)) return AVA_EINVAL;
+  if (!(range != 0.0) || range != range) return AVA_EINVAL;
   BandArgs a;
   a.audio = audio;
   a.file_off = reinterpret_cast<const long long*>(file_off);
@@ -202,7 +203,7 @@ static int band_stft(const void* audio, int audio_dtype, const int64_t* file_off
   a.window = window;
   a.raw = raw;
   a.spec = spec;
-  a.scale = scale; a.spec_min = spec_min; a.range = spec_max - spec_min; a.temperature = temperature;
+  a.scale = scale; a.spec_min = spec_min; a.range = range; a.temperature = temperature;
   a.frames = frames; a.files = files; a.nperseg = nperseg; a.nstep = nperseg - noverlap;
   a.k0 = k0; a.k1 = k1; a.dtype = audio_dtype;
   const int grid = frames < 4096 ? (int)frames : 4096;      // workgroups stride over the frames
@@ -233,7 +234,7 @@ extern "C" int ava_amp_trace(const void* audio, int audio_dtype, const int64_t* 
   double* raw = reinterpret_cast<double*>(base);
   hipStream_t st = to_stream(s);
   const int rc = band_stft(audio, audio_dtype, file_off, file_len, frame_off, files, frames, nperseg, noverlap, window,
-                           scale, k0, k1, spec_min, spec_max, softmax != 0, temperature, raw, spec, st);
+                           scale, k0, k1, spec_min, spec_max - spec_min, softmax != 0, temperature, raw, spec, st);
   if (rc != AVA_OK) return rc;
   const long long* fo = reinterpret_cast<const long long*>(frame_off);
   const dim3 sgrid((unsigned)ceil_div64(frames, AVA_AMP_T));
@@ -254,7 +255,20 @@ extern "C" int ava_tpl_spec(const void* audio, int audio_dtype, const int64_t* f
                             double* spec, double* frame_sum, ava_stream_t s) {
   if (spec == nullptr) return AVA_EINVAL;
   return band_stft(audio, audio_dtype, file_off, file_len, frame_off, files, frames, nperseg, noverlap, window, scale,
-                   k0, k1, spec_min, spec_max, false, 1.0, frame_sum, spec, to_stream(s));
+                   k0, k1, spec_min, spec_max - spec_min, false, 1.0, frame_sum, spec, to_stream(s));
+}
+
+// The inputs of the time-warp fit (ava/models/utils.py:337-418, row f9): the same band stage with the divisor handed in,
+// because _get_spec divides by spec_max_val - spec_min_val + 1e-9 where the segmenters divide by the plain difference.
+// spec [k1 - k0][frames] and the per-frame band sums; the truncation to common shapes and the normalisation of each
+// trace are the host's.
+extern "C" int ava_warp_band_spec(const void* audio, int audio_dtype, const int64_t* file_off, const int64_t* file_len,
+                                  const int64_t* frame_off, int files, int64_t frames, int nperseg, int noverlap,
+                                  const double* window, double scale, int k0, int k1, double spec_min, double divisor,
+                                  double* spec, double* frame_sum, ava_stream_t s) {
+  if (spec == nullptr) return AVA_EINVAL;
+  return band_stft(audio, audio_dtype, file_off, file_len, frame_off, files, frames, nperseg, noverlap, window, scale,
+                   k0, k1, spec_min, divisor, false, 1.0, frame_sum, spec, to_stream(s));
 }
 
 extern "C" int ava_amp_decide(const void* trace, int trace_f64, const int64_t* frame_off, int files, int64_t frames,

@@ -15,42 +15,7 @@
 // FFTs, 0.3 to 2 GFLOP.  The frame times and bin frequencies are computed with the reference's own operation order
 // (scipy's arange / fs - (nperseg/2) / fs + max(0, t1); rfftfreq's k * (1 / (n d))) and without contraction, so that
 // the interval a target point falls into is decided by the same numbers.
-#include "stft.h"
-
-#define AVA_SPEC_EPS 1e-12
-
-struct SpecMeta {        // one per window, written by spec_prep_kernel
-  long long lo;          // first sample of the slice inside the concatenated audio buffer
-  int n;                 // samples in the slice
-  int nframes;           // STFT frames (0: the reference returns zeros for this window; -1: scratch too small)
-  int j0, j1;            // frames the interpolation can touch (inclusive): the others are never computed
-  double mean;           // subtracted DC offset (0 when remove_dc_offset is off)
-  double t_shift;        // max(0, t1)
-};
-
-struct SpecArgs {
-  const void* audio;
-  const long long* file_off;
-  const long long* file_len;
-  const int* file_idx;
-  const double* t1;
-  const double* t2;
-  const double* target_times;    // [n][T]
-  const double* target_freqs;    // [F]
-  const double* window;          // [nperseg]
-  SpecMeta* meta;
-  double* twiddle;               // [nperseg/2][2]: exp(-2 pi i k / nperseg), written by spec_prep_kernel's workgroup 0
-  double* ftimes;                // [n][maxframes]: frame times of each window, written by spec_prep_kernel
-  int* krange;                   // [2]: first / last frequency bin the target frequencies can touch (workgroup 0)
-  double* logmag;                // [n][maxframes][nperseg/2 + 1]
-  float* out;                    // [n][F][T]
-  float* out_max;                // [n] or null
-  double* vals;                  // [n][F*T]: clipped fp64 spectrograms handed to spec_normalize_kernel (normalize only)
-  double q_gamma;                // within_syll_normalize: np.quantile's interpolation weight ...
-  int q_lo, normalize;           // ... between the order statistics q_lo and q_lo + 1 (0-based)
-  double fs, scale, spec_min, range, fill_value, fbin;    // fbin: rfftfreq's 1 / (nperseg * (1 / fs))
-  int n, maxframes, nperseg, nstep, F, T, dtype, remove_dc;
-};
+#include "spec_core.h"
 
 // frame time j of a window: scipy's  arange(nperseg/2, ..., hop) / fs - (nperseg/2) / fs, then utils.py:75's + max(0, t1)
 __device__ __forceinline__ double frame_time(int j, const SpecArgs& a, double t_shift) {
@@ -93,10 +58,7 @@ __global__ __launch_bounds__(AVA_SPEC_PREP_T) void spec_prep_kernel(const SpecAr
       mxf = x2 > mxf ? x2 : mxf;
     }
     if (t == 0) {
-      const int K1 = a.nperseg / 2;
-      const double b0 = floor(mnf / a.fbin) - 2.0, b1 = floor(mxf / a.fbin) + 3.0;
-      a.krange[0] = b0 > 0.0 ? (b0 < (double)K1 ? (int)b0 : K1) : 0;
-      a.krange[1] = b1 < (double)K1 ? (b1 > 0.0 ? (int)b1 : 0) : K1;
+      spec_bin_range(mnf, mxf, a.fbin, a.nperseg, &a.krange[0], &a.krange[1]);
     }
   }
   const long long len = a.file_len[a.file_idx[w]];
@@ -265,8 +227,6 @@ __global__ __launch_bounds__(256) void spec_dft_kernel(const SpecArgs a) {
 // normalisation and clip.  A workgroup owns AVA_SPEC_ROWS frequency rows of one window: the knot interval and the two
 // basis values of every target TIME are computed once per workgroup (LDS), those of a target FREQUENCY once per row
 // visit, so a pixel costs four loads, the 4-term sum and the normalising division.
-#define AVA_SPEC_ROWS 16
-#define AVA_SPEC_TMAX 512        // target times per window the column table holds (num_time_bins; larger: AVA_EINVAL)
 __global__ __launch_bounds__(256) void spec_interp_kernel(const SpecArgs a) {
   __shared__ double chx0[AVA_SPEC_TMAX], chx1[AVA_SPEC_TMAX];
   __shared__ int cl[AVA_SPEC_TMAX];                                  // knot interval of column ti, -1: outside -> fill value
@@ -284,40 +244,9 @@ __global__ __launch_bounds__(256) void spec_interp_kernel(const SpecArgs a) {
   const int K = a.nperseg / 2 + 1;
   const double* ft = a.ftimes + (size_t)w * a.maxframes;
   const double val = a.fbin;                       // bin frequencies: rfftfreq(n, d) = arange(n/2 + 1) * (1 / (n d)), d = 1 / fs
-  const double xmin = ft[0], xmax = ft[m.nframes - 1];
-  for (int ti = t; ti < a.T; ti += 256) {
-    const double x = a.target_times[(size_t)w * a.T + ti];
-    int l = -1;
-    double hx0 = 0.0, hx1 = 0.0;
-    if (!(x < xmin || x > xmax || !(x == x))) {
-      l = (int)floor((x - xmin) * a.fs / (double)a.nstep);
-      l = l < 0 ? 0 : (l > m.nframes - 2 ? m.nframes - 2 : l);
-      while (l > 0 && x < ft[l]) --l;
-      while (l < m.nframes - 2 && x >= ft[l + 1]) ++l;
-      const double tl = ft[l], tr = ft[l + 1];
-      const double fx = __ddiv_rn(1.0, __dsub_rn(tr, tl));
-      hx0 = __dmul_rn(fx, __dsub_rn(tr, x));
-      hx1 = __dmul_rn(fx, __dsub_rn(x, tl));
-    }
-    cl[ti] = l; chx0[ti] = hx0; chx1[ti] = hx1;
-  }
-  if (t < rows) {
-    const double y = a.target_freqs[f0 + t];
-    const double ymax = __dmul_rn((double)(K - 1), val);
-    int q = -1;
-    double hy0 = 0.0, hy1 = 0.0;
-    if (!(y < 0.0 || y > ymax || !(y == y))) {
-      q = (int)floor(y / val);
-      q = q < 0 ? 0 : (q > K - 2 ? K - 2 : q);
-      while (q > 0 && y < __dmul_rn((double)q, val)) --q;
-      while (q < K - 2 && y >= __dmul_rn((double)(q + 1), val)) ++q;
-      const double yl = __dmul_rn((double)q, val), yr = __dmul_rn((double)(q + 1), val);
-      const double fy = __ddiv_rn(1.0, __dsub_rn(yr, yl));
-      hy0 = __dmul_rn(fy, __dsub_rn(yr, y));
-      hy1 = __dmul_rn(fy, __dsub_rn(y, yl));
-    }
-    rq[t] = q; rhy0[t] = hy0; rhy1[t] = hy1;
-  }
+  for (int ti = t; ti < a.T; ti += 256)
+    spec_time_basis(a.target_times[(size_t)w * a.T + ti], ft, m.nframes, a.fs, a.nstep, &cl[ti], &chx0[ti], &chx1[ti]);
+  if (t < rows) spec_freq_basis(a.target_freqs[f0 + t], val, K, &rq[t], &rhy0[t], &rhy1[t]);
   __syncthreads();
   float fmax = 0.f;
   for (int i = t; i < rows * a.T; i += 256) {
@@ -330,16 +259,9 @@ __global__ __launch_bounds__(256) void spec_interp_kernel(const SpecArgs a) {
       const double hx0 = chx0[ti], hx1 = chx1[ti], hy0 = rhy0[r], hy1 = rhy1[r];
       const double* c0 = a.logmag + ((size_t)w * a.maxframes + l) * K + q;       // coefficient c[time l][freq q]
       const double* c1 = c0 + K;
-      double sp = 0.0;
-      sp = __dadd_rn(sp, __dmul_rn(__dmul_rn(c0[0], hx0), hy0));
-      sp = __dadd_rn(sp, __dmul_rn(__dmul_rn(c0[1], hx0), hy1));
-      sp = __dadd_rn(sp, __dmul_rn(__dmul_rn(c1[0], hx1), hy0));
-      sp = __dadd_rn(sp, __dmul_rn(__dmul_rn(c1[1], hx1), hy1));
-      v = sp;
+      v = spec_bilinear(c0[0], c0[1], c1[0], c1[1], hx0, hx1, hy0, hy1);
     }
-    v = __dsub_rn(v, a.spec_min);
-    v = __ddiv_rn(v, a.range);                                         // utils.py:101-102
-    v = v < 0.0 ? 0.0 : (v > 1.0 ? 1.0 : v);
+    v = spec_scale_clip(v, a.spec_min, a.range);                       // utils.py:101-102
     if (a.normalize) {                                                 // utils.py:104-108 follow in spec_normalize_kernel
       a.vals[((size_t)w * a.F + f0) * a.T + i] = v;
     } else {
@@ -355,100 +277,56 @@ __global__ __launch_bounds__(256) void spec_interp_kernel(const SpecArgs a) {
   }
 }
 
-// within_syll_normalize (utils.py:104-108): spec -= np.quantile(spec, q); spec[spec < 0] = 0; spec /= max(spec) + EPSILON.
-// One workgroup per window.  The quantile is numpy's default ('linear'): a[lo] + (a[lo+1] - a[lo]) * gamma with lo and
-// gamma from the host (numpy's own expression for the virtual index), evaluated with numpy's two-sided lerp.  a[lo] is
-// found by an MSB-first radix select over the bit patterns (the values are in [0, 1], so the unsigned order of the
-// patterns is the numeric order; counts are integers: deterministic), a[lo+1] from one more counting pass.
-#define AVA_SPEC_NORM_T 1024
+// within_syll_normalize (utils.py:104-108), one workgroup per window: spec_normalize_window of spec_core.h
 __global__ __launch_bounds__(AVA_SPEC_NORM_T) void spec_normalize_kernel(const SpecArgs a) {
-  __shared__ unsigned hist[256];
-  __shared__ unsigned long long sh_prefix, sh_next;
-  __shared__ unsigned sh_k, sh_le;
-  __shared__ double sh_max[AVA_SPEC_NORM_T / 64];
-  const int w = blockIdx.x, t = threadIdx.x;
-  const SpecMeta m = a.meta[w];
-  if (m.nframes <= 0) return;                                        // zeros (or the NaN marker) were written already
+  const int w = blockIdx.x;
+  if (a.meta[w].nframes <= 0) return;                                // zeros (or the NaN marker) were written already
   const int n = a.F * a.T;
-  const double* v = a.vals + (size_t)w * n;
-  unsigned long long prefix = 0;
-  unsigned k = (unsigned)a.q_lo;
-  for (int shift = 56; shift >= 0; shift -= 8) {
-    if (t < 256) hist[t] = 0;
-    __syncthreads();
-    const unsigned long long himask = shift == 56 ? 0ull : (~0ull << (shift + 8));
-    for (int i = t; i < n; i += AVA_SPEC_NORM_T) {
-      const unsigned long long key = (unsigned long long)__double_as_longlong(v[i]);
-      if ((key & himask) == prefix) atomicAdd(&hist[(key >> shift) & 255ull], 1u);
-    }
-    __syncthreads();
-    if (t == 0) {
-      unsigned c = 0, b = 0;
-      for (; b < 256; ++b) {
-        if (c + hist[b] > k) break;
-        c += hist[b];
-      }
-      sh_prefix = prefix | ((unsigned long long)b << shift);
-      sh_k = k - c;
-    }
-    __syncthreads();
-    prefix = sh_prefix;
-    k = sh_k;
-    __syncthreads();
-  }
-  const double alo = __longlong_as_double((long long)prefix);
-  // a[lo + 1]: alo again when more than lo + 1 values are <= alo, else the smallest value above it; and the maximum
-  if (t == 0) { sh_le = 0; sh_next = ~0ull; }
-  __syncthreads();
-  unsigned le = 0;
-  unsigned long long nxt = ~0ull;
-  double mx = 0.0;
-  for (int i = t; i < n; i += AVA_SPEC_NORM_T) {
-    const double x = v[i];
-    const unsigned long long key = (unsigned long long)__double_as_longlong(x);
-    if (key <= prefix) ++le; else if (key < nxt) nxt = key;
-    mx = x > mx ? x : mx;
-  }
-  atomicAdd(&sh_le, le);
-  atomicMin(&sh_next, nxt);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) { const double y = __shfl_xor(mx, o, 64); mx = y > mx ? y : mx; }
-  if ((t & 63) == 0) sh_max[t >> 6] = mx;
-  __syncthreads();
-  for (int i = 0; i < AVA_SPEC_NORM_T / 64; ++i) mx = sh_max[i] > mx ? sh_max[i] : mx;
-  const double ahi = (sh_le >= (unsigned)a.q_lo + 2u || a.q_lo + 1 >= n) ? alo : __longlong_as_double((long long)sh_next);
-  // numpy's _lerp: a + (b - a) * t, replaced by b - (b - a) * (1 - t) where t >= 0.5
-  const double diff = __dsub_rn(ahi, alo);
-  double qv = __dadd_rn(alo, __dmul_rn(diff, a.q_gamma));
-  if (a.q_gamma >= 0.5) qv = __dsub_rn(ahi, __dmul_rn(diff, __dsub_rn(1.0, a.q_gamma)));
-  double top = __dsub_rn(mx, qv);                                    // max of the shifted, floored spectrogram
-  top = top < 0.0 ? 0.0 : top;
-  const double den = __dadd_rn(top, AVA_SPEC_EPS);
-  float fmax = 0.f;
-  float* o = a.out + (size_t)w * n;
-  for (int i = t; i < n; i += AVA_SPEC_NORM_T) {
-    double x = __dsub_rn(v[i], qv);
-    x = x < 0.0 ? 0.0 : x;
-    const float f = (float)__ddiv_rn(x, den);
-    o[i] = f;
-    fmax = f > fmax ? f : fmax;
-  }
-  if (a.out_max != nullptr && fmax > 0.f) atomicMax(reinterpret_cast<int*>(a.out_max + w), __float_as_int(fmax));
+  spec_normalize_window(a.vals + (size_t)w * n, a.out + (size_t)w * n, n, a.q_lo, a.q_gamma,
+                        a.out_max != nullptr ? a.out_max + w : nullptr);
 }
 
-static int frames_for(int max_samples, int nstep) { return (max_samples + nstep - 1) / nstep + 1; }
+int spec_frames_for(int max_samples, int nstep) { return (max_samples + nstep - 1) / nstep + 1; }
 
-static bool spec_shape_ok(int nperseg, int noverlap) {
+bool spec_shape_ok(int nperseg, int noverlap) {
   if (nperseg < 64 || nperseg > 2048) return false;       // a power of two: radix-2 kernel; any other length: direct transform
   return noverlap >= 0 && noverlap < nperseg;
 }
 
+// bytes of krange, meta, twiddle, ftimes and logmag behind the 256-byte alignment slack
+static size_t spec_frames_bytes(int n, int max_samples, int nperseg, int noverlap) {
+  const size_t frames = (size_t)spec_frames_for(max_samples, nperseg - noverlap);
+  return 256 + 16 + (((size_t)n * sizeof(SpecMeta) + 15) & ~(size_t)15) + (size_t)2 * nperseg * sizeof(double) +
+         (size_t)n * frames * sizeof(double) + (size_t)n * frames * (size_t)(nperseg / 2 + 1) * sizeof(double);
+}
+
 extern "C" size_t ava_spec_workspace_bytes(int n, int max_samples, int nperseg, int noverlap, int F, int T, int normalize) {
   if (n <= 0 || max_samples <= 0 || F <= 0 || T <= 0 || !spec_shape_ok(nperseg, noverlap)) return 0;
-  const size_t frames = (size_t)frames_for(max_samples, nperseg - noverlap);
-  return 256 + 16 + (((size_t)n * sizeof(SpecMeta) + 15) & ~(size_t)15) + (size_t)2 * nperseg * sizeof(double) +
-         (size_t)n * frames * sizeof(double) + (size_t)n * frames * (size_t)(nperseg / 2 + 1) * sizeof(double) +
-         (normalize ? (size_t)n * F * T * sizeof(double) : 0);
+  return spec_frames_bytes(n, max_samples, nperseg, noverlap) + (normalize ? (size_t)n * F * T * sizeof(double) : 0);
+}
+
+void spec_carve(SpecArgs& a, void* ws, int n, int max_samples, int nperseg, int noverlap) {
+  char* base = reinterpret_cast<char*>(ws);
+  base += (256 - (reinterpret_cast<uintptr_t>(base) & 255)) & 255;
+  a.krange = reinterpret_cast<int*>(base);
+  base += 16;
+  a.meta = reinterpret_cast<SpecMeta*>(base);
+  a.twiddle = reinterpret_cast<double*>(base + (((size_t)n * sizeof(SpecMeta) + 15) & ~(size_t)15));
+  a.ftimes = a.twiddle + 2 * nperseg;                 // room for the whole circle (lengths that are not a power of two)
+  a.logmag = a.ftimes + (size_t)n * spec_frames_for(max_samples, nperseg - noverlap);
+  a.vals = a.logmag + (size_t)n * spec_frames_for(max_samples, nperseg - noverlap) * (size_t)(nperseg / 2 + 1);
+}
+
+int spec_launch_frames(const SpecArgs& a, hipStream_t st) {
+  hipLaunchKernelGGL(spec_prep_kernel, dim3(a.n), dim3(AVA_SPEC_PREP_T), 0, st, a);
+  AVA_CHECK_LAUNCH();
+  const dim3 fgrid(a.maxframes < 24 ? a.maxframes : 24, a.n);    // a workgroup strides over its window's needed frames
+  if ((a.nperseg & (a.nperseg - 1)) != 0) hipLaunchKernelGGL(spec_dft_kernel, fgrid, dim3(256), 0, st, a);
+  else stft_dispatch(a.nperseg, [&](auto logn) {
+    hipLaunchKernelGGL(spec_stft_kernel<decltype(logn)::value>, fgrid, dim3(256), 0, st, a);
+  });
+  AVA_CHECK_LAUNCH();
+  return AVA_OK;
 }
 
 extern "C" int ava_get_spec_batch(const void* audio, int audio_dtype, const int64_t* file_off, const int64_t* file_len,
@@ -469,30 +347,16 @@ extern "C" int ava_get_spec_batch(const void* audio, int audio_dtype, const int6
   a.audio = audio; a.file_off = reinterpret_cast<const long long*>(file_off);
   a.file_len = reinterpret_cast<const long long*>(file_len); a.file_idx = file_idx;
   a.t1 = t1; a.t2 = t2; a.target_times = target_times; a.target_freqs = target_freqs; a.window = window;
-  char* base = reinterpret_cast<char*>(ws);
-  base += (256 - (reinterpret_cast<uintptr_t>(base) & 255)) & 255;
-  a.krange = reinterpret_cast<int*>(base);
-  base += 16;
-  a.meta = reinterpret_cast<SpecMeta*>(base);
-  a.twiddle = reinterpret_cast<double*>(base + (((size_t)n * sizeof(SpecMeta) + 15) & ~(size_t)15));
-  a.ftimes = a.twiddle + 2 * nperseg;                 // room for the whole circle (lengths that are not a power of two)
-  a.logmag = a.ftimes + (size_t)n * frames_for(max_samples, nperseg - noverlap);
-  a.vals = a.logmag + (size_t)n * frames_for(max_samples, nperseg - noverlap) * (size_t)(nperseg / 2 + 1);
+  spec_carve(a, ws, n, max_samples, nperseg, noverlap);
   a.normalize = normalize ? 1 : 0; a.q_lo = q_lo; a.q_gamma = q_gamma;
   a.out = out; a.out_max = out_max;
   a.fs = fs; a.scale = scale; a.spec_min = spec_min; a.range = spec_max - spec_min; a.fill_value = fill_value;
-  a.fbin = 1.0 / ((double)nperseg * (1.0 / fs));      // host IEEE arithmetic: the very operations of scipy.fft.rfftfreq
-  a.n = n; a.nperseg = nperseg; a.nstep = nperseg - noverlap; a.maxframes = frames_for(max_samples, a.nstep);
+  a.fbin = spec_fbin(nperseg, fs);
+  a.n = n; a.nperseg = nperseg; a.nstep = nperseg - noverlap; a.maxframes = spec_frames_for(max_samples, a.nstep);
   a.F = F; a.T = T; a.dtype = audio_dtype; a.remove_dc = remove_dc;
   hipStream_t st = to_stream(s);
-  hipLaunchKernelGGL(spec_prep_kernel, dim3(n), dim3(AVA_SPEC_PREP_T), 0, st, a);
-  AVA_CHECK_LAUNCH();
-  const dim3 fgrid(a.maxframes < 24 ? a.maxframes : 24, n);      // a workgroup strides over its window's needed frames
-  if ((nperseg & (nperseg - 1)) != 0) hipLaunchKernelGGL(spec_dft_kernel, fgrid, dim3(256), 0, st, a);
-  else stft_dispatch(nperseg, [&](auto logn) {
-    hipLaunchKernelGGL(spec_stft_kernel<decltype(logn)::value>, fgrid, dim3(256), 0, st, a);
-  });
-  AVA_CHECK_LAUNCH();
+  const int rc = spec_launch_frames(a, st);
+  if (rc != AVA_OK) return rc;
   hipLaunchKernelGGL(spec_interp_kernel, dim3(ceil_div(F, AVA_SPEC_ROWS), n), dim3(256), 0, st, a);
   AVA_CHECK_LAUNCH();
   if (normalize) {

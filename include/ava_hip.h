@@ -405,6 +405,50 @@ int ava_tpl_xcorr(const double* spec, const double* frame_sum, int F, int64_t fr
                   const int64_t* lag_off, const int64_t* tile_off, int files, int64_t lags, int64_t tiles,
                   const double* tmpl, int template_F, int L, double* trace, void* ws, size_t ws_bytes, ava_stream_t s);
 
+/* ---- time-warped shotgun windows on the device -------------------------------------
+ * WarpedWindowDataset (ava/models/window_vae_dataset.py:358-701) draws windows of song motifs under per-file piecewise
+ * linear time warps; every window is get_spec(0.0, template_dur, audio[file], p, fs=fs, target_times=...).  The slice,
+ * its mean and its log-spectrogram are the same for every window of a file: ava_warp_cache_build makes them once for
+ * all files (the kernels of ava_get_spec_batch, run with one window per file), ava_warp_windows interpolates a batch out
+ * of that cache (the interpolation, fill rule, normalisation, clip and within_syll_normalize of ava_get_spec_batch, on
+ * the same fp64 inputs: the two paths give the same bits).
+ *   audio ... file_len    as ava_get_spec_batch; `files` files
+ *   template_dur, fs      the motif is the slice [0, min(len, round(template_dur fs))) of each file; a file with fewer
+ *                         than nperseg samples in it yields zeros (utils.py:68-69)
+ *   nperseg, noverlap, window, scale, remove_dc     as ava_get_spec_batch (64 <= nperseg <= 2048)
+ *   fmin, fmax            smallest / largest target frequency: the cache keeps the bins between them (+- 2)
+ *   cache, cache_bytes    device buffer of ava_warp_cache_bytes(...) bytes: per file the frame count, the frame times
+ *                         and log(|X| + 1e-12) as [file][bin][frame] float64 (frames padded to a multiple of 16), i.e.
+ *                         files x bins x frames x 8 bytes
+ *   ws, ws_bytes          scratch of ava_warp_cache_workspace_bytes(...) (build) /
+ *                         ava_warp_windows_workspace_bytes(n, F, T, normalize) (windows; needed with normalize only)
+ *   file_idx [n], target_times [n][T], target_freqs [F]    device; target times may be non-uniform and may lie
+ *                         outside [0, template_dur] (interp2d's fill rule applies); T <= 512
+ *   spec_min ... q_gamma  as ava_get_spec_batch;  out [n][F][T] fp32
+ * ava_warp_windows must be given the files, template_dur, fs, nperseg, noverlap, fmin, fmax the cache was built with.
+ * AVA_EINVAL before any launch for null pointers, files <= 0, template_dur <= 0, an unsupported nperseg or T;
+ * AVA_EWORKSPACE for a cache or scratch that is too small.  A file index outside [0, files) gives a window of NaNs.
+ *
+ * ava_warp_band_spec: the inputs of the warp fit (ava/models/utils.py:337-418, _get_spec for every file): ava_tpl_spec
+ * with the divisor handed in, S = clip((log(|X| + 1e-9) - spec_min) / divisor, 0, 1), where the reference's divisor is
+ * spec_max_val - spec_min_val + 1e-9 (computed by the caller).  nperseg a power of two in 64..2048. */
+size_t ava_warp_cache_bytes(int files, double template_dur, double fs, int nperseg, int noverlap, double fmin,
+                            double fmax);
+size_t ava_warp_cache_workspace_bytes(int files, double template_dur, double fs, int nperseg, int noverlap);
+int ava_warp_cache_build(const void* audio, int audio_dtype, const int64_t* file_off, const int64_t* file_len, int files,
+                         double template_dur, double fs, int nperseg, int noverlap, const double* window, double scale,
+                         double fmin, double fmax, int remove_dc, void* cache, size_t cache_bytes, void* ws,
+                         size_t ws_bytes, ava_stream_t s);
+size_t ava_warp_windows_workspace_bytes(int n, int F, int T, int normalize);
+int ava_warp_windows(const void* cache, size_t cache_bytes, int files, double template_dur, double fs, int nperseg,
+                     int noverlap, double fmin, double fmax, const int32_t* file_idx, const double* target_times, int n,
+                     const double* target_freqs, int F, int T, double spec_min, double spec_max, double fill_value,
+                     int normalize, int q_lo, double q_gamma, float* out, void* ws, size_t ws_bytes, ava_stream_t s);
+int ava_warp_band_spec(const void* audio, int audio_dtype, const int64_t* file_off, const int64_t* file_len,
+                       const int64_t* frame_off, int files, int64_t frames, int nperseg, int noverlap,
+                       const double* window, double scale, int k0, int k1, double spec_min, double divisor, double* spec,
+                       double* frame_sum, ava_stream_t s);
+
 /* ---- exact 1-nearest-neighbour search ------------------------------------------------
  * The searches of ava/plotting/shotgun_movie.py:shotgun_movie_DC: NearestNeighbors(n_neighbors=1,
  * metric='correlation') over spectrograms (:148-158) and argmin of scipy's euclidean over latent means (:126-133).
