@@ -113,6 +113,7 @@ SIGNATURES = {
     "ava_tpl_spec": (_i, [_p, _i, _p, _p, _p, _i, _i64, _i, _i, _p, _d, _i, _i, _d, _d, _p, _p, _p]),
     "ava_tpl_xcorr": (_i, [_p, _p, _i, _i64, _p, _p, _p, _i, _i64, _i64, _p, _i, _i, _p, _p, _sz, _p]),
     "ava_warp_cache_bytes": (_sz, [_i, _d, _d, _i, _i, _d, _d]),
+    "ava_warp_cache_layout": (_i, [_i, _d, _d, _i, _i, _d, _d, C.POINTER(_i64)]),
     "ava_warp_cache_workspace_bytes": (_sz, [_i, _d, _d, _i, _i]),
     "ava_warp_cache_build": (_i, [_p, _i, _p, _p, _i, _d, _d, _i, _i, _p, _d, _d, _d, _i, _p, _sz, _p, _sz, _p]),
     "ava_warp_windows_workspace_bytes": (_sz, [_i, _i, _i, _i]),

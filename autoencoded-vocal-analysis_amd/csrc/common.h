@@ -43,6 +43,11 @@ static inline int ava_scale_grid(int grid_for_all_cus) {
 }
 static inline int64_t ceil_div64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// Workspace regions start on 256-byte boundaries: a size rounded up, and a caller's pointer moved up to the next
+// boundary (every *_workspace_bytes reserves 256 bytes of slack for that)
+static inline size_t ava_up256(size_t x) { return (x + 255) & ~(size_t)255; }
+static inline char* ava_align256(const void* p) { return reinterpret_cast<char*>(ava_up256(reinterpret_cast<uintptr_t>(p))); }
+
 // Counter-based standard normal: splitmix64 finaliser + Box-Muller; matches ava_amd.synthetic.u01 / gauss (SURVEY
 // Appendix E) so that injected and device-generated noise agree to float rounding when seeded alike.  Element i of a
 // stream depends on (i + offset, seed) only, never on the launch geometry.

@@ -229,9 +229,7 @@ extern "C" int ava_amp_trace(const void* audio, int audio_dtype, const int64_t* 
   if (gauss_w == nullptr || trace == nullptr || radius < 0) return AVA_EINVAL;
   if (softmax && !(temperature != 0.0)) return AVA_EINVAL;
   if (ws == nullptr || ws_bytes < ava_amp_workspace_bytes(frames)) return AVA_EINVAL;
-  char* base = reinterpret_cast<char*>(ws);
-  base += (256 - (reinterpret_cast<uintptr_t>(base) & 255)) & 255;
-  double* raw = reinterpret_cast<double*>(base);
+  double* raw = reinterpret_cast<double*>(ava_align256(ws));
   hipStream_t st = to_stream(s);
   const int rc = band_stft(audio, audio_dtype, file_off, file_len, frame_off, files, frames, nperseg, noverlap, window,
                            scale, k0, k1, spec_min, spec_max - spec_min, softmax != 0, temperature, raw, spec, st);

@@ -6,7 +6,7 @@
 //   scipy.signal.stft (hann, zero boundary, zero padded to whole hops, 'spectrum' scaling), log(|.| + 1e-12)
 //                                                           utils.py:74-76      spec_stft_kernel   (1 workgroup / frame)
 //   interp2d (bilinear on the (t, f) grid, fill outside), (x - min) / (max - min), clip to [0, 1]
-//                                                           utils.py:77-103     spec_interp_kernel (1 thread / pixel)
+//                                                           utils.py:77-103     spec_interp_kernel of spec_core.h (1 thread / pixel)
 //
 // Everything is fp64, as in the reference (int16 audio - float64 mean -> complex128 STFT): the log turns relative
 // errors of small bins into absolute ones, and bins 100 dB under the frame's peak are above the clip floor.  The output
@@ -222,70 +222,6 @@ __global__ __launch_bounds__(256) void spec_dft_kernel(const SpecArgs a) {
   }
 }
 
-// utils.py:77-103.  Linear B-spline evaluation in FITPACK's order (fpbspl: h0 = f (t[l+1] - x), h1 = f (x - t[l]) with
-// f = 1 / (t[l+1] - t[l]); fpbisp: sum over x then y of (c * hx) * hy), then interp2d's out-of-bounds rule, then
-// normalisation and clip.  A workgroup owns AVA_SPEC_ROWS frequency rows of one window: the knot interval and the two
-// basis values of every target TIME are computed once per workgroup (LDS), those of a target FREQUENCY once per row
-// visit, so a pixel costs four loads, the 4-term sum and the normalising division.
-__global__ __launch_bounds__(256) void spec_interp_kernel(const SpecArgs a) {
-  __shared__ double chx0[AVA_SPEC_TMAX], chx1[AVA_SPEC_TMAX];
-  __shared__ int cl[AVA_SPEC_TMAX];                                  // knot interval of column ti, -1: outside -> fill value
-  __shared__ double rhy0[AVA_SPEC_ROWS], rhy1[AVA_SPEC_ROWS];
-  __shared__ int rq[AVA_SPEC_ROWS];
-  const int w = blockIdx.y, f0 = blockIdx.x * AVA_SPEC_ROWS, t = threadIdx.x;
-  const SpecMeta m = a.meta[w];
-  const int rows = a.F - f0 < AVA_SPEC_ROWS ? a.F - f0 : AVA_SPEC_ROWS;
-  float* obase = a.out + ((size_t)w * a.F + f0) * a.T;
-  if (m.nframes <= 0) {                                              // utils.py:68-69: np.zeros / the "scratch too small" marker
-    const float z = m.nframes == 0 ? 0.f : __builtin_nanf("");
-    for (int i = t; i < rows * a.T; i += 256) obase[i] = z;
-    return;
-  }
-  const int K = a.nperseg / 2 + 1;
-  const double* ft = a.ftimes + (size_t)w * a.maxframes;
-  const double val = a.fbin;                       // bin frequencies: rfftfreq(n, d) = arange(n/2 + 1) * (1 / (n d)), d = 1 / fs
-  for (int ti = t; ti < a.T; ti += 256)
-    spec_time_basis(a.target_times[(size_t)w * a.T + ti], ft, m.nframes, a.fs, a.nstep, &cl[ti], &chx0[ti], &chx1[ti]);
-  if (t < rows) spec_freq_basis(a.target_freqs[f0 + t], val, K, &rq[t], &rhy0[t], &rhy1[t]);
-  __syncthreads();
-  float fmax = 0.f;
-  for (int i = t; i < rows * a.T; i += 256) {
-    const int r = i / a.T, ti = i - r * a.T;
-    const int l = cl[ti], q = rq[r];
-    double v;
-    if (l < 0 || q < 0) {
-      v = a.fill_value;
-    } else {
-      const double hx0 = chx0[ti], hx1 = chx1[ti], hy0 = rhy0[r], hy1 = rhy1[r];
-      const double* c0 = a.logmag + ((size_t)w * a.maxframes + l) * K + q;       // coefficient c[time l][freq q]
-      const double* c1 = c0 + K;
-      v = spec_bilinear(c0[0], c0[1], c1[0], c1[1], hx0, hx1, hy0, hy1);
-    }
-    v = spec_scale_clip(v, a.spec_min, a.range);                       // utils.py:101-102
-    if (a.normalize) {                                                 // utils.py:104-108 follow in spec_normalize_kernel
-      a.vals[((size_t)w * a.F + f0) * a.T + i] = v;
-    } else {
-      const float vf = (float)v;
-      obase[i] = vf;
-      fmax = vf > fmax ? vf : fmax;
-    }
-  }
-  if (a.out_max != nullptr && !a.normalize) {                          // one atomic per wave
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { const float y = __shfl_xor(fmax, o, 64); fmax = y > fmax ? y : fmax; }
-    if ((t & 63) == 0 && fmax > 0.f) atomicMax(reinterpret_cast<int*>(a.out_max + w), __float_as_int(fmax));
-  }
-}
-
-// within_syll_normalize (utils.py:104-108), one workgroup per window: spec_normalize_window of spec_core.h
-__global__ __launch_bounds__(AVA_SPEC_NORM_T) void spec_normalize_kernel(const SpecArgs a) {
-  const int w = blockIdx.x;
-  if (a.meta[w].nframes <= 0) return;                                // zeros (or the NaN marker) were written already
-  const int n = a.F * a.T;
-  spec_normalize_window(a.vals + (size_t)w * n, a.out + (size_t)w * n, n, a.q_lo, a.q_gamma,
-                        a.out_max != nullptr ? a.out_max + w : nullptr);
-}
-
 int spec_frames_for(int max_samples, int nstep) { return (max_samples + nstep - 1) / nstep + 1; }
 
 bool spec_shape_ok(int nperseg, int noverlap) {
@@ -306,8 +242,7 @@ extern "C" size_t ava_spec_workspace_bytes(int n, int max_samples, int nperseg, 
 }
 
 void spec_carve(SpecArgs& a, void* ws, int n, int max_samples, int nperseg, int noverlap) {
-  char* base = reinterpret_cast<char*>(ws);
-  base += (256 - (reinterpret_cast<uintptr_t>(base) & 255)) & 255;
+  char* base = ava_align256(ws);
   a.krange = reinterpret_cast<int*>(base);
   base += 16;
   a.meta = reinterpret_cast<SpecMeta*>(base);
@@ -329,6 +264,21 @@ int spec_launch_frames(const SpecArgs& a, hipStream_t st) {
   return AVA_OK;
 }
 
+int spec_out_args(SpecOut& o, const double* target_times, const double* target_freqs, float* out, float* out_max, int n,
+                  int F, int T, double fs, int nperseg, int noverlap, double spec_min, double spec_max, double fill_value,
+                  int normalize, int q_lo, double q_gamma) {
+  if (target_times == nullptr || target_freqs == nullptr || out == nullptr) return AVA_EINVAL;
+  if (n <= 0 || F <= 0 || T <= 0 || T > AVA_SPEC_TMAX) return AVA_EINVAL;
+  if (!(spec_max != spec_min)) return AVA_EINVAL;
+  if (normalize && (q_lo < 0 || q_lo >= F * T || !(q_gamma >= 0.0 && q_gamma <= 1.0))) return AVA_EINVAL;
+  o.target_times = target_times; o.target_freqs = target_freqs; o.out = out; o.out_max = out_max; o.vals = nullptr;
+  o.normalize = normalize ? 1 : 0; o.q_lo = q_lo; o.q_gamma = q_gamma;
+  o.fs = fs; o.spec_min = spec_min; o.range = spec_max - spec_min; o.fill_value = fill_value;
+  o.fbin = spec_fbin(nperseg, fs);
+  o.n = n; o.nperseg = nperseg; o.nstep = nperseg - noverlap; o.F = F; o.T = T;
+  return AVA_OK;
+}
+
 extern "C" int ava_get_spec_batch(const void* audio, int audio_dtype, const int64_t* file_off, const int64_t* file_len,
                                   const int32_t* file_idx, const double* t1, const double* t2, const double* target_times,
                                   int n, int max_samples, double fs, int nperseg, int noverlap, const double* window,
@@ -336,32 +286,22 @@ extern "C" int ava_get_spec_batch(const void* audio, int audio_dtype, const int6
                                   double fill_value, int remove_dc, int normalize, int q_lo, double q_gamma, float* out,
                                   float* out_max, void* ws, size_t ws_bytes, ava_stream_t s) {
   if (audio == nullptr || file_off == nullptr || file_len == nullptr || file_idx == nullptr || t1 == nullptr ||
-      t2 == nullptr || target_times == nullptr || window == nullptr || target_freqs == nullptr || out == nullptr)
+      t2 == nullptr || window == nullptr)
     return AVA_EINVAL;
-  if (n <= 0 || F <= 0 || T <= 0 || T > AVA_SPEC_TMAX || max_samples <= 0 || !(fs > 0.0) || !spec_shape_ok(nperseg, noverlap)) return AVA_EINVAL;
+  if (max_samples <= 0 || !(fs > 0.0) || !spec_shape_ok(nperseg, noverlap)) return AVA_EINVAL;
   if (audio_dtype < AVA_AUDIO_I16 || audio_dtype > AVA_AUDIO_F64) return AVA_EINVAL;
-  if (!(spec_max != spec_min)) return AVA_EINVAL;
-  if (normalize && (q_lo < 0 || q_lo >= F * T || !(q_gamma >= 0.0 && q_gamma <= 1.0))) return AVA_EINVAL;
-  if (ws == nullptr || ws_bytes < ava_spec_workspace_bytes(n, max_samples, nperseg, noverlap, F, T, normalize)) return AVA_EWORKSPACE;
   SpecArgs a;
+  const int rc = spec_out_args(a, target_times, target_freqs, out, out_max, n, F, T, fs, nperseg, noverlap, spec_min,
+                               spec_max, fill_value, normalize, q_lo, q_gamma);
+  if (rc != AVA_OK) return rc;
+  if (ws == nullptr || ws_bytes < ava_spec_workspace_bytes(n, max_samples, nperseg, noverlap, F, T, normalize)) return AVA_EWORKSPACE;
   a.audio = audio; a.file_off = reinterpret_cast<const long long*>(file_off);
   a.file_len = reinterpret_cast<const long long*>(file_len); a.file_idx = file_idx;
-  a.t1 = t1; a.t2 = t2; a.target_times = target_times; a.target_freqs = target_freqs; a.window = window;
+  a.t1 = t1; a.t2 = t2; a.window = window;
   spec_carve(a, ws, n, max_samples, nperseg, noverlap);
-  a.normalize = normalize ? 1 : 0; a.q_lo = q_lo; a.q_gamma = q_gamma;
-  a.out = out; a.out_max = out_max;
-  a.fs = fs; a.scale = scale; a.spec_min = spec_min; a.range = spec_max - spec_min; a.fill_value = fill_value;
-  a.fbin = spec_fbin(nperseg, fs);
-  a.n = n; a.nperseg = nperseg; a.nstep = nperseg - noverlap; a.maxframes = spec_frames_for(max_samples, a.nstep);
-  a.F = F; a.T = T; a.dtype = audio_dtype; a.remove_dc = remove_dc;
+  a.scale = scale; a.maxframes = spec_frames_for(max_samples, a.nstep);
+  a.dtype = audio_dtype; a.remove_dc = remove_dc;
   hipStream_t st = to_stream(s);
-  const int rc = spec_launch_frames(a, st);
-  if (rc != AVA_OK) return rc;
-  hipLaunchKernelGGL(spec_interp_kernel, dim3(ceil_div(F, AVA_SPEC_ROWS), n), dim3(256), 0, st, a);
-  AVA_CHECK_LAUNCH();
-  if (normalize) {
-    hipLaunchKernelGGL(spec_normalize_kernel, dim3(n), dim3(AVA_SPEC_NORM_T), 0, st, a);
-    AVA_CHECK_LAUNCH();
-  }
-  return AVA_OK;
+  const int frc = spec_launch_frames(a, st);
+  return frc != AVA_OK ? frc : spec_launch_out(a, st);
 }

@@ -1,9 +1,11 @@
-// The arithmetic of get_spec (ava/preprocessing/utils.py:77-108) after the transform, shared by the shotgun
-// spectrograms (spec.hip) and the warped windows out of the motif cache (warp_spec.hip,
-// row f9): the linear B-spline basis of a target time / frequency in FITPACK's order, the four-term sum, interp2d's
-// fill rule, the normalisation and clip, and within_syll_normalize.  Both units call these functions, so that a window
-// cut from the cache and the same window transformed on its own are the same bits.  Also the argument block of
-// spec.hip's kernels and the host launcher of its first two stages, which warp_spec.hip runs once per file.
+// get_spec (ava/preprocessing/utils.py:77-108) after the transform, shared by the shotgun spectrograms (spec.hip,
+// SURVEY.md section 8 row f4) and the warped windows out of the motif cache (warp_spec.hip, row f9): the linear
+// B-spline basis of a target time / frequency in FITPACK's order, the four-term sum, interp2d's fill rule, the
+// normalisation and clip, within_syll_normalize -- and the ONE interpolation kernel, normalise kernel, argument check
+// and launcher that run them.  The two rows differ only in where a window's frame count, frame times and log-magnitude
+// coefficients are stored (a "coefficient source", below), so a window cut from the cache and the same window
+// transformed on its own are the same bits.  Also the argument block of spec.hip's first two stages and their host
+// launcher, which warp_spec.hip runs once per file.
 #pragma once
 #include "stft.h"
 
@@ -21,28 +23,60 @@ struct SpecMeta {        // one per window, written by spec_prep_kernel
   double t_shift;        // max(0, t1)
 };
 
-struct SpecArgs {
+struct SpecOut {          // the output half: what runs after the transform, whichever source the coefficients come from
+  const double* target_times;    // [n][T]
+  const double* target_freqs;    // [F]
+  float* out;                    // [n][F][T]
+  float* out_max;                // [n] or null
+  double* vals;                  // [n][F*T]: clipped fp64 spectrograms handed to spec_normalize_kernel (normalize only)
+  double q_gamma;                // within_syll_normalize: np.quantile's interpolation weight ...
+  int q_lo, normalize;           // ... between the order statistics q_lo and q_lo + 1 (0-based)
+  double fs, spec_min, range, fill_value, fbin;    // fbin: rfftfreq's 1 / (nperseg * (1 / fs))
+  int n, nperseg, nstep, F, T;
+};
+
+struct SpecCoef { double t0f0, t0f1, t1f0, t1f1; };   // log-magnitudes at time l / l + 1 (t0 / t1), frequency q / q + 1 (f0 / f1)
+
+// A coefficient source is an argument block derived from SpecOut with  window(w) -> a handle of window w  that holds
+//   nframes         its frame count (0: get_spec returns zeros, utils.py:68-69; -1: NaN marker)
+//   ftimes          its nframes frame times
+//   coef(l, q)      the SpecCoef of knot interval (l, q)
+// SpecArgs: the per-window scratch [window][frame][bin] the transform of spec.hip fills.
+struct SpecScratchWindow {
+  int nframes;
+  const double* ftimes;
+  const double* logmag;          // [frame][K]
+  int K;
+#ifdef __HIPCC__
+  __device__ __forceinline__ SpecCoef coef(int l, int q) const {
+    const double* c0 = logmag + (size_t)l * K + q;
+    const double* c1 = c0 + K;
+    return {c0[0], c0[1], c1[0], c1[1]};
+  }
+#endif
+};
+
+struct SpecArgs : SpecOut {
   const void* audio;
   const long long* file_off;
   const long long* file_len;
   const int* file_idx;
   const double* t1;
   const double* t2;
-  const double* target_times;    // [n][T]
-  const double* target_freqs;    // [F]
   const double* window;          // [nperseg]
   SpecMeta* meta;
   double* twiddle;               // [nperseg/2][2]: exp(-2 pi i k / nperseg), written by spec_prep_kernel's workgroup 0
   double* ftimes;                // [n][maxframes]: frame times of each window, written by spec_prep_kernel
   int* krange;                   // [2]: first / last frequency bin the target frequencies can touch (workgroup 0)
   double* logmag;                // [n][maxframes][nperseg/2 + 1]
-  float* out;                    // [n][F][T]
-  float* out_max;                // [n] or null
-  double* vals;                  // [n][F*T]: clipped fp64 spectrograms handed to spec_normalize_kernel (normalize only)
-  double q_gamma;                // within_syll_normalize: np.quantile's interpolation weight ...
-  int q_lo, normalize;           // ... between the order statistics q_lo and q_lo + 1 (0-based)
-  double fs, scale, spec_min, range, fill_value, fbin;    // fbin: rfftfreq's 1 / (nperseg * (1 / fs))
-  int n, maxframes, nperseg, nstep, F, T, dtype, remove_dc;
+  double scale;
+  int maxframes, dtype, remove_dc;
+#ifdef __HIPCC__
+  __device__ __forceinline__ SpecScratchWindow window_of(int w) const {
+    const int K = nperseg / 2 + 1;
+    return {meta[w].nframes, ftimes + (size_t)w * maxframes, logmag + (size_t)w * maxframes * K, K};
+  }
+#endif
 };
 
 // spec.hip: STFT frames of max_samples samples; the shapes its kernels take; the bytes of the scratch regions
@@ -52,6 +86,13 @@ int spec_frames_for(int max_samples, int nstep);
 bool spec_shape_ok(int nperseg, int noverlap);
 void spec_carve(SpecArgs& a, void* ws, int n, int max_samples, int nperseg, int noverlap);
 int spec_launch_frames(const SpecArgs& a, hipStream_t st);
+
+// The output half of an entry point's arguments: AVA_EINVAL for the ones ava_get_spec_batch and ava_warp_windows both
+// refuse (null pointers, n, F, T, T > AVA_SPEC_TMAX, spec_max == spec_min, the quantile of normalize), else fills
+// every field of o but vals (the caller's workspace) and returns AVA_OK.  Nothing is launched.
+int spec_out_args(SpecOut& o, const double* target_times, const double* target_freqs, float* out, float* out_max, int n,
+                  int F, int T, double fs, int nperseg, int noverlap, double spec_min, double spec_max, double fill_value,
+                  int normalize, int q_lo, double q_gamma);
 
 // rfftfreq's bin width 1 / (n d), d = 1 / fs: host IEEE arithmetic, the very operations of scipy.fft.rfftfreq
 static inline double spec_fbin(int nperseg, double fs) { return 1.0 / ((double)nperseg * (1.0 / fs)); }
@@ -196,5 +237,79 @@ __device__ __forceinline__ void spec_normalize_window(const double* v, float* o,
     fmax = f > fmax ? f : fmax;
   }
   if (out_max != nullptr && fmax > 0.f) atomicMax(reinterpret_cast<int*>(out_max), __float_as_int(fmax));
+}
+
+// utils.py:77-103 for the windows of coefficient source Src.  Linear B-spline evaluation in FITPACK's order (fpbspl,
+// fpbisp: the functions above), then interp2d's out-of-bounds rule, then normalisation and clip.  A workgroup owns
+// AVA_SPEC_ROWS frequency rows of one window: the knot interval and the two basis values of every target TIME are
+// computed once per workgroup (LDS), those of a target FREQUENCY once per row visit, so a pixel costs four loads, the
+// 4-term sum and the normalising division.  Consecutive threads take consecutive target times.
+template <class Src>
+__global__ __launch_bounds__(256) void spec_interp_kernel(const Src a) {
+  __shared__ double chx0[AVA_SPEC_TMAX], chx1[AVA_SPEC_TMAX];
+  __shared__ int cl[AVA_SPEC_TMAX];                                  // knot interval of column ti, -1: outside -> fill value
+  __shared__ double rhy0[AVA_SPEC_ROWS], rhy1[AVA_SPEC_ROWS];
+  __shared__ int rq[AVA_SPEC_ROWS];
+  const int w = blockIdx.y, f0 = blockIdx.x * AVA_SPEC_ROWS, t = threadIdx.x;
+  const auto win = a.window_of(w);
+  const int rows = a.F - f0 < AVA_SPEC_ROWS ? a.F - f0 : AVA_SPEC_ROWS;
+  float* obase = a.out + ((size_t)w * a.F + f0) * a.T;
+  if (win.nframes <= 0) {                                            // np.zeros / the NaN marker
+    const float z = win.nframes == 0 ? 0.f : __builtin_nanf("");
+    for (int i = t; i < rows * a.T; i += 256) obase[i] = z;
+    return;
+  }
+  const int K = a.nperseg / 2 + 1;                 // bin frequencies: rfftfreq(n, d) = arange(n/2 + 1) * (1 / (n d)), d = 1 / fs
+  for (int ti = t; ti < a.T; ti += 256)
+    spec_time_basis(a.target_times[(size_t)w * a.T + ti], win.ftimes, win.nframes, a.fs, a.nstep, &cl[ti], &chx0[ti], &chx1[ti]);
+  if (t < rows) spec_freq_basis(a.target_freqs[f0 + t], a.fbin, K, &rq[t], &rhy0[t], &rhy1[t]);
+  __syncthreads();
+  float fmax = 0.f;
+  for (int i = t; i < rows * a.T; i += 256) {
+    const int r = i / a.T, ti = i - r * a.T;
+    const int l = cl[ti], q = rq[r];
+    double v;
+    if (l < 0 || q < 0) {
+      v = a.fill_value;
+    } else {
+      const SpecCoef c = win.coef(l, q);
+      v = spec_bilinear(c.t0f0, c.t0f1, c.t1f0, c.t1f1, chx0[ti], chx1[ti], rhy0[r], rhy1[r]);
+    }
+    v = spec_scale_clip(v, a.spec_min, a.range);                       // utils.py:101-102
+    if (a.normalize) {                                                 // utils.py:104-108 follow in spec_normalize_kernel
+      a.vals[((size_t)w * a.F + f0) * a.T + i] = v;
+    } else {
+      const float vf = (float)v;
+      obase[i] = vf;
+      fmax = vf > fmax ? vf : fmax;
+    }
+  }
+  if (a.out_max != nullptr && !a.normalize) {                          // one atomic per wave
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { const float y = __shfl_xor(fmax, o, 64); fmax = y > fmax ? y : fmax; }
+    if ((t & 63) == 0 && fmax > 0.f) atomicMax(reinterpret_cast<int*>(a.out_max + w), __float_as_int(fmax));
+  }
+}
+
+// within_syll_normalize (utils.py:104-108), one workgroup per window: spec_normalize_window
+template <class Src>
+__global__ __launch_bounds__(AVA_SPEC_NORM_T) void spec_normalize_kernel(const Src a) {
+  const int w = blockIdx.x;
+  if (a.window_of(w).nframes <= 0) return;                           // zeros (or the NaN marker) were written already
+  const int n = a.F * a.T;
+  spec_normalize_window(a.vals + (size_t)w * n, a.out + (size_t)w * n, n, a.q_lo, a.q_gamma,
+                        a.out_max != nullptr ? a.out_max + w : nullptr);
+}
+
+// interpolate (+ normalise) the a.n windows of source a on stream st: AVA_OK or AVA_ELAUNCH
+template <class Src>
+static int spec_launch_out(const Src& a, hipStream_t st) {
+  hipLaunchKernelGGL(spec_interp_kernel<Src>, dim3(ceil_div(a.F, AVA_SPEC_ROWS), a.n), dim3(256), 0, st, a);
+  AVA_CHECK_LAUNCH();
+  if (a.normalize) {
+    hipLaunchKernelGGL(spec_normalize_kernel<Src>, dim3(a.n), dim3(AVA_SPEC_NORM_T), 0, st, a);
+    AVA_CHECK_LAUNCH();
+  }
+  return AVA_OK;
 }
 #endif

@@ -152,9 +152,7 @@ extern "C" int ava_tpl_xcorr(const double* spec, const double* frame_sum, int F,
   a.lag_off = reinterpret_cast<const long long*>(lag_off);
   a.tile_off = reinterpret_cast<const long long*>(tile_off);
   a.tmpl = tmpl;
-  char* base = reinterpret_cast<char*>(ws);
-  base += (256 - (reinterpret_cast<uintptr_t>(base) & 255)) & 255;
-  a.mu = reinterpret_cast<double*>(base);
+  a.mu = reinterpret_cast<double*>(ava_align256(ws));
   a.trace = trace;
   a.frames = frames; a.lags = lags; a.files = files; a.F = F; a.L = L;
   hipStream_t st = to_stream(s);

@@ -7,21 +7,20 @@
 //                          STFT frame, log(|.| + 1e-12)     spec_prep_kernel + spec_stft_kernel / spec_dft_kernel of spec.hip,
 //                          run with one "window" per file (spec_launch_frames), then
 //                          warp_pack_kernel: [file][bin][frame] for the bins the target frequencies can touch
-//   ava_warp_windows       per batch: warp_interp_kernel (1 workgroup / 16 rows of a window), interpolation straight out
-//                          of the cache under each window's own target times; warp_normalize_kernel if asked for
+//   ava_warp_windows       per batch: spec_interp_kernel of spec_core.h (1 workgroup / 16 rows of a window) with the
+//                          cache as its coefficient source, under each window's own target times; spec_normalize_kernel
+//                          if asked for
 //
-// No arithmetic is restated here: the frames are spec.hip's kernels, and the interpolation, the fill rule, the
-// normalisation, the clip and within_syll_normalize are the functions of spec_core.h that spec.hip's kernels call, on
-// the same fp64 inputs.  A window out of the cache is therefore bit-identical to ava_get_spec_batch(0, template_dur) on
-// the same target times.
+// No arithmetic and no kernel of the window path is restated here: the frames are spec.hip's kernels, and the
+// interpolation and normalisation are the kernels ava_get_spec_batch launches, reading [file][bin][frame] out of the
+// cache instead of [window][frame][bin] out of the scratch.  A window out of the cache is therefore bit-identical to
+// ava_get_spec_batch(0, template_dur) on the same target times.
 #include "spec_core.h"
 
 struct WarpLayout {                // the cache: [nframes int[files]] [ftimes double[files][maxframes]] [logmag]
   int max_samples, maxframes, fstride, k0, nb;
   size_t off_ftimes, off_logmag, bytes;      // offsets behind the 256-byte alignment of the caller's pointer
 };
-
-static inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 static bool warp_layout(int files, double template_dur, double fs, int nperseg, int noverlap, double fmin, double fmax,
                         WarpLayout* L) {
@@ -36,15 +35,10 @@ static bool warp_layout(int files, double template_dur, double fs, int nperseg, 
   spec_bin_range(fmin, fmax, spec_fbin(nperseg, fs), nperseg, &L->k0, &k1);
   L->nb = k1 - L->k0 + 1;
   if (L->nb < 2) return false;
-  L->off_ftimes = up256((size_t)files * sizeof(int));
-  L->off_logmag = L->off_ftimes + up256((size_t)files * L->maxframes * sizeof(double));
+  L->off_ftimes = ava_up256((size_t)files * sizeof(int));
+  L->off_logmag = L->off_ftimes + ava_up256((size_t)files * L->maxframes * sizeof(double));
   L->bytes = 256 + L->off_logmag + (size_t)files * L->nb * L->fstride * sizeof(double);
   return true;
-}
-
-static inline char* align256(const void* p) {
-  char* base = reinterpret_cast<char*>(const_cast<void*>(p));
-  return base + ((256 - (reinterpret_cast<uintptr_t>(base) & 255)) & 255);
 }
 
 // the per-"window" inputs of spec_prep_kernel for one window per file: the whole motif, every frame, every bin in range
@@ -79,78 +73,36 @@ __global__ __launch_bounds__(256) void warp_pack_kernel(const SpecMeta* meta, co
   }
 }
 
-struct WarpArgs {
+// The cache as a coefficient source of spec_interp_kernel (spec_core.h).  Consecutive threads take consecutive target
+// times, whose frames l are equal or adjacent: the four coefficient loads of a wave fall in two rows [bin q], [bin q + 1]
+// of the cache, contiguous along frames.
+struct WarpCacheWindow {
+  int nframes;
+  const double* ftimes;
+  const double* logmag;          // [bin - k0][fstride] of the window's file
+  int fstride, k0, nb;
+  __device__ __forceinline__ SpecCoef coef(int l, int q) const {
+    int b = q - k0;                                         // inside [0, nb - 2] by the slack of spec_bin_range
+    b = b < 0 ? 0 : (b > nb - 2 ? nb - 2 : b);
+    const double* c0 = logmag + (size_t)b * fstride + l;
+    const double* c1 = c0 + fstride;
+    return {c0[0], c1[0], c0[1], c1[1]};
+  }
+};
+
+struct WarpArgs : SpecOut {
   const int* c_nframes;          // the cache
   const double* c_ftimes;
   const double* c_logmag;
   const int* file_idx;           // [n]
-  const double* target_times;    // [n][T]
-  const double* target_freqs;    // [F]
-  float* out;                    // [n][F][T]
-  double* vals;                  // [n][F*T] (normalize only)
-  double fs, spec_min, range, fill_value, fbin, q_gamma;
-  int n, files, maxframes, fstride, k0, nb, nperseg, nstep, F, T, normalize, q_lo;
+  int files, maxframes, fstride, k0, nb;
+  // frames of window w's file: 0 where get_spec returns zeros (utils.py:68-69), -1 for a file index out of range
+  __device__ __forceinline__ WarpCacheWindow window_of(int w) const {
+    const int f = file_idx[w];
+    if (f < 0 || f >= files) return {-1, nullptr, nullptr, fstride, k0, nb};
+    return {c_nframes[f], c_ftimes + (size_t)f * maxframes, c_logmag + (size_t)f * nb * fstride, fstride, k0, nb};
+  }
 };
-
-// frames of window w's file: 0 where get_spec returns zeros (utils.py:68-69), -1 for a file index out of range
-__device__ __forceinline__ int warp_nframes(const WarpArgs& a, int w, int* file) {
-  const int f = a.file_idx[w];
-  *file = f;
-  return (f < 0 || f >= a.files) ? -1 : a.c_nframes[f];
-}
-
-// spec_interp_kernel's grid and tables over the cache: a workgroup owns AVA_SPEC_ROWS frequency rows of one window; the
-// knot interval and basis values of every target time are computed once per workgroup into LDS.  Consecutive threads
-// take consecutive target times, whose frames l are equal or adjacent: the four coefficient loads of a wave fall in two
-// rows [bin q], [bin q + 1] of the cache, contiguous along frames.
-__global__ __launch_bounds__(256) void warp_interp_kernel(const WarpArgs a) {
-  __shared__ double chx0[AVA_SPEC_TMAX], chx1[AVA_SPEC_TMAX];
-  __shared__ int cl[AVA_SPEC_TMAX];
-  __shared__ double rhy0[AVA_SPEC_ROWS], rhy1[AVA_SPEC_ROWS];
-  __shared__ int rq[AVA_SPEC_ROWS];
-  const int w = blockIdx.y, f0 = blockIdx.x * AVA_SPEC_ROWS, t = threadIdx.x;
-  int file;
-  const int nf = warp_nframes(a, w, &file);
-  const int rows = a.F - f0 < AVA_SPEC_ROWS ? a.F - f0 : AVA_SPEC_ROWS;
-  float* obase = a.out + ((size_t)w * a.F + f0) * a.T;
-  if (nf <= 0) {
-    const float z = nf == 0 ? 0.f : __builtin_nanf("");
-    for (int i = t; i < rows * a.T; i += 256) obase[i] = z;
-    return;
-  }
-  const int K = a.nperseg / 2 + 1;
-  const double* ft = a.c_ftimes + (size_t)file * a.maxframes;
-  for (int ti = t; ti < a.T; ti += 256)
-    spec_time_basis(a.target_times[(size_t)w * a.T + ti], ft, nf, a.fs, a.nstep, &cl[ti], &chx0[ti], &chx1[ti]);
-  if (t < rows) spec_freq_basis(a.target_freqs[f0 + t], a.fbin, K, &rq[t], &rhy0[t], &rhy1[t]);
-  __syncthreads();
-  const double* cfile = a.c_logmag + (size_t)file * a.nb * a.fstride;
-  for (int i = t; i < rows * a.T; i += 256) {
-    const int r = i / a.T, ti = i - r * a.T;
-    const int l = cl[ti], q = rq[r];
-    double v;
-    if (l < 0 || q < 0) {
-      v = a.fill_value;
-    } else {
-      int b = q - a.k0;                                     // inside [0, nb - 2] by the slack of spec_bin_range
-      b = b < 0 ? 0 : (b > a.nb - 2 ? a.nb - 2 : b);
-      const double* c0 = cfile + (size_t)b * a.fstride + l;                      // [freq q][time l]
-      const double* c1 = c0 + a.fstride;                                         // [freq q + 1][time l]
-      v = spec_bilinear(c0[0], c1[0], c0[1], c1[1], chx0[ti], chx1[ti], rhy0[r], rhy1[r]);
-    }
-    v = spec_scale_clip(v, a.spec_min, a.range);
-    if (a.normalize) a.vals[((size_t)w * a.F + f0) * a.T + i] = v;
-    else obase[i] = (float)v;
-  }
-}
-
-__global__ __launch_bounds__(AVA_SPEC_NORM_T) void warp_normalize_kernel(const WarpArgs a) {
-  const int w = blockIdx.x;
-  int file;
-  if (warp_nframes(a, w, &file) <= 0) return;               // zeros (or the NaN marker) were written already
-  const int n = a.F * a.T;
-  spec_normalize_window(a.vals + (size_t)w * n, a.out + (size_t)w * n, n, a.q_lo, a.q_gamma, nullptr);
-}
 
 extern "C" size_t ava_warp_cache_bytes(int files, double template_dur, double fs, int nperseg, int noverlap, double fmin,
                                        double fmax) {
@@ -160,8 +112,8 @@ extern "C" size_t ava_warp_cache_bytes(int files, double template_dur, double fs
 
 // scratch of the build: the per-file arguments, then the regions spec_launch_frames fills
 static size_t warp_args_bytes(int files) {
-  return up256((size_t)files * sizeof(int)) + 2 * up256((size_t)files * sizeof(double)) +
-         up256((size_t)2 * files * sizeof(double)) + 256;
+  return ava_up256((size_t)files * sizeof(int)) + 2 * ava_up256((size_t)files * sizeof(double)) +
+         ava_up256((size_t)2 * files * sizeof(double)) + 256;
 }
 
 extern "C" size_t ava_warp_cache_workspace_bytes(int files, double template_dur, double fs, int nperseg, int noverlap) {
@@ -180,15 +132,15 @@ extern "C" int ava_warp_cache_build(const void* audio, int audio_dtype, const in
   if (!warp_layout(files, template_dur, fs, nperseg, noverlap, fmin, fmax, &L)) return AVA_EINVAL;
   if (cache_bytes < L.bytes) return AVA_EWORKSPACE;
   if (ws == nullptr || ws_bytes < ava_warp_cache_workspace_bytes(files, template_dur, fs, nperseg, noverlap)) return AVA_EWORKSPACE;
-  char* base = align256(ws);
+  char* base = ava_align256(ws);
   int* file_idx = reinterpret_cast<int*>(base);
-  base += up256((size_t)files * sizeof(int));
+  base += ava_up256((size_t)files * sizeof(int));
   double* t1 = reinterpret_cast<double*>(base);
-  base += up256((size_t)files * sizeof(double));
+  base += ava_up256((size_t)files * sizeof(double));
   double* t2 = reinterpret_cast<double*>(base);
-  base += up256((size_t)files * sizeof(double));
+  base += ava_up256((size_t)files * sizeof(double));
   double* tt = reinterpret_cast<double*>(base);
-  base += up256((size_t)2 * files * sizeof(double));
+  base += ava_up256((size_t)2 * files * sizeof(double));
   double* tf = reinterpret_cast<double*>(base);
   base += 256;
   hipStream_t st = to_stream(s);
@@ -208,7 +160,7 @@ extern "C" int ava_warp_cache_build(const void* audio, int audio_dtype, const in
   a.F = 2; a.T = 2; a.dtype = audio_dtype; a.remove_dc = remove_dc;
   const int rc = spec_launch_frames(a, st);
   if (rc != AVA_OK) return rc;
-  char* c = align256(cache);
+  char* c = ava_align256(cache);
   hipLaunchKernelGGL(warp_pack_kernel, dim3(L.nb < 64 ? L.nb : 64, files), dim3(256), 0, st, a.meta, a.ftimes, a.logmag, files,
                      L.maxframes, L.fstride, nperseg / 2 + 1, L.k0, L.nb, reinterpret_cast<int*>(c),
                      reinterpret_cast<double*>(c + L.off_ftimes), reinterpret_cast<double*>(c + L.off_logmag));
@@ -221,38 +173,35 @@ extern "C" size_t ava_warp_windows_workspace_bytes(int n, int F, int T, int norm
   return 256 + (normalize ? (size_t)n * F * T * sizeof(double) : 0);
 }
 
+extern "C" int ava_warp_cache_layout(int files, double template_dur, double fs, int nperseg, int noverlap, double fmin,
+                                     double fmax, int64_t out[6]) {
+  WarpLayout L;
+  if (out == nullptr || !warp_layout(files, template_dur, fs, nperseg, noverlap, fmin, fmax, &L)) return AVA_EINVAL;
+  out[0] = L.maxframes; out[1] = L.fstride; out[2] = L.k0; out[3] = L.nb;
+  out[4] = (int64_t)L.off_ftimes; out[5] = (int64_t)L.off_logmag;
+  return AVA_OK;
+}
+
 extern "C" int ava_warp_windows(const void* cache, size_t cache_bytes, int files, double template_dur, double fs,
                                 int nperseg, int noverlap, double fmin, double fmax, const int32_t* file_idx,
                                 const double* target_times, int n, const double* target_freqs, int F, int T,
                                 double spec_min, double spec_max, double fill_value, int normalize, int q_lo,
                                 double q_gamma, float* out, void* ws, size_t ws_bytes, ava_stream_t s) {
-  if (cache == nullptr || file_idx == nullptr || target_times == nullptr || target_freqs == nullptr || out == nullptr)
-    return AVA_EINVAL;
-  if (n <= 0 || F <= 0 || T <= 0 || T > AVA_SPEC_TMAX) return AVA_EINVAL;
-  if (!(spec_max != spec_min)) return AVA_EINVAL;
-  if (normalize && (q_lo < 0 || q_lo >= F * T || !(q_gamma >= 0.0 && q_gamma <= 1.0))) return AVA_EINVAL;
+  if (cache == nullptr || file_idx == nullptr) return AVA_EINVAL;
+  WarpArgs a;
+  const int rc = spec_out_args(a, target_times, target_freqs, out, nullptr, n, F, T, fs, nperseg, noverlap, spec_min,
+                               spec_max, fill_value, normalize, q_lo, q_gamma);
+  if (rc != AVA_OK) return rc;
   WarpLayout L;
   if (!warp_layout(files, template_dur, fs, nperseg, noverlap, fmin, fmax, &L)) return AVA_EINVAL;
   if (cache_bytes < L.bytes) return AVA_EWORKSPACE;
   if (normalize && (ws == nullptr || ws_bytes < ava_warp_windows_workspace_bytes(n, F, T, 1))) return AVA_EWORKSPACE;
-  const char* c = align256(cache);
-  WarpArgs a;
+  const char* c = ava_align256(cache);
   a.c_nframes = reinterpret_cast<const int*>(c);
   a.c_ftimes = reinterpret_cast<const double*>(c + L.off_ftimes);
   a.c_logmag = reinterpret_cast<const double*>(c + L.off_logmag);
-  a.file_idx = file_idx; a.target_times = target_times; a.target_freqs = target_freqs;
-  a.out = out;
-  a.vals = normalize ? reinterpret_cast<double*>(align256(ws)) : nullptr;
-  a.fs = fs; a.spec_min = spec_min; a.range = spec_max - spec_min; a.fill_value = fill_value;
-  a.fbin = spec_fbin(nperseg, fs); a.q_gamma = q_gamma;
-  a.n = n; a.files = files; a.maxframes = L.maxframes; a.fstride = L.fstride; a.k0 = L.k0; a.nb = L.nb;
-  a.nperseg = nperseg; a.nstep = nperseg - noverlap; a.F = F; a.T = T; a.normalize = normalize ? 1 : 0; a.q_lo = q_lo;
-  hipStream_t st = to_stream(s);
-  hipLaunchKernelGGL(warp_interp_kernel, dim3(ceil_div(F, AVA_SPEC_ROWS), n), dim3(256), 0, st, a);
-  AVA_CHECK_LAUNCH();
-  if (normalize) {
-    hipLaunchKernelGGL(warp_normalize_kernel, dim3(n), dim3(AVA_SPEC_NORM_T), 0, st, a);
-    AVA_CHECK_LAUNCH();
-  }
-  return AVA_OK;
+  a.file_idx = file_idx;
+  a.vals = normalize ? reinterpret_cast<double*>(ava_align256(ws)) : nullptr;
+  a.files = files; a.maxframes = L.maxframes; a.fstride = L.fstride; a.k0 = L.k0; a.nb = L.nb;
+  return spec_launch_out(a, to_stream(s));
 }

@@ -20,13 +20,12 @@ numpy rounds a Python float compared with the trace.
 ``NotImplementedError``.  There is no CPU fallback.
 """
 import os
-import warnings
 
 import numpy as np
 import torch
 
 from . import _lib
-from .spec import DeviceAudio, _stft_constants
+from .spec import DeviceAudio, _read_wav, _stft_constants
 
 __all__ = ["EPSILON", "get_onsets_offsets", "get_onsets_offsets_batch", "onsets_offsets_from_trace", "get_spec",
            "segment", "install", "frame_count", "frame_step", "band_indices", "gaussian_weights", "trace_dtype",
@@ -264,7 +263,8 @@ def get_spec(audio, p):
 # ---- files ----------------------------------------------------------------------------------------------------------
 
 def _audio_seg_filenames(audio_dir, seg_dir):
-    """segment.py:194-216"""
+    """segment.py:194-216, whose own name test also takes a file named exactly ``.wav`` (``len >= 4``): not
+    ``spec._is_wav_file``, the ``len > 4`` test of the reference's other modules"""
     names = [i for i in sorted(os.listdir(audio_dir)) if len(i) >= 4 and i[-4:] == '.wav']
     return [os.path.join(audio_dir, i) for i in names], [os.path.join(seg_dir, i[:-4] + '.txt') for i in names]
 
@@ -272,15 +272,6 @@ def _audio_seg_filenames(audio_dir, seg_dir):
 def _is_amplitude_segmentation(fn):
     return fn is get_onsets_offsets or (getattr(fn, '__module__', None) == 'ava.segmenting.amplitude_segmentation'
                                         and getattr(fn, '__name__', None) == 'get_onsets_offsets')
-
-
-def _read_wav(fn):
-    """``scipy.io.wavfile.read(fn)``: (fs, samples), its WavFileWarning silenced"""
-    from scipy.io import wavfile
-    from scipy.io.wavfile import WavFileWarning
-    with warnings.catch_warnings():
-        warnings.filterwarnings("ignore", category=WavFileWarning)
-        return wavfile.read(fn)
 
 
 def _chunks(files, max_bytes):

@@ -31,8 +31,7 @@ import numpy as np
 import torch
 
 from .neighbors import nearest
-from .segment import _read_wav
-from .spec import DeviceAudio, get_spec_batch
+from .spec import DeviceAudio, _read_wav, get_spec_batch
 
 __all__ = ["shotgun_movie_embedding", "shotgun_movie_DC", "window_onsets", "window_spectrograms", "window_latents",
            "ffmpeg_commands", "install", "METHODS"]

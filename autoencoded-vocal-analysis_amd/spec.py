@@ -121,6 +121,75 @@ def _stft_constants(nperseg, device):
     return _CONST_CACHE[key]
 
 
+def _check_stft_shape(p, T=None):
+    """(nperseg, noverlap) of ``p`` if the device transform takes them (and ``T`` target times per window)"""
+    nperseg, noverlap = int(p['nperseg']), int(p['noverlap'])
+    if nperseg < 64 or nperseg > 2048 or not 0 <= noverlap < nperseg:
+        raise NotImplementedError("device get_spec needs 64 <= nperseg <= 2048 and 0 <= noverlap < nperseg")
+    if T is not None and T > 512:
+        raise NotImplementedError("device get_spec handles at most 512 target times per window")
+    return nperseg, noverlap
+
+
+def _quantile_index(p, F, T):
+    """``(normalize, q_lo, q_gamma)`` of within_syll_normalize (utils.py:104-108) for ``[F, T]`` spectrograms: the two
+    order statistics ``q_lo``, ``q_lo + 1`` np.quantile interpolates between and its weight"""
+    if not p.get('within_syll_normalize', False):
+        return 0, 0, 0.0
+    q = float(p['normalize_quantile'])
+    if not 0.0 <= q <= 1.0:
+        raise ValueError("Quantiles must be in the range [0, 1]")                   # np.quantile's own check
+    # numpy's 'linear' method: virtual index n q + (alpha + q (1 - alpha - beta)) - 1 with alpha = beta = 1
+    cnt = F * T
+    virtual = cnt * q + (1 + q * (1 - 1 - 1)) - 1
+    if virtual >= cnt - 1:
+        return 1, cnt - 1, 0.0
+    return 1, int(np.floor(virtual)), float(virtual - np.floor(virtual))
+
+
+def _upload(dev, arrays, file_idx):
+    """One small upload per batch out of the page-locked ring: the float64 ``arrays`` back to back, then the int32
+    ``file_idx``.  Returns the flat float64 device views of the arrays and the int32 device view of the indices."""
+    ends, nd = [], 0
+    for a in arrays:
+        nd += a.size
+        ends.append(nd)
+    n = file_idx.size
+    slot = _staging(dev, 8 * nd + 4 * n)
+    hd = slot[0][:8 * nd].numpy().view(np.float64)
+    for a, e in zip(arrays, ends):
+        hd[e - a.size:e] = a.reshape(-1)
+    slot[0][8 * nd:8 * nd + 4 * n].numpy().view(np.int32)[:] = file_idx
+    params = slot[0][:8 * nd + 4 * n].to(dev, non_blocking=True)
+    if slot[1] is not None:
+        slot[1].record()
+    pd = params[:8 * nd].view(torch.float64)
+    return [pd[e - a.size:e] for a, e in zip(arrays, ends)], params[8 * nd:].view(torch.int32)
+
+
+def _index_list(index):
+    """``(indices, single)`` of a dataset's ``__getitem__`` argument: an int is a list of one"""
+    try:
+        iter(index)
+    except TypeError:
+        return [index], True
+    return index, False
+
+
+def _read_wav(fn):
+    """``scipy.io.wavfile.read(fn)``: (fs, samples), its WavFileWarning silenced"""
+    from scipy.io import wavfile
+    from scipy.io.wavfile import WavFileWarning
+    with warnings.catch_warnings():
+        warnings.filterwarnings("ignore", category=WavFileWarning)
+        return wavfile.read(fn)
+
+
+def _is_wav_file(filename):
+    """the reference's test in models/utils.py and segmenting/template_segmentation.py (a file named ``.wav`` is none)"""
+    return len(filename) > 4 and filename[-4:] == '.wav'
+
+
 def get_spec_batch(audio, file_idx, t1, t2, p, fs, target_times, target_freqs=None, fill_value=-1 / EPSILON,
                    max_dur=None, remove_dc_offset=True, return_max=False):
     """``get_spec`` (utils.py:18-110) for n windows at once.
@@ -152,40 +221,12 @@ def get_spec_batch(audio, file_idx, t1, t2, p, fs, target_times, target_freqs=No
         warnings.warn("Found segment longer than max_dur: " + str(t2[i] - t1[i]) + "s, max_dur = " + str(max_dur) + "s")
     s1, s2 = np.rint(t1 * fs), np.rint(t2 * fs)                                     # int(round(.)): half to even
     assert (s1 < s2).all(), "s1 >= s2 for window %d" % int(np.argmin(s2 - s1))     # utils.py:60-61
-    nperseg, noverlap = int(p['nperseg']), int(p['noverlap'])
-    if nperseg < 64 or nperseg > 2048 or not 0 <= noverlap < nperseg:
-        raise NotImplementedError("device get_spec needs 64 <= nperseg <= 2048 and 0 <= noverlap < nperseg")
-    if T > 512:
-        raise NotImplementedError("device get_spec handles at most 512 target times per window")
+    nperseg, noverlap = _check_stft_shape(p, T)
     max_samples = int((s2 - s1).max())
+    normalize, q_lo, q_gamma = _quantile_index(p, F, T)
     lib, dev = _lib.load(), audio.device
     window, scale = _stft_constants(nperseg, dev)
-    # one small upload per batch out of a page-locked ring: [t1 | t2 | target_freqs | target_times] float64, file_idx int32
-    nd = 2 * n + F + n * T
-    slot = _staging(dev, 8 * nd + 4 * n)
-    hd = slot[0][:8 * nd].numpy().view(np.float64)
-    hd[:n] = t1; hd[n:2 * n] = t2; hd[2 * n:2 * n + F] = target_freqs; hd[2 * n + F:] = target_times.reshape(-1)
-    slot[0][8 * nd:8 * nd + 4 * n].numpy().view(np.int32)[:] = file_idx
-    params = slot[0][:8 * nd + 4 * n].to(dev, non_blocking=True)
-    if slot[1] is not None:
-        slot[1].record()
-    pd = params[:8 * nd].view(torch.float64)
-    fidx = params[8 * nd:].view(torch.int32)
-    d_t1, d_t2, d_tf, d_tt = pd[:n], pd[n:2 * n], pd[2 * n:2 * n + F], pd[2 * n + F:]
-    normalize, q_lo, q_gamma = 0, 0, 0.0
-    if p.get('within_syll_normalize', False):                                      # utils.py:104-108
-        q = float(p['normalize_quantile'])
-        if not 0.0 <= q <= 1.0:
-            raise ValueError("Quantiles must be in the range [0, 1]")               # np.quantile's own check
-        # numpy's 'linear' method: virtual index n q + (alpha + q (1 - alpha - beta)) - 1 with alpha = beta = 1
-        cnt = F * T
-        virtual = cnt * q + (1 + q * (1 - 1 - 1)) - 1
-        if virtual >= cnt - 1:
-            q_lo, q_gamma = cnt - 1, 0.0
-        else:
-            q_lo = int(np.floor(virtual))
-            q_gamma = float(virtual - np.floor(virtual))
-        normalize = 1
+    (d_t1, d_t2, d_tf, d_tt), fidx = _upload(dev, [t1, t2, target_freqs, target_times], file_idx)
     nbytes = lib.ava_spec_workspace_bytes(n, max_samples, nperseg, noverlap, F, T, normalize)
     ws = _workspace(dev, nbytes)
     out = torch.empty((n, F, T), dtype=torch.float32, device=dev)
@@ -235,13 +276,9 @@ class DeviceWindowDataset:
 
     def __init__(self, audio_filenames, roi_filenames, p, transform=None, dataset_length=2048, min_spec_val=None,
                  device="cuda"):
-        from scipy.io import wavfile
-        from scipy.io.wavfile import WavFileWarning
         filenames = np.array(sorted(audio_filenames))                                # :164
-        with warnings.catch_warnings():
-            warnings.filterwarnings("ignore", category=WavFileWarning)
-            audio = [wavfile.read(fn)[1] for fn in filenames]                        # :167
-            fs = wavfile.read(audio_filenames[0])[0]                                 # :168
+        audio = [_read_wav(fn)[1] for fn in filenames]                               # :167
+        fs = _read_wav(audio_filenames[0])[0]                                        # :168: the first name AS GIVEN
         rois = [np.loadtxt(i, ndmin=2) for i in roi_filenames]                       # :173
         self._setup(audio, fs, rois, p, dataset_length, min_spec_val, device)
         self.filenames = filenames
@@ -308,12 +345,7 @@ class DeviceWindowDataset:
                               self.fs, target_times, target_freqs=self._target_freqs, return_max=return_max)
 
     def __getitem__(self, index, seed=None, shoulder=0.05, return_seg_info=False):
-        single_index = False
-        try:
-            iter(index)
-        except TypeError:
-            index = [index]
-            single_index = True
+        index, single_index = _index_list(index)
         n = len(index)
         rs = np.random.RandomState(seed)          # the stream np.random.seed(seed) starts (window_vae_dataset.py:203)
         if self.min_spec_val is None:

@@ -29,7 +29,7 @@ import torch
 
 from . import _lib
 from . import segment as _seg
-from .spec import DeviceAudio, _stft_constants
+from .spec import DeviceAudio, _is_wav_file, _read_wav, _stft_constants
 
 __all__ = ["EPSILON", "get_template", "get_template_from_audio", "segment_files", "read_segment_decisions",
            "xcorr_batch", "segment_batch", "segments_from_trace", "install"]
@@ -38,12 +38,8 @@ EPSILON = 1e-9                       # template_segmentation.py:31
 DEFAULT_CHUNK_BYTES = 1 << 30        # audio bytes per batch of segment_files()
 
 
-def _is_wav_file(filename):
-    return len(filename) > 4 and filename[-4:] == '.wav'
-
-
 def _read(filename, p):
-    fs, audio = _seg._read_wav(filename)
+    fs, audio = _read_wav(filename)
     assert fs == p['fs'], "Found samplerate=" + str(fs) + ", expected " + str(p['fs'])
     return audio
 

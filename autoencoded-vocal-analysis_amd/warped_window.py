@@ -24,6 +24,7 @@ Not mirrored: ``write_hdf5_files`` (``h5py`` is no dependency of this package). 
 ``nperseg`` in 64..2048, at most 512 target times per window (``NotImplementedError``); the fit inputs need ``nperseg``
 a power of two.  There is no CPU fallback.
 """
+import ctypes
 import os
 import warnings
 
@@ -32,8 +33,8 @@ import torch
 
 from . import _lib
 from . import segment as _seg
-from .spec import (EPSILON as SPEC_EPSILON, DeviceAudio, DeviceWindowLoader, _staging, _stft_constants, _workspace,
-                   target_freqs_of)
+from .spec import (EPSILON as SPEC_EPSILON, DeviceAudio, DeviceWindowLoader, _check_stft_shape, _index_list,
+                   _is_wav_file, _quantile_index, _read_wav, _stft_constants, _upload, _workspace, target_freqs_of)
 
 __all__ = ["EPSILON", "DEFAULT_WARP_PARAMS", "DeviceWarpedWindowDataset", "get_warped_window_data_loaders",
            "get_specs_and_amplitude_traces", "template_duration", "install"]
@@ -47,22 +48,9 @@ DEFAULT_WARP_PARAMS = {              # window_vae_dataset.py:28-33
 }
 
 
-def _is_wav_file(filename):
-    return len(filename) > 4 and filename[-4:] == '.wav'
-
-
 def _get_wavs_from_dir(d):
     """models/utils.py:433-436"""
     return [os.path.join(d, f) for f in sorted(os.listdir(d)) if _is_wav_file(f)]
-
-
-def _check_stft_shape(p, T=None):
-    nperseg, noverlap = int(p['nperseg']), int(p['noverlap'])
-    if nperseg < 64 or nperseg > 2048 or not 0 <= noverlap < nperseg:
-        raise NotImplementedError("device get_spec needs 64 <= nperseg <= 2048 and 0 <= noverlap < nperseg")
-    if T is not None and T > 512:
-        raise NotImplementedError("device get_spec handles at most 512 target times per window")
-    return nperseg, noverlap
 
 
 def template_duration(lengths, fs, p):
@@ -132,15 +120,11 @@ class DeviceWarpedWindowDataset:
 
     def __init__(self, audio_filenames, p, transform=None, dataset_length=2048, load_warp=False, save_warp=True,
                  start_q=-0.1, stop_q=1.1, warp_fn=None, warp_params={}, warp_type='spectrogram', device="cuda"):
-        from scipy.io import wavfile
-        from scipy.io.wavfile import WavFileWarning
         assert type(p) == type({})                                                   # :402
         assert warp_type in ['amplitude', 'spectrogram', 'null']                     # :403
         self.audio_filenames = sorted(audio_filenames)                               # :404
-        with warnings.catch_warnings():
-            warnings.filterwarnings("ignore", category=WavFileWarning)
-            audio = [wavfile.read(fn)[1] for fn in self.audio_filenames]             # :407
-            fs = wavfile.read(self.audio_filenames[0])[0]                            # :408
+        audio = [_read_wav(fn)[1] for fn in self.audio_filenames]                    # :407
+        fs = _read_wav(self.audio_filenames[0])[0]                                   # :408: the first SORTED name
         self.transform = transform
         self._setup(audio, fs, p, dataset_length, start_q, stop_q, warp_fn, warp_params, device)
         self._compute_warp(load_warp=load_warp, save_warp=save_warp, warp_type=warp_type)
@@ -349,16 +333,14 @@ class DeviceWarpedWindowDataset:
         """The cached fp64 log-magnitudes ``[touched bins, frames]`` of one file (a view into the cache)"""
         if self._cache is None:
             self.build_cache()
-        (files, template_dur, fs, nperseg, noverlap), _ = self._cache_geometry()
-        nstep = nperseg - noverlap
-        maxframes = (int(round(template_dur * fs)) + nstep - 1) // nstep + 1
-        fstride = (maxframes + 15) & ~15
-        up = lambda x: (x + 255) & ~255
+        geo, band = self._cache_geometry()
+        lay = (ctypes.c_int64 * 6)()
+        _lib.check(_lib.load().ava_warp_cache_layout(*geo, *band, lay), "ava_warp_cache_layout")
+        _, fstride, _, nb, _, off_logmag = lay
+        files = geo[0]
         base = (-self._cache.data_ptr()) % 256                                       # the library aligns the buffer itself
-        off_logmag = base + up(4 * files) + up(8 * files * maxframes)
-        nb = (self._cache.numel() - 256 - up(4 * files) - up(8 * files * maxframes)) // (8 * files * fstride)
         nframes = int(self._cache[base:base + 4 * files].view(torch.int32)[file])
-        logmag = self._cache[off_logmag:off_logmag + 8 * files * nb * fstride].view(torch.float64)
+        logmag = self._cache[base + off_logmag:base + off_logmag + 8 * files * nb * fstride].view(torch.float64)
         return logmag.view(files, nb, fstride)[file, :, :max(nframes, 0)]
 
     def windows(self, file_index, target_times):
@@ -379,46 +361,19 @@ class DeviceWarpedWindowDataset:
             self.build_cache()
         geo, band = self._cache_geometry()
         lib, dev = _lib.load(), self.device
-        normalize, q_lo, q_gamma = 0, 0, 0.0
-        if p.get('within_syll_normalize', False):                                    # utils.py:104-108, as get_spec_batch
-            q = float(p['normalize_quantile'])
-            if not 0.0 <= q <= 1.0:
-                raise ValueError("Quantiles must be in the range [0, 1]")
-            cnt = F * T
-            virtual = cnt * q + (1 + q * (1 - 1 - 1)) - 1
-            if virtual >= cnt - 1:
-                q_lo, q_gamma = cnt - 1, 0.0
-            else:
-                q_lo = int(np.floor(virtual))
-                q_gamma = float(virtual - np.floor(virtual))
-            normalize = 1
-        # one small upload per batch out of the page-locked ring: [target_freqs | target_times] float64, file_idx int32
-        nd = F + n * T
-        slot = _staging(dev, 8 * nd + 4 * n)
-        hd = slot[0][:8 * nd].numpy().view(np.float64)
-        hd[:F] = tf; hd[F:] = target_times.reshape(-1)
-        slot[0][8 * nd:8 * nd + 4 * n].numpy().view(np.int32)[:] = file_index
-        params = slot[0][:8 * nd + 4 * n].to(dev, non_blocking=True)
-        if slot[1] is not None:
-            slot[1].record()
-        pd = params[:8 * nd].view(torch.float64)
-        fidx = params[8 * nd:].view(torch.int32)
+        normalize, q_lo, q_gamma = _quantile_index(p, F, T)
+        (d_tf, d_tt), fidx = _upload(dev, [tf, target_times], file_index)
         ws = _workspace(dev, lib.ava_warp_windows_workspace_bytes(n, F, T, normalize))
         out = torch.empty((n, F, T), dtype=torch.float32, device=dev)
         rc = lib.ava_warp_windows(self._cache.data_ptr(), self._cache.numel(), *geo, *band, fidx.data_ptr(),
-                                  pd[F:].data_ptr(), n, pd[:F].data_ptr(), F, T, float(p['spec_min_val']),
+                                  d_tt.data_ptr(), n, d_tf.data_ptr(), F, T, float(p['spec_min_val']),
                                   float(p['spec_max_val']), float(-1 / SPEC_EPSILON), normalize, q_lo, q_gamma,
                                   out.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream())
         _lib.check(rc, "ava_warp_windows")
         return out
 
     def __getitem__(self, index, seed=None):
-        single_index = False
-        try:
-            iter(index)
-        except TypeError:
-            index = [index]
-            single_index = True
+        index, single_index = _index_list(index)
         file_index, target_times = self._draw(len(index), seed)
         specs = self.windows(file_index, target_times)
         return specs[0] if single_index else specs

@@ -410,8 +410,8 @@ int ava_tpl_xcorr(const double* spec, const double* frame_sum, int F, int64_t fr
  * linear time warps; every window is get_spec(0.0, template_dur, audio[file], p, fs=fs, target_times=...).  The slice,
  * its mean and its log-spectrogram are the same for every window of a file: ava_warp_cache_build makes them once for
  * all files (the kernels of ava_get_spec_batch, run with one window per file), ava_warp_windows interpolates a batch out
- * of that cache (the interpolation, fill rule, normalisation, clip and within_syll_normalize of ava_get_spec_batch, on
- * the same fp64 inputs: the two paths give the same bits).
+ * of that cache with the interpolation and normalisation kernels ava_get_spec_batch itself launches, reading their
+ * coefficients from the cache: the two paths give the same bits.
  *   audio ... file_len    as ava_get_spec_batch; `files` files
  *   template_dur, fs      the motif is the slice [0, min(len, round(template_dur fs))) of each file; a file with fewer
  *                         than nperseg samples in it yields zeros (utils.py:68-69)
@@ -426,6 +426,11 @@ int ava_tpl_xcorr(const double* spec, const double* frame_sum, int F, int64_t fr
  *                         outside [0, template_dur] (interp2d's fill rule applies); T <= 512
  *   spec_min ... q_gamma  as ava_get_spec_batch;  out [n][F][T] fp32
  * ava_warp_windows must be given the files, template_dur, fs, nperseg, noverlap, fmin, fmax the cache was built with.
+ * ava_warp_cache_layout: where things are in a cache of that geometry, out = {maxframes, fstride (doubles from one bin
+ * row to the next), k0 (first cached bin), nb (cached bins), off_ftimes, off_logmag}; the offsets are bytes from the
+ * first 256-byte boundary at or after `cache`: int32 nframes[files] there, double ftimes[files][maxframes] at off_ftimes,
+ * double logmag[files][nb][fstride] at off_logmag, so that
+ * ava_warp_cache_bytes(...) == 256 + off_logmag + files * nb * fstride * 8.  AVA_EINVAL where ava_warp_cache_bytes is 0.
  * AVA_EINVAL before any launch for null pointers, files <= 0, template_dur <= 0, an unsupported nperseg or T;
  * AVA_EWORKSPACE for a cache or scratch that is too small.  A file index outside [0, files) gives a window of NaNs.
  *
@@ -434,6 +439,8 @@ int ava_tpl_xcorr(const double* spec, const double* frame_sum, int F, int64_t fr
  * spec_max_val - spec_min_val + 1e-9 (computed by the caller).  nperseg a power of two in 64..2048. */
 size_t ava_warp_cache_bytes(int files, double template_dur, double fs, int nperseg, int noverlap, double fmin,
                             double fmax);
+int ava_warp_cache_layout(int files, double template_dur, double fs, int nperseg, int noverlap, double fmin, double fmax,
+                          int64_t out[6]);
 size_t ava_warp_cache_workspace_bytes(int files, double template_dur, double fs, int nperseg, int noverlap);
 int ava_warp_cache_build(const void* audio, int audio_dtype, const int64_t* file_off, const int64_t* file_len, int files,
                          double template_dur, double fs, int nperseg, int noverlap, const double* window, double scale,

@@ -6,6 +6,7 @@ Tolerances.  Cache path against f4 path: none, torch.equal -- both run the same 
 inputs.  Against the oracle: f4's bound (tests/test_gpu_spec.py): at most one fp32 ulp anywhere,
 bit-identical on >= 99.9 % of the pixels; float32 audio: 2e-3, what f4 states for it (the reference transforms float32
 audio in single precision).  Fit inputs: 4x the noise floor stored with the golden."""
+import ctypes
 import os
 
 import numpy as np
@@ -255,6 +256,15 @@ def test_c_abi_argument_checks():
     assert lib.ava_warp_cache_bytes(3, 0.0, 32000.0, 512, 256, *band) == 0
     assert lib.ava_warp_cache_bytes(3, 0.25, 32000.0, 500, 250, *band) > 0             # any length in 64..2048
     assert lib.ava_warp_windows_workspace_bytes(4, 16, 16, 1) == 256 + 4 * 256 * 8
+    lay = (ctypes.c_int64 * 6)()
+    for bad in ((0, 0.25, 32000.0, 512, 256), (3, 0.25, 32000.0, 4096, 256), (3, 0.25, 32000.0, 512, 512),
+                (3, 0.0, 32000.0, 512, 256)):                                           # where ava_warp_cache_bytes is 0
+        assert lib.ava_warp_cache_layout(*bad, *band, lay) == -1
+    assert lib.ava_warp_cache_layout(*geo, *band, lay) == 0
+    maxframes, fstride, k0, nb, off_ftimes, off_logmag = lay
+    assert nbytes == 256 + off_logmag + geo[0] * nb * fstride * 8
+    assert maxframes == 33 and fstride == 48 and 0 <= k0 < 400 * 512 // 32000 and nb > 100
+    assert off_ftimes == 256 and off_logmag == 256 + 1024                               # 3 int32, 3 x 33 doubles, each up to 256
     dev = torch.device("cuda")
     audio = torch.zeros(3 * 9000, dtype=torch.int16, device=dev)
     off = torch.tensor([0, 9000, 18000], dtype=torch.int64, device=dev)
