@@ -68,7 +68,6 @@ SIGNATURES = {
     "ava_last_z": (_p, [_p]),
     "ava_last_xrec": (_p, [_p]),
     "ava_debug_buffer": (_p, [_p, C.c_char_p, C.POINTER(_i64)]),
-    "ava_debug_materialize": (_i, [_p, _p, _i, _p]),
     "ava_set_cu_reserve": (_i, [_i]),
     "ava_get_cu_reserve": (_i, []),
     "ava_model_set_cu_reserve": (_i, [_p, _i]),

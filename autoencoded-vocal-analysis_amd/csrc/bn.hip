@@ -15,10 +15,6 @@
 #define BN_EPS AVA_BN_EPS
 #define BN_MOMENTUM AVA_BN_MOMENTUM
 
-int ava_bn_finalize_bwd_ex(const float* partials, int nparts, int64_t n, int C, const float* gamma, const float* mean,
-                           const float* invstd, float* dgamma, float* dbeta, float* A, float* Bc, float* Cc, int eval,
-                           hipStream_t st);
-
 // ---- statistics of a raw tensor x[n][C] (used for bn1, whose input has no producer kernel) --------
 template <int C>
 __global__ __launch_bounds__(256) void bn_stats_kernel(const float* __restrict__ x, int64_t n,
@@ -400,15 +396,10 @@ extern "C" int ava_bn_finalize(const float* partials, int nparts, int64_t n, int
 extern "C" int ava_bn_finalize_bwd(const float* partials, int nparts, int64_t n, int C, const float* gamma,
                                    const float* mean, const float* invstd, float* dgamma, float* dbeta, float* A,
                                    float* Bc, float* Cc, ava_stream_t s) {
-  return ava_bn_finalize_bwd_ex(partials, nparts, n, C, gamma, mean, invstd, dgamma, dbeta, A, Bc, Cc, 0, to_stream(s));
-}
-// eval = 1: backward of a BatchNorm that ran on its running statistics (module.eval())
-int ava_bn_finalize_bwd_ex(const float* partials, int nparts, int64_t n, int C, const float* gamma, const float* mean,
-                           const float* invstd, float* dgamma, float* dbeta, float* A, float* Bc, float* Cc, int eval,
-                           hipStream_t st) {
   if (C < 1 || C > 32 || partials == nullptr || gamma == nullptr) return AVA_EINVAL;
-  hipLaunchKernelGGL(bn_finalize_bwd_kernel, dim3(1), dim3(1024), 0, st, partials, nparts, (double)n, C,
-                     gamma, mean, invstd, dgamma, dbeta, A, Bc, Cc, eval);
+  // (the kernel's last argument, eval = 0: a BatchNorm that ran on its batch statistics)
+  hipLaunchKernelGGL(bn_finalize_bwd_kernel, dim3(1), dim3(1024), 0, to_stream(s), partials, nparts, (double)n, C,
+                     gamma, mean, invstd, dgamma, dbeta, A, Bc, Cc, 0);
   AVA_CHECK_LAUNCH();
   return AVA_OK;
 }

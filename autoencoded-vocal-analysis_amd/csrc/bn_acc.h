@@ -1,6 +1,6 @@
 // BatchNorm sums accumulated INSIDE the producing kernel, finalised in the prologue of the consuming kernel:
 // removes the one-workgroup bn_finalize launches (5 us kernel + a dependent-launch boundary each, 28 per step) from
-// the step's critical path for the layer pairs whose kernels use it (model.hip: acc_pair_fwd / acc_pair_bwd).
+// the step's critical path: every BatchNorm of a training step but bn1's forward under graph capture (model.hip).
 //
 // Determinism.  Every workgroup adds its fp32 partial sums with INTEGER atomics, so the total does not depend on the
 // order of arrival: a partial p is split exactly into three 32-bit limbs of the fixed-point number |p| * 2^48

@@ -479,14 +479,6 @@ struct WgradArgs {
   float* partials;     // [grid][9*CIN*COUT + COUT]
   int B, Hi, Wi, Ho, Wo;
   int tiles_y, tiles_x, ntiles;
-  int act_bf16;        // x and dy2 (activations) are stored as bfloat16
-};
-
-// one weight-gradient launch as data (model.hip defers the 16 x 16 layers' calls and issues them in pairs)
-struct WgradCall {
-  const float *x, *xa, *xb, *dy, *dy2, *da, *db, *dc;
-  float* partials;
-  int Hi, Wi, Cin, Cout, mode, dy_pro;
 };
 
 // all 14 weight-gradient reductions in one launch (model.hip)

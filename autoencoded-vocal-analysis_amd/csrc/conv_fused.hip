@@ -15,7 +15,7 @@
 // The kernels are the thin (1 <-> 8-channel) VALU kernels of conv_thin.hip and the bf16 limb-MFMA kernels of
 // conv_fused_limb.hip, whose tiles divide every supported image size (W in {128, 256}, H a multiple of 128:
 // low-resolution sides >= 16 against tiles of at most 32 x 8).  A shape neither serves reports "no fused kernel"
-// (grid 0) and the caller runs the separate data-gradient and weight-gradient kernels.
+// (grid 0); the model driver treats that as an error, it has no second path.
 #include "conv_fused.h"
 
 // number of workgroups (= partial rows of both outputs) of the fused kernel, 0 when the shape has none

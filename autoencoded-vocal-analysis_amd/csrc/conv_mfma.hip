@@ -322,6 +322,8 @@ int ava_conv3x3_mfma(const ConvArgs& a, int grid, int Cin, int Cout, int mode, i
 // across ALL tiles of the workgroup; at the end the four waves are summed through LDS in a fixed order
 // and the workgroup writes one partial row [9*CIN*COUT + COUT] (same format as the VALU kernel).
 // The bias gradient is the column sum of the B fragments (one VALU add per LDS read).
+// ACT is the storage type of the activations (x, dy2); only float is instantiated: these kernels are reached through the
+// per-kernel entry point ava_conv3x3_wgrad alone, the model's backward runs the fused kernels (conv_fused.hip).
 // ================================================================================================
 template <int CIN, int COUT, int MODE, int DYPRO, int TW, int TH, typename ACT>
 __global__ __launch_bounds__(256) void conv3x3_wgrad_mfma_kernel(const WgradArgs a) {
@@ -454,8 +456,9 @@ __global__ __launch_bounds__(256) void conv3x3_wgrad_mfma_kernel(const WgradArgs
   for (int e = t; e < NW + COUT; e += 256) prow[e] = wacc[e];
 }
 
-// the kernel's body as a device function of (workgroup index, workgroups of this layer): conv3x3_wgrad_split_kernel runs it
-// for its whole grid, conv3x3_wgrad_pair_kernel runs two layers' bodies in one launch
+// the split variant (the M tiles (tap, cin) are dealt out to the four waves, each sweeps all pixels of a tile): the kernel's
+// body as a device function of (workgroup index, workgroups).  Its one caller is the kernel below; written into the kernel
+// itself, the compiler allocates 4 more VGPRs for the same source, so it stays a function.
 template <int CIN, int COUT, int MODE, int DYPRO, int TW, int TH, typename ACT>
 __device__ __forceinline__ void wgrad_split_body(const WgradArgs& a, const int wg, const int nwg) {
   using G = Geom<MODE, TW, TH>;
@@ -592,20 +595,9 @@ __global__ __launch_bounds__(256) void conv3x3_wgrad_split_kernel(const WgradArg
   wgrad_split_body<CIN, COUT, MODE, DYPRO, TW, TH, ACT>(a, (int)blockIdx.x, (int)gridDim.x);
 }
 
-// Two layers' weight-gradient kernels in ONE launch: workgroups [0, grid_a) run layer A's body, the rest layer B's.  The
-// four 16 x 16 layers' weight gradients are independent of the data-gradient chain once their dU exists, and each is a
-// latency-bound launch of one or two tiles per workgroup; issued as pairs (conv7 + conv6, convt2 + convt1) behind both
-// data-gradient kernels they overlap each other.  Every workgroup computes exactly what it computed in its own launch
-// (same tiles, same partial row), so the gradients are bit-identical.
-template <int CA, int OA, int MA, int PA, int TWA, int THA, int CB, int OB, int MB, int PB, int TWB, int THB, typename ACT>
-__global__ __launch_bounds__(256) void conv3x3_wgrad_pair_kernel(const WgradArgs a, const WgradArgs b, const int grid_a) {
-  if ((int)blockIdx.x < grid_a) wgrad_split_body<CA, OA, MA, PA, TWA, THA, ACT>(a, (int)blockIdx.x, grid_a);
-  else wgrad_split_body<CB, OB, MB, PB, TWB, THB, ACT>(b, (int)blockIdx.x - grid_a, (int)gridDim.x - grid_a);
-}
-
-// tile geometry, workgroups (= partial rows written) and LDS bytes of one layer's weight-gradient kernel
+// tile geometry, workgroups (= partial rows written) and LDS bytes of one layer's weight-gradient kernel, and its launch
 template <int CIN, int COUT, int MODE, int DYPRO, int TW, int TH, typename ACT>
-static int wgrad_plan(const WgradArgs& a, int grid, WgradArgs* b, size_t* lds_out) {
+static int launch_wgrad_mfma_t(const WgradArgs& a, int grid, hipStream_t st) {
   using G = Geom<MODE, TW, TH>;
   // layers with many (tap, cin) rows deal the M tiles out to the waves (fewer registers, no cross-wave reduction)
   constexpr bool SPLIT = CIN >= 24 && COUT > 16;   // measured: 24->24, 24->32, 32->24 gain 10-55 %, 16-channel sides lose
@@ -614,29 +606,17 @@ static int wgrad_plan(const WgradArgs& a, int grid, WgradArgs* b, size_t* lds_ou
   const size_t tiles_f = (size_t)G::IR * G::IC * CIN + TH * TW * COUT + 16 + 192;
   const size_t red_f = (size_t)9 * CIN * COUT + 4 * COUT;
   const size_t lds = (tiles_f > red_f ? tiles_f : red_f) * sizeof(float);
-  *lds_out = lds;
-  *b = a;
-  b->tiles_y = a.Ho / TH;
-  b->tiles_x = a.Wo / TW;
-  b->ntiles = a.B * b->tiles_y * b->tiles_x;
-  if (grid > b->ntiles) grid = b->ntiles;
+  WgradArgs b = a;
+  b.tiles_y = a.Ho / TH;
+  b.tiles_x = a.Wo / TW;
+  b.ntiles = a.B * b.tiles_y * b.tiles_x;
+  if (grid > b.ntiles) grid = b.ntiles;
   static const int resident = ava_resident_grid(kernel, lds);
   if (grid > ava_scale_grid(resident)) grid = ava_scale_grid(resident);          // one resident wave of workgroups = partial rows written
   // the split kernels (the 16 x 16 layers): one workgroup per CU.  Each workgroup ends with a 5-7 k-float partial row,
   // which at one or two tiles per workgroup costs more than the tiles (same-box A/B of the step: 512 -> 256 workgroups
   // -13 us, 384 +-0, 128 +13 us)
   if (SPLIT && grid > ava_scale_grid(256)) grid = ava_scale_grid(256);
-  return grid;
-}
-
-template <int CIN, int COUT, int MODE, int DYPRO, int TW, int TH, typename ACT>
-static int launch_wgrad_mfma_t(const WgradArgs& a, int grid, hipStream_t st) {
-  constexpr bool SPLIT = CIN >= 24 && COUT > 16;
-  const auto kernel = SPLIT ? &conv3x3_wgrad_split_kernel<CIN, COUT, MODE, DYPRO, TW, TH, ACT>
-                            : &conv3x3_wgrad_mfma_kernel<CIN, COUT, MODE, DYPRO, TW, TH, ACT>;
-  WgradArgs b;
-  size_t lds;
-  grid = wgrad_plan<CIN, COUT, MODE, DYPRO, TW, TH, ACT>(a, grid, &b, &lds);
   static bool attr_set = false;
   if (!attr_set && lds > 64 * 1024) {
     if (hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -650,57 +630,11 @@ static int launch_wgrad_mfma_t(const WgradArgs& a, int grid, hipStream_t st) {
   return AVA_OK;
 }
 
-// the pair launch: each layer keeps the grid (tile partition, partial rows) of its own launch
-template <int CA, int OA, int MA, int PA, int TWA, int THA, int CB, int OB, int MB, int PB, int TWB, int THB, typename ACT>
-static int launch_wgrad_pair_t(const WgradArgs& a, int grid_a, const WgradArgs& b, int grid_b, hipStream_t st) {
-  static_assert(CA >= 24 && OA > 16 && CB >= 24 && OB > 16, "pairs of split kernels only");
-  const auto kernel = &conv3x3_wgrad_pair_kernel<CA, OA, MA, PA, TWA, THA, CB, OB, MB, PB, TWB, THB, ACT>;
-  WgradArgs pa, pb;
-  size_t lds_a, lds_b;
-  grid_a = wgrad_plan<CA, OA, MA, PA, TWA, THA, ACT>(a, grid_a, &pa, &lds_a);
-  grid_b = wgrad_plan<CB, OB, MB, PB, TWB, THB, ACT>(b, grid_b, &pb, &lds_b);
-  const size_t lds = lds_a > lds_b ? lds_a : lds_b;
-  static bool attr_set = false;
-  if (!attr_set && lds > 64 * 1024) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)lds) != hipSuccess)
-      return AVA_ELAUNCH;
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(kernel, dim3(grid_a + grid_b), dim3(256), lds, st, pa, pb, grid_a);
-  AVA_CHECK_LAUNCH();
-  return AVA_OK;
-}
-
-int ava_conv3x3_wgrad_mfma_pair(const WgradArgs& a, int grid_a, const WgradCall& ca, const WgradArgs& b, int grid_b,
-                                const WgradCall& cb, hipStream_t st) {
-  auto is = [](const WgradCall& c, const WgradArgs& w, int ci, int co, int md, int pro, int tw, int th) {
-    return c.Cin == ci && c.Cout == co && c.mode == md && c.dy_pro == pro && w.Wo % tw == 0 && w.Ho % th == 0;
-  };
-  // encoder: conv7 (24 -> 32, given dU) + conv6 (24 -> 24, stride 2)
-  if (is(ca, a, 24, 32, MODE_S1, PRO_ID, 16, 8) && is(cb, b, 24, 24, MODE_DOWN, PRO_BWD, 16, 4)) {
-    if (a.act_bf16) return launch_wgrad_pair_t<24, 32, MODE_S1, PRO_ID, 16, 8, 24, 24, MODE_DOWN, PRO_BWD, 16, 4, ava_bf16>(a, grid_a, b, grid_b, st);
-    return launch_wgrad_pair_t<24, 32, MODE_S1, PRO_ID, 16, 8, 24, 24, MODE_DOWN, PRO_BWD, 16, 4, float>(a, grid_a, b, grid_b, st);
-  }
-  // decoder: convt2 (24 -> 24, x2) + convt1 (32 -> 24)
-  if (is(ca, a, 24, 24, MODE_UP, PRO_BWD, 32, 8) && is(cb, b, 32, 24, MODE_S1, PRO_BWD, 16, 8)) {
-    if (a.act_bf16) return launch_wgrad_pair_t<24, 24, MODE_UP, PRO_BWD, 32, 8, 32, 24, MODE_S1, PRO_BWD, 16, 8, ava_bf16>(a, grid_a, b, grid_b, st);
-    return launch_wgrad_pair_t<24, 24, MODE_UP, PRO_BWD, 32, 8, 32, 24, MODE_S1, PRO_BWD, 16, 8, float>(a, grid_a, b, grid_b, st);
-  }
-  return AVA_EINVAL;
-}
-
-template <int CIN, int COUT, int MODE, int DYPRO, int TW, int TH>
-static int launch_wgrad_mfma(const WgradArgs& a, int grid, hipStream_t st) {
-  if (a.act_bf16) return launch_wgrad_mfma_t<CIN, COUT, MODE, DYPRO, TW, TH, ava_bf16>(a, grid, st);
-  return launch_wgrad_mfma_t<CIN, COUT, MODE, DYPRO, TW, TH, float>(a, grid, st);
-}
-
 int ava_conv3x3_wgrad_mfma(const WgradArgs& a, int grid, int Cin, int Cout, int mode, int dy_pro, hipStream_t st) {
 #define AVA_WGM_CASE(ci, co, md, tww, thh)                                                     \
   if (Cin == ci && Cout == co && mode == md && a.Wo % tww == 0 && a.Ho % thh == 0) {                                    \
-    if (dy_pro == PRO_BWD) return launch_wgrad_mfma<ci, co, md, PRO_BWD, tww, thh>(a, grid, st); \
-    if (dy_pro == PRO_ID) return launch_wgrad_mfma<ci, co, md, PRO_ID, tww, thh>(a, grid, st);   \
+    if (dy_pro == PRO_BWD) return launch_wgrad_mfma_t<ci, co, md, PRO_BWD, tww, thh, float>(a, grid, st); \
+    if (dy_pro == PRO_ID) return launch_wgrad_mfma_t<ci, co, md, PRO_ID, tww, thh, float>(a, grid, st); \
     return AVA_EINVAL;                                                                         \
   }
   AVA_WGM_CASE(8, 8, MODE_DOWN, 32, 4)

@@ -49,7 +49,6 @@ static int conv3x3_wgrad_thin_w(const WgradArgs& a0, int grid, int Cin, int Cout
   const size_t kThin8Lds = (size_t)(THIN_IR * THIN_IC * 8 + 96 + 8) * sizeof(float);
   const dim3 block(2 * W);
   WgradArgs a = a0;
-  if (a.act_bf16) return AVA_EINVAL;                     // per-op kernels: fp32 activations only
   a.ntiles = a.B * (a.Ho / THIN_TH);
   if (Cin == 1 && Cout == 8) {
     if (W == 256 && grid > 256) grid = 256;              // 200-register kernel: one 512-thread workgroup per CU

@@ -11,10 +11,6 @@
 // internal entry points of the other translation units
 int ava_nchw_to_nhwc_stats(const float* in, float* out, float* partials, int B, int P, int act_bf16, long long* acc_out,
                            int* nparts, hipStream_t st);
-int ava_conv3x3_wgrad_ex(const float* x, const float* xa, const float* xb, const float* dy, const float* dy2,
-                         const float* da, const float* db_, const float* dc, float* partials, int B, int Hi, int Wi,
-                         int Cin, int Cout, int mode, int dy_pro, int act_bf16, ava_stream_t s);
-int ava_conv_wgrad_rows_ex(int B, int Hi, int Wi, int Cin, int Cout, int mode, int dy_pro, int act_bf16);
 int ava_bn_eval_all(const float* const* gamma, const float* const* beta, const int* C, const float* running, float* save,
                     hipStream_t st);
 int ava_conv3x3_ex(const float* in, const float* in2, const float* pa, const float* pb, const float* pc,
@@ -30,9 +26,6 @@ int ava_gemm_defer2(const float* A, int lda, const float* B, int ldb, const floa
                     void* ws, size_t ws_bytes, ava_stream_t s, int* slabs);
 int ava_bn_bwd_apply_to_nchw(const float* g, const float* f8, const float* A, const float* Bc, const float* Cc,
                              float* out, int B, int P, int act_bf16, const BnFin* fin, hipStream_t st);
-int ava_bn_finalize_bwd_ex(const float* partials, int nparts, int64_t n, int C, const float* gamma, const float* mean,
-                           const float* invstd, float* dgamma, float* dbeta, float* A, float* Bc, float* Cc, int eval,
-                           hipStream_t st);
 int ava_scale_backward_roots(float* seed, int64_t n, float* wg, int64_t nwg, long long* slot, const float* scale, hipStream_t st);
 int ava_adam_flat_guarded(float* p, const float* g, float* m, float* v, int64_t n, double lr, double beta1, double beta2,
                           double eps, int step, const int* skip_if_set, hipStream_t st);
@@ -247,13 +240,27 @@ static size_t max_dy7_ws(int maxB, int F) {
   return mx;
 }
 
+// CUs left free by every persistent launch (common.h: ava_scale_grid).  The grids are sized deep inside the launchers, which
+// read the CURRENT value: a thread-local that every model entry point (forward, backward part, Adam, encode, decode) sets for
+// its own duration from the model's setting (ava_model_set_cu_reserve; -1 = the process-wide default below) and restores on
+// return (ReserveScope).  So a producer / consumer pair of launches inside one entry point (partial rows written by one
+// kernel, counted by the next) always sees one value, two models or two host threads cannot disturb each other, and the
+// per-kernel entry points (ava_conv3x3 ..., tests and tools) run under the process-wide default.
+static int g_cu_reserve_default = 0;
+static thread_local int t_cu_reserve = -1;             // -1: no model entry point is active on this thread
+int ava_cu_reserve(void) { return t_cu_reserve >= 0 ? t_cu_reserve : g_cu_reserve_default; }
+
+// partial rows of layer l's weight / bias gradient that a step at batch B can write: one per workgroup of its fused backward
+// (for convt7 also one per row of its folding forward's SSE partials).  Sized at reserve 0, the largest grids: the reserve
+// may change after the workspace has been carved.
 static size_t wgrad_part_floats(const ava_model* m, int B, int l) {
   const ConvLayer& L = kLayers[l];
   const LayerDims& D = m->lay[l];
-  int grid = ava_conv_wgrad_grid(B, D.ho, D.wo, L.mode);
-  const int fg = ava_conv_fused_grid_for(B, D.hi, D.wi, L.cin, L.cout, L.mode);     // fused backward kernel's rows
-  if (fg > grid) grid = fg;
-  if (l == NCONV - 1) {            // convt7: its training forward writes the partial rows (one per row of its SSE partials)
+  const int saved = t_cu_reserve;
+  t_cu_reserve = 0;
+  int grid = ava_conv_fused_grid_for(B, D.hi, D.wi, L.cin, L.cout, L.mode);
+  t_cu_reserve = saved;
+  if (l == NCONV - 1) {
     const int fw = ava_conv_grid(B, D.ho, D.wo, L.mode);
     if (fw > grid) grid = fw;
   }
@@ -301,15 +308,6 @@ static void carve(ava_model* m, void* ws, size_t* total) {
 
 extern "C" int ava_version(void) { return 100; }
 
-// CUs left free by every persistent launch (common.h: ava_scale_grid).  The grids are sized deep inside the launchers, which
-// read the CURRENT value: a thread-local that every model entry point (forward, backward part, Adam, encode, decode) sets for
-// its own duration from the model's setting (ava_model_set_cu_reserve; -1 = the process-wide default below) and restores on
-// return (ReserveScope).  So a producer / consumer pair of launches inside one entry point (partial rows written by one
-// kernel, counted by the next) always sees one value, two models or two host threads cannot disturb each other, and the
-// per-kernel entry points (ava_conv3x3 ..., tests and tools) run under the process-wide default.
-static int g_cu_reserve_default = 0;
-static thread_local int t_cu_reserve = -1;             // -1: no model entry point is active on this thread
-int ava_cu_reserve(void) { return t_cu_reserve >= 0 ? t_cu_reserve : g_cu_reserve_default; }
 extern "C" int ava_set_cu_reserve(int cus) {
   if (cus < 0 || cus > 128) return AVA_EINVAL;
   g_cu_reserve_default = cus;
@@ -666,21 +664,12 @@ static int pack_weights(ava_model* m, bool with_bwd, hipStream_t st, const float
 }
 
 // ---- BatchNorm sums accumulated in the producing kernel and finalised in the consumer's prologue (bn_acc.h) ----------
-// Forward: BatchNorm j (input of layer j) when layer j runs the wave-specialised / plain matrix-core forward kernel (the
-// consumer side) and its input comes from such a kernel, from conv1's packed-FMA kernel (j = 1) or from the
-// fc8 -> NHWC layout kernel (j = 7), and the direct convt6 / convt7 kernels (j = 12, 13): j = 1..13.  Backward: BatchNorm j when the backward of layer j (fused kernel; j = 5:
-// the wave-specialised data-gradient kernel; j = 13: convt7's weight-gradient + sums kernel) hands over to the fused
-// backward, or to the data-gradient kernel, of layer j-1 (j = 7: to bn8's layout kernel; j = 1: to conv1's packed-FMA backward;
-// j = 0: to the weight-gradient reduction that ends the pass): j = 13 .. 0.  Forward bn1's sums come from the pack launch,
+// Forward, BatchNorm j = 1 .. 13 (input of layer j): summed by the kernel that produces that input (layer j-1's forward; j = 7:
+// the fc8 -> NHWC layout kernel) into slot j, finalised in layer j's forward.  bn1's sums (j = 0) come from the pack launch,
 // which also zeroes the accumulators: two slots (0 and 28) alternate, the launch adds to the one its predecessor zeroed.
-static bool acc_pair_fwd(const ava_model* m, int j) {
-  (void)m;
-  return j >= 1 && j <= 13;
-}
-static bool acc_pair_bwd(const ava_model* m, int j) {
-  (void)m;
-  return j >= 0 && j <= 13;
-}
+// Backward, BatchNorm j = 13 .. 0: summed by the backward of layer j (fused kernel; j = 13: convt7's forward fold or its
+// weight-gradient + sums kernel) into slot 14 + j, finalised by the backward of layer j-1 (j = 7: by bn8's layout kernel;
+// j = 0: by the weight-gradient reduction that ends the pass).
 static long long* acc_slot(ava_model* m, int slot) { return m->bn_acc + (size_t)slot * AVA_ACC_SLOT_LL; }
 static BnFin fin_none() { BnFin f = {}; f.acc = nullptr; return f; }
 static BnFin fin_fwd(ava_model* m, int j, int B) {
@@ -714,16 +703,6 @@ static int finalize_fwd(ava_model* m, int l, int nparts, int64_t n, hipStream_t 
   const int rc = ava_bn_finalize(m->bn_part, nparts, n, L.cin, PP(m, L.pg), PP(m, L.pbeta), m->bn_running + l * 32,
                                  m->bn_running + (NCONV + l) * 32, m->bn_batches + l, 1, bn_mean(m, l), bn_invstd(m, l),
                                  bn_scale(m, l), bn_shift(m, l), st);
-  mark(m, CAT_BN, st);
-  return rc;
-}
-static int finalize_bwd(ava_model* m, int l, int nparts, int64_t n, hipStream_t st) {
-  const ConvLayer& L = kLayers[l];
-  // a forward in eval mode normalised with the running statistics: they are constants, so dx = gamma*invstd*g
-  // (no batch-statistic terms); dgamma / dbeta keep their forms with xhat built from the running statistics
-  const int rc = ava_bn_finalize_bwd_ex(m->bn_part, nparts, n, L.cin, PP(m, L.pg), bn_mean(m, l), bn_invstd(m, l),
-                                        GG(m, L.pg), GG(m, L.pbeta), bn_A(m, l), bn_B(m, l), bn_C(m, l),
-                                        m->last_train ? 0 : 1, st);
   mark(m, CAT_BN, st);
   return rc;
 }
@@ -768,20 +747,9 @@ static RecompArgs recomp_args(ava_model* m) {
   rc.G1 = m->Gf[0]; rc.bias1 = PP(m, kLayers[0].pb); rc.pa1 = bn_scale(m, 0); rc.pb1 = bn_shift(m, 0);
   return rc;
 }
-// y1 is stored by conv1's forward.  Recomputing it in conv2's forward from x instead was measured (profiles/r03): correct
-// (bit-identical y1, all step tests green) but SLOWER -- conv2's forward 44 -> 67 us (the staging waves' 9-tap
-// recomputation costs ~40 us of vector issue chip-wide) and the store-free conv1 pass takes the 36 us of the storing one
-// (that kernel is bound by its LDS-staged compute chain, not by its 128 MiB of stores).  y1 is therefore always in its
-// workspace slot and there is nothing to materialise.
-extern "C" int ava_debug_materialize(ava_model* m, const float* x, int B, ava_stream_t s) {
-  (void)s;
-  if (m == nullptr || x == nullptr || B < 1 || B > m->maxB) return AVA_EINVAL;
-  return AVA_OK;
-}
-
-// stop_at_fc2 (historic name): stop behind fc31|32|33, the caller continues with the fused middle (forward_impl)
+// stop_before_heads: return behind fc31|32|33, the caller continues with the fused middle (forward_impl)
 static int encoder_forward(ava_model* m, const float* x, int B, int train, float* mu, float* u, float* logd_or_d,
-                           int last_act, hipStream_t st, int pre_nparts = 0, bool stop_at_fc2 = false) {
+                           int last_act, hipStream_t st, int pre_nparts = 0, bool stop_before_heads = false) {
   const int z = m->z;
   int nparts = pre_nparts;                 // > 0: pack_stats_kernel already wrote the input statistics' partial rows
   if (train) {
@@ -801,22 +769,20 @@ static int encoder_forward(ava_model* m, const float* x, int B, int train, float
     // conv7's matrix-core kernel also writes the NCHW-flatten copy fc1 reads (saves the transpose launch)
     float* nchw = l == 6 ? m->y7t : nullptr;
     ConvAcc acc;
-    acc.fin = (train && acc_pair_fwd(m, l)) ? fin_fwd(m, l, B) : fin_none();                 // BatchNorm l: finalised in this kernel
+    acc.fin = (train && l >= 1) ? fin_fwd(m, l, B) : fin_none();                 // BatchNorm l: finalised in this kernel
     if (train && l == 0 && m->acc0_used >= 0) { acc.fin = fin_fwd(m, 0, B); acc.fin.acc = acc_slot(m, m->acc0_used); }
-    acc.acc_out = (train && l < 6 && acc_pair_fwd(m, l + 1)) ? acc_slot(m, l + 1) : nullptr;    // BatchNorm l+1: summed by this kernel
+    acc.acc_out = (train && l < 6) ? acc_slot(m, l + 1) : nullptr;    // BatchNorm l+1: summed by this kernel
     TRY(ava_conv3x3_ex(in, nullptr, bn_scale(m, l), bn_shift(m, l), nullptr, m->Gf[l], PP(m, L.pb), out, nchw,
                        nullptr, nullptr, nullptr, m->bn_part, B, D.hi, D.wi, L.cin, L.cout, L.mode, PRO_BN, EPI_FWD, 1,
                        0.f, m->act_bf16, &acc, reinterpret_cast<ava_stream_t>(st)));
     mark(m, CAT_CONV_FWD, st);
-    if (train && l < 6 && acc.acc_out == nullptr)
-      TRY(finalize_fwd(m, l + 1, ava_conv_grid(B, D.ho, D.wo, L.mode), (int64_t)B * D.ho * D.wo, st));
   }
   mark(m, CAT_LAYOUT, st);
   TRY(gemm(m, m->y7t, 0, PP(m, FC1), 0, PP(m, FC1 + 1), m->h1, 0, nullptr, nullptr, B, 1024, m->F, 1, 1, ACT_RELU, st));
   TRY(gemm(m, m->h1, 0, PP(m, FC2), 0, PP(m, FC2 + 1), m->h2, 0, nullptr, nullptr, B, 256, 1024, 1, 1, ACT_RELU, st));
   // fc31|fc32|fc33 as one [192,256] layer (arena keeps the three weights, then the three biases, contiguous)
   TRY(gemm(m, m->h2, 0, PP(m, FC31), 0, PP(m, FC31 + 1), m->h3, 0, nullptr, nullptr, B, 192, 256, 1, 1, ACT_RELU, st));
-  if (stop_at_fc2) return AVA_OK;               // the caller continues with the fused middle (heads .. fc6)
+  if (stop_before_heads) return AVA_OK;               // the caller continues with the fused middle (heads .. fc6)
   // the three 64 -> z heads (mu, u, log d) on the 64-wide slices of h3: one grouped launch
   const AvaGemmProblem heads[3] = {
       {m->h3 + 0, 192, PP(m, FC41), 0, PP(m, FC41 + 1), mu, 0, nullptr, nullptr, B, z, 64, ACT_NONE},
@@ -827,15 +793,8 @@ static int encoder_forward(ava_model* m, const float* x, int B, int train, float
 }
 
 // from_fc7: h6 already exists (the fused middle wrote it)
-static bool dd6_fused(const ava_model* m);
-static bool acc_pair_bwd(const ava_model* m, int j);
-// convt7's TRAINING forward also forms its weight-gradient partials and the BatchNorm-backward sums of its input
-// (conv_thin_kernels.h: FOLD).
-static bool fold13_on(const ava_model* m) {
-  return m->G != nullptr && acc_pair_bwd(m, 13) && m->lay[13].hi % 8 == 0;
-}
-
-// `fold`: the caller is a training forward a backward may follow (forward_impl)
+// `fold`: the caller is a training forward a backward may follow (forward_impl); with a gradient arena, convt7's forward
+// then also forms its weight-gradient partials and the BatchNorm-backward sums of its input (conv_thin_kernels.h: FOLD)
 static int decoder_forward(ava_model* m, const float* zin, const float* x_target, int B, int train, float* xrec,
                            hipStream_t st, bool from_fc7 = false, bool fold = false) {
   const int z = m->z;
@@ -849,7 +808,7 @@ static int decoder_forward(ava_model* m, const float* zin, const float* x_target
   int slabs8 = 1;
   TRY(gemm_defer2(m, m->h7, 0, PP(m, FC8), 0, PP(m, FC8 + 1), m->f8, 0, B, m->F, 1024, 1, 1, ACT_RELU, st, &slabs8));
   int nparts = 0;
-  long long* acc7 = (train && acc_pair_fwd(m, 7)) ? acc_slot(m, 7) : nullptr;     // bn8's sums: finalised by convt1's kernel
+  long long* acc7 = train ? acc_slot(m, 7) : nullptr;     // bn8's sums: finalised by convt1's kernel
   if (slabs8 == 2) {
     const float* s0 = reinterpret_cast<const float*>(m->gemm_ws);
     TRY(ava_nchw_to_nhwc_stats_slabs(s0, s0 + (size_t)B * m->F, PP(m, FC8 + 1), 1, m->f8, m->X[7], m->bn_part, B, m->P8,
@@ -858,16 +817,15 @@ static int decoder_forward(ava_model* m, const float* zin, const float* x_target
     TRY(ava_nchw_to_nhwc_stats(m->f8, m->X[7], m->bn_part, B, m->P8, m->act_bf16, acc7, &nparts, st));
   }
   mark(m, CAT_LAYOUT, st);
-  if (train && acc7 == nullptr) TRY(finalize_fwd(m, 7, nparts, (int64_t)B * m->P8, st));
   for (int l = 7; l < NCONV; ++l) {
     const ConvLayer& L = kLayers[l];
     const LayerDims& D = m->lay[l];
     const bool last = l == NCONV - 1;
     float* out = last ? xrec : m->X[l + 1];
     ConvAcc acc;
-    acc.fin = (train && acc_pair_fwd(m, l)) ? fin_fwd(m, l, B) : fin_none();
-    acc.acc_out = (train && !last && acc_pair_fwd(m, l + 1)) ? acc_slot(m, l + 1) : nullptr;
-    if (last && fold && train && x_target != nullptr && fold13_on(m)) {
+    acc.fin = train ? fin_fwd(m, l, B) : fin_none();
+    acc.acc_out = (train && !last) ? acc_slot(m, l + 1) : nullptr;
+    if (last && fold && train && x_target != nullptr && m->G != nullptr) {
       acc.fold.wg_partials = m->wg_part[l];
       acc.fold.acc_out = acc_slot(m, 14 + l);
       acc.fold.mean = bn_mean(m, l); acc.fold.invstd = bn_invstd(m, l);
@@ -879,8 +837,6 @@ static int decoder_forward(ava_model* m, const float* zin, const float* x_target
                        L.cin, L.cout, L.mode, PRO_BN, last ? EPI_SSE : EPI_FWD, 1, m->prec, m->act_bf16, &acc,
                        reinterpret_cast<ava_stream_t>(st)));
     mark(m, CAT_CONV_FWD, st);
-    if (train && !last && acc.acc_out == nullptr)
-      TRY(finalize_fwd(m, l + 1, ava_conv_grid(B, D.ho, D.wo, L.mode), (int64_t)B * D.ho * D.wo, st));
     if (last) m->sse_parts = ava_conv_grid(B, D.ho, D.wo, L.mode);
   }
   return AVA_OK;
@@ -958,91 +914,53 @@ extern "C" int ava_decode(ava_model* m, const float* z, int B, int bn_train, flo
   return decoder_forward(m, z, nullptr, B, bn_train, x_rec, st);
 }
 
-// ---- all 14 weight-gradient reductions are issued per layer (partials buffer is shared) --------------
-// workgroups (= partial rows) of layer l's fused backward kernel; 0: the layer runs the separate kernels
+// workgroups (= partial rows of both outputs) of layer l's fused backward kernel.  Every layer has one at every supported
+// size (tests/test_gpu_kernels.py: test_every_layer_has_a_fused_backward): the twelve layers with >= 8 channels on both sides
+// run the limb kernel, whose tiles (at most 32 x 8 low-resolution pixels) divide every side size_ok admits, conv1 and convt7
+// the thin kernels.
 static int fused_grid(const ava_model* m, int l, int B) {
   const ConvLayer& L = kLayers[l];
   return ava_conv_fused_grid_for(B, m->lay[l].hi, m->lay[l].wi, L.cin, L.cout, L.mode);
 }
 
-// convt7's data gradient formed inside convt6's fused backward (the shape that kernel is instantiated for: W = 128 tiles of
-// 32 x 4 low-resolution pixels).
-static bool dd6_fused(const ava_model* m) {
-  return fused_grid(m, 12, m->lastB > 0 ? m->lastB : 1) > 0 && m->lay[12].wi % 32 == 0 && m->lay[12].hi % 4 == 0;
-}
-
-int ava_conv3x3_wgrad_pair(const WgradCall& p, const WgradCall& q, int B, int act_bf16, ava_stream_t s);
-
-// `defer`: a layer without a fused kernel records its weight-gradient call there instead of launching it (the caller
-// issues two layers' calls as one pair launch; gin / gin2 must stay valid until then)
+// Backward of layer l in one pass: data gradient, BatchNorm-backward sums and weight/bias partial rows.
 static int conv_layer_backward(ava_model* m, int l, const float* x0, const float* gin, const float* gin2,
                                const float* ca, const float* cb, const float* cc, int pro, float* gout, int B,
-                               hipStream_t st, WgradCall* defer = nullptr) {
+                               hipStream_t st) {
   const ConvLayer& L = kLayers[l];
   const LayerDims& D = m->lay[l];
-  const float* X = l == 0 ? x0 : m->X[l];
-  // layers with a fused kernel: data gradient, BatchNorm-backward sums and weight/bias partials from one pass
   const int fgrid = fused_grid(m, l, B);
+  if (fgrid <= 0 || (gout == nullptr && l != 0)) return AVA_EINVAL;      // no second path: a layer without a fused kernel is an error
   if (l == 13) {
     // convt7: the training forward has already left this layer's weight-gradient partials and BatchNorm-backward sums behind
     // (FOLD) and convt6's kernel forms its data gradient itself -- nothing to launch.  They are those of loss scale 1; both are
     // linear in the seed, so a backward with another scale (ava_set_backward_scale) has had them multiplied in place together
     // with the seed (backward_part0: ava_scale_backward_roots).  After a forward that did not fold the separate kernel runs.
-    if (m->fold13 && dd6_fused(m)) return AVA_OK;
-    if (m->fold13) {
-      if (hipMemsetAsync(acc_slot(m, 14 + l), 0, (size_t)AVA_ACC_SLOT_LL * sizeof(long long), st) != hipSuccess) return AVA_ELAUNCH;
-      m->fold13 = 0;
-    }
+    if (m->fold13) return AVA_OK;
     m->wg13_rows = fgrid;
   }
-  if (fgrid > 0 && (gout != nullptr || l == 0)) {
-    FusedArgs a = {};
-    a.x = X; a.xa = bn_scale(m, l); a.xb = bn_shift(m, l);
-    a.dy = gin; a.dy2 = gin2; a.da = ca; a.db = cb; a.dc = cc;
-    a.Gb = m->Gb[l]; a.dx = gout; a.mean = bn_mean(m, l); a.invstd = bn_invstd(m, l);
-    a.bn_partials = m->bn_part; a.wg_partials = m->wg_part[l];
-    a.B = B; a.Hi = D.hi; a.Wi = D.wi; a.Ho = D.ho; a.Wo = D.wo;
-    a.act_bf16 = m->act_bf16;
-    // BatchNorm l+1's A, Bc, Cc finalised in this kernel / BatchNorm l's sums accumulated by it (bn_acc.h); the thin
-    // kernels of conv1 / convt7 (Cin or Cout = 1) keep arrays and partial rows
-    const bool thin = L.cin == 1 || L.cout == 1;
-    a.fin = ((!thin || l == 0) && pro == PRO_BWD && acc_pair_bwd(m, l + 1)) ? fin_bwd(m, l + 1, B) : fin_none();   // l = 0: conv1's packed-FMA backward
-    a.acc_out = ((!thin || l == 13 || l == 0) && acc_pair_bwd(m, l)) ? acc_slot(m, 14 + l) : nullptr;   // l = 13: convt7's sums kernel; l = 0: conv1's
-    a.tiles_y = a.tiles_x = a.ntiles = 0;
-    if (dd6_fused(m)) {
-      // convt7's data gradient dd6 (8 channels at full resolution: 128 MiB written and read back at batch 256) is never
-      // stored: convt7's launch only forms its weight gradient and BatchNorm sums, and convt6's fused backward gathers its
-      // dy window from the 1-channel seed in the staging waves (conv_recomp.h)
-      if (l == 13) a.skip_dx = 1;
-      if (l == 12) { a.dy = m->seed; a.rcd.G1 = m->Gb[13]; }
-    }
-    // conv1's backward recomputes y1 from the x window it stages instead of reading it (conv_thin_kernels.h: RECY)
-    if (l == 0 && pro == PRO_BWD) a.rc = recomp_args(m);
-    TRY(ava_conv3x3_bwd_fused_launch(a, L.cin, L.cout, L.mode, pro, st));
-    mark(m, CAT_CONV_BWD_DATA, st);
-    if (a.acc_out != nullptr) return AVA_OK;                  // finalised by the next backward kernel
-    return finalize_bwd(m, l, fgrid, (int64_t)B * D.hi * D.wi, st);
-  }
-  // Layers without a fused kernel (the four at 16x16).  The data gradient w.r.t. the BatchNorm output (plus the
-  // BatchNorm-backward sums against X) goes FIRST: its prologue can finalise BatchNorm l+1's A, Bc, Cc from the
-  // accumulated sums (bn_acc.h) and workgroup 0 publishes them, so the weight-gradient kernel behind it reads the arrays.
-  const int bmode = L.mode == MODE_S1 ? MODE_S1 : (L.mode == MODE_DOWN ? MODE_UP : MODE_DOWN);
-  ConvAcc acc;
-  acc.fin = (pro == PRO_BWD && acc_pair_bwd(m, l + 1)) ? fin_bwd(m, l + 1, B) : fin_none();
-  acc.acc_out = acc_pair_bwd(m, l) ? acc_slot(m, 14 + l) : nullptr;
-  TRY(ava_conv3x3_ex(gin, gin2, ca, cb, cc, m->Gb[l], nullptr, gout, nullptr, X, bn_mean(m, l), bn_invstd(m, l),
-                     m->bn_part, B, D.ho, D.wo, L.cout, L.cin, bmode, pro, EPI_BWD, 0, 0.f, m->act_bf16, &acc,
-                     reinterpret_cast<ava_stream_t>(st)));
+  FusedArgs a = {};
+  a.x = l == 0 ? x0 : m->X[l]; a.xa = bn_scale(m, l); a.xb = bn_shift(m, l);
+  a.dy = gin; a.dy2 = gin2; a.da = ca; a.db = cb; a.dc = cc;
+  a.Gb = m->Gb[l]; a.dx = gout; a.mean = bn_mean(m, l); a.invstd = bn_invstd(m, l);
+  a.bn_partials = m->bn_part; a.wg_partials = m->wg_part[l];
+  a.B = B; a.Hi = D.hi; a.Wi = D.wi; a.Ho = D.ho; a.Wo = D.wo;
+  a.act_bf16 = m->act_bf16;
+  // BatchNorm l+1's A, Bc, Cc finalised in this kernel (not in convt7's thin kernel, which reads the seed as it is) /
+  // BatchNorm l's sums accumulated by it (bn_acc.h), finalised by the next backward kernel
+  a.fin = (l != 13 && pro == PRO_BWD) ? fin_bwd(m, l + 1, B) : fin_none();
+  a.acc_out = acc_slot(m, 14 + l);
+  a.tiles_y = a.tiles_x = a.ntiles = 0;
+  // convt7's data gradient dd6 (8 channels at full resolution: 128 MiB written and read back at batch 256) is never
+  // stored: convt7's launch only forms its weight gradient and BatchNorm sums, and convt6's fused backward gathers its
+  // dy window from the 1-channel seed in the staging waves (conv_recomp.h).  That kernel's tile is 32 x 4 low-resolution
+  // pixels, which divides convt6's input at every supported size (W in {128, 256}: 64 or 128 wide, 64 or 128 high).
+  if (l == 13) a.skip_dx = 1;
+  if (l == 12) { a.dy = m->seed; a.rcd.G1 = m->Gb[13]; }
+  // conv1's backward recomputes y1 from the x window it stages instead of reading it (conv_thin_kernels.h: RECY)
+  if (l == 0 && pro == PRO_BWD) a.rc = recomp_args(m);
+  TRY(ava_conv3x3_bwd_fused_launch(a, L.cin, L.cout, L.mode, pro, st));
   mark(m, CAT_CONV_BWD_DATA, st);
-  if (acc.acc_out == nullptr) TRY(finalize_bwd(m, l, ava_conv_grid(B, D.hi, D.wi, bmode), (int64_t)B * D.hi * D.wi, st));
-  // weight + bias gradient (forward gather form), reduced into the reference layout inside the grad arena
-  if (defer != nullptr) {
-    *defer = WgradCall{X, bn_scale(m, l), bn_shift(m, l), gin, gin2, ca, cb, cc, m->wg_part[l], D.hi, D.wi, L.cin, L.cout, L.mode, pro};
-    return AVA_OK;
-  }
-  TRY(ava_conv3x3_wgrad_ex(X, bn_scale(m, l), bn_shift(m, l), gin, gin2, ca, cb, cc, m->wg_part[l], B, D.hi, D.wi, L.cin,
-                           L.cout, L.mode, pro, m->act_bf16, st));
-  mark(m, CAT_CONV_WGRAD, st);
   return AVA_OK;
 }
 
@@ -1055,15 +973,14 @@ static int reduce_wgrads(ava_model* m, int l0, int l1, int B, hipStream_t st) {
     tab.e[n].partials = m->wg_part[l];
     tab.e[n].dw = GG(m, L.pw);
     tab.e[n].dbias = GG(m, L.pb);
-    const int fg = l == 13 && m->wg13_rows > 0 ? m->wg13_rows : fused_grid(m, l, B);
-    tab.e[n].nparts = fg > 0 ? fg : ava_conv_wgrad_rows_ex(B, m->lay[l].hi, m->lay[l].wi, L.cin, L.cout, L.mode, l == 13 || l == 6 ? PRO_ID : PRO_BWD, m->act_bf16);
+    tab.e[n].nparts = l == 13 ? m->wg13_rows : fused_grid(m, l, B);      // convt7: its forward's rows after a fold
     tab.e[n].cin = L.cin; tab.e[n].cout = L.cout;
     tab.e[n].kind = !L.transposed ? 0 : (L.mode == MODE_S1 ? 1 : 2);
     tab.e[n].block0 = blocks;
     blocks += ceil_div(9 * L.cin * L.cout + L.cout, 32);
   }
   tab.n = n;
-  tab.fin0 = (l0 == 0 && acc_pair_bwd(m, 0)) ? fin_bwd(m, 0, B) : fin_none();     // bn1's own gradient: no consumer kernel, finalised here
+  tab.fin0 = l0 == 0 ? fin_bwd(m, 0, B) : fin_none();     // bn1's own gradient: no consumer kernel, finalised here
   TRY(ava_conv_wgrad_reduce_all(tab, blocks, st));
   mark(m, CAT_CONV_WGRAD, st);
   return AVA_OK;
@@ -1123,38 +1040,26 @@ extern "C" int ava_backward_part(ava_model* m, const float* x, int B, int part, 
   return backward_part2(m, x, B, to_stream(s), false);
 }
 
-// offset (floats) of the upper half of a gradient ping-pong buffer (B * H * W * 8 floats each, model workspace)
-static size_t grad_half(const ava_model* m, int B) { return (size_t)B * m->H * m->W * 4; }
-
 static int backward_part0(ava_model* m, const float* x, int B, hipStream_t st, bool whole) {
   // ---- decoder convolutions, last to first ----
   float* gcur = m->gA;
   float* gnext = m->gB;
   mark(m, -1, st);
   if (m->bwd_scale != nullptr) {       // d(result)/d(loss) may differ from 1: scale the roots of the backward (here and latent_bwd)
-    const bool folded = m->fold13 && dd6_fused(m);          // ... and what convt7's forward left behind for this backward
+    const bool folded = m->fold13 != 0;                     // ... and what convt7's forward left behind for this backward
     TRY(ava_scale_backward_roots(m->seed, (int64_t)B * m->H * m->W, folded ? m->wg_part[13] : nullptr,
                                  folded ? (int64_t)m->wg13_rows * 73 : 0, folded ? acc_slot(m, 14 + 13) : nullptr, m->bwd_scale, st));
     mark(m, CAT_LAYOUT, st);
   }
   TRY(conv_layer_backward(m, 13, x, m->seed, nullptr, nullptr, nullptr, nullptr, PRO_ID, gcur, B, st));
-  const bool pair = fused_grid(m, 8, B) == 0 && fused_grid(m, 7, B) == 0;
-  WgradCall wc[2];
   for (int l = 12; l >= 7; --l) {
     // dU_l = (X_{l+1} > 0) ? A*g + Bc*X_{l+1} + Cc : 0 with the coefficients of BatchNorm l+1
-    // convt2 + convt1 (16 x 16, no fused kernel): both data gradients first, then the two weight gradients as ONE launch.
-    // convt1's data gradient goes to the upper half of the buffer that still holds convt2's dU (both are small)
-    float* gout = (pair && l == 7) ? gnext + grad_half(m, B) : gnext;
-    TRY(conv_layer_backward(m, l, x, gcur, m->X[l + 1], bn_A(m, l + 1), bn_B(m, l + 1), bn_C(m, l + 1), PRO_BWD, gout,
-                            B, st, pair && l <= 8 ? &wc[8 - l] : nullptr));
-    gnext = gcur; gcur = gout;
-  }
-  if (pair) {
-    TRY(ava_conv3x3_wgrad_pair(wc[0], wc[1], B, m->act_bf16, reinterpret_cast<ava_stream_t>(st)));
-    mark(m, CAT_CONV_WGRAD, st);
+    TRY(conv_layer_backward(m, l, x, gcur, m->X[l + 1], bn_A(m, l + 1), bn_B(m, l + 1), bn_C(m, l + 1), PRO_BWD, gnext,
+                            B, st));
+    { float* t = gcur; gcur = gnext; gnext = t; }
   }
   // gcur = dXhat_8 (NHWC [B,256,32]); through bn8 and fc8's ReLU back to NCHW-flatten
-  const BnFin fin8 = acc_pair_bwd(m, 7) ? fin_bwd(m, 7, B) : fin_none();      // bn8: finalised inside the layout kernel
+  const BnFin fin8 = fin_bwd(m, 7, B);      // bn8: finalised inside the layout kernel
   TRY(ava_bn_bwd_apply_to_nchw(gcur, m->f8, bn_A(m, 7), bn_B(m, 7), bn_C(m, 7), m->dF8, B, m->P8, m->act_bf16, &fin8, st));
   mark(m, CAT_LAYOUT, st);
   if (!whole) TRY(reduce_wgrads(m, 7, NCONV, B, st));
@@ -1224,27 +1129,16 @@ static int backward_part2(ava_model* m, const float* x, int B, hipStream_t st, b
     TRY(ava_relu_mask_to_nhwc(m->dy7, nullptr, m->y7, gcur, B, m->P8, st));  // dU_7 (ReLU of conv7)
   }
   mark(m, CAT_LAYOUT, st);
-  // conv7 + conv6 (16 x 16, no fused kernel): both data gradients first, then the two weight gradients as ONE launch
-  const bool pair = fused_grid(m, 6, B) == 0 && fused_grid(m, 5, B) == 0;
-  WgradCall wc[2];
-  TRY(conv_layer_backward(m, 6, x, gcur, nullptr, nullptr, nullptr, nullptr, PRO_ID, gnext, B, st, pair ? &wc[0] : nullptr));
+  TRY(conv_layer_backward(m, 6, x, gcur, nullptr, nullptr, nullptr, nullptr, PRO_ID, gnext, B, st));
   { float* t = gcur; gcur = gnext; gnext = t; }
-  bool upper = false;
   for (int l = 5; l >= 0; --l) {
-    // conv6's data gradient goes to the upper half of the buffer that still holds conv7's dU (both are small)
-    float* gout = l == 0 ? nullptr : ((pair && l == 5) ? gnext + grad_half(m, B) : gnext);
-    TRY(conv_layer_backward(m, l, x, gcur, m->X[l + 1], bn_A(m, l + 1), bn_B(m, l + 1), bn_C(m, l + 1), PRO_BWD, gout, B, st,
-                            pair && l == 5 ? &wc[1] : nullptr));
-    if (pair && l == 5) {
-      TRY(ava_conv3x3_wgrad_pair(wc[0], wc[1], B, m->act_bf16, reinterpret_cast<ava_stream_t>(st)));
-      mark(m, CAT_CONV_WGRAD, st);
-    }
-    float* freed = upper ? gcur - grad_half(m, B) : gcur;      // an upper half read by this layer: the whole buffer is free again
-    gcur = gout; gnext = freed;
-    upper = pair && l == 5;
+    // conv1 (l = 0) has no data gradient to write: its kernel only forms the weight gradient and bn1's sums
+    TRY(conv_layer_backward(m, l, x, gcur, m->X[l + 1], bn_A(m, l + 1), bn_B(m, l + 1), bn_C(m, l + 1), PRO_BWD,
+                            l == 0 ? nullptr : gnext, B, st));
+    { float* t = gcur; gcur = gnext; gnext = t; }
   }
   m->bwd_scale = nullptr;              // consumed
-  return reduce_wgrads(m, whole ? 0 : 0, whole ? NCONV : 7, B, st);      // encoder (whole: all 14) weight/bias gradients
+  return reduce_wgrads(m, 0, whole ? NCONV : 7, B, st);      // encoder (whole: all 14) weight/bias gradients
 }
 
 // the same update on the slice [offset, offset + count) of the arenas (data parallelism with a sharded optimizer:

@@ -146,10 +146,6 @@ const float* ava_last_z(ava_model* m);
 const float* ava_last_xrec(ava_model* m);
 /* name -> workspace buffer of an intermediate (tests): "y1".."y7","d1".."d6","f8","mu","u","logd",... */
 const float* ava_debug_buffer(ava_model* m, const char* name, int64_t* floats);
-/* Intermediates the step does not keep in memory because their consumers recompute them (y1 = relu(conv1(bn1 x)),
- * vae.py:217) are written into their ava_debug_buffer slots ("y1") by the kernel whose store-free form took their
- * statistics: same arithmetic, bit for bit.  Call after the ava_forward whose intermediates are wanted, with its x. */
-int ava_debug_materialize(ava_model* m, const float* x, int B, ava_stream_t s);
 
 /* Optional timing of the driver's launches with HIP events recorded on the launch stream
  * (bench.py's roofline leg).  Categories, in order: conv forward, conv backward-data, conv weight-grad
@@ -207,9 +203,9 @@ int ava_conv_wgrad_rows(int B, int Hi, int Wi, int Cin, int Cout, int mode, int 
  * x, dy (and dy2) produces what ava_conv3x3(pro 1|2, epi 1) in the backward-data pattern and ava_conv3x3_wgrad produce
  * separately -- dx = gradient w.r.t. the BatchNorm output [B,Hi,Wi,Cin], bn_partials [grid][2*Cin] = {sum dx,
  * sum dx*xhat} with xhat = (x - mean)*invstd, wg_partials [grid][9*Cin*Cout + Cout].  Gb = backward-data weights
- * (pack kinds 3..6).  grid = ava_conv_fused_grid(...); 0 means the shape has no fused instantiation (the layers
- * with 8 or 16 channels on both sides and the 1 -> 8 layer have one) and ava_conv3x3_bwd_fused returns AVA_EINVAL
- * for it.  The 1 -> 8 layer (first layer: nothing upstream) never forms dx: pass dx = NULL, the sums are exact. */
+ * (pack kinds 3..6).  grid = ava_conv_fused_grid(...); 0 means the shape has no fused instantiation and
+ * ava_conv3x3_bwd_fused returns AVA_EINVAL for it.  Every layer of the model has one at every size the model accepts
+ * (the model's backward runs nothing else).  The 1 -> 8 layer (first layer: nothing upstream) never forms dx: pass dx = NULL, the sums are exact. */
 int ava_conv_fused_grid(int B, int Hi, int Wi, int Cin, int Cout, int mode);
 int ava_conv3x3_bwd_fused(const float* x, const float* xa, const float* xb,
                           const float* dy, const float* dy2, const float* da, const float* db_, const float* dc,

@@ -114,14 +114,24 @@ def test_conv_backward_data_and_wgrad(layer):
     for pro, dy_t, extra in ((PRO_BWD, gn, dict(dy2=dev(nhwc(y)), da=dev(A), db=dev(Bc), dc=dev(Cc))), (PRO_ID, dU, {})):
         res = bwd_fused(dev(nhwc(x)), dev(scale), dev(shift), dev(nhwc(dy_t)), Gb, dev(mean), dev(invstd), cin, cout,
                         mode, pro, B, hi, kind=kind_f, **extra)
-        if res is None:
-            assert max(cin, cout) > 16                           # every layer up to 16 channels has a fused kernel
-            continue
+        assert res is not None                                   # every layer has a fused kernel (the model runs nothing else)
         fdx, fsums, fdw, fdb = res
         assert fdx is None or rel(fdx.cpu(), nhwc(xhat.grad)) < TOL
         assert float((fsums[:cin] - xhat.grad.sum(dim=(0, 2, 3))).abs().max() / scale_ref) < 1e-5
         assert float((fsums[cin:] - (xhat.grad * xn).sum(dim=(0, 2, 3))).abs().max() / scale_ref) < 1e-5
         assert rel(fdw.cpu(), wr.grad.reshape(-1)) < TOL and rel(fdb.cpu(), br.grad) < TOL
+
+
+def test_every_layer_has_a_fused_backward():
+    """The model's backward has no second path: every layer must have a fused backward kernel at every spectrogram size
+    the model accepts (H, W in {128, 256}) and at any batch.  Host-side grid queries only, nothing is launched."""
+    lib = _lib.load()
+    for name, cin, cout, mode, hi, _ in LAYERS:
+        for H, W in ((128, 128), (256, 256), (128, 256), (256, 128)):
+            for B in (1, 3, 256):
+                Hi, Wi = hi * H // 128, hi * W // 128
+                grid = lib.ava_conv_fused_grid(B, Hi, Wi, cin, cout, mode)
+                assert grid > 0, "%s at %d x %d, B = %d: ava_conv_fused_grid = %d" % (name, H, W, B, grid)
 
 
 def test_conv7_writes_nchw_copy():
