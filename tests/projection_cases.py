@@ -55,6 +55,13 @@ PCA_CASES = {
     "wide_f64": (200, 32, 9520, np.float64),
     "tiny_f64": (12, 5, 9530, np.float64),
 }
+# PCA cases beyond the golden file (checked against ``pca`` alone): more than one 2048-row chunk of the Gram kernel,
+# and D = 129 columns (5 x 5 tiles)
+PCA_KERNEL_CASES = {
+    "chunks_f64": (5000, 32, 9540, np.float64),
+    "chunks_f32": (5000, 32, 9550, np.float32),
+    "tiles_f64": (3000, 128, 9560, np.float64),
+}
 
 
 def golden_input(name):
@@ -64,7 +71,7 @@ def golden_input(name):
 
 
 def pca_input(name):
-    n, d, salt, dtype = PCA_CASES[name]
+    n, d, salt, dtype = PCA_CASES[name] if name in PCA_CASES else PCA_KERNEL_CASES[name]
     scale = 1.0 + 3.0 * np.arange(d)                    # well separated variances
     return (syn.gauss(n * d, salt).reshape(n, d) * scale + 0.5).astype(dtype)
 
@@ -108,7 +115,7 @@ def smooth_knn(idx, dist, local_connectivity=1.0, n_iter=64):
                 rho[i] = nz[index - 1]
                 if interp > 1e-5:
                     rho[i] += interp * (nz[index] - nz[index - 1])
-            else:
+            elif len(nz) > 0:                           # local_connectivity 0 admits a row with no nonzero distance
                 rho[i] = interp * nz[0]
         elif len(nz) > 0:
             rho[i] = np.max(nz)
@@ -166,10 +173,13 @@ def prune(G, n_epochs):
     return G
 
 
-def layout(G, Y0, n_epochs, a, b, salt, epochs=None, gamma=1.0, learning_rate=1.0, negative_sample_rate=5):
+def layout(G, Y0, n_epochs, a, b, salt, epochs=None, gamma=1.0, learning_rate=1.0, negative_sample_rate=5,
+           cap=False):
     """``epochs`` (default all) of the synchronous layout over the pruned CSR graph ``G`` from ``Y0``: each vertex
     sums, in CSR order, 2 alpha clip(g (y_v - y_j)) for every active edge followed by that edge's negative samples,
-    all from the previous epoch's positions"""
+    all from the previous epoch's positions.  An edge that is due more than ``MAX_NEG`` negative samples in one epoch
+    is an error, or, with ``cap``, draws ``MAX_NEG`` and advances its counter by as many, as the kernel does; then the
+    result is ``(Y, flagged)``, ``flagged`` telling whether any edge was capped"""
     epochs = n_epochs if epochs is None else epochs
     n = G.shape[0]
     nnz = G.nnz
@@ -182,6 +192,7 @@ def layout(G, Y0, n_epochs, a, b, salt, epochs=None, gamma=1.0, learning_rate=1.
     epn = eps / negative_sample_rate
     next_s, next_n = eps.copy(), epn.copy()
     Y = np.array(Y0, dtype=np.float64)
+    flagged = False
 
     def clip(v):
         return np.clip(v, -4.0, 4.0)
@@ -200,7 +211,11 @@ def layout(G, Y0, n_epochs, a, b, salt, epochs=None, gamma=1.0, learning_rate=1.
         next_s[act] += eps[act]
         nneg = np.zeros(nnz, dtype=np.int64)
         nneg[act] = ((ep - next_n[act]) / epn[act]).astype(np.int64)
-        assert nneg.max(initial=0) <= MAX_NEG
+        if cap:
+            flagged = flagged or bool(nneg.max(initial=0) > MAX_NEG)
+            nneg = np.minimum(nneg, MAX_NEG)
+        else:
+            assert nneg.max(initial=0) <= MAX_NEG
         u = syn.u01(nnz * MAX_NEG, salt, start=ep * nnz * MAX_NEG).reshape(nnz, MAX_NEG)
         kk = np.minimum(np.floor(u * n).astype(np.int64), n - 1)
         ndiff = Y[head][:, None, :] - Y[kk]
@@ -214,10 +229,64 @@ def layout(G, Y0, n_epochs, a, b, salt, epochs=None, gamma=1.0, learning_rate=1.
         M = np.zeros((n, 2))
         np.add.at(M, np.repeat(head, 1 + MAX_NEG)[use.ravel()], moves.reshape(-1, 2)[use.ravel()])
         Y = Y + M
-    return Y
+    return (Y, flagged) if cap else Y
+
+
+LAYOUT_ISOLATED = [3, 17, 64, 129]        # one in each 64-vertex workgroup, the last vertex among them
+LAYOUT_CLUSTER = list(range(20, 30))      # vertices that start at one position
+LAYOUT_SALT = 9820                        # of the negative samples
+
+
+def layout_edge_graph(n_epochs=12):
+    """a small pruned graph with isolated vertices: the fuzzy graph of ``blobs(n=130, d=8, c=3)`` at k = 10 with the
+    rows and columns of ``LAYOUT_ISOLATED`` emptied, pruned at ``n_epochs``"""
+    X, _ = blobs(n=130, d=8, c=3, salt=9800)
+    idx, dist = knn(X, 10)
+    _, _, w = smooth_knn(idx, dist)
+    A = fuzzy_union_dense(idx, w, len(X))
+    A[LAYOUT_ISOLATED, :] = 0.0
+    A[:, LAYOUT_ISOLATED] = 0.0
+    return prune(scipy.sparse.csr_matrix(A), n_epochs)
+
+
+def layout_edge_start(G, salt=9810):
+    """``Y0`` (uniform in [0, 10)^2) for ``layout_edge_graph``: the vertices of ``LAYOUT_CLUSTER`` share one position
+    (negative samples meet coincident points), and so do the two ends of the first edge of the largest weight (period
+    1: active from epoch 1) that lies among the first 40 vertices outside the cluster; returns ``(Y0, (i, j))``"""
+    n = G.shape[0]
+    Y0 = 10.0 * syn.u01(2 * n, salt).reshape(n, 2)
+    Y0[LAYOUT_CLUSTER] = Y0[LAYOUT_CLUSTER[0]]
+    head = np.repeat(np.arange(n), np.diff(G.indptr))
+    tail = G.indices
+    top = (G.data == G.data.max()) & (head < tail) & (tail < 40)
+    top &= ~np.isin(head, LAYOUT_CLUSTER) & ~np.isin(tail, LAYOUT_CLUSTER)
+    e = int(np.flatnonzero(top)[0])
+    i, j = int(head[e]), int(tail[e])
+    Y0[j] = Y0[i]
+    return Y0, (i, j)
+
+
+def induced(G, m, n_epochs=12):
+    """the subgraph of ``G`` induced by its first ``m`` vertices, pruned again (its largest weight may be smaller)"""
+    return prune(scipy.sparse.csr_matrix(G)[:m][:, :m], n_epochs)
 
 
 # ---- PCA -----------------------------------------------------------------------------------------------------------
+def gram(X):
+    """``(G, A)``: the (d + 1) x (d + 1) Gram matrix ``[X, 1]^T [X, 1]`` of the rows converted to fp64 (as the kernel
+    reads them) and summed in ``np.longdouble``, and ``A = [|X|, 1]^T [|X|, 1]``, the scale of its rounding error"""
+    X = np.asarray(X, dtype=np.float64)
+    Z = np.concatenate([X, np.ones((len(X), 1))], 1).astype(np.longdouble)
+    return Z.T @ Z, np.abs(Z).T @ np.abs(Z)
+
+
+def gram_bound(n, absgram):
+    """first-order bound on the error of an fp64 sum of ``n`` fused multiply-adds taken in any order: every partial sum
+    is rounded once, so no term passes through more than ``n`` roundings of 2^-53 each (the 2 more are slack for the
+    rounding of the restatement and of the bound themselves)"""
+    return (n + 2) * 2.0 ** -53 * absgram
+
+
 def pca(X, n_components=2):
     """sklearn 1.7 PCA(copy=False).fit_transform along the covariance_eigh path, in fp64"""
     X = np.asarray(X, dtype=np.float64)

@@ -145,3 +145,120 @@ def test_umap_argument_validation(kwargs, exc):
 def test_transform_is_not_supported():
     with pytest.raises(NotImplementedError):
         P.UMAP().transform(np.zeros((10, 3)))
+
+
+# ---- the restatements and inputs of tests/test_gpu_projection_kernels.py ------------------------------------------
+def test_restated_gram_matches_fp64_numpy():
+    X = PC.gaussian(3000, 32, 9830) * (1.0 + np.arange(32)) + 0.5
+    n, d = X.shape
+    G, A = PC.gram(X)
+    assert G.dtype == np.longdouble and G.shape == A.shape == (d + 1, d + 1)
+    X64 = np.concatenate([X.astype(np.float64), np.ones((n, 1))], 1)
+    assert np.all(np.abs(X64.T @ X64 - G) <= PC.gram_bound(n, A))
+    assert G[d, d] == n and np.array_equal(G, G.T)
+    # the bound tells a missing row
+    assert not np.all(np.abs(X64[:-1].T @ X64[:-1] - G) <= PC.gram_bound(n, A))
+
+
+def test_restated_local_connectivity():
+    """rho at local_connectivity != 1: umap's smooth_knn_dist takes the floor(lc)-th nonzero distance, interpolates
+    towards the next one by the fraction, and scales the first one by the fraction when lc < 1"""
+    X, _ = PC.blobs(n=300, d=16, c=3, salt=9130)
+    idx, dist = PC.knn(X, 20)
+    assert np.all(np.diff(dist, axis=1) > 0)                  # tie-free: the nonzero distances are columns 1, 2, ...
+    rho = {lc: PC.smooth_knn(idx, dist, lc)[1] for lc in (0.0, 0.5, 1.5, 2.0, 3.0)}
+    np.testing.assert_array_equal(rho[0.0], np.zeros(len(X)))
+    np.testing.assert_array_equal(rho[0.5], 0.5 * dist[:, 1])
+    np.testing.assert_array_equal(rho[1.5], dist[:, 1] + 0.5 * (dist[:, 2] - dist[:, 1]))
+    np.testing.assert_array_equal(rho[2.0], dist[:, 2])
+    np.testing.assert_array_equal(rho[3.0], dist[:, 3])
+    for lc in rho:
+        sigma, r, w = PC.smooth_knn(idx, dist, lc)
+        assert np.all(sigma > 0) and np.all((w >= 0) & (w <= 1)) and np.all(w[:, 0] == 0)
+        np.testing.assert_allclose(PC.psum(dist, r, sigma), np.log2(20), atol=1e-5)
+
+
+@pytest.mark.parametrize("k", [20, 22])
+def test_restated_local_connectivity_with_few_nonzero_distances(k):
+    """rows 40..59 of duplicates() are equal: at k = 20 such a row has no nonzero distance (rho = 0), at k = 22 it has
+    two, fewer than local_connectivity = 3 (rho = the larger one)"""
+    idx, dist = PC.knn(PC.duplicates(), k)
+    assert np.all((dist[40:60] > 0).sum(1) == k - 20)
+    _, rho, _ = PC.smooth_knn(idx, dist, 3.0)
+    np.testing.assert_array_equal(rho[40:60], dist[40:60].max(1))
+    assert np.all(rho[40:60] > 0) == (k == 22)
+    third = (dist[:40] == 0).sum(1) + 2                         # the zeros (column 0 among them) come first
+    np.testing.assert_array_equal(rho[:40], dist[np.arange(40), third])
+    # local_connectivity 0 on a row with no nonzero distance: rho = 0
+    assert np.all(PC.smooth_knn(idx, dist, 0.0)[1] == 0)
+
+
+def _edge_layout():
+    G = PC.layout_edge_graph()
+    Y0, pair = PC.layout_edge_start(G)
+    a, b = PC.find_ab_params()
+    return G, Y0, pair, a, b
+
+
+def test_layout_edge_inputs_reach_the_edges():
+    G, Y0, (i, j), a, b = _edge_layout()
+    n, nnz = G.shape[0], G.nnz
+    assert n == 130 and np.array_equal(G.toarray(), G.toarray().T)
+    deg = np.diff(G.indptr)
+    assert np.all(deg[PC.LAYOUT_ISOLATED] == 0) and 129 in PC.LAYOUT_ISOLATED and min(PC.LAYOUT_ISOLATED) < 40
+    # an edge of period 1 between two vertices at one position
+    assert G[i, j] == G.data.max() and np.array_equal(Y0[i], Y0[j]) and i < 40 and j < 40
+    # a good share of the edges is sampled within 3 epochs (period <= 2)
+    assert (G.data >= G.data.max() / 2).mean() > 0.25
+    # epoch 1 (the first that samples; it reads Y0): a negative sample of a period-1 edge lands on another vertex at
+    # the head's own position
+    head = np.repeat(np.arange(n), deg)
+    u = PC.syn.u01(nnz * PC.MAX_NEG, PC.LAYOUT_SALT, start=nnz * PC.MAX_NEG).reshape(nnz, PC.MAX_NEG)
+    kk = np.minimum(np.floor(u * n).astype(np.int64), n - 1)[:, :3]          # 5 per period: at least 3 in epoch 1
+    hit = (G.data == G.data.max())[:, None] & (kk != head[:, None]) & np.all(Y0[kk] == Y0[head][:, None], axis=2)
+    assert hit.any()
+    # the first 40 vertices keep an isolated vertex, the pair, the cluster and period-1 edges
+    G40 = PC.induced(G, 40)
+    assert G40.shape == (40, 40) and G40.data.max() == G.data.max() and np.diff(G40.indptr)[3] == 0
+
+
+@pytest.mark.parametrize("kwargs", [dict(), dict(gamma=2.0, learning_rate=0.5, negative_sample_rate=1)])
+def test_layout_edge_inputs_are_well_conditioned(kwargs):
+    """the 1e-9 of the GPU tests measures the kernel: the restatement itself moves by less than 1e-10 when the start
+    changes in the last bit"""
+    G, Y0, _, a, b = _edge_layout()
+    for graph, start in ((G, Y0), (PC.induced(G, 40), Y0[:40])):
+        for epochs in (1, 3):
+            y = PC.layout(graph, start, 12, a, b, PC.LAYOUT_SALT, epochs=epochs, **kwargs)
+            y2 = PC.layout(graph, start * (1 + 2.0 ** -52), 12, a, b, PC.LAYOUT_SALT, epochs=epochs, **kwargs)
+            assert np.all(np.isfinite(y)) and np.abs(y - y2).max() < 1e-10
+            np.testing.assert_array_equal(y[PC.LAYOUT_ISOLATED[:1]], start[PC.LAYOUT_ISOLATED[:1]])
+
+
+def test_restated_layout_cap():
+    G, Y0, _, a, b = _edge_layout()
+    # rate 5: at most 2 * 5 + 1 samples fall due in one epoch, so nothing is capped and the bits are those of cap=False
+    y, flagged = PC.layout(G, Y0, 12, a, b, PC.LAYOUT_SALT, epochs=3, cap=True)
+    assert flagged is False
+    np.testing.assert_array_equal(y, PC.layout(G, Y0, 12, a, b, PC.LAYOUT_SALT, epochs=3))
+    # rate 40: a period-1 edge is due 39 samples in epoch 1
+    with pytest.raises(AssertionError):
+        PC.layout(G, Y0, 12, a, b, PC.LAYOUT_SALT, epochs=3, negative_sample_rate=40)
+    y, flagged = PC.layout(G, Y0, 12, a, b, PC.LAYOUT_SALT, epochs=3, negative_sample_rate=40, cap=True)
+    assert flagged is True and np.all(np.isfinite(y))
+    y2, _ = PC.layout(G, Y0 * (1 + 2.0 ** -52), 12, a, b, PC.LAYOUT_SALT, epochs=3, negative_sample_rate=40, cap=True)
+    assert np.abs(y - y2).max() < 1e-10
+
+
+@pytest.mark.parametrize("name", sorted(PC.PCA_KERNEL_CASES))
+def test_pca_kernel_cases_are_well_conditioned(name):
+    """the rows in another order give the same projection to 1e-11 max|want|: the 1e-9 max|want| of the GPU test
+    measures the Gram kernel and not eigh's sensitivity to the rounding of its input"""
+    X = PC.pca_input(name)
+    n = len(X)
+    assert X.dtype == PC.PCA_KERNEL_CASES[name][3] and n > 2048
+    want = PC.pca(X)
+    perm = np.argsort(PC.syn.u01(n, 9570), kind="stable")
+    got = np.empty_like(want)
+    got[perm] = PC.pca(X[perm])
+    assert np.abs(got - want).max() <= 1e-11 * np.abs(want).max()
