@@ -125,6 +125,10 @@ SIGNATURES = {
     "ava_pj_knn": (_i, [_p, _i, _i, _i, _i, _i, _i, _p, _p, _p]),
     "ava_pj_smooth": (_i, [_p, _p, _i, _i, _d, _p, _p, _p, _p, _p]),
     "ava_pj_layout": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i64, _i, _i, _i, _d, _d, _d, _d, C.c_uint64, _p, _p]),
+    "ava_pj_knn_query": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p]),
+    "ava_pj_smooth_bipartite": (_i, [_p, _p, _i, _i, _d, _p, _p, _p, _p, _p]),
+    "ava_pj_transform_init": (_i, [_p, _p, _p, _i, _i, _p, _p, _p]),
+    "ava_pj_transform_layout": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _d, _d, _d, _d, C.c_uint64, _p, _p]),
     "ava_pj_gram_workspace_bytes": (_sz, [_i, _i]),
     "ava_pj_gram": (_i, [_p, _i, _i, _i, _p, _p, _sz, _p]),
     "ava_pj_project": (_i, [_p, _i, _i, _i, _p, _p, _i, _p, _p]),

@@ -10,6 +10,11 @@
 // layout    one synchronous, gather-only SGD epoch per launch over the symmetric CSR graph (rows = heads): a thread
 //           per vertex sums, in CSR order, the attractive moves of its active edges and their negative samples, all
 //           read from the previous epoch's positions, and advances the edges' sample counters.
+// query     the out-of-sample half (umap's transform): the k nearest reference rows of every query row (the kNN kernel
+//           with a query pointer and no excluded row), the bipartite memberships (the smooth kernel without the zeroed
+//           own column), the l1-normalised weights with the weighted-mean start positions, and a layout in which only
+//           the new points move: a thread per query row runs every epoch in one launch and applies its moves edge by
+//           edge, the per-slot sample counters in LDS.
 // PCA       column sums and X^T X as the Gram matrix of [X, 1] (chunks of rows, chunks summed in order), and the
 //           projection X V^T - mu V^T.
 #include "common.h"
@@ -30,16 +35,19 @@ __device__ __forceinline__ bool pj_before(double d1, int i1, double d2, int i2) 
   return d1 < d2 || (d1 == d2 && i1 < i2);
 }
 
-// rows [q0, q0 + nq) of the kNN table; dynamic LDS holds the running lists: slot s of local query t at [s * 64 + t]
+// rows [q0, q0 + nq) of the kNN table of the query rows Q among the n reference rows X; dynamic LDS holds the running
+// lists: slot s of local query t at [s * 64 + t].  With exclude_self (Q == X) reference q is skipped for query q and
+// column 0 is the row itself at 0; without, all k columns come from the list.
 template <typename T>
-__global__ __launch_bounds__(256) void pj_knn_kernel(const T* __restrict__ X, int n, int d, int k, int q0, int nq,
+__global__ __launch_bounds__(256) void pj_knn_kernel(const T* __restrict__ Q, const T* __restrict__ X, int n, int d,
+                                                     int k, int q0, int nq, int exclude_self,
                                                      int64_t* __restrict__ out_idx, double* __restrict__ out_dist) {
   __shared__ double stage[2 * PJ_T * PJ_LD];        // xs | ys while staging, then the 64 x 64 distance tile
-  extern __shared__ double lists[];                 // (k - 1) x 64 distances, then (k - 1) x 64 int indices
+  extern __shared__ double lists[];                 // m x 64 distances, then m x 64 int indices
   double* xs = stage;
   double* ys = stage + PJ_T * PJ_LD;
   double* dt = stage;
-  const int m = k - 1;
+  const int m = k - exclude_self;
   double* ld = lists;
   int* li = reinterpret_cast<int*>(lists + (size_t)m * PJ_T);
   const int t = threadIdx.x, ty = t >> 4, tx = t & 15;
@@ -62,7 +70,7 @@ __global__ __launch_bounds__(256) void pj_knn_kernel(const T* __restrict__ X, in
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         const int r = sr + 8 * j;
-        xs[r * PJ_LD + sc] = (c < d && qb + r < qe) ? (double)X[(size_t)(qb + r) * d + c] : 0.0;
+        xs[r * PJ_LD + sc] = (c < d && qb + r < qe) ? (double)Q[(size_t)(qb + r) * d + c] : 0.0;
         ys[r * PJ_LD + sc] = (c < d && r0 + r < n) ? (double)X[(size_t)(r0 + r) * d + c] : 0.0;
       }
       __syncthreads();
@@ -97,7 +105,7 @@ __global__ __launch_bounds__(256) void pj_knn_kernel(const T* __restrict__ X, in
       for (int c = 0; c < cn; ++c) {
         const int r = r0 + c;
         const double dd = dt[t * PJ_DLD + c];
-        if (r == q || !pj_before(dd, r, wd, wi)) continue;
+        if ((exclude_self && r == q) || !pj_before(dd, r, wd, wi)) continue;
         int s = m - 1;
         while (s > 0 && pj_before(dd, r, ld[(s - 1) * PJ_T + t], li[(s - 1) * PJ_T + t])) {
           ld[s * PJ_T + t] = ld[(s - 1) * PJ_T + t];
@@ -114,11 +122,13 @@ __global__ __launch_bounds__(256) void pj_knn_kernel(const T* __restrict__ X, in
   __syncthreads();
   if (t < PJ_T && qb + t < qe) {
     const size_t o = (size_t)(qb + t - q0) * k;
-    out_idx[o] = qb + t;
-    out_dist[o] = 0.0;
+    if (exclude_self) {
+      out_idx[o] = qb + t;
+      out_dist[o] = 0.0;
+    }
     for (int s = 0; s < m; ++s) {
-      out_idx[o + 1 + s] = li[s * PJ_T + t];
-      out_dist[o + 1 + s] = ld[s * PJ_T + t];
+      out_idx[o + exclude_self + s] = li[s * PJ_T + t];
+      out_dist[o + exclude_self + s] = ld[s * PJ_T + t];
     }
   }
 }
@@ -143,9 +153,10 @@ __global__ __launch_bounds__(256) void pj_mean_kernel(const double* __restrict__
   if (t == 0) mean[0] = red[0] / ((double)n * (double)k);
 }
 
-// smooth_knn_dist (n_iter 64, bandwidth 1) and compute_membership_strengths of one row per thread
+// smooth_knn_dist (n_iter 64, bandwidth 1) and compute_membership_strengths of one row per thread; bipartite (the
+// columns index another set than the rows) keeps the weight of column idx == row
 __global__ __launch_bounds__(256) void pj_smooth_kernel(const double* __restrict__ dist, const int64_t* __restrict__ idx,
-                                                        int n, int k, double local_connectivity,
+                                                        int n, int k, double local_connectivity, int bipartite,
                                                         const double* __restrict__ mean_all,
                                                         double* __restrict__ sigma, double* __restrict__ rho,
                                                         double* __restrict__ w) {
@@ -210,7 +221,7 @@ __global__ __launch_bounds__(256) void pj_smooth_kernel(const double* __restrict
   rho[i] = r;
   for (int j = 0; j < k; ++j) {
     double v;
-    if (idx[(size_t)i * k + j] == i) v = 0.0;
+    if (!bipartite && idx[(size_t)i * k + j] == i) v = 0.0;
     else if (row[j] - r <= 0.0 || mid == 0.0) v = 1.0;
     else v = exp(-((row[j] - r) / mid));
     w[(size_t)i * k + j] = v;
@@ -270,6 +281,98 @@ __global__ __launch_bounds__(64) void pj_layout_kernel(const double* __restrict_
   }
   y_out[2 * (size_t)v] = y0 + m0;
   y_out[2 * (size_t)v + 1] = y1 + m1;
+}
+
+// transform: l1-normalised weights (summed left to right; a row of sum 0 stays 0) and the start position of every new
+// point, the weighted mean of the training positions of its neighbours in slot order (umap's init_transform)
+__global__ __launch_bounds__(256) void pj_transform_init_kernel(const double* __restrict__ w,
+                                                                const int64_t* __restrict__ idx,
+                                                                const double* __restrict__ emb, int m, int k,
+                                                                double* __restrict__ wn, double* __restrict__ y0) {
+#pragma clang fp contract(off)
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= m) return;
+  double sum = 0.0;
+  for (int s = 0; s < k; ++s) sum += w[(size_t)i * k + s];
+  double a0 = 0.0, a1 = 0.0;
+  for (int s = 0; s < k; ++s) {
+    const double v = sum > 0.0 ? w[(size_t)i * k + s] / sum : 0.0;
+    const int64_t j = idx[(size_t)i * k + s];
+    wn[(size_t)i * k + s] = v;
+    a0 += v * emb[2 * (size_t)j];
+    a1 += v * emb[2 * (size_t)j + 1];
+  }
+  y0[2 * (size_t)i] = a0;
+  y0[2 * (size_t)i + 1] = a1;
+}
+
+// transform layout: epochs [0, epochs) of n_epochs for every new point in one launch.  The training positions emb are
+// read-only and the rows do not depend on each other, so a thread owns a row and applies its moves edge by edge as
+// umap-learn does: slot s, when due, pulls y towards emb[idx[i][s]] (once: there is no tail move to stand in for) and
+// then pushes it from that slot's negative samples, each from the position the moves before it left.  eps / epn are
+// slot-major [k][m] (eps <= 0: a pruned slot); the counters of slot s of local row t live in LDS at [s * 64 + t] and
+// [(k + s) * 64 + t].
+__global__ __launch_bounds__(64) void pj_transform_layout_kernel(double* __restrict__ y, const double* __restrict__ emb,
+                                                                  const int64_t* __restrict__ idx,
+                                                                  const double* __restrict__ eps,
+                                                                  const double* __restrict__ epn, int m, int k,
+                                                                  int n_train, int epochs, int n_epochs, double alpha0,
+                                                                  double a, double b, double gamma, uint64_t salt,
+                                                                  int* __restrict__ flag) {
+  // unfused for the reason given in pj_layout_kernel
+#pragma clang fp contract(off)
+  extern __shared__ double counters[];
+  const int t = threadIdx.x;
+  const int i = blockIdx.x * 64 + t;
+  if (i >= m) return;
+  double* next_s = counters;
+  double* next_n = counters + (size_t)k * 64;
+  for (int s = 0; s < k; ++s) {
+    const double e = eps[(size_t)s * m + i];
+    next_s[s * 64 + t] = e > 0.0 ? e : INFINITY;
+    next_n[s * 64 + t] = epn[(size_t)s * m + i];
+  }
+  double y0 = y[2 * (size_t)i], y1 = y[2 * (size_t)i + 1];
+  for (int epoch = 0; epoch < epochs; ++epoch) {
+    const double ep = (double)epoch;
+    const double alpha = epoch == 0 ? alpha0 : alpha0 * (1.0 - (double)(epoch - 1) / (double)n_epochs);
+    for (int s = 0; s < k; ++s) {
+      if (!(next_s[s * 64 + t] <= ep)) continue;
+      const int64_t j = idx[(size_t)i * k + s];
+      const double es = eps[(size_t)s * m + i], en = epn[(size_t)s * m + i];
+      double d0 = y0 - emb[2 * (size_t)j], d1 = y1 - emb[2 * (size_t)j + 1];
+      double d2 = d0 * d0 + d1 * d1;
+      double g = 0.0;
+      if (d2 > 0.0) g = -2.0 * a * b * pow(d2, b - 1.0) / (a * pow(d2, b) + 1.0);
+      y0 += alpha * pj_clip(g * d0);
+      y1 += alpha * pj_clip(g * d1);
+      next_s[s * 64 + t] += es;
+      int nneg = (int)((ep - next_n[s * 64 + t]) / en);
+      if (nneg > PJ_MAX_NEG) {
+        flag[0] = 1;
+        nneg = PJ_MAX_NEG;
+      }
+      for (int p = 0; p < nneg; ++p) {
+        const uint64_t ctr = (((uint64_t)epoch * (uint64_t)m + (uint64_t)i) * (uint64_t)k + (uint64_t)s) * PJ_MAX_NEG +
+                             (uint64_t)p;
+        int64_t kk = (int64_t)floor(ava_u01_hash(ctr, salt) * (double)n_train);
+        if (kk > n_train - 1) kk = n_train - 1;
+        d0 = y0 - emb[2 * (size_t)kk];
+        d1 = y1 - emb[2 * (size_t)kk + 1];
+        d2 = d0 * d0 + d1 * d1;
+        if (d2 > 0.0) {
+          const double c = 2.0 * gamma * b / ((0.001 + d2) * (a * pow(d2, b) + 1.0));
+          if (c > 0.0) {
+            y0 += alpha * pj_clip(c * d0);
+            y1 += alpha * pj_clip(c * d1);
+          }
+        }
+      }
+      next_n[s * 64 + t] += nneg * en;
+    }
+  }
+  y[2 * (size_t)i] = y0;
+  y[2 * (size_t)i + 1] = y1;
 }
 
 // partial Gram matrices of [X, 1] (D = d + 1 columns): part[chunk][i][j] = sum over the chunk's rows, in row order
@@ -348,11 +451,11 @@ static bool pj_knn_ok(int n, int d, int k, int q0, int nq) {
 }
 
 template <typename T>
-static int pj_knn_launch(const void* x, int n, int d, int k, int q0, int nq, int64_t* idx, double* dist,
-                         hipStream_t st) {
-  const size_t lds = (size_t)(k - 1) * PJ_T * (sizeof(double) + sizeof(int));
-  hipLaunchKernelGGL(pj_knn_kernel<T>, dim3(ceil_div(nq, PJ_T)), dim3(256), lds, st, reinterpret_cast<const T*>(x), n,
-                     d, k, q0, nq, idx, dist);
+static int pj_knn_launch(const void* q, const void* x, int n, int d, int k, int q0, int nq, int exclude_self,
+                         int64_t* idx, double* dist, hipStream_t st) {
+  const size_t lds = (size_t)(k - exclude_self) * PJ_T * (sizeof(double) + sizeof(int));
+  hipLaunchKernelGGL(pj_knn_kernel<T>, dim3(ceil_div(nq, PJ_T)), dim3(256), lds, st, reinterpret_cast<const T*>(q),
+                     reinterpret_cast<const T*>(x), n, d, k, q0, nq, exclude_self, idx, dist);
   AVA_CHECK_LAUNCH();
   return AVA_OK;
 }
@@ -362,12 +465,22 @@ extern "C" int ava_pj_knn(const void* x, int dtype, int n, int d, int k, int q0,
   if (x == nullptr || out_idx == nullptr || out_dist == nullptr || (dtype != 0 && dtype != 1) ||
       !pj_knn_ok(n, d, k, q0, nq))
     return AVA_EINVAL;
-  if (dtype == 0) return pj_knn_launch<float>(x, n, d, k, q0, nq, out_idx, out_dist, to_stream(s));
-  return pj_knn_launch<double>(x, n, d, k, q0, nq, out_idx, out_dist, to_stream(s));
+  if (dtype == 0) return pj_knn_launch<float>(x, x, n, d, k, q0, nq, 1, out_idx, out_dist, to_stream(s));
+  return pj_knn_launch<double>(x, x, n, d, k, q0, nq, 1, out_idx, out_dist, to_stream(s));
 }
 
-extern "C" int ava_pj_smooth(const double* dist, const int64_t* idx, int n, int k, double local_connectivity,
-                             double* mean_all, double* sigma, double* rho, double* w, ava_stream_t s) {
+extern "C" int ava_pj_knn_query(const void* q, const void* x, int dtype, int m, int n, int d, int k, int q0, int nq,
+                                int64_t* out_idx, double* out_dist, ava_stream_t s) {
+  if (q == nullptr || x == nullptr || out_idx == nullptr || out_dist == nullptr || (dtype != 0 && dtype != 1) ||
+      n < 1 || m < 1 || d < 1 || d > 65536 || k < 1 || k > PJ_MAX_K || k > n || q0 < 0 || nq < 1 ||
+      (int64_t)q0 + nq > m)
+    return AVA_EINVAL;
+  if (dtype == 0) return pj_knn_launch<float>(q, x, n, d, k, q0, nq, 0, out_idx, out_dist, to_stream(s));
+  return pj_knn_launch<double>(q, x, n, d, k, q0, nq, 0, out_idx, out_dist, to_stream(s));
+}
+
+static int pj_smooth_launch(const double* dist, const int64_t* idx, int n, int k, double local_connectivity,
+                            int bipartite, double* mean_all, double* sigma, double* rho, double* w, ava_stream_t s) {
   if (dist == nullptr || idx == nullptr || mean_all == nullptr || sigma == nullptr || rho == nullptr ||
       w == nullptr || n < 1 || k < 1 || k > PJ_MAX_K || !(local_connectivity >= 0.0))
     return AVA_EINVAL;
@@ -375,9 +488,20 @@ extern "C" int ava_pj_smooth(const double* dist, const int64_t* idx, int n, int 
   hipLaunchKernelGGL(pj_mean_kernel, dim3(1), dim3(256), 0, st, dist, n, k, mean_all);
   AVA_CHECK_LAUNCH();
   hipLaunchKernelGGL(pj_smooth_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, st, dist, idx, n, k, local_connectivity,
-                     mean_all, sigma, rho, w);
+                     bipartite, mean_all, sigma, rho, w);
   AVA_CHECK_LAUNCH();
   return AVA_OK;
+}
+
+extern "C" int ava_pj_smooth(const double* dist, const int64_t* idx, int n, int k, double local_connectivity,
+                             double* mean_all, double* sigma, double* rho, double* w, ava_stream_t s) {
+  return pj_smooth_launch(dist, idx, n, k, local_connectivity, 0, mean_all, sigma, rho, w, s);
+}
+
+extern "C" int ava_pj_smooth_bipartite(const double* dist, const int64_t* idx, int n, int k,
+                                       double local_connectivity, double* mean_all, double* sigma, double* rho,
+                                       double* w, ava_stream_t s) {
+  return pj_smooth_launch(dist, idx, n, k, local_connectivity, 1, mean_all, sigma, rho, w, s);
 }
 
 extern "C" int ava_pj_layout(double* y, double* y_tmp, const int64_t* indptr, const int* col, const double* eps,
@@ -403,6 +527,34 @@ extern "C" int ava_pj_layout(double* y, double* y_tmp, const int64_t* indptr, co
   }
   if (cur != y && hipMemcpyAsync(y, cur, 2 * (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, st) != hipSuccess)
     return AVA_ELAUNCH;
+  return AVA_OK;
+}
+
+extern "C" int ava_pj_transform_init(const double* w, const int64_t* idx, const double* emb, int m, int k,
+                                     double* wn, double* y0, ava_stream_t s) {
+  if (w == nullptr || idx == nullptr || emb == nullptr || wn == nullptr || y0 == nullptr || m < 1 || k < 1 ||
+      k > PJ_MAX_K)
+    return AVA_EINVAL;
+  hipLaunchKernelGGL(pj_transform_init_kernel, dim3(ceil_div(m, 256)), dim3(256), 0, to_stream(s), w, idx, emb, m, k,
+                     wn, y0);
+  AVA_CHECK_LAUNCH();
+  return AVA_OK;
+}
+
+extern "C" int ava_pj_transform_layout(double* y, const double* emb, const int64_t* idx, const double* eps,
+                                       const double* epn, int m, int k, int n_train, int epochs, int n_epochs,
+                                       double learning_rate, double a, double b, double gamma, uint64_t salt,
+                                       int* flag, ava_stream_t s) {
+  if (y == nullptr || emb == nullptr || idx == nullptr || eps == nullptr || epn == nullptr || flag == nullptr ||
+      m < 1 || k < 1 || k > PJ_MAX_K || n_train < 1 || epochs < 0 || n_epochs < 1 || epochs > n_epochs)
+    return AVA_EINVAL;
+  if (epochs == 0) return AVA_OK;
+  // one-wave workgroups, as the fit layout: a row is a chain of dependent gathers, so the rows go to as many CUs as
+  // there are; the two counters of every slot take k KiB of LDS per workgroup
+  const size_t lds = (size_t)k * 64 * 2 * sizeof(double);
+  hipLaunchKernelGGL(pj_transform_layout_kernel, dim3(ceil_div(m, 64)), dim3(64), lds, to_stream(s), y, emb, idx, eps,
+                     epn, m, k, n_train, epochs, n_epochs, learning_rate / 4.0, a, b, gamma, salt, flag);
+  AVA_CHECK_LAUNCH();
   return AVA_OK;
 }
 

@@ -6,6 +6,10 @@
                       ``csrc/projection.hip``; the fuzzy union, the schedule, ``(a, b)`` and the init on the host
   ``pca_projection``  ``PCA(n_components, copy=False, random_state=42).fit_transform(X)`` through sklearn's
                       ``covariance_eigh`` path: device column sums and Gram matrix, host ``eigh``, device projection
+  ``TransformableUMAP``  ``UMAP`` that also keeps its float32 training rows on the device (N x d x 4 bytes of HBM: about
+                      0.65 GB for the 10 000 spectrograms of ~16 000 bins that ``refine_segments`` fits) and embeds
+                      new rows with ``transform``: query kNN, bipartite memberships, weighted-mean start positions and a
+                      layout that moves only the new points, all in ``csrc/projection.hip``
   ``install``         points ``DataContainer._make_latent_mean_umap_projection`` / ``_make_latent_mean_pca_projection``
                       here
 
@@ -20,7 +24,12 @@ Deviations from umap-learn, on purpose (INTEGRATION.md lists them too):
   moves nothing;
 * a disconnected graph, or an ``eigsh`` that fails, falls back to the random init with a warning (umap-learn lays
   the components out with a meta-embedding);
-* ``transform`` (new points) is not supported.
+* ``UMAP.transform`` (new points) is not supported: ``UMAP.fit`` keeps no training rows.  ``TransformableUMAP`` does,
+  and its ``transform`` follows umap-learn 0.5's with the same deviations: the query kNN is exact and ordered by
+  (distance, index) (umap-learn searches its NN-descent index), everything is fp64 (umap-learn initialises and lays
+  out in float32), the negative samples come from the counter-based hash salted by
+  ``RandomState(transform_seed).randint(2**31 - 1)``, and a negative sample at distance 0 moves nothing.  The moves
+  are applied edge by edge, as umap-learn applies them, in slot order.
 
 There is no CPU fallback: the kernels need the MI355X.
 """
@@ -32,7 +41,8 @@ import torch
 
 from . import _lib
 
-__all__ = ["UMAP", "pca_projection", "install", "knn", "smooth_knn", "fuzzy_union", "find_ab_params",
+__all__ = ["UMAP", "TransformableUMAP", "pca_projection", "install", "knn", "knn_query", "smooth_knn",
+           "smooth_knn_bipartite", "transform_init", "transform_layout", "fuzzy_union", "find_ab_params",
            "epochs_per_sample", "init_embedding", "Layout", "MAX_K", "MAX_DIM", "MAX_PCA_DIM"]
 
 MAX_K = 64                 # n_neighbors the kNN kernel keeps per row (the row itself included)
@@ -103,27 +113,82 @@ def knn(X, k, chunk_rows=None):
     return idx.cpu().numpy(), dist.cpu().numpy()
 
 
-def _smooth_device(idx, dist, local_connectivity):
+def _knn_query_device(qd, xd, k, chunk_rows=None):
+    m, n, d = int(qd.shape[0]), int(xd.shape[0]), int(xd.shape[1])
+    if int(qd.shape[1]) != d:
+        raise ValueError("queries have %d columns, references %d" % (int(qd.shape[1]), d))
+    if qd.dtype != xd.dtype:
+        raise ValueError("queries and references must have one dtype")
+    if not 1 <= k <= min(MAX_K, n):
+        raise ValueError("k must be in [1, min(%d, n)], got %d" % (MAX_K, k))
+    if d > MAX_DIM or n >= 2 ** 31 or m >= 2 ** 31:
+        raise ValueError("unsupported shapes [%d, %d], [%d, %d]" % (m, d, n, d))
+    if chunk_rows is None:
+        chunk_rows = m
+    elif int(chunk_rows) != chunk_rows or chunk_rows < 1:
+        raise ValueError("chunk_rows must be a positive integer")
+    chunk_rows = min(int(chunk_rows), m)
+    lib = _lib.load()
+    idx = torch.empty((m, k), dtype=torch.int64, device=xd.device)
+    dist = torch.empty((m, k), dtype=torch.float64, device=xd.device)
+    st = _lib.stream()
+    for q0 in range(0, m, chunk_rows):
+        nq = min(chunk_rows, m - q0)
+        _lib.check(lib.ava_pj_knn_query(qd.data_ptr(), xd.data_ptr(), _code(xd), m, n, d, k, q0, nq,
+                                        idx[q0:].data_ptr(), dist[q0:].data_ptr(), st), "ava_pj_knn_query")
+    return idx, dist
+
+
+def knn_query(Q, X, k, chunk_rows=None):
+    """Exact euclidean kNN of every row of ``Q`` among the rows of ``X`` (fp64 from the given values, the arithmetic of
+    ``knn``): ``(idx int64 [m, k], dist float64 [m, k])`` ordered by (distance, index).  No row is excluded: a query
+    that is a copy of reference row ``r`` gets ``(r, 0.0)`` first.  ``Q`` is read in the dtype of ``X``.
+    ``chunk_rows`` query rows go to one launch; the result does not depend on it."""
+    xd = _as_rows(X, _native_dtype(X))
+    qd = _as_rows(Q, xd.dtype)
+    idx, dist = _knn_query_device(qd, xd, int(k), chunk_rows)
+    return idx.cpu().numpy(), dist.cpu().numpy()
+
+
+def _smooth_device(idx, dist, local_connectivity, bipartite=False):
     n, k = int(idx.shape[0]), int(idx.shape[1])
     lib = _lib.load()
     mean = torch.empty(1, dtype=torch.float64, device=idx.device)
     sigma = torch.empty(n, dtype=torch.float64, device=idx.device)
     rho = torch.empty_like(sigma)
     w = torch.empty((n, k), dtype=torch.float64, device=idx.device)
-    _lib.check(lib.ava_pj_smooth(dist.data_ptr(), idx.data_ptr(), n, k, float(local_connectivity), mean.data_ptr(),
-                                 sigma.data_ptr(), rho.data_ptr(), w.data_ptr(), _lib.stream()), "ava_pj_smooth")
+    fn = lib.ava_pj_smooth_bipartite if bipartite else lib.ava_pj_smooth
+    _lib.check(fn(dist.data_ptr(), idx.data_ptr(), n, k, float(local_connectivity), mean.data_ptr(),
+                  sigma.data_ptr(), rho.data_ptr(), w.data_ptr(), _lib.stream()),
+               "ava_pj_smooth_bipartite" if bipartite else "ava_pj_smooth")
     return sigma, rho, w
+
+
+def _upload_table(idx, dist):
+    dev = _device()
+    idx = torch.as_tensor(np.ascontiguousarray(idx, dtype=np.int64)).to(dev)
+    dist = torch.as_tensor(np.ascontiguousarray(dist, dtype=np.float64)).to(dev)
+    if idx.dim() != 2 or idx.shape != dist.shape or idx.shape[0] < 1 or not 1 <= idx.shape[1] <= MAX_K:
+        raise ValueError("idx and dist must both be [n, k] with k <= %d" % MAX_K)
+    return idx, dist
 
 
 def smooth_knn(idx, dist, local_connectivity=1.0):
     """umap's ``smooth_knn_dist`` and ``compute_membership_strengths`` of a kNN table (as ``knn`` returns it), on the
     device: ``(sigma [n], rho [n], w [n, k])`` float64 numpy arrays."""
-    dev = _device()
-    idx = torch.as_tensor(np.ascontiguousarray(idx, dtype=np.int64)).to(dev)
-    dist = torch.as_tensor(np.ascontiguousarray(dist, dtype=np.float64)).to(dev)
-    if idx.dim() != 2 or idx.shape != dist.shape or not 1 <= idx.shape[1] <= MAX_K:
-        raise ValueError("idx and dist must both be [n, k] with k <= %d" % MAX_K)
+    idx, dist = _upload_table(idx, dist)
     sigma, rho, w = _smooth_device(idx, dist, local_connectivity)
+    return sigma.cpu().numpy(), rho.cpu().numpy(), w.cpu().numpy()
+
+
+def smooth_knn_bipartite(idx, dist, local_connectivity=0.0):
+    """``smooth_knn`` for a query table (as ``knn_query`` returns it), umap's ``compute_membership_strengths(...,
+    bipartite=True)``: no weight is zeroed where ``idx`` equals the row number.  ``transform`` passes
+    ``max(0, local_connectivity - 1)``."""
+    if not local_connectivity >= 0.0:
+        raise ValueError("local_connectivity must be >= 0")
+    idx, dist = _upload_table(idx, dist)
+    sigma, rho, w = _smooth_device(idx, dist, local_connectivity, bipartite=True)
     return sigma.cpu().numpy(), rho.cpu().numpy(), w.cpu().numpy()
 
 
@@ -251,6 +316,82 @@ class Layout:
         return self.y.cpu().numpy()
 
 
+def _transform_init_device(w, idx, emb):
+    m, k = int(idx.shape[0]), int(idx.shape[1])
+    lib = _lib.load()
+    wn = torch.empty((m, k), dtype=torch.float64, device=idx.device)
+    y0 = torch.empty((m, 2), dtype=torch.float64, device=idx.device)
+    _lib.check(lib.ava_pj_transform_init(w.data_ptr(), idx.data_ptr(), emb.data_ptr(), m, k, wn.data_ptr(),
+                                         y0.data_ptr(), _lib.stream()), "ava_pj_transform_init")
+    return wn, y0
+
+
+def _transform_layout_device(y, emb, idx, eps, epn, n_epochs, a, b, gamma, learning_rate, salt, epochs=None):
+    """moves ``y`` [m, 2] (device, in place); ``eps`` / ``epn`` [k, m] slot-major device tensors"""
+    m, k = int(idx.shape[0]), int(idx.shape[1])
+    epochs = int(n_epochs) if epochs is None else int(epochs)
+    if not 0 <= epochs <= n_epochs:
+        raise ValueError("epochs must be in [0, n_epochs]")
+    flag = torch.zeros(1, dtype=torch.int32, device=y.device)
+    lib = _lib.load()
+    _lib.check(lib.ava_pj_transform_layout(y.data_ptr(), emb.data_ptr(), idx.data_ptr(), eps.data_ptr(),
+                                           epn.data_ptr(), m, k, int(emb.shape[0]), epochs, int(n_epochs),
+                                           float(learning_rate), float(a), float(b), float(gamma), int(salt),
+                                           flag.data_ptr(), _lib.stream()), "ava_pj_transform_layout")
+    return flag
+
+
+def _upload_neighbours(idx, w, emb):
+    dev = _device()
+    idx = torch.as_tensor(np.ascontiguousarray(idx, dtype=np.int64)).to(dev)
+    w = torch.as_tensor(np.ascontiguousarray(w, dtype=np.float64)).to(dev)
+    emb = torch.as_tensor(np.ascontiguousarray(emb, dtype=np.float64)).to(dev)
+    if idx.dim() != 2 or idx.shape != w.shape or idx.shape[0] < 1 or not 1 <= idx.shape[1] <= MAX_K:
+        raise ValueError("idx and the weights must both be [m, k] with k <= %d" % MAX_K)
+    if emb.dim() != 2 or emb.shape[1] != 2 or emb.shape[0] < 1:
+        raise ValueError("the training embedding must be [n, 2]")
+    if int(idx.min()) < 0 or int(idx.max()) >= emb.shape[0]:
+        raise ValueError("idx must lie in [0, %d)" % emb.shape[0])
+    return idx, w, emb
+
+
+def transform_init(idx, w, embedding):
+    """sklearn's ``normalize(w, norm='l1')`` (rows summed left to right, a row of sum 0 stays 0) and umap's
+    ``init_transform``: ``(wn [m, k], Y0 [m, 2])`` float64, ``Y0[i] = sum_s wn[i, s] embedding[idx[i, s]]`` in slot
+    order, on the device."""
+    idx, w, emb = _upload_neighbours(idx, w, embedding)
+    wn, y0 = _transform_init_device(w, idx, emb)
+    return wn.cpu().numpy(), y0.cpu().numpy()
+
+
+def transform_schedule(w, n_epochs, negative_sample_rate=5):
+    """``(eps, epn)`` [m, k]: umap's ``make_epochs_per_sample`` of the slots that survive ``w < w.max() / n_epochs``
+    (the maximum of the whole batch), -1 for the pruned ones, and ``eps / negative_sample_rate``"""
+    w = np.asarray(w, dtype=np.float64)
+    eps = np.full(w.shape, -1.0)
+    keep = ~(w < w.max() / float(n_epochs)) & (w != 0.0)
+    if keep.any():
+        eps[keep] = epochs_per_sample(w[keep], n_epochs)
+    return eps, eps / negative_sample_rate
+
+
+def transform_layout(Y0, embedding, idx, eps, epn, n_epochs, a, b, salt, epochs=None, gamma=1.0, learning_rate=1.0):
+    """``epochs`` (default all) of ``n_epochs`` of the transform layout from ``Y0`` [m, 2] against the fixed
+    ``embedding`` [n, 2], on the device, one launch: ``(Y float64 [m, 2], flagged)``.  ``eps`` / ``epn`` [m, k] as
+    ``transform_schedule`` returns them; ``flagged`` tells whether a slot was due more than 16 negative samples in one
+    epoch (it drew 16)."""
+    idx, eps, emb = _upload_neighbours(idx, eps, embedding)
+    epn = torch.as_tensor(np.ascontiguousarray(epn, dtype=np.float64)).to(idx.device)
+    y = torch.as_tensor(np.ascontiguousarray(Y0, dtype=np.float64)).to(idx.device)
+    if epn.shape != eps.shape or y.shape != (idx.shape[0], 2):
+        raise ValueError("epn must be [m, k] and Y0 [m, 2]")
+    if int(n_epochs) < 1:
+        raise ValueError("n_epochs must be positive")
+    flag = _transform_layout_device(y, emb, idx, eps.t().contiguous(), epn.t().contiguous(), int(n_epochs), a, b, gamma,
+                                    learning_rate, salt, epochs)
+    return y.cpu().numpy(), bool(int(flag.item()))
+
+
 class UMAP:
     """``umap.UMAP`` for ``n_components=2`` and ``metric='euclidean'`` with the hot path on the device (see the
     module docstring for the deviations).  ``fit_transform(X)`` returns float32 ``[N, 2]``."""
@@ -303,11 +444,13 @@ class UMAP:
             self.graph_ = scipy.sparse.csr_matrix((1, 1), dtype=np.float64)
             self.sigmas_, self.rhos_ = np.zeros(1), np.zeros(1)
             self.a_, self.b_ = find_ab_params(self.spread, self.min_dist)
+            self._n_neighbors = 1
             return self
         k = int(self.n_neighbors)
         if n <= k:
             warnings.warn("n_neighbors is larger than the dataset size; truncating to X.shape[0] - 1")
             k = n - 1
+        self._n_neighbors = k
         idx, dist = _knn_device(x32, k)
         sigma, rho, w = _smooth_device(idx, dist, self.local_connectivity)
         self.graph_ = fuzzy_union(idx.cpu().numpy(), w.cpu().numpy(), n, self.set_op_mix_ratio)
@@ -332,6 +475,86 @@ class UMAP:
 
     def transform(self, X):
         raise NotImplementedError("UMAP.transform (embedding new points) is not supported")
+
+
+class TransformableUMAP(UMAP):
+    """``UMAP`` that can embed new rows: ``fit`` additionally keeps the float32 training rows on the device (N x d x 4
+    bytes of HBM for as long as the object lives; 10 000 rows of 16 000 bins are 0.64 GB), beside ``embedding_``,
+    ``a_`` and ``b_``; ``transform(X)`` follows umap-learn 0.5's ``transform`` (see the module docstring for the
+    deviations) and returns float32 ``[m, 2]``.  ``transform_seed`` is umap-learn's argument of that name.
+
+    Pickling drops the device tensor: the pickle holds a host copy of the training rows, uploaded again by the first
+    ``transform`` after loading."""
+
+    def __init__(self, n_components=2, n_neighbors=20, min_dist=0.1, metric='euclidean', random_state=42,
+                 n_epochs=None, init='spectral', spread=1.0, learning_rate=1.0, repulsion_strength=1.0,
+                 negative_sample_rate=5, set_op_mix_ratio=1.0, local_connectivity=1.0, transform_seed=42):
+        super().__init__(n_components, n_neighbors, min_dist, metric, random_state, n_epochs, init, spread,
+                         learning_rate, repulsion_strength, negative_sample_rate, set_op_mix_ratio, local_connectivity)
+        self.transform_seed = transform_seed
+        self._train_rows = None          # float32 [N, d] on the device
+        self._train_host = None          # the same as numpy, only after unpickling and until the next transform
+
+    def fit(self, X):
+        self._validate()
+        x32 = _as_rows(X, torch.float32)
+        super().fit(x32)
+        # _as_rows hands a tensor that is already float32, contiguous and on the device back as it is: keep a copy,
+        # so that the caller may overwrite its own
+        self._train_rows = x32.clone() if torch.is_tensor(X) and x32.data_ptr() == X.data_ptr() else x32
+        self._train_host = None
+        return self
+
+    def __getstate__(self):
+        state = dict(self.__dict__)
+        rows = state.pop('_train_rows', None)
+        if rows is not None:
+            state['_train_host'] = rows.cpu().numpy()
+        state['_train_rows'] = None
+        return state
+
+    def __setstate__(self, state):
+        self.__dict__.update(state)
+
+    def _rows(self):
+        if self._train_rows is None:
+            if self._train_host is None:
+                raise ValueError("transform needs a fitted TransformableUMAP: call fit first")
+            self._train_rows = _as_rows(self._train_host, torch.float32)
+            self._train_host = None
+        return self._train_rows
+
+    def transform(self, X):
+        if self._train_rows is None and self._train_host is None:
+            raise ValueError("transform needs a fitted TransformableUMAP: call fit first")
+        shape = tuple(X.shape) if torch.is_tensor(X) else np.shape(X)
+        if len(shape) == 2 and shape[0] == 0:
+            raise ValueError("transform needs at least one row")
+        d = int(self._train_host.shape[1] if self._train_rows is None else self._train_rows.shape[1])
+        if len(shape) == 2 and shape[1] != d:
+            raise ValueError("X has %d columns, the training rows have %d" % (shape[1], d))
+        q32 = _as_rows(X, torch.float32)
+        train = self._rows()
+        m, n = int(q32.shape[0]), int(train.shape[0])
+        idx, dist = _knn_query_device(q32, train, int(self._n_neighbors))
+        _, _, w = _smooth_device(idx, dist, max(0.0, self.local_connectivity - 1.0), bipartite=True)
+        emb = torch.from_numpy(np.ascontiguousarray(self.embedding_, dtype=np.float64)).to(q32.device)
+        _, y = _transform_init_device(w, idx, emb)        # from the weights of all slots: pruning comes after
+        if self.n_epochs is None:
+            n_epochs = 100 if m <= 10000 else 30
+        else:
+            n_epochs = int(self.n_epochs // 3)
+        if n_epochs > 0:
+            eps, epn = transform_schedule(w.cpu().numpy(), n_epochs, self.negative_sample_rate)
+            salt = np.random.RandomState(self.transform_seed).randint(2 ** 31 - 1)
+
+            def up(a):
+                return torch.from_numpy(np.ascontiguousarray(a.T)).to(q32.device)
+            flag = _transform_layout_device(y, emb, idx, up(eps), up(epn), n_epochs, self.a_, self.b_,
+                                            self.repulsion_strength, self.learning_rate, salt)
+            if int(flag.item()):
+                raise _lib.AvaHipError("a slot needed more than %d negative samples in one epoch" % MAX_NEG)
+        return y.cpu().numpy().astype(np.float32)
 
 
 def pca_projection(X, n_components=2):

@@ -499,6 +499,21 @@ int ava_nn_merge(int64_t* best_idx, double* best_dist, const int64_t* idx, const
  *   splitmix64 hash of ((e nnz + edge) 16 + p, salt).  flag [1] int is set to 1 if an edge needed more than 16
  *   negative samples in one epoch (they are clamped to 16).  All epochs are enqueued without a host synchronisation.
  *
+ * The out-of-sample half (umap's transform; nothing below writes the training data):
+ * ava_pj_knn_query: rows [q0, q0 + nq) of the table of the k nearest of the n reference rows x [n][d] of each of the m
+ *   query rows q [m][d] (one dtype for both), ordered by (distance, index), no row excluded; the distance arithmetic
+ *   is that of ava_pj_knn.  1 <= k <= min(64, n), 1 <= d <= 65536.
+ * ava_pj_smooth_bipartite: ava_pj_smooth for a table whose columns index another set than its rows: no weight is
+ *   zeroed for idx == row.
+ * ava_pj_transform_init: wn [m][k] = w / (row sum, left to right; a row of sum 0 stays 0) and y0 [m][2] =
+ *   sum_s wn[i][s] emb[idx[i][s]] in slot order; emb [n_train][2] float64.  idx must lie in [0, n_train).
+ * ava_pj_transform_layout: epochs [0, epochs) of n_epochs of the layout of the new points y [m][2] (in / out) against
+ *   the fixed emb, in one launch, a thread per row moving edge by edge: a due slot pulls y towards its neighbour once,
+ *   then pushes it from min(16, due) negative samples emb[min(floor(u n_train), n_train - 1)], u the splitmix64 hash
+ *   of (((e m + i) k + s) 16 + p, salt), each from the already moved y (a sample at distance 0 moves nothing).
+ *   eps / epn [k][m] slot-major (eps <= 0: the slot is pruned); the step of epoch e is learning_rate / 4 for e = 0
+ *   and (learning_rate / 4) (1 - (e - 1) / n_epochs) after; flag as in ava_pj_layout.
+ *
  * ava_pj_gram_workspace_bytes / ava_pj_gram: gram [(d+1)][(d+1)] = [x, 1]^T [x, 1] (so gram[i][d] is the sum of column
  *   i and gram[d][d] = n), summed over fixed row chunks in order.  1 <= d <= 512.
  *
@@ -513,6 +528,15 @@ int ava_pj_smooth(const double* dist, const int64_t* idx, int n, int k, double l
 int ava_pj_layout(double* y, double* y_tmp, const int64_t* indptr, const int* col, const double* eps,
                   const double* epn, double* next_s, double* next_n, int n, int64_t nnz, int e0, int e1, int n_epochs,
                   double learning_rate, double a, double b, double gamma, uint64_t salt, int* flag, ava_stream_t s);
+int ava_pj_knn_query(const void* q, const void* x, int dtype, int m, int n, int d, int k, int q0, int nq,
+                     int64_t* out_idx, double* out_dist, ava_stream_t s);
+int ava_pj_smooth_bipartite(const double* dist, const int64_t* idx, int n, int k, double local_connectivity,
+                            double* mean_all, double* sigma, double* rho, double* w, ava_stream_t s);
+int ava_pj_transform_init(const double* w, const int64_t* idx, const double* emb, int m, int k, double* wn, double* y0,
+                          ava_stream_t s);
+int ava_pj_transform_layout(double* y, const double* emb, const int64_t* idx, const double* eps, const double* epn,
+                            int m, int k, int n_train, int epochs, int n_epochs, double learning_rate, double a,
+                            double b, double gamma, uint64_t salt, int* flag, ava_stream_t s);
 size_t ava_pj_gram_workspace_bytes(int n, int d);
 int ava_pj_gram(const void* x, int dtype, int n, int d, double* gram, void* ws, size_t ws_bytes, ava_stream_t s);
 int ava_pj_project(const void* x, int dtype, int n, int d, const double* V, const double* muv, int nc, double* out,
