@@ -122,3 +122,106 @@ extern "C" int ava_host_gather_rows(void* dst, const void* src, const int64_t* i
   for (auto& th : pool) th.join();
   return AVA_OK;
 }
+
+// ---- device side: gather n rows of a resident dataset into one fp32 batch ---------------
+// dst[j, :] = float(src[idx[j], :]): the device twin of ava_host_gather_rows + ava_cast_to_f32 for datasets that live
+// in HBM (syllable_dataset.DeviceSyllableDataset).  Replaces SyllableDataset.__getitem__ + numpy_to_tensor + the
+// DataLoader's collation (ava/models/vae_dataset.py:125-145, :89-96) with one launch per batch; same rounding as
+// cast_to_f32_kernel.  A workgroup of 256 lanes holds 256 >> tpr_log2 rows of 1 << tpr_log2 lanes each (short rows
+// share a workgroup, a long row spreads over gridDim.y workgroups), so no lane divides.  WIDE: every lane moves
+// GatherVec<DT>::V elements per step with 16-byte loads and 16-byte stores; the host picks it only when a row is a
+// whole number of such steps and both base pointers are 16-byte aligned, which makes every row start aligned too.
+// Otherwise one element per lane and step.  A row whose index is outside [0, n_rows) is skipped: nothing is read,
+// nothing is written.  All offsets are 64-bit.
+template <int DT> struct GatherVec { enum { V = 4 }; };                   // f32: one float4; f64: two double2
+template <> struct GatherVec<AVA_DT_U8> { enum { V = 16 }; };
+template <> struct GatherVec<AVA_DT_F16> { enum { V = 8 }; };
+template <> struct GatherVec<AVA_DT_BF16> { enum { V = 8 }; };
+
+template <int DT>
+__device__ __forceinline__ float gather_cvt16(unsigned short h) {
+  if (DT == AVA_DT_BF16) return __uint_as_float((unsigned)h << 16);
+  return __half2float(__ushort_as_half(h));
+}
+
+template <int DT, bool WIDE>
+__global__ __launch_bounds__(256) void gather_rows_f32_kernel(const void* __restrict__ src, int64_t n_rows, int64_t row_elems,
+                                                              const int64_t* __restrict__ idx, int64_t n,
+                                                              float* __restrict__ dst, int tpr_log2) {
+  const int tpr = 1 << tpr_log2;
+  const int lane = threadIdx.x & (tpr - 1);
+  const int64_t rows_per_wg = 256 >> tpr_log2;
+  const int64_t steps = WIDE ? row_elems / GatherVec<DT>::V : row_elems;      // per row
+  const int64_t step_stride = (int64_t)gridDim.y * tpr;
+  for (int64_t j = (int64_t)blockIdx.x * rows_per_wg + (threadIdx.x >> tpr_log2); j < n; j += (int64_t)gridDim.x * rows_per_wg) {
+    const int64_t r = idx[j];
+    if (r < 0 || r >= n_rows) continue;
+    const int64_t so = r * row_elems;                                         // in elements
+    float* __restrict__ d = dst + j * row_elems;
+    for (int64_t c = (int64_t)blockIdx.y * tpr + lane; c < steps; c += step_stride) {
+      if (!WIDE) {
+        float v;
+        if (DT == AVA_DT_F64) v = (float)reinterpret_cast<const double*>(src)[so + c];
+        else if (DT == AVA_DT_U8) v = (float)reinterpret_cast<const unsigned char*>(src)[so + c];
+        else if (DT == AVA_DT_F16 || DT == AVA_DT_BF16) v = gather_cvt16<DT>(reinterpret_cast<const unsigned short*>(src)[so + c]);
+        else v = reinterpret_cast<const float*>(src)[so + c];
+        d[c] = v;
+      } else if (DT == AVA_DT_F64) {
+        const double2* s2 = reinterpret_cast<const double2*>(reinterpret_cast<const double*>(src) + so);
+        const double2 a = s2[2 * c], b = s2[2 * c + 1];
+        reinterpret_cast<float4*>(d)[c] = make_float4((float)a.x, (float)a.y, (float)b.x, (float)b.y);
+      } else if (DT == AVA_DT_U8) {
+        const uint4 v = reinterpret_cast<const uint4*>(reinterpret_cast<const unsigned char*>(src) + so)[c];
+        const unsigned w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+          reinterpret_cast<float4*>(d)[4 * c + q] = make_float4((float)(w[q] & 0xffu), (float)((w[q] >> 8) & 0xffu),
+                                                                (float)((w[q] >> 16) & 0xffu), (float)(w[q] >> 24));
+      } else if (DT == AVA_DT_F16 || DT == AVA_DT_BF16) {
+        const uint4 v = reinterpret_cast<const uint4*>(reinterpret_cast<const unsigned short*>(src) + so)[c];
+        reinterpret_cast<float4*>(d)[2 * c] = make_float4(gather_cvt16<DT>(v.x & 0xffff), gather_cvt16<DT>(v.x >> 16),
+                                                          gather_cvt16<DT>(v.y & 0xffff), gather_cvt16<DT>(v.y >> 16));
+        reinterpret_cast<float4*>(d)[2 * c + 1] = make_float4(gather_cvt16<DT>(v.z & 0xffff), gather_cvt16<DT>(v.z >> 16),
+                                                              gather_cvt16<DT>(v.w & 0xffff), gather_cvt16<DT>(v.w >> 16));
+      } else {
+        reinterpret_cast<float4*>(d)[c] = reinterpret_cast<const float4*>(reinterpret_cast<const float*>(src) + so)[c];
+      }
+    }
+  }
+}
+
+template <int DT>
+static void gather_rows_launch(const void* src, int64_t n_rows, int64_t row_elems, const int64_t* idx, int64_t n,
+                               float* dst, hipStream_t st) {
+  const bool wide = row_elems % GatherVec<DT>::V == 0 && (reinterpret_cast<uintptr_t>(src) & 15) == 0 &&
+                    (reinterpret_cast<uintptr_t>(dst) & 15) == 0;
+  const int64_t steps = wide ? row_elems / GatherVec<DT>::V : row_elems;
+  int tpr_log2 = 0;                                   // lanes per row: the power of two that covers a row, at most 256
+  while (tpr_log2 < 8 && ((int64_t)1 << tpr_log2) < steps) ++tpr_log2;
+  const int64_t tpr = (int64_t)1 << tpr_log2, rows_per_wg = 256 / tpr;
+  int64_t gx = (n + rows_per_wg - 1) / rows_per_wg;   // the kernel strides over what the caps leave
+  if (gx > 65536) gx = 65536;
+  int64_t gy = (steps + tpr - 1) / tpr;
+  if (gy > 32) gy = 32;
+  const dim3 grid((unsigned)gx, (unsigned)gy);
+  if (wide)
+    hipLaunchKernelGGL((gather_rows_f32_kernel<DT, true>), grid, dim3(256), 0, st, src, n_rows, row_elems, idx, n, dst, tpr_log2);
+  else
+    hipLaunchKernelGGL((gather_rows_f32_kernel<DT, false>), grid, dim3(256), 0, st, src, n_rows, row_elems, idx, n, dst, tpr_log2);
+}
+
+extern "C" int ava_gather_rows_f32(const void* src, int src_dtype, int64_t n_rows, int64_t row_elems, const int64_t* idx,
+                                   int64_t n, float* dst, ava_stream_t s) {
+  if (src == nullptr || idx == nullptr || dst == nullptr || n <= 0 || row_elems <= 0 || n_rows <= 0) return AVA_EINVAL;
+  hipStream_t st = to_stream(s);
+  switch (src_dtype) {
+    case AVA_DT_F32: gather_rows_launch<AVA_DT_F32>(src, n_rows, row_elems, idx, n, dst, st); break;
+    case AVA_DT_F64: gather_rows_launch<AVA_DT_F64>(src, n_rows, row_elems, idx, n, dst, st); break;
+    case AVA_DT_U8: gather_rows_launch<AVA_DT_U8>(src, n_rows, row_elems, idx, n, dst, st); break;
+    case AVA_DT_F16: gather_rows_launch<AVA_DT_F16>(src, n_rows, row_elems, idx, n, dst, st); break;
+    case AVA_DT_BF16: gather_rows_launch<AVA_DT_BF16>(src, n_rows, row_elems, idx, n, dst, st); break;
+    default: return AVA_EINVAL;
+  }
+  AVA_CHECK_LAUNCH();
+  return AVA_OK;
+}

@@ -683,7 +683,10 @@ class VAE(nn.Module):
         from .plotting import grid_plot
         assert num_specs <= len(loader.dataset) and num_specs >= 1
         indices = np.random.choice(np.arange(len(loader.dataset)), size=num_specs, replace=False)
-        specs = torch.stack(loader.dataset[indices]).to(self.device)
+        specs = loader.dataset[indices]         # a list of [F,T] tensors (vae_dataset.py:130-145), or a device dataset's [n,F,T]
+        if not torch.is_tensor(specs):
+            specs = torch.stack(specs)
+        specs = specs.to(self.device)
         with torch.no_grad():
             _, _, rec_specs = self.forward(specs, return_latent_rec=True)
         specs = specs.detach().cpu().numpy()

@@ -269,6 +269,16 @@ int ava_cast_to_f32(const void* src, int src_dtype, int64_t n, float* dst, ava_s
  * per-item collation of the reference's DataLoader (ava/models/vae_dataset.py:89-96) for array-backed datasets. */
 int ava_host_gather_rows(void* dst, const void* src, const int64_t* idx, int64_t first, int64_t n, size_t row_bytes,
                          int threads);
+/* Row gather with the cast, on the device: dst[j, :] = float(src[idx[j], :]) for j < n, the
+ * per-step path of a dataset that is resident in HBM (replaces SyllableDataset.__getitem__ + numpy_to_tensor + the
+ * DataLoader's collation, ava/models/vae_dataset.py:125-145).  src: [n_rows][row_elems] of src_dtype (the codes of
+ * ava_cast_to_f32, same rounding); idx: n int64 row numbers ON THE DEVICE, in any order, repeats allowed; dst:
+ * [n][row_elems] float32.  16-byte loads and stores when a row is a whole number of 16-byte source vectors and of
+ * float4s and src and dst are 16-byte aligned, one element per lane otherwise (any alignment the dtype allows).  A
+ * row whose index is outside [0, n_rows) is neither read nor written.  Null pointers, n <= 0, n_rows <= 0,
+ * row_elems <= 0 and an unknown dtype return AVA_EINVAL before any launch. */
+int ava_gather_rows_f32(const void* src, int src_dtype, int64_t n_rows, int64_t row_elems, const int64_t* idx, int64_t n,
+                        float* dst, ava_stream_t s);
 
 /* ---- MMD^2 between sets of latent means (downstream consumer of get_latent) ------------ */
 /* _estimate_mmd2 (ava/plotting/mmd_plots.py:255-296, Gretton et al. 2012, unbiased quadratic-time estimator with a
