@@ -4,16 +4,18 @@
 // (ava/plotting/mmd_plots.py:255-296), `_estimate_mmd2_linear_time` (:299-312) and the pair distances of
 // `estimate_median_sigma` (:450-474).  The reference works on float64 numpy arrays; so do these kernels (fp64 VALU;
 // the differences are formed directly, sum_k (x_k - y_k)^2, exactly as the reference does -- no |x|^2 + |y|^2 - 2xy
-// expansion, which cancels for near pairs).  Every sum is a fixed-order two-stage reduction (per-workgroup partial,
-// then one workgroup over the partials): deterministic, no atomics.
+// expansion, which cancels for near pairs; the pairwise kernel's tile and the order of its sums are those of
+// sqdist_tile.h).  Every sum is a fixed-order two-stage reduction (per-workgroup partial, then one workgroup over the
+// partials): deterministic, no atomics.
 //
 // Pairwise kernel: a workgroup owns a 64 x 64 tile of (i, j) pairs; the 64 + 64 latent rows are gathered through the
 // index lists into LDS once (row stride z|1 doubles: conflict-free column walks) and each thread accumulates a 4 x 4
 // block of squared distances in registers while sweeping the z latent dimensions, then adds exp(A * dist) of the
 // pairs that exist (and, for the within-set terms, lie above the diagonal: i < j).
 #include "common.h"
+#include "sqdist_tile.h"
 
-#define MMD_T 64
+#define MMD_T SQD_T
 
 __global__ __launch_bounds__(256) void mmd_pair_kernel(const double* __restrict__ L, int z,
                                                        const int64_t* __restrict__ ia, int na,
@@ -44,20 +46,7 @@ __global__ __launch_bounds__(256) void mmd_pair_kernel(const double* __restrict_
   for (int r = 0; r < 4; ++r)
 #pragma unroll
     for (int c = 0; c < 4; ++c) acc[r][c] = 0.0;
-  for (int k = 0; k < z; ++k) {
-    double x[4], y[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) x[r] = xs[(ty + 16 * r) * zp + k];
-#pragma unroll
-    for (int c = 0; c < 4; ++c) y[c] = ys[(tx + 16 * c) * zp + k];
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        const double d = x[r] - y[c];
-        acc[r][c] = fma(d, d, acc[r][c]);
-      }
-  }
+  sqd_accumulate(xs, ys, zp, z, ty, tx, acc);
   double s = 0.0;
 #pragma unroll
   for (int r = 0; r < 4; ++r)

@@ -13,18 +13,19 @@
 // v_mfma_f64_16x16x4_f64 (16 accumulators of 4 doubles per lane).  The epilogue forms 1 - dot / sqrt(ss_q ss_r)
 // (clipped to [0, 2] as scipy clips the cosine) and writes one (dist, idx) partial per (query, reference tile).
 //
-// Euclidean: fp64 VALU with direct differences sum_k (q_k - r_k)^2 (as mmd.hip; no |q|^2 + |r|^2 - 2qr expansion),
-// 64 x 64 tiles, a 4 x 4 block of pairs per thread, then sqrt (the reference compares the square roots).
+// Euclidean: the fp64 direct-difference tile of sqdist_tile.h (64 x 64 pairs, a 4 x 4 block per thread), then sqrt
+// (the reference compares the square roots).
 //
 // A fixed-order reduce kernel combines the partials of each query.  The candidates are ordered by nn_better, a total
 // order, so every tile, every reduce step and the host's merge of reference chunks pick the same winner: the result
-// is bit-reproducible and independent of the tiling and of the chunking.  Every pair's sum runs over k in one fixed
-// order, whatever tile it falls in.
+// is bit-reproducible and independent of the tiling and of the chunking (the euclidean sums: the order contract of
+// sqdist_tile.h; the correlation dot products run over k in one fixed order, whatever tile they fall in).
 //   ties        equal distances resolve to the lowest reference index
 //   correlation a zero-variance row gives NaN (0 / 0, as scipy); NaN loses to any number; a query whose distances are
 //               all NaN gets index 0 and distance NaN
 //   euclidean   NaN wins and the first NaN is taken, as np.argmin does
 #include "common.h"
+#include "sqdist_tile.h"
 
 #define NN_CORR 0
 #define NN_EUCL 1
@@ -33,10 +34,6 @@
 #define NC_BR 128        //                   references
 #define NC_KC 16         // k per LDS stage
 #define NC_LD 17         // LDS row stride in doubles (odd: the staging writes and fragment reads spread over the banks)
-
-#define NE_T 64          // euclidean tile (queries = references)
-#define NE_KC 32
-#define NE_LD 33
 
 typedef double nn_d4 __attribute__((ext_vector_type(4)));
 
@@ -193,41 +190,20 @@ template <typename TQ, typename TR>
 __global__ __launch_bounds__(256) void nn_eucl_kernel(const TQ* __restrict__ Q, int nq, const TR* __restrict__ R, int nr,
                                                       int d, int rtiles, double* __restrict__ pdist,
                                                       int64_t* __restrict__ pidx) {
-  __shared__ double xs[NE_T * NE_LD];
-  __shared__ double ys[NE_T * NE_LD];
+  __shared__ double xs[SQD_T * SQD_LD];
+  __shared__ double ys[SQD_T * SQD_LD];
   const int t = threadIdx.x, ty = t >> 4, tx = t & 15;
   const int rt = blockIdx.x;
-  const int q0 = blockIdx.y * NE_T, r0 = rt * NE_T;
-  const int sc = t & 31, sr = t >> 5;                // staging: row sr + 8 j, column sc
+  const int q0 = blockIdx.y * SQD_T, r0 = rt * SQD_T;
   double acc[4][4];
 #pragma unroll
   for (int i = 0; i < 4; ++i)
 #pragma unroll
     for (int j = 0; j < 4; ++j) acc[i][j] = 0.0;
-  for (int k0 = 0; k0 < d; k0 += NE_KC) {
-    const int k = k0 + sc;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int r = sr + 8 * j;
-      xs[r * NE_LD + sc] = (k < d && q0 + r < nq) ? (double)Q[(size_t)(q0 + r) * d + k] : 0.0;
-      ys[r * NE_LD + sc] = (k < d && r0 + r < nr) ? (double)R[(size_t)(r0 + r) * d + k] : 0.0;
-    }
+  for (int k0 = 0; k0 < d; k0 += SQD_KC) {
+    sqd_stage(xs, ys, Q, q0, nq, R, r0, nr, d, k0, t);
     __syncthreads();
-    const int kn = d - k0 < NE_KC ? d - k0 : NE_KC;
-    for (int kk = 0; kk < kn; ++kk) {
-      double x[4], y[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) x[i] = xs[(ty + 16 * i) * NE_LD + kk];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) y[j] = ys[(tx + 16 * j) * NE_LD + kk];
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const double df = x[i] - y[j];
-          acc[i][j] = fma(df, df, acc[i][j]);
-        }
-    }
+    sqd_accumulate(xs, ys, SQD_LD, d - k0 < SQD_KC ? d - k0 : SQD_KC, ty, tx, acc);
     __syncthreads();
   }
 #pragma unroll
@@ -291,11 +267,11 @@ __global__ __launch_bounds__(256) void nn_merge_kernel(int64_t* __restrict__ bes
   }
 }
 
-static inline int nn_tile(int metric) { return metric == NN_CORR ? NC_BR : NE_T; }
+static inline int nn_tile(int metric) { return metric == NN_CORR ? NC_BR : SQD_T; }
 
 static bool nn_shape_ok(int nq, int nr, int d, int metric) {
   if (nq < 1 || nr < 1 || d < 1 || d > 65536 || (metric != NN_CORR && metric != NN_EUCL)) return false;
-  const int qt = metric == NN_CORR ? NC_BQ : NE_T;
+  const int qt = metric == NN_CORR ? NC_BQ : SQD_T;
   return ceil_div(nq, qt) <= 65535;                  // grid.y
 }
 
@@ -321,7 +297,7 @@ static int nn_launch(const void* queries, int nq, const void* refs, int nr, int 
     hipLaunchKernelGGL((nn_corr_kernel<TQ, TR>), dim3(rtiles, ceil_div(nq, NC_BQ)), dim3(256), 0, st, Q, nq, R, nr, d,
                        qstat, rstat, rtiles, pdist, pidx);
   } else {
-    hipLaunchKernelGGL((nn_eucl_kernel<TQ, TR>), dim3(rtiles, ceil_div(nq, NE_T)), dim3(256), 0, st, Q, nq, R, nr, d,
+    hipLaunchKernelGGL((nn_eucl_kernel<TQ, TR>), dim3(rtiles, ceil_div(nq, SQD_T)), dim3(256), 0, st, Q, nq, R, nr, d,
                        rtiles, pdist, pidx);
   }
   AVA_CHECK_LAUNCH();

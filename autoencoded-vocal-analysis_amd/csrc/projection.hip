@@ -3,8 +3,8 @@
 // fixed order, so every result is bit-reproducible and independent of the launch shape.
 //
 // kNN       exact euclidean k-nearest neighbours of every row among all rows.  A workgroup owns 64 query rows and walks
-//           the references in 64-row tiles (direct differences sum_c (x_c - y_c)^2 in one fixed order over c, as
-//           neighbors.hip); each query keeps a running top-(k-1) list in LDS ordered by (distance, index), the query
+//           the references in 64-row tiles (the fp64 direct-difference tile of sqdist_tile.h, which states the order
+//           of every sum); each query keeps a running top-(k-1) list in LDS ordered by (distance, index), the query
 //           itself excluded.  Column 0 of the output is the row itself at distance 0.
 // smooth    umap's smooth_knn_dist + compute_membership_strengths, one row per thread.
 // layout    one synchronous, gather-only SGD epoch per launch over the symmetric CSR graph (rows = heads): a thread
@@ -18,10 +18,8 @@
 // PCA       column sums and X^T X as the Gram matrix of [X, 1] (chunks of rows, chunks summed in order), and the
 //           projection X V^T - mu V^T.
 #include "common.h"
+#include "sqdist_tile.h"
 
-#define PJ_T 64          // kNN tile: queries = references
-#define PJ_KC 32         // columns per LDS stage
-#define PJ_LD 33         // staging row stride (doubles)
 #define PJ_DLD 65        // distance tile row stride (doubles)
 #define PJ_MAX_K 64
 #define PJ_MAX_NEG 16
@@ -42,53 +40,32 @@ template <typename T>
 __global__ __launch_bounds__(256) void pj_knn_kernel(const T* __restrict__ Q, const T* __restrict__ X, int n, int d,
                                                      int k, int q0, int nq, int exclude_self,
                                                      int64_t* __restrict__ out_idx, double* __restrict__ out_dist) {
-  __shared__ double stage[2 * PJ_T * PJ_LD];        // xs | ys while staging, then the 64 x 64 distance tile
+  __shared__ double stage[2 * SQD_T * SQD_LD];      // xs | ys while staging, then the 64 x 64 distance tile
   extern __shared__ double lists[];                 // m x 64 distances, then m x 64 int indices
   double* xs = stage;
-  double* ys = stage + PJ_T * PJ_LD;
+  double* ys = stage + SQD_T * SQD_LD;
   double* dt = stage;
   const int m = k - exclude_self;
   double* ld = lists;
-  int* li = reinterpret_cast<int*>(lists + (size_t)m * PJ_T);
+  int* li = reinterpret_cast<int*>(lists + (size_t)m * SQD_T);
   const int t = threadIdx.x, ty = t >> 4, tx = t & 15;
-  const int qb = q0 + blockIdx.x * PJ_T;             // first query row of this workgroup
+  const int qb = q0 + blockIdx.x * SQD_T;            // first query row of this workgroup
   const int qe = q0 + nq;
-  const int sc = t & 31, sr = t >> 5;
-  for (int s = t; s < m * PJ_T; s += 256) {
+  for (int s = t; s < m * SQD_T; s += 256) {
     ld[s] = 0.0;
     li[s] = -1;
   }
-  for (int r0 = 0; r0 < n; r0 += PJ_T) {
+  for (int r0 = 0; r0 < n; r0 += SQD_T) {
     double acc[4][4];
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
       for (int j = 0; j < 4; ++j) acc[i][j] = 0.0;
-    for (int k0 = 0; k0 < d; k0 += PJ_KC) {
-      const int c = k0 + sc;
+    for (int k0 = 0; k0 < d; k0 += SQD_KC) {
       __syncthreads();                               // previous stage / distance tile consumed
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int r = sr + 8 * j;
-        xs[r * PJ_LD + sc] = (c < d && qb + r < qe) ? (double)Q[(size_t)(qb + r) * d + c] : 0.0;
-        ys[r * PJ_LD + sc] = (c < d && r0 + r < n) ? (double)X[(size_t)(r0 + r) * d + c] : 0.0;
-      }
+      sqd_stage(xs, ys, Q, qb, qe, X, r0, n, d, k0, t);
       __syncthreads();
-      const int kn = d - k0 < PJ_KC ? d - k0 : PJ_KC;
-      for (int kk = 0; kk < kn; ++kk) {
-        double x[4], y[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) x[i] = xs[(ty + 16 * i) * PJ_LD + kk];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) y[j] = ys[(tx + 16 * j) * PJ_LD + kk];
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            const double df = x[i] - y[j];
-            acc[i][j] = fma(df, df, acc[i][j]);
-          }
-      }
+      sqd_accumulate(xs, ys, SQD_LD, d - k0 < SQD_KC ? d - k0 : SQD_KC, ty, tx, acc);
     }
     __syncthreads();                                 // staging reads done: the tile reuses the buffer
 #pragma unroll
@@ -97,38 +74,38 @@ __global__ __launch_bounds__(256) void pj_knn_kernel(const T* __restrict__ Q, co
       for (int j = 0; j < 4; ++j) dt[(ty + 16 * i) * PJ_DLD + tx + 16 * j] = sqrt(acc[i][j]);
     __syncthreads();
     // one thread per query folds the tile's candidates into its list, in reference order
-    if (t < PJ_T && qb + t < qe && m > 0) {
+    if (t < SQD_T && qb + t < qe && m > 0) {
       const int q = qb + t;
-      const int cn = n - r0 < PJ_T ? n - r0 : PJ_T;
-      double wd = ld[(m - 1) * PJ_T + t];
-      int wi = li[(m - 1) * PJ_T + t];
+      const int cn = n - r0 < SQD_T ? n - r0 : SQD_T;
+      double wd = ld[(m - 1) * SQD_T + t];
+      int wi = li[(m - 1) * SQD_T + t];
       for (int c = 0; c < cn; ++c) {
         const int r = r0 + c;
         const double dd = dt[t * PJ_DLD + c];
         if ((exclude_self && r == q) || !pj_before(dd, r, wd, wi)) continue;
         int s = m - 1;
-        while (s > 0 && pj_before(dd, r, ld[(s - 1) * PJ_T + t], li[(s - 1) * PJ_T + t])) {
-          ld[s * PJ_T + t] = ld[(s - 1) * PJ_T + t];
-          li[s * PJ_T + t] = li[(s - 1) * PJ_T + t];
+        while (s > 0 && pj_before(dd, r, ld[(s - 1) * SQD_T + t], li[(s - 1) * SQD_T + t])) {
+          ld[s * SQD_T + t] = ld[(s - 1) * SQD_T + t];
+          li[s * SQD_T + t] = li[(s - 1) * SQD_T + t];
           --s;
         }
-        ld[s * PJ_T + t] = dd;
-        li[s * PJ_T + t] = r;
-        wd = ld[(m - 1) * PJ_T + t];
-        wi = li[(m - 1) * PJ_T + t];
+        ld[s * SQD_T + t] = dd;
+        li[s * SQD_T + t] = r;
+        wd = ld[(m - 1) * SQD_T + t];
+        wi = li[(m - 1) * SQD_T + t];
       }
     }
   }
   __syncthreads();
-  if (t < PJ_T && qb + t < qe) {
+  if (t < SQD_T && qb + t < qe) {
     const size_t o = (size_t)(qb + t - q0) * k;
     if (exclude_self) {
       out_idx[o] = qb + t;
       out_dist[o] = 0.0;
     }
     for (int s = 0; s < m; ++s) {
-      out_idx[o + exclude_self + s] = li[s * PJ_T + t];
-      out_dist[o + exclude_self + s] = ld[s * PJ_T + t];
+      out_idx[o + exclude_self + s] = li[s * SQD_T + t];
+      out_dist[o + exclude_self + s] = ld[s * SQD_T + t];
     }
   }
 }
@@ -453,8 +430,8 @@ static bool pj_knn_ok(int n, int d, int k, int q0, int nq) {
 template <typename T>
 static int pj_knn_launch(const void* q, const void* x, int n, int d, int k, int q0, int nq, int exclude_self,
                          int64_t* idx, double* dist, hipStream_t st) {
-  const size_t lds = (size_t)(k - exclude_self) * PJ_T * (sizeof(double) + sizeof(int));
-  hipLaunchKernelGGL(pj_knn_kernel<T>, dim3(ceil_div(nq, PJ_T)), dim3(256), lds, st, reinterpret_cast<const T*>(q),
+  const size_t lds = (size_t)(k - exclude_self) * SQD_T * (sizeof(double) + sizeof(int));
+  hipLaunchKernelGGL(pj_knn_kernel<T>, dim3(ceil_div(nq, SQD_T)), dim3(256), lds, st, reinterpret_cast<const T*>(q),
                      reinterpret_cast<const T*>(x), n, d, k, q0, nq, exclude_self, idx, dist);
   AVA_CHECK_LAUNCH();
   return AVA_OK;

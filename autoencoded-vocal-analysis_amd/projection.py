@@ -82,47 +82,19 @@ def _code(t):
     return 0 if t.dtype == torch.float32 else 1
 
 
-def _knn_device(xd, k, chunk_rows=None):
-    n, d = int(xd.shape[0]), int(xd.shape[1])
-    if not 1 <= k <= min(MAX_K, n):
-        raise ValueError("k must be in [1, min(%d, n)], got %d" % (MAX_K, k))
-    if d > MAX_DIM or n >= 2 ** 31:
-        raise ValueError("unsupported shape [%d, %d]" % (n, d))
-    if chunk_rows is None:
-        chunk_rows = n
-    elif int(chunk_rows) != chunk_rows or chunk_rows < 1:
-        raise ValueError("chunk_rows must be a positive integer")
-    chunk_rows = min(int(chunk_rows), n)
-    lib = _lib.load()
-    idx = torch.empty((n, k), dtype=torch.int64, device=xd.device)
-    dist = torch.empty((n, k), dtype=torch.float64, device=xd.device)
-    st = _lib.stream()
-    for q0 in range(0, n, chunk_rows):
-        nq = min(chunk_rows, n - q0)
-        _lib.check(lib.ava_pj_knn(xd.data_ptr(), _code(xd), n, d, k, q0, nq, idx[q0:].data_ptr(),
-                                  dist[q0:].data_ptr(), st), "ava_pj_knn")
-    return idx, dist
-
-
-def knn(X, k, chunk_rows=None):
-    """Exact euclidean kNN of every row of ``X`` among its rows (fp64 from the given values): ``(idx int64 [n, k],
-    dist float64 [n, k])``.  Column 0 is the row itself at distance 0, then the ``k - 1`` nearest other rows ordered
-    by (distance, index).  ``chunk_rows`` query rows go to one launch; the result does not depend on it."""
-    xd = _as_rows(X, _native_dtype(X))
-    idx, dist = _knn_device(xd, int(k), chunk_rows)
-    return idx.cpu().numpy(), dist.cpu().numpy()
-
-
-def _knn_query_device(qd, xd, k, chunk_rows=None):
-    m, n, d = int(qd.shape[0]), int(xd.shape[0]), int(xd.shape[1])
-    if int(qd.shape[1]) != d:
+def _knn_device(xd, k, chunk_rows=None, qd=None):
+    """the kNN table of the rows of ``qd`` among the rows of ``xd``; without ``qd`` of ``xd``'s own rows, the row itself
+    first (``ava_pj_knn``)"""
+    m, n, d = int((xd if qd is None else qd).shape[0]), int(xd.shape[0]), int(xd.shape[1])
+    if qd is not None and int(qd.shape[1]) != d:
         raise ValueError("queries have %d columns, references %d" % (int(qd.shape[1]), d))
-    if qd.dtype != xd.dtype:
+    if qd is not None and qd.dtype != xd.dtype:
         raise ValueError("queries and references must have one dtype")
     if not 1 <= k <= min(MAX_K, n):
         raise ValueError("k must be in [1, min(%d, n)], got %d" % (MAX_K, k))
     if d > MAX_DIM or n >= 2 ** 31 or m >= 2 ** 31:
-        raise ValueError("unsupported shapes [%d, %d], [%d, %d]" % (m, d, n, d))
+        raise ValueError("unsupported shape [%d, %d]" % (n, d) if qd is None else
+                         "unsupported shapes [%d, %d], [%d, %d]" % (m, d, n, d))
     if chunk_rows is None:
         chunk_rows = m
     elif int(chunk_rows) != chunk_rows or chunk_rows < 1:
@@ -134,9 +106,25 @@ def _knn_query_device(qd, xd, k, chunk_rows=None):
     st = _lib.stream()
     for q0 in range(0, m, chunk_rows):
         nq = min(chunk_rows, m - q0)
-        _lib.check(lib.ava_pj_knn_query(qd.data_ptr(), xd.data_ptr(), _code(xd), m, n, d, k, q0, nq,
-                                        idx[q0:].data_ptr(), dist[q0:].data_ptr(), st), "ava_pj_knn_query")
+        out = (k, q0, nq, idx[q0:].data_ptr(), dist[q0:].data_ptr(), st)
+        if qd is None:
+            _lib.check(lib.ava_pj_knn(xd.data_ptr(), _code(xd), n, d, *out), "ava_pj_knn")
+        else:
+            _lib.check(lib.ava_pj_knn_query(qd.data_ptr(), xd.data_ptr(), _code(xd), m, n, d, *out), "ava_pj_knn_query")
     return idx, dist
+
+
+def _knn_query_device(qd, xd, k, chunk_rows=None):
+    return _knn_device(xd, k, chunk_rows, qd)
+
+
+def knn(X, k, chunk_rows=None):
+    """Exact euclidean kNN of every row of ``X`` among its rows (fp64 from the given values): ``(idx int64 [n, k],
+    dist float64 [n, k])``.  Column 0 is the row itself at distance 0, then the ``k - 1`` nearest other rows ordered
+    by (distance, index).  ``chunk_rows`` query rows go to one launch; the result does not depend on it."""
+    xd = _as_rows(X, _native_dtype(X))
+    idx, dist = _knn_device(xd, int(k), chunk_rows)
+    return idx.cpu().numpy(), dist.cpu().numpy()
 
 
 def knn_query(Q, X, k, chunk_rows=None):

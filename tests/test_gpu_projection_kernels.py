@@ -1,9 +1,9 @@
 """The kernels of csrc/projection.hip on the MI355X, one by one, at the shapes where their code takes another path:
 the Gram kernel's row chunks and tiles, the projection at several component counts, the kNN kernel at its smallest and
-fullest lists, the bandwidth kernel at every branch of local_connectivity, and the layout kernel's clamp, coincident
-points, isolated vertices and single partial workgroup.  The oracles are the fp64 / long double numpy restatements of
-tests/projection_cases.py; tests/test_cpu_projection.py shows that the inputs are well conditioned at the tolerances
-used here."""
+fullest lists (and bit for bit against the other users of csrc/sqdist_tile.h), the bandwidth kernel at every branch of
+local_connectivity, and the layout kernel's clamp, coincident points, isolated vertices and single partial workgroup.
+The oracles are the fp64 / long double numpy restatements of tests/projection_cases.py; tests/test_cpu_projection.py
+shows that the inputs are well conditioned at the tolerances used here."""
 import functools
 import warnings
 
@@ -13,6 +13,7 @@ import torch
 
 import projection_cases as PC
 from ava_amd import _lib
+from ava_amd import neighbors as N
 from ava_amd import projection as P
 
 pytestmark = pytest.mark.gpu
@@ -168,6 +169,62 @@ def test_knn_edges(name, chunk_rows):
     np.testing.assert_allclose(dist, want_dist, rtol=1e-12, atol=0)
     if k == len(X):                                       # every row lists every row once
         np.testing.assert_array_equal(np.sort(idx, axis=1), np.broadcast_to(np.arange(k), idx.shape))
+
+
+# ---- one squared-distance tile (csrc/sqdist_tile.h) behind nearest, knn and knn_query --------------------------------
+def _check_nearest_is_knn_query(Q, X):
+    idx, dist = N.nearest(Q, X, 'euclidean')
+    qidx, qdist = P.knn_query(Q, X, 1)
+    np.testing.assert_array_equal(idx, qidx[:, 0])
+    np.testing.assert_array_equal(dist, qdist[:, 0])
+    return idx, dist
+
+
+# a partial tile; a second tile of one row and a column stage with a tail of 1; three reference tiles, two full stages
+@pytest.mark.parametrize("dtype", sorted(DTYPES))
+@pytest.mark.parametrize("m, n, d", [(5, 7, 1), (63, 65, 33), (65, 130, 64)])
+def test_nearest_equals_knn_query_k1(m, n, d, dtype):
+    Q = PC.gaussian(m, d, 9950 + m + d, DTYPES[dtype])
+    X = PC.gaussian(n, d, 9951 + n + d, DTYPES[dtype])
+    _check_nearest_is_knn_query(Q, X)
+
+
+@pytest.mark.parametrize("dtype", sorted(DTYPES))
+def test_nearest_equals_knn_query_k1_duplicates(dtype):
+    """references 3 and 70 (another tile) are copies of query 2, references 64 and 129 of query 64: distance 0 twice,
+    and both searches take the lower index"""
+    Q = PC.gaussian(65, 33, 9960, DTYPES[dtype])
+    X = PC.gaussian(130, 33, 9961, DTYPES[dtype])
+    X[[3, 70]] = Q[2]
+    X[[64, 129]] = Q[64]
+    idx, dist = _check_nearest_is_knn_query(Q, X)
+    assert idx[2] == 3 and idx[64] == 64 and dist[2] == 0.0 and dist[64] == 0.0
+
+
+def test_knn_equals_knn_query_on_same_rows():
+    """the self search and the query search of the same rows: the row itself first at 0.0, then (the case has no ties)
+    the same neighbours at the same distances, bit for bit"""
+    X, k, _, _ = _knn_case("65x65-k20")
+    idx, dist = P.knn(X, k)
+    qidx, qdist = P.knn_query(X, X, k)
+    np.testing.assert_array_equal(qidx[:, 0], np.arange(len(X)))
+    np.testing.assert_array_equal(qdist[:, 0], np.zeros(len(X)))
+    np.testing.assert_array_equal(qidx[:, 1:], idx[:, 1:])
+    np.testing.assert_array_equal(qdist[:, 1:], dist[:, 1:])
+
+
+def test_knn_query_equals_pair_sqdist():
+    """the tile's sum over k is the scalar kernel's: knn_query distances are the square roots of ava_pair_sqdist (called
+    as mmd.estimate_median_sigma calls it) of the same index pairs, bit for bit"""
+    n, z, k = 65, 33, 5
+    X = PC.gaussian(n, z, 9970, np.float64)
+    qidx, qdist = P.knn_query(X, X, k)
+    L, a, b = _up(X), _up(np.repeat(np.arange(n, dtype=np.int64), k)), _up(qidx.ravel())
+    out = torch.empty(n * k, dtype=torch.float64, device="cuda")
+    rc = _lib.load().ava_pair_sqdist(L.data_ptr(), z, a.data_ptr(), b.data_ptr(), n * k, out.data_ptr(), _lib.stream())
+    assert rc == AVA_OK
+    np.testing.assert_array_equal(np.sqrt(out.cpu().numpy()).reshape(n, k), qdist)
+    assert np.all(qdist[:, 1:] > 0)
 
 
 # ---- bandwidths ------------------------------------------------------------------------------------------------------
