@@ -1,0 +1,282 @@
+// The shift-and-slope time-warp fit on the device: the arithmetic of the reference's
+// ava/preprocessing/warping.py (apply_warp :25-50, the objectives :148-163) and the kernels ava_amd/warp_fit.py chains
+// into align_specs.  All arithmetic is fp64; spectrograms are [N][F][T] contiguous, fp32 or fp64.
+//
+//   warpfit_apply_kernel       out[n][f][j] = interp1d(spec[n][f][:])(shift + slope j), the ends held (fill_value)
+//   warpfit_mean_kernel        target[f][j] = sum_n spec[n][f][j] / N, summed n = 0, 1, ... (np.mean(axis=0))
+//   warpfit_candidates_kernel  the grid of (shift, log slope) candidates around every motif's current best
+//   warpfit_loss_kernel        loss[n][c] = sum_{f,j} (interp(n; candidate c) - target)^2 + the two penalties: the hot one
+//   warpfit_argmin_kernel      per motif the best candidate (lowest index on ties, NaN never wins) and its parameters
+//
+// The interpolation restates scipy's interp1d(kind='linear') on the grid 0 .. T-1 operation for operation:
+// i = clip(searchsorted(x, p), 1, T-1), lo = i - 1, value = (y[lo+1] - y[lo]) * (p - lo) + y[lo], every product and sum
+// rounded on its own (__dmul_rn / __dadd_rn: -ffp-contract=on must not fuse them), so a warped pixel has the reference's
+// bits.  p < 0 gives y[0], p > T-1 gives y[T-1]; p == T-1 takes lo = T-2 and weight 1 and reads nothing behind the row.
+//
+// The loss kernel: one workgroup (4 waves) per (motif, block of WF_CB = 8 candidates).  A wave owns two candidates and
+// first writes their per-column (lo, weight) tables to LDS, once for all F rows.  Then WF_FR = 4 rows of the motif and of
+// the target are staged in LDS at a time (one coalesced HBM read per candidate BLOCK, not per candidate) and every lane
+// walks the columns j = lane, lane + 64, ... of its candidates over the staged rows: two adjacent LDS reads of the
+// motif row (neighbouring lanes read neighbouring columns, since slopes are near 1), one of the target, five fp64
+// operations.  Sums run lane-sequentially and then through one xor-shuffle tree: a fixed order, no atomics.
+// LDS: (4 (T+1) + 4 T + 8 T) 8 + 8 T 4 bytes = 160 T + 32: 20.5 KB at T = 128 (7 workgroups / CU), 82 KB at the cap
+// T = 512, where one more row set no longer fits twice on a CU.
+#include "common.h"
+
+#define WF_CB 8          // candidates per workgroup (two per wave)
+#define WF_FR 4          // motif / target rows staged per pass
+#define WF_MAX_T 512
+#define WF_MAX_C 4096
+
+struct WfTap { int lo; double w; };
+
+// scipy interp1d's tap for position p on the grid 0 .. T-1 (T >= 2).  Above the grid: lo = T-1, w = 0, and the caller
+// supplies y[T] = y[T-1] (LDS) or clamps (global).  NaN: weight NaN, so the value and any sum over it are NaN.
+__device__ __forceinline__ WfTap wf_tap(double p, int T) {
+  if (p != p) return {0, p};
+  if (p < 0.0) return {0, 0.0};
+  if (p > (double)(T - 1)) return {T - 1, 0.0};
+  int i = (int)ceil(p);                                     // searchsorted(arange(T), p), side='left'
+  i = i < 1 ? 1 : i;                                        // .clip(1, T-1)
+  return {i - 1, __dsub_rn(p, (double)(i - 1))};
+}
+
+__device__ __forceinline__ double wf_lerp(double a, double b, double w) {
+  return __dadd_rn(__dmul_rn(__dsub_rn(b, a), w), a);       // slope * (x_new - x_lo) + y_lo, scipy's order
+}
+
+__device__ __forceinline__ double wf_pos(double shift, double slope, int j) {
+  return __dadd_rn(shift, __dmul_rn(slope, (double)j));     // shifts[i] + slopes[i] * np.arange(T)
+}
+
+template <typename T_>
+__global__ __launch_bounds__(256) void warpfit_apply_kernel(const T_* __restrict__ spec, const double* __restrict__ params,
+                                                            int F, int T, T_* __restrict__ out) {
+  const int n = blockIdx.x;
+  const double shift = params[2 * (size_t)n], slope = params[2 * (size_t)n + 1];
+  for (int j = threadIdx.x; j < T; j += 256) {
+    const WfTap t = wf_tap(wf_pos(shift, slope, j), T);
+    const int hi = t.lo + 1 < T ? t.lo + 1 : T - 1;
+    for (int f = blockIdx.y; f < F; f += gridDim.y) {
+      const T_* row = spec + ((size_t)n * F + f) * T;
+      out[((size_t)n * F + f) * T + j] = (T_)wf_lerp((double)row[t.lo], (double)row[hi], t.w);
+    }
+  }
+}
+
+template <typename T_>
+__global__ __launch_bounds__(256) void warpfit_mean_kernel(const T_* __restrict__ spec, int N, int64_t FT,
+                                                           double* __restrict__ target) {
+  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= FT) return;
+  double acc = 0.0;
+  for (int n = 0; n < N; ++n) acc += (double)spec[(size_t)n * FT + e];
+  target[e] = acc / (double)N;
+}
+
+// Candidate c = a * (2 kl + 1) + b of motif n, (a, b) walking the offsets 0, -1, +1, -2, +2, ... of each axis, so that
+// candidate 0 is the centre x[n].  log slope = l0 + ob hl; the shift is moved so that the warp pivots about the middle
+// column, shift = s0 + oa hs - (exp(log slope) - exp(l0)) (T-1)/2: the two axes of the grid are then nearly independent
+// directions of the objective (a slope change about column 0 would drag the far end of the motif along).
+__global__ __launch_bounds__(256) void warpfit_candidates_kernel(const double* __restrict__ x, int N, int T, int ks, int kl,
+                                                                 double hs, double hl, double* __restrict__ cand) {
+  const int C = (2 * ks + 1) * (2 * kl + 1);
+  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= (int64_t)N * C) return;
+  const int n = (int)(e / C), c = (int)(e - (int64_t)n * C);
+  const int a = c / (2 * kl + 1), b = c - a * (2 * kl + 1);
+  const int oa = (a & 1) ? -((a + 1) >> 1) : (a >> 1), ob = (b & 1) ? -((b + 1) >> 1) : (b >> 1);
+  const double s0 = x[2 * (size_t)n], l0 = x[2 * (size_t)n + 1];
+  double shift = s0 + oa * hs, ls = l0;
+  if (ob != 0) {
+    ls = l0 + ob * hl;
+    shift -= (exp(ls) - exp(l0)) * (0.5 * (T - 1));
+  }
+  cand[2 * e] = shift;
+  cand[2 * e + 1] = ls;
+}
+
+template <typename T_>
+__global__ __launch_bounds__(256) void warpfit_loss_kernel(const T_* __restrict__ spec, const double* __restrict__ target,
+                                                           const double* __restrict__ cand, int F, int T, int C,
+                                                           double shift_lambda, double slope_lambda, int fixed_slope,
+                                                           double* __restrict__ loss) {
+  extern __shared__ __align__(16) double wf_sm[];
+  const int TS = T + 1;
+  double* s_spec = wf_sm;                                   // [WF_FR][T + 1], column T repeats column T-1
+  double* s_tgt = s_spec + WF_FR * TS;                      // [WF_FR][T]
+  double* s_w = s_tgt + WF_FR * T;                          // [WF_CB][T]
+  int* s_lo = reinterpret_cast<int*>(s_w + WF_CB * T);      // [WF_CB][T]
+  const int n = blockIdx.x, c0 = blockIdx.y * WF_CB;
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+
+  double shift[2], ls[2];
+#pragma unroll
+  for (int k = 0; k < 2; ++k) {
+    const int cc = wave + 4 * k, c = c0 + cc;
+    shift[k] = ls[k] = 0.0;
+    if (c < C) {                                            // wave-uniform
+      shift[k] = cand[2 * ((size_t)n * C + c)];
+      ls[k] = cand[2 * ((size_t)n * C + c) + 1];
+      const double slope = fixed_slope ? 1.0 : exp(ls[k]);
+      for (int j = lane; j < T; j += 64) {
+        const WfTap t = wf_tap(wf_pos(shift[k], slope, j), T);
+        s_lo[cc * T + j] = t.lo;
+        s_w[cc * T + j] = t.w;
+      }
+    }
+  }
+
+  double acc[2] = {0.0, 0.0};
+  const T_* motif = spec + (size_t)n * F * T;
+  for (int f0 = 0; f0 < F; f0 += WF_FR) {
+    const int nr = F - f0 < WF_FR ? F - f0 : WF_FR;
+    __syncthreads();                                        // the previous rows are consumed (first pass: tables written)
+    for (int e = tid; e < nr * T; e += 256) {
+      const int r = e / T, j = e - r * T;
+      const double v = (double)motif[(size_t)f0 * T + e];
+      s_spec[r * TS + j] = v;
+      if (j == T - 1) s_spec[r * TS + T] = v;
+      s_tgt[r * T + j] = target[(size_t)f0 * T + e];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      const int cc = wave + 4 * k;
+      if (c0 + cc >= C) continue;
+      for (int j = lane; j < T; j += 64) {
+        const int lo = s_lo[cc * T + j];
+        const double w = s_w[cc * T + j];
+        for (int r = 0; r < nr; ++r) {
+          const double d = wf_lerp(s_spec[r * TS + lo], s_spec[r * TS + lo + 1], w) - s_tgt[r * T + j];
+          acc[k] += d * d;
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < 2; ++k) {
+    const int c = c0 + wave + 4 * k;
+    if (c >= C) continue;
+    double tot = wave_sum_d(acc[k]);
+    // loss + shift_l * x[0]**2 + slope_l * x[1]**2, left to right
+    tot = __dadd_rn(tot, __dmul_rn(shift_lambda, __dmul_rn(shift[k], shift[k])));
+    if (!fixed_slope) tot = __dadd_rn(tot, __dmul_rn(slope_lambda, __dmul_rn(ls[k], ls[k])));
+    if (lane == 0) loss[(size_t)n * C + c] = tot;
+  }
+}
+
+// one wave per motif: lanes take candidates lane, lane + 64, ... in rising order, then a (loss, index) min over the wave
+__global__ __launch_bounds__(256) void warpfit_argmin_kernel(const double* __restrict__ loss, const double* __restrict__ cand,
+                                                             int N, int C, int* __restrict__ best, double* __restrict__ x,
+                                                             double* __restrict__ best_loss) {
+  const int n = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (n >= N) return;
+  double bv = 0.0;
+  int bi = -1;                                              // -1: nothing but NaN seen
+  for (int c = lane; c < C; c += 64) {
+    const double v = loss[(size_t)n * C + c];
+    if (v == v && (bi < 0 || v < bv)) { bv = v; bi = c; }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const double ov = __shfl_xor(bv, o, 64);
+    const int oi = __shfl_xor(bi, o, 64);
+    if (oi >= 0 && (bi < 0 || ov < bv || (ov == bv && oi < bi))) { bv = ov; bi = oi; }
+  }
+  if (lane == 0) {
+    const int c = bi < 0 ? 0 : bi;                          // all NaN: candidate 0 and its NaN
+    best[n] = c;
+    if (x != nullptr) {
+      x[2 * (size_t)n] = cand[2 * ((size_t)n * C + c)];
+      x[2 * (size_t)n + 1] = cand[2 * ((size_t)n * C + c) + 1];
+    }
+    if (best_loss != nullptr) best_loss[n] = loss[(size_t)n * C + c];
+  }
+}
+
+static bool wf_shape_ok(int dtype, int N, int F, int T) {
+  return (dtype == 0 || dtype == 1) && N >= 1 && F >= 1 && T >= 2 && T <= WF_MAX_T;
+}
+
+static size_t wf_loss_lds(int T) {
+  return ((size_t)WF_FR * (T + 1) + (size_t)WF_FR * T + (size_t)WF_CB * T) * sizeof(double) + (size_t)WF_CB * T * sizeof(int);
+}
+
+extern "C" int ava_warpfit_max_t(void) { return WF_MAX_T; }
+
+extern "C" int ava_warpfit_apply(const void* spec, int dtype, int N, int F, int T, const double* params, void* out,
+                                 ava_stream_t s) {
+  if (spec == nullptr || params == nullptr || out == nullptr || !wf_shape_ok(dtype, N, F, T)) return AVA_EINVAL;
+  const dim3 grid(N, F < 64 ? F : 64);
+  if (dtype == 0)
+    hipLaunchKernelGGL(warpfit_apply_kernel<float>, grid, dim3(256), 0, to_stream(s), static_cast<const float*>(spec), params,
+                       F, T, static_cast<float*>(out));
+  else
+    hipLaunchKernelGGL(warpfit_apply_kernel<double>, grid, dim3(256), 0, to_stream(s), static_cast<const double*>(spec),
+                       params, F, T, static_cast<double*>(out));
+  AVA_CHECK_LAUNCH();
+  return AVA_OK;
+}
+
+extern "C" int ava_warpfit_mean(const void* spec, int dtype, int N, int F, int T, double* target, ava_stream_t s) {
+  if (spec == nullptr || target == nullptr || !wf_shape_ok(dtype, N, F, T)) return AVA_EINVAL;
+  const int64_t FT = (int64_t)F * T;
+  if (ceil_div64(FT, 256) > 2147483647) return AVA_EINVAL;
+  const dim3 grid((unsigned)ceil_div64(FT, 256));
+  if (dtype == 0)
+    hipLaunchKernelGGL(warpfit_mean_kernel<float>, grid, dim3(256), 0, to_stream(s), static_cast<const float*>(spec), N, FT,
+                       target);
+  else
+    hipLaunchKernelGGL(warpfit_mean_kernel<double>, grid, dim3(256), 0, to_stream(s), static_cast<const double*>(spec), N, FT,
+                       target);
+  AVA_CHECK_LAUNCH();
+  return AVA_OK;
+}
+
+extern "C" int ava_warpfit_candidates(const double* x, int N, int T, int ks, int kl, double hs, double hl, double* cand,
+                                      ava_stream_t s) {
+  if (x == nullptr || cand == nullptr || N < 1 || T < 2 || T > WF_MAX_T || ks < 0 || kl < 0 || ks > 31 || kl > 31) return AVA_EINVAL;
+  if (!(hs >= 0.0) || !(hl >= 0.0) || (2 * ks + 1) * (2 * kl + 1) > WF_MAX_C) return AVA_EINVAL;
+  const int64_t total = (int64_t)N * (2 * ks + 1) * (2 * kl + 1);
+  if (ceil_div64(total, 256) > 2147483647) return AVA_EINVAL;
+  hipLaunchKernelGGL(warpfit_candidates_kernel, dim3((unsigned)ceil_div64(total, 256)), dim3(256), 0, to_stream(s), x, N, T, ks,
+                     kl, hs, hl, cand);
+  AVA_CHECK_LAUNCH();
+  return AVA_OK;
+}
+
+template <typename T_>
+static int wf_launch_loss(const T_* spec, int N, int F, int T, const double* target, const double* cand, int C,
+                          double shift_lambda, double slope_lambda, double* loss, hipStream_t st) {
+  static bool attr = false;
+  if (!attr) {
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&warpfit_loss_kernel<T_>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)wf_loss_lds(WF_MAX_T)) != hipSuccess)
+      return AVA_ELAUNCH;
+    attr = true;
+  }
+  const int fixed = slope_lambda > 1.7976931348623157e308;  // +inf: the shift objective
+  hipLaunchKernelGGL(warpfit_loss_kernel<T_>, dim3(N, ceil_div(C, WF_CB)), dim3(256), wf_loss_lds(T), st, spec, target, cand, F,
+                     T, C, shift_lambda, fixed ? 0.0 : slope_lambda, fixed, loss);
+  AVA_CHECK_LAUNCH();
+  return AVA_OK;
+}
+
+extern "C" int ava_warpfit_loss(const void* spec, int dtype, int N, int F, int T, const double* target, const double* cand,
+                                int C, double shift_lambda, double slope_lambda, double* loss, ava_stream_t s) {
+  if (spec == nullptr || target == nullptr || cand == nullptr || loss == nullptr || !wf_shape_ok(dtype, N, F, T)) return AVA_EINVAL;
+  if (C < 1 || C > WF_MAX_C || shift_lambda != shift_lambda || slope_lambda != slope_lambda) return AVA_EINVAL;
+  if (dtype == 0)
+    return wf_launch_loss(static_cast<const float*>(spec), N, F, T, target, cand, C, shift_lambda, slope_lambda, loss, to_stream(s));
+  return wf_launch_loss(static_cast<const double*>(spec), N, F, T, target, cand, C, shift_lambda, slope_lambda, loss, to_stream(s));
+}
+
+extern "C" int ava_warpfit_argmin(const double* loss, const double* cand, int N, int C, int32_t* best, double* x,
+                                  double* best_loss, ava_stream_t s) {
+  if (loss == nullptr || best == nullptr || N < 1 || C < 1 || C > WF_MAX_C) return AVA_EINVAL;
+  if (x != nullptr && cand == nullptr) return AVA_EINVAL;
+  hipLaunchKernelGGL(warpfit_argmin_kernel, dim3(ceil_div(N, 4)), dim3(256), 0, to_stream(s), loss, cand, N, C, best, x, best_loss);
+  AVA_CHECK_LAUNCH();
+  return AVA_OK;
+}

@@ -1,0 +1,273 @@
+"""The shift-and-slope time-warp fit on the device.
+
+Mirror of the reference's own replacement for affinewarp, ``ava/preprocessing/warping.py``:
+
+  ``apply_warp``              warping.py:25-50
+  ``align_specs``             warping.py:53-145    alternate a mean template with a per-spectrogram minimisation
+  ``minimize_warp``           warping.py:121-131   the ``scipy.optimize.minimize(method='Powell')`` of every motif, batched
+  ``warp_loss``               warping.py:148-163   both objectives, for a batch of candidates per motif
+  ``knots_from_warp_params``  the fitted shifts and slopes as the knots of ``DeviceWarpedWindowDataset``
+  ``install``                 points the reference module's two public functions here
+
+Every number is made by the kernels of ``csrc/warp_fit.hip`` in fp64; there is no CPU fallback.  The functions take
+numpy arrays or device tensors ``[N, F, T]`` of float32 or float64 and answer in kind (numpy in, numpy out) and in the
+input's dtype: like the reference, ``align_specs`` keeps the warped spectrograms in the input's dtype and takes the next
+iteration's mean template from those stored values.  ``T`` is at most ``ava_warpfit_max_t()`` = 512
+(``NotImplementedError``); N and F are unbounded.
+
+The search.  Powell is replaced by a deterministic derivative-free search made of batched loss evaluations.  Every round
+evaluates, for all motifs in one launch, a grid of candidates centred on the motif's current best: ``2 GRID_KS + 1 = 7``
+shifts in steps of ``hs`` times ``2 GRID_KL + 1 = 5`` log slopes in steps of ``hl``; with ``slope_λ = inf`` the grid is a
+line of ``2 LINE_KS + 1 = 15`` shifts.  A slope step pivots the warp about the middle column (the shift moves along with
+it), which keeps the two grid axes nearly independent directions of the objective.  The best candidate becomes the
+next centre -- the centre is candidate 0 and wins ties, so the loss never rises -- and both steps halve.  The first
+round spans ``shift ± T * SHIFT_SPAN`` (``T / 8`` columns) and ``log slope ± LOG_SLOPE_SPAN`` (0.25, slopes from 0.78
+to 1.28) about ``x0``; the search ends when both steps are below ``XTOL = 1e-4``, the ``xtol`` Powell is called with
+(16 rounds at T = 128).  Why the shift axis is the wide one: under linear interpolation the objective is piecewise
+quadratic in the shift, with a kink wherever a position crosses a column -- at slope 1 all columns cross together, at
+every whole shift -- so neighbouring cells can each hold a local minimum.  A grid that keeps only one cell on either
+side of its best point when it halves (5 points) was seen to settle in the cell next to the one Powell found, 1.2e-4
+above it in loss; 15 points keep 3.5 cells on either side, 7 points 1.5.  The number of rounds depends on ``T`` alone,
+so nothing is read back: one ``align_specs`` iteration is enqueued without a host synchronisation.  The search always
+returns a result: the reference's ``(None, None)`` on an optimiser failure has no counterpart here.
+"""
+import warnings
+
+import numpy as np
+import torch
+
+from . import _lib
+
+__all__ = ["WARNING_MSG", "XTOL", "GRID_KS", "GRID_KL", "LINE_KS", "SHIFT_SPAN", "LOG_SLOPE_SPAN", "DEFAULT_SHIFT_LAMBDAS",
+           "DEFAULT_SLOPE_LAMBDAS", "apply_warp", "align_specs", "minimize_warp", "warp_loss", "search_rounds",
+           "check_schedule", "knots_from_warp_params", "install"]
+
+WARNING_MSG = "ava.preprocessing.warping is experimental and may change in " + \
+    "a future version of AVA!"                 # warping.py:20-21
+
+XTOL = 1e-4                # scipy's default xtol of method='Powell' (warping.py:130 passes no options)
+GRID_KS, GRID_KL = 3, 2    # grid points on either side of the centre: shifts, log slopes
+LINE_KS = 7                # the same for the line of shifts searched when slope_λ = inf
+SHIFT_SPAN = 0.125         # half-span of the first round's shifts, as a fraction of T
+LOG_SLOPE_SPAN = 0.25      # half-span of the first round's log slopes
+
+# the schedule fit='device' of DeviceWarpedWindowDataset uses when warp_params names none: shift-only first, then
+# decreasing penalties down to the maximum-likelihood fit (the advice of the reference's docstring, warping.py:67-72)
+DEFAULT_SHIFT_LAMBDAS = (1e-2, 1e-2, 1e-2, 1e-2, 1e-3, 1e-3, 0.0, 0.0)
+DEFAULT_SLOPE_LAMBDAS = (np.inf, np.inf, np.inf, 1e2, 1e1, 1.0, 0.0, 0.0)
+
+_DTYPES = {torch.float32: 0, torch.float64: 1}
+
+
+def _specs_tensor(specs):
+    """``(contiguous device tensor [N, F, T], came as numpy)``"""
+    is_numpy = not torch.is_tensor(specs)
+    if is_numpy:
+        specs = np.asarray(specs)
+        if specs.dtype not in (np.float32, np.float64):
+            raise TypeError("spectrograms must be float32 or float64, got %s" % specs.dtype)
+        specs = torch.from_numpy(np.ascontiguousarray(specs)).to("cuda")
+    elif specs.dtype not in _DTYPES:
+        raise TypeError("spectrograms must be float32 or float64, got %s" % specs.dtype)
+    if specs.dim() != 3 or specs.shape[0] < 1 or specs.shape[1] < 1:
+        raise ValueError("expected spectrograms of shape [n_specs, freq_bins, time_bins]")
+    T = specs.shape[2]
+    if T < 2:
+        raise ValueError("a warp needs at least two time bins")
+    if T > _lib.load().ava_warpfit_max_t():
+        raise NotImplementedError("at most %d time bins per spectrogram" % _lib.load().ava_warpfit_max_t())
+    return specs.contiguous(), is_numpy
+
+
+def _f64(a, dev, shape):
+    t = a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype=np.float64)))
+    t = t.to(device=dev, dtype=torch.float64).contiguous()
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError("expected shape %s, got %s" % (tuple(shape), tuple(t.shape)))
+    return t
+
+
+def _apply(specs, params):
+    """``specs`` [N, F, T] under ``params`` [N, 2] = (shift, slope), device tensors; enqueued, nothing synchronises"""
+    N, F, T = specs.shape
+    out = torch.empty_like(specs)
+    rc = _lib.load().ava_warpfit_apply(specs.data_ptr(), _DTYPES[specs.dtype], N, F, T, params.data_ptr(), out.data_ptr(),
+                                       _lib.stream())
+    _lib.check(rc, "ava_warpfit_apply")
+    return out
+
+
+def apply_warp(specs, warp_params):
+    """``apply_warp`` (warping.py:25-50): ``warped[n, f, j] = interp1d(specs[n, f])(shifts[n] + slopes[n] * j)`` with the
+    end columns held outside the spectrogram.  ``warp_params`` maps ``'shifts'`` and ``'slopes'`` to ``[n_specs]``
+    arrays or tensors.  Same shape, dtype and kind (numpy array or device tensor) as ``specs``."""
+    specs, is_numpy = _specs_tensor(specs)
+    N = specs.shape[0]
+    params = torch.stack([_f64(warp_params['shifts'], specs.device, (N,)),
+                          _f64(warp_params['slopes'], specs.device, (N,))], dim=1).contiguous()
+    out = _apply(specs, params)
+    return out.cpu().numpy() if is_numpy else out
+
+
+def warp_loss(specs, target, candidates, shift_λ, slope_λ):
+    """The objectives of warping.py:148-163 for a batch of candidates: ``loss[n, c] = sum((interp(specs[n])(shift +
+    exp(log_slope) * arange(T)) - target) ** 2) + shift_λ * shift ** 2 + slope_λ * log_slope ** 2`` for ``candidates``
+    ``[N, C, 2]`` = (shift, log_slope).  With ``slope_λ = inf`` the slope is 1 and the slope term is dropped
+    (``_get_shift_objective``).  Sums run in a fixed order: two calls give the same bits.  Returns ``[N, C]`` float64
+    (numpy for numpy ``specs``)."""
+    specs, is_numpy = _specs_tensor(specs)
+    N, F, T = specs.shape
+    target = _f64(target, specs.device, (F, T))
+    cand = candidates if torch.is_tensor(candidates) else torch.from_numpy(np.asarray(candidates, dtype=np.float64))
+    if cand.dim() != 3 or cand.shape[0] != N or cand.shape[1] < 1 or cand.shape[2] != 2:
+        raise ValueError("expected candidates of shape [n_specs, n_candidates, 2]")
+    cand = cand.to(device=specs.device, dtype=torch.float64).contiguous()
+    shift_λ, slope_λ = _check_lambdas(shift_λ, slope_λ)
+    loss = torch.empty((N, cand.shape[1]), dtype=torch.float64, device=specs.device)
+    rc = _lib.load().ava_warpfit_loss(specs.data_ptr(), _DTYPES[specs.dtype], N, F, T, target.data_ptr(), cand.data_ptr(),
+                                      cand.shape[1], shift_λ, slope_λ, loss.data_ptr(), _lib.stream())
+    _lib.check(rc, "ava_warpfit_loss")
+    return loss.cpu().numpy() if is_numpy else loss
+
+
+def _check_lambdas(shift_λ, slope_λ):
+    shift_λ, slope_λ = float(shift_λ), float(slope_λ)
+    if not np.isfinite(shift_λ) or shift_λ < 0:
+        raise ValueError("shift_λ must be finite and not negative (only slope_λ may be inf), got %r" % shift_λ)
+    if np.isnan(slope_λ) or slope_λ < 0:
+        raise ValueError("slope_λ must be inf or not negative, got %r" % slope_λ)
+    return shift_λ, slope_λ
+
+
+def check_schedule(shift_λs, slope_λs):
+    """The two λ sequences of ``align_specs`` as lists of floats: equally long, not empty, every ``shift_λ`` finite and
+    not negative, every ``slope_λ`` not negative or ``inf`` (a shift-only iteration).  ``ValueError`` otherwise."""
+    shift_λs, slope_λs = list(shift_λs), list(slope_λs)
+    if len(shift_λs) != len(slope_λs):
+        raise ValueError("shift_λs and slope_λs must have one entry per iteration each: %d and %d entries"
+                         % (len(shift_λs), len(slope_λs)))
+    if len(shift_λs) == 0:
+        raise ValueError("an empty schedule fits nothing")
+    pairs = [_check_lambdas(a, b) for a, b in zip(shift_λs, slope_λs)]
+    return [a for a, _ in pairs], [b for _, b in pairs]
+
+
+def search_rounds(T, fixed_slope):
+    """``(ks, kl, [(hs, hl), ...])``: the grid half-widths and the grid steps of every round of ``minimize_warp`` for
+    ``T`` time bins.  The steps halve each round from ``T * SHIFT_SPAN / ks`` and ``LOG_SLOPE_SPAN / kl`` until both
+    (with ``fixed_slope``: the shift step) are below ``XTOL``."""
+    ks, kl = (LINE_KS, 0) if fixed_slope else (GRID_KS, GRID_KL)
+    hs, hl = T * SHIFT_SPAN / ks, LOG_SLOPE_SPAN / max(kl, 1)
+    rounds = []
+    while hs >= XTOL or (not fixed_slope and hl >= XTOL):
+        rounds.append((hs, hl))
+        hs, hl = hs / 2, hl / 2
+    return ks, kl, rounds
+
+
+def _minimize(specs, target, x, shift_λ, slope_λ, best_loss):
+    """the search of ``minimize_warp`` on device tensors; ``x`` [N, 2] and ``best_loss`` [N] are updated in place"""
+    lib = _lib.load()
+    N, F, T = specs.shape
+    fixed = slope_λ == np.inf
+    ks, kl, rounds = search_rounds(T, fixed)
+    C = (2 * ks + 1) * (2 * kl + 1)
+    dev, st = specs.device, _lib.stream()
+    cand = torch.empty((N, C, 2), dtype=torch.float64, device=dev)
+    loss = torch.empty((N, C), dtype=torch.float64, device=dev)
+    best = torch.empty(N, dtype=torch.int32, device=dev)
+    for hs, hl in rounds:
+        _lib.check(lib.ava_warpfit_candidates(x.data_ptr(), N, T, ks, kl, hs, hl, cand.data_ptr(), st),
+                   "ava_warpfit_candidates")
+        _lib.check(lib.ava_warpfit_loss(specs.data_ptr(), _DTYPES[specs.dtype], N, F, T, target.data_ptr(), cand.data_ptr(),
+                                        C, shift_λ, slope_λ, loss.data_ptr(), st), "ava_warpfit_loss")
+        _lib.check(lib.ava_warpfit_argmin(loss.data_ptr(), cand.data_ptr(), N, C, best.data_ptr(), x.data_ptr(),
+                                          best_loss.data_ptr(), st), "ava_warpfit_argmin")
+
+
+def minimize_warp(specs, target, x0, shift_λ, slope_λ):
+    """The per-motif minimisation ``align_specs`` calls (warping.py:121-131), for all motifs at once: ``(x [N, 2],
+    loss [N])`` with ``x`` = (shift, log_slope) minimising ``warp_loss(specs, target, ., shift_λ, slope_λ)`` from
+    ``x0`` [N, 2], by the grid search of the module docstring (first round ``shift ± T / 8``, ``log slope ± 0.25``
+    about ``x0``, halving to ``XTOL = 1e-4``).  With ``slope_λ = inf`` only the shift is searched and ``x[:, 1]`` is
+    ``x0[:, 1]`` (the objective ignores it).  The loss returned is never above the loss at ``x0``.  Unlike Powell the
+    search cannot fail: it always returns a result."""
+    specs, is_numpy = _specs_tensor(specs)
+    N, F, T = specs.shape
+    target = _f64(target, specs.device, (F, T))
+    x = _f64(x0, specs.device, (N, 2)).clone()
+    shift_λ, slope_λ = _check_lambdas(shift_λ, slope_λ)
+    best_loss = torch.empty(N, dtype=torch.float64, device=specs.device)
+    _minimize(specs, target, x, shift_λ, slope_λ, best_loss)
+    return (x.cpu().numpy(), best_loss.cpu().numpy()) if is_numpy else (x, best_loss)
+
+
+def align_specs(specs, shift_λs, slope_λs, verbose=True):
+    """``align_specs`` (warping.py:53-145): align the spectrograms ``[n_specs, freq_bins, time_bins]`` by per-spectrogram
+    shifts and slopes, alternating the mean warped spectrogram as the target with ``minimize_warp`` under
+    ``shift_λs[i]``, ``slope_λs[i]`` (``slope_λ = inf``: a shift-only iteration, after which the log slope is 0), for
+    ``min(len(shift_λs), len(slope_λs))`` iterations.  Returns ``(warped_specs, warp_params)``: the warped spectrograms
+    in the shape, dtype and kind of ``specs``, and ``{'shifts': [n_specs], 'slopes': [n_specs]}`` in time bins, such that
+    ``apply_warp(specs, warp_params)`` is ``warped_specs``.  Warns that the module is experimental, as the reference
+    does.  The iterations are enqueued back to back; the ``verbose`` lines (the last spectrogram's loss per iteration,
+    warping.py:141-143) are printed once all of them are.  There is no ``(None, None)`` return."""
+    warnings.warn(WARNING_MSG)
+    specs, is_numpy = _specs_tensor(specs)
+    N, F, T = specs.shape
+    lib, dev = _lib.load(), specs.device
+    total_iterations = min(len(shift_λs), len(slope_λs))
+    schedule = [_check_lambdas(shift_λs[i], slope_λs[i]) for i in range(total_iterations)]
+    warped = specs.clone()
+    x = torch.zeros((N, 2), dtype=torch.float64, device=dev)
+    params = torch.stack([x[:, 0], torch.exp(x[:, 1])], dim=1)
+    target = torch.empty((F, T), dtype=torch.float64, device=dev)
+    best_loss = torch.empty(N, dtype=torch.float64, device=dev)
+    last_losses = torch.zeros(max(total_iterations, 1), dtype=torch.float64, device=dev)
+    for warp_iter, (shift_λ, slope_λ) in enumerate(schedule):
+        _lib.check(lib.ava_warpfit_mean(warped.data_ptr(), _DTYPES[warped.dtype], N, F, T, target.data_ptr(),
+                                        _lib.stream()), "ava_warpfit_mean")
+        _minimize(specs, target, x, shift_λ, slope_λ, best_loss)
+        if slope_λ == np.inf:
+            x[:, 1] = 0.0                                   # slope = 1, log slope = 0 (warping.py:132-133)
+        params = torch.stack([x[:, 0], torch.exp(x[:, 1])], dim=1)
+        warped = _apply(specs, params)
+        last_losses[warp_iter] = best_loss[-1]
+    if verbose:
+        for warp_iter, loss in enumerate(last_losses[:total_iterations].cpu().numpy()):
+            print("Iteration {}, loss={}".format(warp_iter, round(float(loss), 3)))
+    warp_params = {'shifts': params[:, 0].contiguous(), 'slopes': params[:, 1].contiguous()}
+    if is_numpy:
+        return warped.cpu().numpy(), {k: v.cpu().numpy() for k, v in warp_params.items()}
+    return warped, warp_params
+
+
+def knots_from_warp_params(warp_params, num_time_bins):
+    """The fitted warps as knots of ``DeviceWarpedWindowDataset``: ``(x_knots [N, 2], y_knots [N, 2])`` in quantiles of
+    ``template_dur``.  Time bin ``j`` of the fit inputs is the STFT frame at ``j * frame_step`` seconds, i.e. at
+    quantile ``j / num_time_bins`` of ``template_dur = num_time_bins * frame_step``; ``warped(j) = spec(shift + slope *
+    j)`` therefore maps the template quantile ``y`` to the measured quantile ``x = shift / T + slope * y``:
+    ``y_knots = [0, 1]``, ``x_knots = [shift / T, shift / T + slope]``."""
+    shifts = np.asarray(_host(warp_params['shifts']), dtype=np.float64).reshape(-1)
+    slopes = np.asarray(_host(warp_params['slopes']), dtype=np.float64).reshape(-1)
+    if shifts.shape != slopes.shape:
+        raise ValueError("'shifts' and 'slopes' must have one entry per spectrogram each")
+    if not (slopes > 0).all():
+        raise ValueError("slopes must be positive")
+    T = float(num_time_bins)
+    x_knots = np.stack([shifts / T, shifts / T + slopes], axis=1)
+    y_knots = np.tile([0.0, 1.0], (len(shifts), 1))
+    return x_knots, y_knots
+
+
+def _host(a):
+    return a.detach().cpu().numpy() if torch.is_tensor(a) else a
+
+
+def install(module=None):
+    """Point ``align_specs`` and ``apply_warp`` of ``module`` (by default ``ava.preprocessing.warping``, imported after
+    the reference package) at this module."""
+    if module is None:
+        import ava.preprocessing.warping as module
+    module.align_specs = align_specs
+    module.apply_warp = apply_warp
+    return module

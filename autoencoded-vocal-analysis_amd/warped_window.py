@@ -18,7 +18,9 @@ uses, so a window is bit-identical to ``get_spec_batch(audio, file, 0.0, templat
 On the host stay: the window draw (``np.random`` in the reference's call order, so that a seeded batch is the
 reference's batch), the inverse warp (``scipy.interpolate.interp1d`` on ``n x T`` doubles), the knots file, and the
 optional warp fit, which is ``affinewarp.PiecewiseWarping.fit`` exactly as the reference calls it when ``affinewarp``
-can be imported (``ImportError`` otherwise; ``warp_type='null'`` and ``load_warp=True`` need no fit).
+can be imported (``ImportError`` otherwise; ``warp_type='null'`` and ``load_warp=True`` need no fit).  ``fit='device'``
+fits the reference's own shift-and-slope warp (``ava/preprocessing/warping.py``) on the device instead
+(``ava_amd.warp_fit``, row f12) and needs no affinewarp.
 
 Not mirrored: ``write_hdf5_files`` (``h5py`` is no dependency of this package).  Limits as ``spec.get_spec_batch``:
 ``nperseg`` in 64..2048, at most 512 target times per window (``NotImplementedError``); the fit inputs need ``nperseg``
@@ -112,22 +114,25 @@ def _stack_specs_and_amps(spec, fsum, frame_off, dtype):
 
 class DeviceWarpedWindowDataset:
     """``WarpedWindowDataset`` (window_vae_dataset.py:358-701) with the audio and the log-spectrogram of every motif
-    resident in HBM.  Same constructor arguments plus ``device`` (``transform`` is accepted and ignored: the items
-    already are fp32 device tensors); ``from_arrays`` builds one from in-memory recordings and knots.
+    resident in HBM.  Same constructor arguments plus ``device`` and ``fit`` (``'affinewarp'``: the reference's fit;
+    ``'device'``: ``ava_amd.warp_fit.align_specs``, one linear segment per file) (``transform`` is accepted and ignored:
+    the items already are fp32 device tensors); ``from_arrays`` builds one from in-memory recordings and knots.
 
     ``__getitem__(index, seed=None)``: for a list ``index`` one device tensor ``[len(index), F, T]`` (the reference
     returns a list of arrays), for an int ``[F, T]``.  With a ``seed`` the windows are the ones the reference draws."""
 
     def __init__(self, audio_filenames, p, transform=None, dataset_length=2048, load_warp=False, save_warp=True,
-                 start_q=-0.1, stop_q=1.1, warp_fn=None, warp_params={}, warp_type='spectrogram', device="cuda"):
+                 start_q=-0.1, stop_q=1.1, warp_fn=None, warp_params={}, warp_type='spectrogram', device="cuda",
+                 fit='affinewarp'):
         assert type(p) == type({})                                                   # :402
         assert warp_type in ['amplitude', 'spectrogram', 'null']                     # :403
+        assert fit in ['affinewarp', 'device']
         self.audio_filenames = sorted(audio_filenames)                               # :404
         audio = [_read_wav(fn)[1] for fn in self.audio_filenames]                    # :407
         fs = _read_wav(self.audio_filenames[0])[0]                                   # :408: the first SORTED name
         self.transform = transform
         self._setup(audio, fs, p, dataset_length, start_q, stop_q, warp_fn, warp_params, device)
-        self._compute_warp(load_warp=load_warp, save_warp=save_warp, warp_type=warp_type)
+        self._compute_warp(load_warp=load_warp, save_warp=save_warp, warp_type=warp_type, fit=fit)
         self._finish()
 
     @classmethod
@@ -188,8 +193,9 @@ class DeviceWarpedWindowDataset:
             self._audio = DeviceAudio(self._host_audio, self.device)
         return self._audio
 
-    def _compute_warp(self, load_warp=False, save_warp=True, warp_type='spectrogram'):
-        """window_vae_dataset.py:480-586"""
+    def _compute_warp(self, load_warp=False, save_warp=True, warp_type='spectrogram', fit='affinewarp'):
+        """window_vae_dataset.py:480-586.  ``fit='device'``: where the reference fits affinewarp's ``PiecewiseWarping``,
+        fit the shift-and-slope warp of ``ava_amd.warp_fit`` instead (with ``n_knots: 0`` the same family of warps)."""
         if save_warp:
             assert self.warp_fn is not None, "``warp_fn`` must be specified to save warps!"
         if warp_type == 'null':
@@ -241,6 +247,8 @@ class DeviceWarpedWindowDataset:
                     return
                 except IOError:
                     warnings.warn("Can't load warps from: " + str(self.warp_fn), UserWarning)
+        if fit == 'device':
+            return self._fit_on_device(warp_type, save_warp)
         try:
             from affinewarp import PiecewiseWarping
         except ImportError as e:
@@ -259,6 +267,39 @@ class DeviceWarpedWindowDataset:
             raise NotImplementedError
         self.x_knots = model.x_knots
         self.y_knots = model.y_knots
+        if save_warp:
+            print("Saving warp to:", self.warp_fn)
+            to_save = {
+                'x_knots': self.x_knots,
+                'y_knots': self.y_knots,
+                'template_dur': self.template_dur,
+                'audio_filenames': self.audio_filenames,
+                'amplitude_traces': amps,
+                'warp_params': self.warp_params,
+            }
+            np.save(self.warp_fn, to_save)
+
+    def _fit_on_device(self, warp_type, save_warp):
+        """The fit of ``fit='device'``: ``warp_fit.align_specs`` on the spectrograms (``warp_type='spectrogram'``) or the
+        amplitude traces (``'amplitude'``) of ``get_specs_and_amplitude_traces`` as ``[files, bins, frames]``, under the
+        schedule ``warp_params['shift_lambdas']`` / ``['slope_lambdas']`` (default: ``warp_fit.DEFAULT_*_LAMBDAS``);
+        the shifts and slopes become two knots per file.  The saved dict has the reference's keys."""
+        from . import warp_fit
+        shift_λs, slope_λs = warp_fit.check_schedule(self.warp_params.get('shift_lambdas', warp_fit.DEFAULT_SHIFT_LAMBDAS),
+                                                     self.warp_params.get('slope_lambdas', warp_fit.DEFAULT_SLOPE_LAMBDAS))
+        specs, amps, template_dur = get_specs_and_amplitude_traces(self.audio, self.fs, self.p)
+        self.template_dur = template_dur
+        if warp_type == 'amplitude':
+            print("Computing amplitude warp:", amps.shape)
+            fit_input = amps
+        elif warp_type == 'spectrogram':
+            print("Computing spectrogram warp:", specs.shape)
+            fit_input = specs
+        else:
+            raise NotImplementedError
+        _, fitted = warp_fit.align_specs(np.ascontiguousarray(fit_input.transpose(0, 2, 1)), shift_λs, slope_λs,
+                                         verbose=False)
+        self.x_knots, self.y_knots = warp_fit.knots_from_warp_params(fitted, fit_input.shape[1])
         if save_warp:
             print("Saving warp to:", self.warp_fn)
             to_save = {
@@ -402,16 +443,17 @@ class DeviceWarpedWindowDataset:
 
 
 def get_warped_window_data_loaders(audio_dirs, p, batch_size=64, num_workers=4, load_warp=False, warp_fn=None,
-                                   warp_params={}, warp_type='spectrogram', device="cuda"):
+                                   warp_params={}, warp_type='spectrogram', device="cuda", fit='affinewarp'):
     """Mirror of window_vae_dataset.py:297-354: ``{'train': loader, 'test': loader}``, the same loader twice, over a
-    ``DeviceWarpedWindowDataset`` of the wav files of ``audio_dirs``."""
+    ``DeviceWarpedWindowDataset`` of the wav files of ``audio_dirs``.  ``fit``: as the dataset's."""
     assert type(p) == type({})
     assert warp_type in ['amplitude', 'spectrogram', 'null']
+    assert fit in ['affinewarp', 'device']
     audio_fns = []
     for audio_dir in audio_dirs:
         audio_fns += _get_wavs_from_dir(audio_dir)
     dataset = DeviceWarpedWindowDataset(audio_fns, p, load_warp=load_warp, warp_fn=warp_fn, warp_params=warp_params,
-                                        warp_type=warp_type, device=device)
+                                        warp_type=warp_type, device=device, fit=fit)
     dataloader = DeviceWindowLoader(dataset, batch_size=batch_size, shuffle=True, num_workers=num_workers)
     return {'train': dataloader, 'test': dataloader}
 

@@ -462,6 +462,40 @@ int ava_warp_band_spec(const void* audio, int audio_dtype, const int64_t* file_o
                        const double* window, double scale, int k0, int k1, double spec_min, double divisor, double* spec,
                        double* frame_sum, ava_stream_t s);
 
+/* ---- the shift-and-slope time-warp fit ---------------------------------------------
+ * ava/preprocessing/warping.py: apply_warp (:25-50), align_specs (:53-145) and its two objectives (:148-163).
+ * spec / dtype: [N][F][T] contiguous on the device, 0 = float32, 1 = float64; 2 <= T <= ava_warpfit_max_t() (512: the
+ * loss kernel keeps a candidate block's column tables and a set of rows in LDS); N, F >= 1.  All arithmetic is fp64 and
+ * no kernel uses atomics: every result is bit-reproducible.  Linear interpolation is scipy's interp1d on the grid
+ * 0 .. T-1, operation for operation: value = (y[lo+1] - y[lo]) * (p - lo) + y[lo] with lo = clip(ceil(p), 1, T-1) - 1,
+ * nothing fused; p < 0 gives y[0], p > T-1 gives y[T-1], p == T-1 reads columns T-2 and T-1.
+ *
+ * ava_warpfit_apply: out[n][f][j] = interp(spec[n][f][:])(shift_n + slope_n j), out of spec's dtype.
+ *   params [N][2] float64 = (shift, slope).
+ * ava_warpfit_mean: target [F][T] float64 = the sum over n = 0, 1, ... in that order, divided by N.
+ * ava_warpfit_candidates: cand [N][C][2] = (shift, log slope), C = (2 ks + 1)(2 kl + 1), around x [N][2]: candidate
+ *   c = a (2 kl + 1) + b with the offsets oa, ob = 0, -1, +1, -2, +2, ... of a and b, so candidate 0 is x itself;
+ *   log slope = x1 + ob hl and shift = x0 + oa hs - (exp(log slope) - exp(x1)) (T - 1) / 2 (the warp pivots about the
+ *   middle column).  0 <= ks, kl <= 31, C <= 4096, hs, hl >= 0.
+ * ava_warpfit_loss: loss [N][C] float64 = sum_{f,j} (interp(spec[n][f][:])(shift + exp(log slope) j) - target[f][j])^2
+ *   + shift_lambda shift^2 + slope_lambda (log slope)^2 for every candidate of cand [N][C][2].  slope_lambda = +inf:
+ *   the slope is 1 whatever the candidate says and the slope term is dropped (_get_shift_objective).  1 <= C <= 4096.
+ * ava_warpfit_argmin: best [N] int32 = the candidate of least loss; equal losses resolve to the lowest index, NaN never
+ *   wins, a motif whose losses are all NaN gets 0.  x [N][2] (needs cand) and best_loss [N] receive that candidate's
+ *   parameters and loss when not null.
+ *
+ * All return AVA_EINVAL before any launch for null pointers, an unknown dtype, N, F or C < 1, T < 2 or T over the cap,
+ * a NaN lambda or a grid outside the limits above. */
+int ava_warpfit_max_t(void);
+int ava_warpfit_apply(const void* spec, int dtype, int N, int F, int T, const double* params, void* out, ava_stream_t s);
+int ava_warpfit_mean(const void* spec, int dtype, int N, int F, int T, double* target, ava_stream_t s);
+int ava_warpfit_candidates(const double* x, int N, int T, int ks, int kl, double hs, double hl, double* cand,
+                           ava_stream_t s);
+int ava_warpfit_loss(const void* spec, int dtype, int N, int F, int T, const double* target, const double* cand, int C,
+                     double shift_lambda, double slope_lambda, double* loss, ava_stream_t s);
+int ava_warpfit_argmin(const double* loss, const double* cand, int N, int C, int32_t* best, double* x, double* best_loss,
+                       ava_stream_t s);
+
 /* ---- exact 1-nearest-neighbour search ------------------------------------------------
  * The searches of ava/plotting/shotgun_movie.py:shotgun_movie_DC: NearestNeighbors(n_neighbors=1,
  * metric='correlation') over spectrograms (:148-158) and argmin of scipy's euclidean over latent means (:126-133).
