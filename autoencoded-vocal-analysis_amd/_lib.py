@@ -133,6 +133,9 @@ SIGNATURES = {
     "ava_pj_smooth": (_i, [_p, _p, _i, _i, _d, _p, _p, _p, _p, _p]),
     "ava_pj_layout": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i64, _i, _i, _i, _d, _d, _d, _d, C.c_uint64, _p, _p]),
     "ava_pj_knn_query": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p]),
+    "ava_pj_row_stats": (_i, [_p, _i, _i, _i, _p, _p]),
+    "ava_pj_knn_corr": (_i, [_p, _i, _p, _i, _i, _i, _i, _i, _p, _p, _p]),
+    "ava_pj_knn_corr_query": (_i, [_p, _p, _i, _p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _p]),
     "ava_pj_smooth_bipartite": (_i, [_p, _p, _i, _i, _d, _p, _p, _p, _p, _p]),
     "ava_pj_transform_init": (_i, [_p, _p, _p, _i, _i, _p, _p, _p]),
     "ava_pj_transform_layout": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _d, _d, _d, _d, C.c_uint64, _p, _p]),

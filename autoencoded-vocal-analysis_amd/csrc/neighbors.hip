@@ -6,9 +6,9 @@
 // arithmetic is fp64, like scipy's.
 //
 // Correlation: scipy centres both operands (x - mean(x)) and takes the cosine distance of the centred rows.  Here the
-// row statistics kernel computes every row's fp64 mean and centred sum of squares (fixed-order two-stage reduction),
-// and the tile kernel subtracts the mean while it converts the operands to fp64 into LDS -- the dot products are of
-// the centred values, never sum(uv) - d u v, which cancels for the near-constant rows real spectrograms have.  A
+// row statistics kernel computes every row's fp64 mean and centred sum of squares, and the tile kernel subtracts the
+// mean while it converts the operands to fp64 into LDS; the statistics, the staging and the MFMA stage are the shared
+// pieces of corr_tile.h, which states the order of every sum.  A
 // workgroup owns 128 queries x 128 references; each of its four waves a 64 x 64 quarter, i.e. 4 x 4 blocks of
 // v_mfma_f64_16x16x4_f64 (16 accumulators of 4 doubles per lane).  The epilogue forms 1 - dot / sqrt(ss_q ss_r)
 // (clipped to [0, 2] as scipy clips the cosine) and writes one (dist, idx) partial per (query, reference tile).
@@ -19,12 +19,13 @@
 // A fixed-order reduce kernel combines the partials of each query.  The candidates are ordered by nn_better, a total
 // order, so every tile, every reduce step and the host's merge of reference chunks pick the same winner: the result
 // is bit-reproducible and independent of the tiling and of the chunking (the euclidean sums: the order contract of
-// sqdist_tile.h; the correlation dot products run over k in one fixed order, whatever tile they fall in).
+// sqdist_tile.h; the correlation dot products: that of corr_tile.h).
 //   ties        equal distances resolve to the lowest reference index
 //   correlation a zero-variance row gives NaN (0 / 0, as scipy); NaN loses to any number; a query whose distances are
 //               all NaN gets index 0 and distance NaN
 //   euclidean   NaN wins and the first NaN is taken, as np.argmin does
 #include "common.h"
+#include "corr_tile.h"
 #include "sqdist_tile.h"
 
 #define NN_CORR 0
@@ -32,10 +33,6 @@
 
 #define NC_BQ 128        // correlation tile: queries
 #define NC_BR 128        //                   references
-#define NC_KC 16         // k per LDS stage
-#define NC_LD 17         // LDS row stride in doubles (odd: the staging writes and fragment reads spread over the banks)
-
-typedef double nn_d4 __attribute__((ext_vector_type(4)));
 
 // true when candidate (d1, i1) beats (d2, i2); an empty candidate (index < 0) loses to everything
 __device__ __forceinline__ bool nn_better(double d1, int64_t i1, double d2, int64_t i2, int nan_wins) {
@@ -61,27 +58,7 @@ __device__ __forceinline__ void nn_best16(double& d, int64_t& i, int nan_wins) {
 template <typename T>
 __global__ __launch_bounds__(256) void nn_row_stats_kernel(const T* __restrict__ x, int d, double* __restrict__ stats) {
   __shared__ double red[4];
-  const int t = threadIdx.x;
-  const T* row = x + (size_t)blockIdx.x * d;
-  double s = 0.0;
-  for (int k = t; k < d; k += 256) s += (double)row[k];
-  s = wave_sum_d(s);
-  if ((t & 63) == 0) red[t >> 6] = s;
-  __syncthreads();
-  const double mean = ((red[0] + red[1]) + (red[2] + red[3])) / (double)d;
-  __syncthreads();
-  double q = 0.0;
-  for (int k = t; k < d; k += 256) {
-    const double c = (double)row[k] - mean;
-    q = fma(c, c, q);
-  }
-  q = wave_sum_d(q);
-  if ((t & 63) == 0) red[t >> 6] = q;
-  __syncthreads();
-  if (t == 0) {
-    stats[2 * (size_t)blockIdx.x] = mean;
-    stats[2 * (size_t)blockIdx.x + 1] = (red[0] + red[1]) + (red[2] + red[3]);
-  }
+  corr_row_stats(x + (size_t)blockIdx.x * d, d, threadIdx.x, red, stats + 2 * (size_t)blockIdx.x);
 }
 
 // one (dist, idx) partial per (query, 128-reference tile): partial[q * rtiles + tile]
@@ -90,8 +67,8 @@ __global__ __launch_bounds__(256) void nn_corr_kernel(const TQ* __restrict__ Q, 
                                                       int d, const double* __restrict__ qstat,
                                                       const double* __restrict__ rstat, int rtiles,
                                                       double* __restrict__ pdist, int64_t* __restrict__ pidx) {
-  __shared__ double qs[NC_BQ * NC_LD];
-  __shared__ double rs[NC_BR * NC_LD];
+  __shared__ double qs[NC_BQ * CORR_LD];
+  __shared__ double rs[NC_BR * CORR_LD];
   __shared__ double qm[NC_BQ], rm[NC_BR];
   __shared__ double bd[2][NC_BQ];
   __shared__ int64_t bi[2][NC_BQ];
@@ -104,51 +81,25 @@ __global__ __launch_bounds__(256) void nn_corr_kernel(const TQ* __restrict__ Q, 
   } else {
     rm[t - NC_BQ] = r0 + t - NC_BQ < nr ? rstat[2 * (size_t)(r0 + t - NC_BQ)] : 0.0;
   }
-  // staging: element t + 256 j (j < 8) of a 128 x 16 stage is row (t >> 4) + 16 j, column t & 15
-  const int sc = t & 15, sr = t >> 4;
-  TQ vq[8];
-  TR vr[8];
-  auto fetch = [&](int k0) {
-    const int k = k0 + sc;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int gq = q0 + sr + 16 * j, gr = r0 + sr + 16 * j;
-      vq[j] = (k < d && gq < nq) ? Q[(size_t)gq * d + k] : (TQ)0;
-      vr[j] = (k < d && gr < nr) ? R[(size_t)gr * d + k] : (TR)0;
-    }
-  };
-  nn_d4 acc[4][4];
+  TQ vq[NC_BQ / 16];
+  TR vr[NC_BR / 16];
+  corr_d4 acc[4][4];
 #pragma unroll
   for (int a = 0; a < 4; ++a)
 #pragma unroll
-    for (int b = 0; b < 4; ++b) acc[a][b] = nn_d4{0.0, 0.0, 0.0, 0.0};
-  fetch(0);
+    for (int b = 0; b < 4; ++b) acc[a][b] = corr_d4{0.0, 0.0, 0.0, 0.0};
+  corr_fetch<NC_BQ>(vq, Q, q0, nq, d, 0, t);
+  corr_fetch<NC_BR>(vr, R, r0, nr, d, 0, t);
   __syncthreads();                                   // qm / rm
-  for (int k0 = 0; k0 < d; k0 += NC_KC) {
-    const bool kin = k0 + sc < d;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int r = sr + 16 * j;
-      // centred on the fp64 conversion; padding rows / columns stay exactly 0
-      qs[r * NC_LD + sc] = (kin && q0 + r < nq) ? (double)vq[j] - qm[r] : 0.0;
-      rs[r * NC_LD + sc] = (kin && r0 + r < nr) ? (double)vr[j] - rm[r] : 0.0;
-    }
+  for (int k0 = 0; k0 < d; k0 += CORR_KC) {
+    corr_store<NC_BQ>(qs, vq, qm, q0, nq, d, k0, t);
+    corr_store<NC_BR>(rs, vr, rm, r0, nr, d, k0, t);
     __syncthreads();
-    if (k0 + NC_KC < d) fetch(k0 + NC_KC);           // next stage's loads in flight during the MFMAs
-#pragma unroll
-    for (int kk = 0; kk < NC_KC / 4; ++kk) {
-      // A: lane holds A[row lane & 15][k lane >> 4]; B: B[k lane >> 4][col lane & 15]
-      double fa[4], fb[4];
-#pragma unroll
-      for (int b = 0; b < 4; ++b) {
-        fa[b] = qs[(wq * 64 + b * 16 + (lane & 15)) * NC_LD + kk * 4 + (lane >> 4)];
-        fb[b] = rs[(wr * 64 + b * 16 + (lane & 15)) * NC_LD + kk * 4 + (lane >> 4)];
-      }
-#pragma unroll
-      for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int b = 0; b < 4; ++b) acc[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(fa[a], fb[b], acc[a][b], 0, 0, 0);
+    if (k0 + CORR_KC < d) {                          // next stage's loads in flight during the MFMAs
+      corr_fetch<NC_BQ>(vq, Q, q0, nq, d, k0 + CORR_KC, t);
+      corr_fetch<NC_BR>(vr, R, r0, nr, d, k0 + CORR_KC, t);
     }
+    corr_mfma_stage<4, 4>(qs, rs, wq * 64, wr * 64, lane, acc);
     __syncthreads();
   }
   // epilogue: f64 C/D layout col = lane & 15, row = (lane >> 4) + 4 reg

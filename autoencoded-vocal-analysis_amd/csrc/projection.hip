@@ -6,6 +6,9 @@
 //           the references in 64-row tiles (the fp64 direct-difference tile of sqdist_tile.h, which states the order
 //           of every sum); each query keeps a running top-(k-1) list in LDS ordered by (distance, index), the query
 //           itself excluded.  Column 0 of the output is the row itself at distance 0.
+// kNN corr  the same table under umap-learn's correlation distance (TransformableUMAP(metric='correlation')): the
+//           centred dot products of corr_tile.h on the fp64 matrix cores, the row statistics from a kernel of their
+//           own; the lists, the fold and both modes are the euclidean kernel's.  Every distance is finite.
 // smooth    umap's smooth_knn_dist + compute_membership_strengths, one row per thread.
 // layout    one synchronous, gather-only SGD epoch per launch over the symmetric CSR graph (rows = heads): a thread
 //           per vertex sums, in CSR order, the attractive moves of its active edges and their negative samples, all
@@ -18,6 +21,7 @@
 // PCA       column sums and X^T X as the Gram matrix of [X, 1] (chunks of rows, chunks summed in order), and the
 //           projection X V^T - mu V^T.
 #include "common.h"
+#include "corr_tile.h"
 #include "sqdist_tile.h"
 
 #define PJ_DLD 65        // distance tile row stride (doubles)
@@ -31,6 +35,46 @@
 __device__ __forceinline__ bool pj_before(double d1, int i1, double d2, int i2) {
   if (i2 < 0) return true;
   return d1 < d2 || (d1 == d2 && i1 < i2);
+}
+
+// one thread folds the candidates of a distance tile's row (references r0 + c at distance row[c], c < cn, in reference
+// order) into the running list of local query t (global row q): m slots ordered by (distance, index), slot s at
+// [s * 64 + t]; with exclude_self reference q is skipped
+__device__ __forceinline__ void pj_fold_tile(const double* row, int r0, int cn, int q, int exclude_self, int m,
+                                             double* ld, int* li, int t) {
+  double wd = ld[(m - 1) * SQD_T + t];
+  int wi = li[(m - 1) * SQD_T + t];
+  for (int c = 0; c < cn; ++c) {
+    const int r = r0 + c;
+    const double dd = row[c];
+    if ((exclude_self && r == q) || !pj_before(dd, r, wd, wi)) continue;
+    int s = m - 1;
+    while (s > 0 && pj_before(dd, r, ld[(s - 1) * SQD_T + t], li[(s - 1) * SQD_T + t])) {
+      ld[s * SQD_T + t] = ld[(s - 1) * SQD_T + t];
+      li[s * SQD_T + t] = li[(s - 1) * SQD_T + t];
+      --s;
+    }
+    ld[s * SQD_T + t] = dd;
+    li[s * SQD_T + t] = r;
+    wd = ld[(m - 1) * SQD_T + t];
+    wi = li[(m - 1) * SQD_T + t];
+  }
+}
+
+// the lists of local query t (global row q, output row orow) to the table: with exclude_self column 0 is the row itself
+__device__ __forceinline__ void pj_write_list(size_t orow, int q, int k, int exclude_self, const double* ld,
+                                              const int* li, int t, int64_t* __restrict__ out_idx,
+                                              double* __restrict__ out_dist) {
+  const size_t o = orow * k;
+  const int m = k - exclude_self;
+  if (exclude_self) {
+    out_idx[o] = q;
+    out_dist[o] = 0.0;
+  }
+  for (int s = 0; s < m; ++s) {
+    out_idx[o + exclude_self + s] = li[s * SQD_T + t];
+    out_dist[o + exclude_self + s] = ld[s * SQD_T + t];
+  }
 }
 
 // rows [q0, q0 + nq) of the kNN table of the query rows Q among the n reference rows X; dynamic LDS holds the running
@@ -73,41 +117,112 @@ __global__ __launch_bounds__(256) void pj_knn_kernel(const T* __restrict__ Q, co
 #pragma unroll
       for (int j = 0; j < 4; ++j) dt[(ty + 16 * i) * PJ_DLD + tx + 16 * j] = sqrt(acc[i][j]);
     __syncthreads();
-    // one thread per query folds the tile's candidates into its list, in reference order
-    if (t < SQD_T && qb + t < qe && m > 0) {
-      const int q = qb + t;
-      const int cn = n - r0 < SQD_T ? n - r0 : SQD_T;
-      double wd = ld[(m - 1) * SQD_T + t];
-      int wi = li[(m - 1) * SQD_T + t];
-      for (int c = 0; c < cn; ++c) {
-        const int r = r0 + c;
-        const double dd = dt[t * PJ_DLD + c];
-        if ((exclude_self && r == q) || !pj_before(dd, r, wd, wi)) continue;
-        int s = m - 1;
-        while (s > 0 && pj_before(dd, r, ld[(s - 1) * SQD_T + t], li[(s - 1) * SQD_T + t])) {
-          ld[s * SQD_T + t] = ld[(s - 1) * SQD_T + t];
-          li[s * SQD_T + t] = li[(s - 1) * SQD_T + t];
-          --s;
-        }
-        ld[s * SQD_T + t] = dd;
-        li[s * SQD_T + t] = r;
-        wd = ld[(m - 1) * SQD_T + t];
-        wi = li[(m - 1) * SQD_T + t];
-      }
-    }
+    if (t < SQD_T && qb + t < qe && m > 0)
+      pj_fold_tile(dt + t * PJ_DLD, r0, n - r0 < SQD_T ? n - r0 : SQD_T, qb + t, exclude_self, m, ld, li, t);
   }
   __syncthreads();
-  if (t < SQD_T && qb + t < qe) {
-    const size_t o = (size_t)(qb + t - q0) * k;
-    if (exclude_self) {
-      out_idx[o] = qb + t;
-      out_dist[o] = 0.0;
-    }
-    for (int s = 0; s < m; ++s) {
-      out_idx[o + exclude_self + s] = li[s * SQD_T + t];
-      out_dist[o + exclude_self + s] = ld[s * SQD_T + t];
-    }
+  if (t < SQD_T && qb + t < qe)
+    pj_write_list((size_t)(qb + t - q0), qb + t, k, exclude_self, ld, li, t, out_idx, out_dist);
+}
+
+// stats[2 r] = mean of row r, stats[2 r + 1] = sum_k (x_rk - mean)^2 (corr_tile.h): one workgroup per row
+template <typename T>
+__global__ __launch_bounds__(256) void pj_row_stats_kernel(const T* __restrict__ x, int d, double* __restrict__ stats) {
+  __shared__ double red[4];
+  corr_row_stats(x + (size_t)blockIdx.x * d, d, threadIdx.x, red, stats + 2 * (size_t)blockIdx.x);
+}
+
+// umap-learn's correlation distance of two rows from their centred dot product and centred sums of squares:
+// 1 - dot / sqrt(ss_q ss_r) with the cosine clipped to [-1, 1]; 0 when both rows have no variance, 1 when exactly one
+// has none.  Always finite: a quotient that is no number (a product of sums of squares that left the fp64 range)
+// counts as cosine 0.
+__device__ __forceinline__ double pj_corr_dist(double dot, double ssq, double ssr) {
+  if (ssq == 0.0 || ssr == 0.0) return (ssq == 0.0 && ssr == 0.0) ? 0.0 : 1.0;
+  double c = dot / sqrt(ssq * ssr);
+  if (!(fabs(c) <= 1.0)) c = isnan(c) ? 0.0 : copysign(1.0, c);
+  return 1.0 - c;
+}
+
+// The correlation counterpart of pj_knn_kernel: same modes, same lists, same fold, same output.  A workgroup owns 64
+// query rows and walks the references in 64-row tiles; each of its four waves owns a 32 x 32 quarter of the tile,
+// 2 x 2 blocks of v_mfma_f64_16x16x4_f64 over the centred operands (the stages and the order of corr_tile.h: 16
+// columns per stage, 4 per MFMA step).  The accumulators go through pj_corr_dist into the 64 x 64 distance tile in
+// LDS (C/D layout: col = lane & 15, row = (lane >> 4) + 4 reg), which one thread per query folds into its list.
+// LDS: 33 280 B static for the distance tile (64 x 65 doubles; its first 17 408 B are the two 64 x 17 staging buffers
+// while the MFMAs run), 2 048 B for the means and sums of squares of the 64 + 64 rows, and 768 (k - exclude_self) B of
+// dynamic lists: 84 480 B at k = 64 in query mode, of the 160 KiB a workgroup may use.
+template <typename T>
+__global__ __launch_bounds__(256) void pj_knn_corr_kernel(const T* __restrict__ Q, const T* __restrict__ X,
+                                                          const double* __restrict__ qstat,
+                                                          const double* __restrict__ xstat, int n, int d, int k, int q0,
+                                                          int nq, int exclude_self, int64_t* __restrict__ out_idx,
+                                                          double* __restrict__ out_dist) {
+  __shared__ double stage[SQD_T * PJ_DLD];          // qs | rs while staging, then the 64 x 64 distance tile
+  __shared__ double qm[SQD_T], qss[SQD_T], rm[SQD_T], rss[SQD_T];
+  extern __shared__ double lists[];                 // m x 64 distances, then m x 64 int indices
+  double* qs = stage;
+  double* rs = stage + SQD_T * CORR_LD;
+  double* dt = stage;
+  const int m = k - exclude_self;
+  double* ld = lists;
+  int* li = reinterpret_cast<int*>(lists + (size_t)m * SQD_T);
+  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+  const int wq = w & 1, wr = w >> 1;                 // this wave's 32 x 32 quarter of the tile
+  const int qb = q0 + blockIdx.x * SQD_T;            // first query row of this workgroup
+  const int qe = q0 + nq;
+  for (int s = t; s < m * SQD_T; s += 256) {
+    ld[s] = 0.0;
+    li[s] = -1;
   }
+  if (t < SQD_T) {
+    const bool in = qb + t < qe;
+    qm[t] = in ? qstat[2 * (size_t)(qb + t)] : 0.0;
+    qss[t] = in ? qstat[2 * (size_t)(qb + t) + 1] : 1.0;
+  }
+  T vq[SQD_T / 16], vr[SQD_T / 16];
+  for (int r0 = 0; r0 < n; r0 += SQD_T) {
+    __syncthreads();                                 // previous tile folded: the buffer and rm / rss are free
+    if (t < SQD_T) {
+      const bool in = r0 + t < n;
+      rm[t] = in ? xstat[2 * (size_t)(r0 + t)] : 0.0;
+      rss[t] = in ? xstat[2 * (size_t)(r0 + t) + 1] : 1.0;
+    }
+    corr_d4 acc[2][2];
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+      for (int b = 0; b < 2; ++b) acc[a][b] = corr_d4{0.0, 0.0, 0.0, 0.0};
+    corr_fetch<SQD_T>(vq, Q, qb, qe, d, 0, t);
+    corr_fetch<SQD_T>(vr, X, r0, n, d, 0, t);
+    __syncthreads();                                 // qm / rm
+    for (int k0 = 0; k0 < d; k0 += CORR_KC) {
+      corr_store<SQD_T>(qs, vq, qm, qb, qe, d, k0, t);
+      corr_store<SQD_T>(rs, vr, rm, r0, n, d, k0, t);
+      __syncthreads();
+      if (k0 + CORR_KC < d) {                        // next stage's loads in flight during the MFMAs
+        corr_fetch<SQD_T>(vq, Q, qb, qe, d, k0 + CORR_KC, t);
+        corr_fetch<SQD_T>(vr, X, r0, n, d, k0 + CORR_KC, t);
+      }
+      corr_mfma_stage<2, 2>(qs, rs, wq * 32, wr * 32, lane, acc);
+      __syncthreads();                               // staging reads done: the next stage / the tile reuses the buffer
+    }
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+      for (int b = 0; b < 2; ++b)
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) {
+          const int lr = wq * 32 + a * 16 + (lane >> 4) + 4 * reg;
+          const int lc = wr * 32 + b * 16 + (lane & 15);
+          dt[lr * PJ_DLD + lc] = pj_corr_dist(acc[a][b][reg], qss[lr], rss[lc]);
+        }
+    __syncthreads();
+    if (t < SQD_T && qb + t < qe && m > 0)
+      pj_fold_tile(dt + t * PJ_DLD, r0, n - r0 < SQD_T ? n - r0 : SQD_T, qb + t, exclude_self, m, ld, li, t);
+  }
+  __syncthreads();
+  if (t < SQD_T && qb + t < qe)
+    pj_write_list((size_t)(qb + t - q0), qb + t, k, exclude_self, ld, li, t, out_idx, out_dist);
 }
 
 // mean of the whole [n][k] distance table: thread t sums rows t, t + 256, ... (each row left to right), then a fixed tree
@@ -454,6 +569,53 @@ extern "C" int ava_pj_knn_query(const void* q, const void* x, int dtype, int m, 
     return AVA_EINVAL;
   if (dtype == 0) return pj_knn_launch<float>(q, x, n, d, k, q0, nq, 0, out_idx, out_dist, to_stream(s));
   return pj_knn_launch<double>(q, x, n, d, k, q0, nq, 0, out_idx, out_dist, to_stream(s));
+}
+
+template <typename T>
+static int pj_knn_corr_launch(const void* q, const void* x, const double* qstat, const double* xstat, int n, int d,
+                              int k, int q0, int nq, int exclude_self, int64_t* idx, double* dist, hipStream_t st) {
+  const size_t lds = (size_t)(k - exclude_self) * SQD_T * (sizeof(double) + sizeof(int));
+  hipLaunchKernelGGL(pj_knn_corr_kernel<T>, dim3(ceil_div(nq, SQD_T)), dim3(256), lds, st,
+                     reinterpret_cast<const T*>(q), reinterpret_cast<const T*>(x), qstat, xstat, n, d, k, q0, nq,
+                     exclude_self, idx, dist);
+  AVA_CHECK_LAUNCH();
+  return AVA_OK;
+}
+
+extern "C" int ava_pj_row_stats(const void* x, int dtype, int n, int d, double* stats, ava_stream_t s) {
+  if (x == nullptr || stats == nullptr || (dtype != 0 && dtype != 1) || n < 1 || d < 1 || d > 65536)
+    return AVA_EINVAL;
+  hipStream_t st = to_stream(s);
+  if (dtype == 0)
+    hipLaunchKernelGGL(pj_row_stats_kernel<float>, dim3(n), dim3(256), 0, st, reinterpret_cast<const float*>(x), d,
+                       stats);
+  else
+    hipLaunchKernelGGL(pj_row_stats_kernel<double>, dim3(n), dim3(256), 0, st, reinterpret_cast<const double*>(x), d,
+                       stats);
+  AVA_CHECK_LAUNCH();
+  return AVA_OK;
+}
+
+extern "C" int ava_pj_knn_corr(const void* x, int dtype, const double* xstat, int n, int d, int k, int q0, int nq,
+                               int64_t* out_idx, double* out_dist, ava_stream_t s) {
+  if (x == nullptr || xstat == nullptr || out_idx == nullptr || out_dist == nullptr || (dtype != 0 && dtype != 1) ||
+      !pj_knn_ok(n, d, k, q0, nq))
+    return AVA_EINVAL;
+  if (dtype == 0)
+    return pj_knn_corr_launch<float>(x, x, xstat, xstat, n, d, k, q0, nq, 1, out_idx, out_dist, to_stream(s));
+  return pj_knn_corr_launch<double>(x, x, xstat, xstat, n, d, k, q0, nq, 1, out_idx, out_dist, to_stream(s));
+}
+
+extern "C" int ava_pj_knn_corr_query(const void* q, const void* x, int dtype, const double* qstat, const double* xstat,
+                                     int m, int n, int d, int k, int q0, int nq, int64_t* out_idx, double* out_dist,
+                                     ava_stream_t s) {
+  if (q == nullptr || x == nullptr || qstat == nullptr || xstat == nullptr || out_idx == nullptr ||
+      out_dist == nullptr || (dtype != 0 && dtype != 1) || n < 1 || m < 1 || d < 1 || d > 65536 || k < 1 ||
+      k > PJ_MAX_K || k > n || q0 < 0 || nq < 1 || (int64_t)q0 + nq > m)
+    return AVA_EINVAL;
+  if (dtype == 0)
+    return pj_knn_corr_launch<float>(q, x, qstat, xstat, n, d, k, q0, nq, 0, out_idx, out_dist, to_stream(s));
+  return pj_knn_corr_launch<double>(q, x, qstat, xstat, n, d, k, q0, nq, 0, out_idx, out_dist, to_stream(s));
 }
 
 static int pj_smooth_launch(const double* dist, const int64_t* idx, int n, int k, double local_connectivity,

@@ -10,6 +10,9 @@
                       0.65 GB for the 10 000 spectrograms of ~16 000 bins that ``refine_segments`` fits) and embeds
                       new rows with ``transform``: query kNN, bipartite memberships, weighted-mean start positions and a
                       layout that moves only the new points, all in ``csrc/projection.hip``
+                      ``TransformableUMAP(metric='correlation')`` is ``umap.UMAP(metric='correlation')``: the kNN of
+                      ``fit`` and ``transform`` under the correlation distance (``pj_knn_corr_kernel``, the centred
+                      dot products on the fp64 matrix cores), the rows' means and sums of squares kept beside the rows
   ``install``         points ``DataContainer._make_latent_mean_umap_projection`` / ``_make_latent_mean_pca_projection``
                       here
 
@@ -29,7 +32,13 @@ Deviations from umap-learn, on purpose (INTEGRATION.md lists them too):
   (distance, index) (umap-learn searches its NN-descent index), everything is fp64 (umap-learn initialises and lays
   out in float32), the negative samples come from the counter-based hash salted by
   ``RandomState(transform_seed).randint(2**31 - 1)``, and a negative sample at distance 0 moves nothing.  The moves
-  are applied edge by edge, as umap-learn applies them, in slot order.
+  are applied edge by edge, as umap-learn applies them, in slot order;
+* ``metric='correlation'`` is accepted by ``TransformableUMAP`` only (``UMAP`` keeps refusing it; every other metric
+  is ``NotImplementedError`` in both).  The distance is fp64 ``1 - c`` with ``c`` clipped to [-1, 1] (umap-learn's
+  numba ``correlation`` works in float32 and does not clip).  Zero-variance rows follow what umap-learn's
+  ``correlation`` does as far as it was recalled when this was written: 0.0 between two constant rows, 1.0 between a
+  constant row and any other, a row being constant when its centred sum of squares is exactly 0.  That rule was
+  recalled from memory and not checked against umap-learn, which was not installed where this was written.
 
 There is no CPU fallback: the kernels need the MI355X.
 """
@@ -82,9 +91,31 @@ def _code(t):
     return 0 if t.dtype == torch.float32 else 1
 
 
-def _knn_device(xd, k, chunk_rows=None, qd=None):
+METRICS = ('euclidean', 'correlation')     # of knn / knn_query
+
+
+def _check_metric(metric):
+    if metric not in METRICS:
+        raise NotImplementedError("metric must be one of %r, got %r" % (METRICS, metric))
+
+
+def _row_stats_device(xd):
+    """``[n, 2]`` float64 on the device: the fp64 mean and the centred sum of squares of every row
+    (``ava_pj_row_stats``), what the correlation kNN needs of either operand"""
+    n, d = int(xd.shape[0]), int(xd.shape[1])
+    if d > MAX_DIM or n >= 2 ** 31:
+        raise ValueError("unsupported shape [%d, %d]" % (n, d))
+    stats = torch.empty((n, 2), dtype=torch.float64, device=xd.device)
+    _lib.check(_lib.load().ava_pj_row_stats(xd.data_ptr(), _code(xd), n, d, stats.data_ptr(), _lib.stream()),
+               "ava_pj_row_stats")
+    return stats
+
+
+def _knn_device(xd, k, chunk_rows=None, qd=None, metric='euclidean', xstat=None):
     """the kNN table of the rows of ``qd`` among the rows of ``xd``; without ``qd`` of ``xd``'s own rows, the row itself
-    first (``ava_pj_knn``)"""
+    first (``ava_pj_knn``).  ``metric='correlation'`` goes to ``ava_pj_knn_corr``; ``xstat`` are ``xd``'s row
+    statistics if the caller keeps them."""
+    _check_metric(metric)
     m, n, d = int((xd if qd is None else qd).shape[0]), int(xd.shape[0]), int(xd.shape[1])
     if qd is not None and int(qd.shape[1]) != d:
         raise ValueError("queries have %d columns, references %d" % (int(qd.shape[1]), d))
@@ -104,37 +135,56 @@ def _knn_device(xd, k, chunk_rows=None, qd=None):
     idx = torch.empty((m, k), dtype=torch.int64, device=xd.device)
     dist = torch.empty((m, k), dtype=torch.float64, device=xd.device)
     st = _lib.stream()
+    corr = metric == 'correlation'
+    if corr:
+        if xstat is None:
+            xstat = _row_stats_device(xd)
+        if tuple(xstat.shape) != (n, 2) or xstat.dtype != torch.float64 or not xstat.is_contiguous():
+            raise ValueError("the row statistics must be a contiguous float64 [%d, 2]" % n)
+        qstat = None if qd is None else _row_stats_device(qd)
     for q0 in range(0, m, chunk_rows):
         nq = min(chunk_rows, m - q0)
         out = (k, q0, nq, idx[q0:].data_ptr(), dist[q0:].data_ptr(), st)
-        if qd is None:
+        if corr and qd is None:
+            _lib.check(lib.ava_pj_knn_corr(xd.data_ptr(), _code(xd), xstat.data_ptr(), n, d, *out), "ava_pj_knn_corr")
+        elif corr:
+            _lib.check(lib.ava_pj_knn_corr_query(qd.data_ptr(), xd.data_ptr(), _code(xd), qstat.data_ptr(),
+                                                 xstat.data_ptr(), m, n, d, *out), "ava_pj_knn_corr_query")
+        elif qd is None:
             _lib.check(lib.ava_pj_knn(xd.data_ptr(), _code(xd), n, d, *out), "ava_pj_knn")
         else:
             _lib.check(lib.ava_pj_knn_query(qd.data_ptr(), xd.data_ptr(), _code(xd), m, n, d, *out), "ava_pj_knn_query")
     return idx, dist
 
 
-def _knn_query_device(qd, xd, k, chunk_rows=None):
-    return _knn_device(xd, k, chunk_rows, qd)
+def _knn_query_device(qd, xd, k, chunk_rows=None, metric='euclidean', xstat=None):
+    return _knn_device(xd, k, chunk_rows, qd, metric, xstat)
 
 
-def knn(X, k, chunk_rows=None):
-    """Exact euclidean kNN of every row of ``X`` among its rows (fp64 from the given values): ``(idx int64 [n, k],
+def knn(X, k, chunk_rows=None, metric='euclidean'):
+    """Exact kNN of every row of ``X`` among its rows (fp64 from the given values): ``(idx int64 [n, k],
     dist float64 [n, k])``.  Column 0 is the row itself at distance 0, then the ``k - 1`` nearest other rows ordered
-    by (distance, index).  ``chunk_rows`` query rows go to one launch; the result does not depend on it."""
+    by (distance, index).  ``chunk_rows`` query rows go to one launch; the result does not depend on it.
+
+    ``metric`` is ``'euclidean'`` or ``'correlation'`` (anything else: ``NotImplementedError``).  The correlation
+    distance is ``1 - c``, ``c`` the cosine of the two centred rows clipped to [-1, 1]; a row is constant when its
+    centred sum of squares is exactly 0, and then the distance is 0 to another constant row and 1 to any other, so
+    every distance is finite."""
+    _check_metric(metric)
     xd = _as_rows(X, _native_dtype(X))
-    idx, dist = _knn_device(xd, int(k), chunk_rows)
+    idx, dist = _knn_device(xd, int(k), chunk_rows, metric=metric)
     return idx.cpu().numpy(), dist.cpu().numpy()
 
 
-def knn_query(Q, X, k, chunk_rows=None):
-    """Exact euclidean kNN of every row of ``Q`` among the rows of ``X`` (fp64 from the given values, the arithmetic of
-    ``knn``): ``(idx int64 [m, k], dist float64 [m, k])`` ordered by (distance, index).  No row is excluded: a query
-    that is a copy of reference row ``r`` gets ``(r, 0.0)`` first.  ``Q`` is read in the dtype of ``X``.
-    ``chunk_rows`` query rows go to one launch; the result does not depend on it."""
+def knn_query(Q, X, k, chunk_rows=None, metric='euclidean'):
+    """Exact kNN of every row of ``Q`` among the rows of ``X`` (fp64 from the given values, the arithmetic and the
+    metrics of ``knn``): ``(idx int64 [m, k], dist float64 [m, k])`` ordered by (distance, index).  No row is
+    excluded: under the euclidean metric a query that is a copy of reference row ``r`` gets ``(r, 0.0)`` first.  ``Q``
+    is read in the dtype of ``X``.  ``chunk_rows`` query rows go to one launch; the result does not depend on it."""
+    _check_metric(metric)
     xd = _as_rows(X, _native_dtype(X))
     qd = _as_rows(Q, xd.dtype)
-    idx, dist = _knn_query_device(qd, xd, int(k), chunk_rows)
+    idx, dist = _knn_query_device(qd, xd, int(k), chunk_rows, metric)
     return idx.cpu().numpy(), dist.cpu().numpy()
 
 
@@ -401,11 +451,14 @@ class UMAP:
         self.set_op_mix_ratio = set_op_mix_ratio
         self.local_connectivity = local_connectivity
 
+    METRICS = ('euclidean',)                # the metrics _validate accepts
+
     def _validate(self):
         if self.n_components != 2:
             raise NotImplementedError("only n_components=2 is supported, got %r" % (self.n_components,))
-        if self.metric != 'euclidean':
-            raise NotImplementedError("only metric='euclidean' is supported, got %r" % (self.metric,))
+        if self.metric not in self.METRICS:
+            raise NotImplementedError("%s supports metric in %r, got %r"
+                                      % (type(self).__name__, self.METRICS, self.metric))
         if int(self.n_neighbors) != self.n_neighbors or not 2 <= self.n_neighbors <= MAX_K:
             raise ValueError("n_neighbors must be an integer in [2, %d], got %r" % (MAX_K, self.n_neighbors))
         if self.init not in ('spectral', 'random'):
@@ -439,7 +492,7 @@ class UMAP:
             warnings.warn("n_neighbors is larger than the dataset size; truncating to X.shape[0] - 1")
             k = n - 1
         self._n_neighbors = k
-        idx, dist = _knn_device(x32, k)
+        idx, dist = self._fit_knn(x32, k)
         sigma, rho, w = _smooth_device(idx, dist, self.local_connectivity)
         self.graph_ = fuzzy_union(idx.cpu().numpy(), w.cpu().numpy(), n, self.set_op_mix_ratio)
         self.sigmas_, self.rhos_ = sigma.cpu().numpy(), rho.cpu().numpy()
@@ -458,6 +511,9 @@ class UMAP:
         self.embedding_ = lay.run().positions().astype(np.float32)
         return self
 
+    def _fit_knn(self, x32, k):
+        return _knn_device(x32, k)
+
     def fit_transform(self, X, y=None):
         return self.fit(X).embedding_
 
@@ -471,8 +527,14 @@ class TransformableUMAP(UMAP):
     ``a_`` and ``b_``; ``transform(X)`` follows umap-learn 0.5's ``transform`` (see the module docstring for the
     deviations) and returns float32 ``[m, 2]``.  ``transform_seed`` is umap-learn's argument of that name.
 
-    Pickling drops the device tensor: the pickle holds a host copy of the training rows, uploaded again by the first
-    ``transform`` after loading."""
+    ``metric='correlation'`` (what ``template_segmentation.clean_collected_segments`` fits) runs the kNN of ``fit`` and
+    of ``transform`` under the correlation distance of ``knn``; the training rows' statistics (``N x 2`` doubles) stay
+    on the device beside the rows.  Everything after the kNN works in the embedding plane and is the same.
+
+    Pickling drops the device tensors: the pickle holds a host copy of the training rows, uploaded again by the first
+    ``transform`` after loading, which also recomputes the statistics."""
+
+    METRICS = ('euclidean', 'correlation')
 
     def __init__(self, n_components=2, n_neighbors=20, min_dist=0.1, metric='euclidean', random_state=42,
                  n_epochs=None, init='spectral', spread=1.0, learning_rate=1.0, repulsion_strength=1.0,
@@ -481,11 +543,13 @@ class TransformableUMAP(UMAP):
                          learning_rate, repulsion_strength, negative_sample_rate, set_op_mix_ratio, local_connectivity)
         self.transform_seed = transform_seed
         self._train_rows = None          # float32 [N, d] on the device
-        self._train_host = None          # the same as numpy, only after unpickling and until the next transform
+        self._train_stats = None         # float64 [N, 2] on the device: the rows' statistics (metric='correlation')
+        self._train_host = None          # the rows as numpy, only after unpickling and until the next transform
 
     def fit(self, X):
         self._validate()
         x32 = _as_rows(X, torch.float32)
+        self._train_stats = None
         super().fit(x32)
         # _as_rows hands a tensor that is already float32, contiguous and on the device back as it is: keep a copy,
         # so that the caller may overwrite its own
@@ -493,12 +557,18 @@ class TransformableUMAP(UMAP):
         self._train_host = None
         return self
 
+    def _fit_knn(self, x32, k):
+        if self.metric == 'correlation':
+            self._train_stats = _row_stats_device(x32)
+        return _knn_device(x32, k, metric=self.metric, xstat=self._train_stats)
+
     def __getstate__(self):
         state = dict(self.__dict__)
         rows = state.pop('_train_rows', None)
         if rows is not None:
             state['_train_host'] = rows.cpu().numpy()
         state['_train_rows'] = None
+        state['_train_stats'] = None
         return state
 
     def __setstate__(self, state):
@@ -510,6 +580,8 @@ class TransformableUMAP(UMAP):
                 raise ValueError("transform needs a fitted TransformableUMAP: call fit first")
             self._train_rows = _as_rows(self._train_host, torch.float32)
             self._train_host = None
+        if self.metric == 'correlation' and self.__dict__.get('_train_stats') is None:
+            self._train_stats = _row_stats_device(self._train_rows)
         return self._train_rows
 
     def transform(self, X):
@@ -524,7 +596,8 @@ class TransformableUMAP(UMAP):
         q32 = _as_rows(X, torch.float32)
         train = self._rows()
         m, n = int(q32.shape[0]), int(train.shape[0])
-        idx, dist = _knn_query_device(q32, train, int(self._n_neighbors))
+        idx, dist = _knn_query_device(q32, train, int(self._n_neighbors), metric=self.metric,
+                                      xstat=self.__dict__.get('_train_stats'))
         _, _, w = _smooth_device(idx, dist, max(0.0, self.local_connectivity - 1.0), bipartite=True)
         emb = torch.from_numpy(np.ascontiguousarray(self.embedding_, dtype=np.float64)).to(q32.device)
         _, y = _transform_init_device(w, idx, emb)        # from the weights of all slots: pruning comes after

@@ -25,7 +25,7 @@ import numpy as np
 import torch
 
 from . import projection, segment
-from .spec import DeviceAudio, _read_wav
+from .spec import _read_wav
 
 __all__ = ["get_specs", "embed", "update_segments", "refine_segments_pre_vae", "install", "in_bounds"]
 
@@ -96,30 +96,7 @@ def get_specs(audio_dirs, seg_dirs, p, max_num_specs=None, max_len=None, return_
     for int16 / float32 audio).  The audio slices go to the device in batches of at most ``max_chunk_bytes``; the
     result does not depend on the batching."""
     slices, all_fns, onsets = _collect(audio_dirs, seg_dirs, p, max_num_specs)
-    nperseg, noverlap = int(p['nperseg']), int(p['noverlap'])
-    segment._check_shape(nperseg, noverlap)
-    T = segment.frame_count([len(a) for a in slices], nperseg, noverlap)
-    dt = segment.frame_step(p['fs'], nperseg, noverlap)
-    if max_len is None:
-        max_len = int(T.max())
-    max_len = int(max_len)
-    q = {k: p[k] for k in ('fs', 'nperseg', 'noverlap', 'min_freq', 'max_freq', 'spec_min_val', 'spec_max_val')}
-    i1, i2, _ = segment.band_indices(p)
-    dev = torch.device(device)
-    specs = torch.empty((len(slices), i2 - i1, max_len), dtype=torch.float64, device=dev)
-    cols = torch.arange(max_len, device=dev)
-    for chunk in segment._chunks(enumerate(slices), max_chunk_bytes):
-        audio = DeviceAudio([a for _, a in chunk], device)
-        rows = [i for i, _ in chunk]
-        _, frame_off = segment._frame_offsets(audio.lengths, nperseg, noverlap)
-        _, fo, spec = segment._trace(audio, frame_off, q, dt, want_spec=True)            # [F, frames of the chunk]
-        if segment.trace_dtype(audio.dtype) == np.float32:
-            spec = spec.to(torch.float32).to(torch.float64)
-        # padding / truncation: a device gather of every segment's first max_len frames, zeros behind its last
-        kept = torch.clamp(fo[1:] - fo[:-1], max=max_len)
-        src = torch.clamp(fo[:-1, None] + cols[None, :], max=spec.shape[1] - 1)
-        out = spec[:, src] * (cols[None, :] < kept[:, None])
-        specs[rows[0]:rows[-1] + 1] = out.permute(1, 0, 2)
+    specs, max_len, dt = segment.padded_specs(slices, p, max_len, device, max_chunk_bytes)
     segs = np.array([[onset, onset + dt * max_len] for onset in onsets])
     if return_segs:
         return specs, max_len, all_fns, segs

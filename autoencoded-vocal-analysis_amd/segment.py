@@ -6,6 +6,7 @@ Mirror of the reference's amplitude segmentation:
   ``get_onsets_offsets_batch``  the same for every recording of a ``DeviceAudio`` in one set of launches
   ``onsets_offsets_from_trace`` the decisions (lines 69-121) on a given amplitude trace
   ``get_spec``                  ava/segmenting/utils.py:22-61
+  ``padded_specs``              ``get_spec`` of many audio slices in batches, zero-padded to one length
   ``segment``                   ava/segmenting/segment.py:28-66
   ``install``                   points ``ava.segmenting.amplitude_segmentation.get_onsets_offsets`` here
 
@@ -28,8 +29,8 @@ from . import _lib
 from .spec import DeviceAudio, _read_wav, _stft_constants
 
 __all__ = ["EPSILON", "get_onsets_offsets", "get_onsets_offsets_batch", "onsets_offsets_from_trace", "get_spec",
-           "segment", "install", "frame_count", "frame_step", "band_indices", "gaussian_weights", "trace_dtype",
-           "decide_thresholds", "chain", "duration_filter"]
+           "padded_specs", "segment", "install", "frame_count", "frame_step", "band_indices", "gaussian_weights",
+           "trace_dtype", "decide_thresholds", "chain", "duration_filter"]
 
 EPSILON = 1e-9                       # segmenting/utils.py:19
 DEFAULT_CHUNK_BYTES = 1 << 30        # audio bytes per batch of segment()
@@ -258,6 +259,41 @@ def get_spec(audio, p):
     _, _, spec = _trace(dev_audio, frame_off, q, dt, want_spec=True)
     i1, i2, f = band_indices(p)
     return spec.cpu().numpy().astype(trace_dtype(dev_audio.dtype)), dt, f[i1:i2]
+
+
+def padded_specs(slices, p, max_len=None, device='cuda', max_chunk_bytes=None):
+    """The band spectrogram (``get_spec``) of every audio slice of the list ``slices`` (each at least ``nperseg``
+    samples), zero-padded or truncated to ``max_len`` time bins (default: the longest): ``(specs, max_len, dt)``.
+    ``specs`` is one device tensor ``[N, F, max_len]``, float64, holding the values of the reference's spectrogram dtype
+    (float32-rounded for int16 / float32 audio).  The slices go to the device in batches of at most ``max_chunk_bytes``
+    (default ``DEFAULT_CHUNK_BYTES``); the result does not depend on the batching.  Shared by
+    ``refine_segments.get_specs`` and ``template_segmentation.segment_specs``."""
+    max_chunk_bytes = DEFAULT_CHUNK_BYTES if max_chunk_bytes is None else max_chunk_bytes
+    nperseg, noverlap = int(p['nperseg']), int(p['noverlap'])
+    _check_shape(nperseg, noverlap)
+    T = frame_count([len(a) for a in slices], nperseg, noverlap)
+    dt = frame_step(p['fs'], nperseg, noverlap)
+    if max_len is None:
+        max_len = int(T.max())
+    max_len = int(max_len)
+    q = {k: p[k] for k in ('fs', 'nperseg', 'noverlap', 'min_freq', 'max_freq', 'spec_min_val', 'spec_max_val')}
+    i1, i2, _ = band_indices(p)
+    dev = torch.device(device)
+    specs = torch.empty((len(slices), i2 - i1, max_len), dtype=torch.float64, device=dev)
+    cols = torch.arange(max_len, device=dev)
+    for chunk in _chunks(enumerate(slices), max_chunk_bytes):
+        audio = DeviceAudio([a for _, a in chunk], device)
+        rows = [i for i, _ in chunk]
+        _, frame_off = _frame_offsets(audio.lengths, nperseg, noverlap)
+        _, fo, spec = _trace(audio, frame_off, q, dt, want_spec=True)                    # [F, frames of the chunk]
+        if trace_dtype(audio.dtype) == np.float32:
+            spec = spec.to(torch.float32).to(torch.float64)
+        # padding / truncation: a device gather of every slice's first max_len frames, zeros behind its last
+        kept = torch.clamp(fo[1:] - fo[:-1], max=max_len)
+        src = torch.clamp(fo[:-1, None] + cols[None, :], max=spec.shape[1] - 1)
+        out = spec[:, src] * (cols[None, :] < kept[:, None])
+        specs[rows[0]:rows[-1] + 1] = out.permute(1, 0, 2)
+    return specs, max_len, dt
 
 
 # ---- files ----------------------------------------------------------------------------------------------------------

@@ -10,13 +10,23 @@ Mirror of the computational surface of ava/segmenting/template_segmentation.py, 
   ``xcorr_batch``              the normalised cross-correlation trace of every file of a ``DeviceAudio``
   ``segment_batch``            ``_segment_file``'s segments for every file of a ``DeviceAudio``
   ``segments_from_trace``      the decisions (lines 246-264) on a given trace
-  ``install``                  points the reference module's ``get_template``, ``segment_files``, ``_segment_file`` here
+  ``segment_specs``            the batch counterpart of ``_get_spec`` (lines 758-790) as ``clean_collected_segments``
+                               uses it (lines 311-334): one zero-padded band spectrogram per collected segment
+  ``clean_collected_segments`` lines 281-452   same signature, prints, prompts and picture; ``clean_collected_data`` is
+                               its deprecated alias (lines 267-278)
+  ``_in_region``               lines 817-827
+  ``install``                  points the reference module's ``get_template``, ``segment_files``, ``_segment_file``,
+                               ``clean_collected_segments``, ``clean_collected_data`` here and adds ``segment_specs``
 
 The band spectrogram of whole files (``_get_spec``, lines 758-790) and the correlation with the template run on the
 device in fp64 (the band kernel of ``csrc/segment.hip`` in sum mode, then ``csrc/template_seg.hip``); the host
 receives the fp64 trace and runs the threshold, the maxima and ``_clean_max_indices`` on it (O(lags) per file,
-vectorised numpy).  The template's smoothing, truncation, mean and normalisation are the reference's own numpy calls
-on a few F x L arrays.  Unlike the reference, this module imports without affinewarp, umap, h5py or bokeh.
+vectorised numpy).  ``clean_collected_segments`` makes its spectrograms with the band kernel too
+(``segment.padded_specs``, shared with ``refine_segments.get_specs``) and embeds them with
+``projection.TransformableUMAP(metric='correlation')``: the correlation kNN of ``csrc/projection.hip`` for the fit and
+for the ``transform`` of every directory's segments.  Directories are processed one after the other in this process.
+The template's smoothing, truncation, mean and normalisation are the reference's own numpy calls on a few F x L
+arrays.  Unlike the reference, this module imports without affinewarp, umap, h5py or bokeh.
 
 ``nperseg`` must be a power of two in 64..2048; other lengths raise ``NotImplementedError``.  There is no CPU fallback.
 """
@@ -28,11 +38,13 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import projection
 from . import segment as _seg
 from .spec import DeviceAudio, _is_wav_file, _read_wav, _stft_constants
 
 __all__ = ["EPSILON", "get_template", "get_template_from_audio", "segment_files", "read_segment_decisions",
-           "xcorr_batch", "segment_batch", "segments_from_trace", "install"]
+           "xcorr_batch", "segment_batch", "segments_from_trace", "segment_specs", "clean_collected_segments",
+           "clean_collected_data", "_in_region", "install"]
 
 EPSILON = 1e-9                       # template_segmentation.py:31
 DEFAULT_CHUNK_BYTES = 1 << 30        # audio bytes per batch of segment_files()
@@ -299,12 +311,231 @@ def read_segment_decisions(audio_dirs, segment_dirs, verbose=True):
     return result
 
 
+# ---- removal of false positives -------------------------------------------------------------------------------------
+
+def _segment_slices(audio, segments, fs, p, name):
+    """the samples ``audio[int(round(onset fs)):int(round(offset fs))]`` of every segment (lines 318-320)"""
+    slices = []
+    for segment in segments:
+        i1 = int(round(segment[0] * fs))
+        i2 = int(round(segment[1] * fs))
+        piece = audio[i1:i2]
+        if len(piece) < p['nperseg']:
+            raise ValueError("segment [%s, %s] of %s has %d samples, fewer than nperseg = %d"
+                             % (segment[0], segment[1], name, len(piece), p['nperseg']))
+        slices.append(piece)
+    return slices
+
+
+def _padded(slices, p, max_len, device, max_chunk_bytes):
+    specs, max_len, _ = _seg.padded_specs(slices, p, max_len, device, max_chunk_bytes)
+    return specs
+
+
+def segment_specs(result, p, device='cuda', max_chunk_bytes=DEFAULT_CHUNK_BYTES):
+    """The reference's ``_get_spec(fs, audio[i1:i2], p)[0]`` of every segment of ``result`` (``{filename: [[onset,
+    offset], ...]}``, what ``segment_files`` returns), ``i = int(round(t fs))``, files in dict order, zero-padded to
+    the longest one's length as lines 330-334 pad them: one device tensor ``[N, F, max_t]`` with the dtype convention
+    of ``refine_segments.get_specs`` (float64 holding the reference's values: float32-rounded for int16 / float32
+    audio).  ``[0, F, 0]`` when there is no segment.  The slices go through the band kernel in batches of at most
+    ``max_chunk_bytes`` of audio; the result does not depend on the batching.
+
+    A segment of fewer than ``nperseg`` samples raises ``ValueError`` (the reference lets scipy shrink the window
+    there; template segments, one template long, never are that short)."""
+    slices = []
+    for filename in result.keys():
+        segments = np.asarray(result[filename]).reshape(-1, 2)
+        if len(segments) == 0:
+            continue
+        fs, audio = _read_wav(filename)
+        assert fs == p['fs'], "Found samplerate=" + str(fs) + ", expected " + str(p['fs'])
+        slices += _segment_slices(audio, segments, fs, p, filename)
+    if not slices:
+        _, _, i1, i2 = _seg._band_params(p)
+        return torch.zeros((0, i2 - i1, 0), dtype=torch.float64, device=torch.device(device))
+    return _padded(slices, p, None, device, max_chunk_bytes)
+
+
+def _in_region(point, bounds):
+    """Is the point strictly inside one of the rectangles of ``bounds`` (lines 817-827)?  The two x answers and the
+    two y answers of a rectangle may come in either order."""
+    for i in range(len(bounds['x1s'])):
+        x_min = min(bounds['x1s'][i], bounds['x2s'][i])
+        x_max = max(bounds['x1s'][i], bounds['x2s'][i])
+        y_min = min(bounds['y1s'][i], bounds['y2s'][i])
+        y_max = max(bounds['y1s'][i], bounds['y2s'][i])
+        if point[0] > x_min and point[0] < x_max and point[1] > y_min and point[1] < y_max:
+            return True
+    return False
+
+
+def _is_number(answer):
+    try:
+        float(answer)
+        return True
+    except (TypeError, ValueError):
+        if answer != 'initial input':
+            print("Invalid input!")
+        return False
+
+
+def _new_transform():
+    """``umap.UMAP(random_state=42, metric='correlation')`` (line 354; umap-learn's defaults n_neighbors=15,
+    min_dist=0.1) as the device class that keeps its training rows for ``transform``"""
+    return projection.TransformableUMAP(n_components=2, n_neighbors=15, min_dist=0.1, metric='correlation',
+                                        random_state=42)
+
+
+def _region_plot(embedding, colors, title, img_fn):
+    """the scatter plot with unit grid lines of lines 382-390"""
+    import matplotlib.pyplot as plt
+    plt.switch_backend('agg')
+    X, Y = embedding[:, 0], embedding[:, 1]
+    plt.scatter(X, Y, c=colors, s=0.9, alpha=0.5)
+    for x_tick in np.arange(np.floor(np.min(X)), np.ceil(np.max(X))):
+        plt.axvline(x=x_tick, c='k', alpha=0.1, lw=0.5)
+    for y_tick in np.arange(np.floor(np.min(Y)), np.ceil(np.max(Y))):
+        plt.axhline(y=y_tick, c='k', alpha=0.1, lw=0.5)
+    plt.title(title)
+    plt.savefig(img_fn)
+    plt.close('all')
+
+
+def _to_numpy(a):
+    return a.cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+
+
+def clean_collected_segments(result, audio_dirs, segment_dirs, p, max_num_specs=10000, verbose=True,
+                             img_fn='temp.pdf', tooltip_plot_dir='html'):
+    """Mirror of ``ava.segmenting.template_segmentation.clean_collected_segments`` (same arguments, prints and
+    prompts): embed the spectrograms of up to ``max_num_specs`` collected segments (the seed-42 subsample) with
+    correlation-metric UMAP, let the user box the real song in the embedding (the picture is saved to ``img_fn`` before
+    every box; the tooltip plot is written when ``ava.plotting.tooltip_plot`` imports, with a warning otherwise), then
+    embed every file's segments with the fitted object's ``transform`` and rewrite the segment files in place with the
+    segments inside the boxes (a file none of whose segments is kept is rewritten empty).
+
+    Differences from the reference: the segments of a whole directory go through one ``transform`` (the rows do not
+    depend on each other), the directories are processed serially in this process, and a segment whose spectrogram is
+    longer than the longest fitted one raises ``ValueError`` (the reference fails there with a numpy broadcast
+    error), as does one of fewer than ``nperseg`` samples.  The fitted object keeps ``max_num_specs x F x max_t x 4``
+    bytes of training rows on the device until this function returns."""
+    from .refine_segments import _tooltip_plot
+    # Collect spectrograms.
+    if verbose:
+        print("Collecting spectrograms...")
+    specs = segment_specs(result, p) if any(len(result[fn]) for fn in result.keys()) else []
+    if len(specs) == 0:
+        warnings.warn("Found no spectrograms in ava.segmenting.template_segmentation.clean_collected_segments.\n" +
+                      "Consider reducing the `num_mad` parameter in `segment_files`.", UserWarning)
+        return
+    max_t = int(specs.shape[2])
+    if len(specs) > max_num_specs:
+        warnings.warn("Found more spectrograms than `max_num_specs` (" + str(max_num_specs) +
+                      "). Consider increasing `max_num_specs` or `num_mad`.", UserWarning)
+    if verbose:
+        print("\tCollected", len(specs), "spectrograms.")
+        print("\tSpectrogram shape:", tuple(specs.shape[1:]))
+        if len(specs) > max_num_specs:
+            print("\tRandomly sampling", max_num_specs, "spectrograms.")
+        print("\tDone.")
+    perm = np.random.RandomState(42).permutation(len(specs))[:max_num_specs]      # np.random.seed(42); permutation
+    specs = specs[torch.from_numpy(perm).to(specs.device)]
+    # UMAP the spectrograms.
+    if verbose:
+        print("Running UMAP. n =", len(specs))
+    transform = _new_transform()
+    embedding = _to_numpy(transform.fit_transform(specs.reshape(len(specs), -1)))
+    if verbose:
+        print("\tDone.")
+    # Plot and ask for user input.
+    bounds = {'x1s': [], 'x2s': [], 'y1s': [], 'y2s': []}
+    bounds_keys = ['x1s', 'x2s', 'y1s', 'y2s']
+    queries = ['x1: ', 'x2: ', 'y1: ', 'y2: ']
+    i = 0
+    while True:
+        colors = ['b' if _in_region(embed, bounds) else 'r' for embed in embedding]
+        print("Selected", len([c for c in colors if c == 'b']), "out of", len(colors))
+        title = "Find relevant song"
+        _region_plot(embedding, colors, title, img_fn)
+        # Plot the tooltip plot.
+        if i == 0:
+            tooltip_plot = _tooltip_plot()
+            if tooltip_plot is not None:
+                if verbose:
+                    print("Writing tooltip plot...")
+                tooltip_plot(embedding, _to_numpy(specs), output_dir=tooltip_plot_dir, num_imgs=1000, title=title,
+                             grid=True)
+                if verbose:
+                    print("\tDone.")
+        # Get input from user.
+        for key, query in zip(bounds_keys, queries):
+            answer = 'initial input'
+            while not _is_number(answer):
+                answer = input(query)
+            bounds[key].append(float(answer))
+        # Continue?
+        temp = input('[Enter] to select more regions, [c] to continue: ')
+        if temp == 'c':
+            break
+        i += 1
+    del specs
+    # Save only the good segments.
+    if verbose:
+        print("Saving segments...")
+    num_deleted, num_total = 0, 0
+    for audio_dir, seg_dir in zip(audio_dirs, segment_dirs):
+        audio_fns = [os.path.join(audio_dir, i) for i in os.listdir(audio_dir) if _is_wav_file(i)]
+        slices, files = [], []                                          # files: (segment file, its segments)
+        for audio_fn in audio_fns:
+            audio = _read(audio_fn, p)
+            segment_fn = os.path.join(seg_dir, os.path.split(audio_fn)[-1][:-4] + '.txt')
+            with warnings.catch_warnings():
+                warnings.simplefilter("ignore", UserWarning)            # numpy's "input contained no data"
+                segments = np.loadtxt(segment_fn).reshape(-1, 2)
+            if len(segments) == 0:
+                continue
+            slices += _segment_slices(audio, segments, p['fs'], p, audio_fn)
+            files.append((segment_fn, segments))
+        if not slices:
+            continue
+        T = _seg.frame_count([len(a) for a in slices], int(p['nperseg']), int(p['noverlap']))
+        if int(T.max()) > max_t:
+            raise ValueError("a segment of %s has a spectrogram of %d time bins, more than the %d of the longest "
+                             "collected one" % (audio_dir, int(T.max()), max_t))
+        specs = _padded(slices, p, max_t, 'cuda', DEFAULT_CHUNK_BYTES)
+        embed = _to_numpy(transform.transform(specs.reshape(len(specs), -1)))
+        row = 0
+        for segment_fn, segments in files:
+            keep = [_in_region(embed[row + j], bounds) for j in range(len(segments))]
+            row += len(segments)
+            new_segments = segments[np.array(keep, dtype=bool)]
+            num_total += len(new_segments)
+            num_deleted += len(segments) - len(new_segments)
+            np.savetxt(segment_fn, new_segments, fmt='%.5f')
+    if verbose:
+        print("\tdeleted:", num_deleted, "remaining:", num_total)
+        print("\tDone.")
+
+
+def clean_collected_data(result, audio_dirs, segment_dirs, p, max_num_specs=10000, verbose=True, img_fn='temp.pdf',
+                         tooltip_plot_dir='html'):
+    """Deprecated. See ``clean_collected_segments``."""
+    warnings.warn("ava.segmenting.template_segmentation.clean_collected_data has been renamed to "
+                  "clean_collected_segments in v0.3.0.", UserWarning)
+    clean_collected_segments(result, audio_dirs, segment_dirs, p, max_num_specs=max_num_specs, verbose=verbose,
+                             img_fn=img_fn, tooltip_plot_dir=tooltip_plot_dir)
+
+
 def install(module=None):
-    """Point ``get_template``, ``segment_files`` and ``_segment_file`` of ``module`` (by default
-    ``ava.segmenting.template_segmentation``, imported after the reference package) at this module."""
+    """Point ``get_template``, ``segment_files``, ``_segment_file``, ``clean_collected_segments`` and
+    ``clean_collected_data`` of ``module`` (by default ``ava.segmenting.template_segmentation``, imported after the
+    reference package) at this module, and give it ``segment_specs``, the batch counterpart of its ``_get_spec``."""
     if module is None:
         import ava.segmenting.template_segmentation as module
     module.get_template = get_template
     module.segment_files = segment_files
     module._segment_file = _segment_file
+    module.clean_collected_segments = clean_collected_segments
+    module.clean_collected_data = clean_collected_data
+    module.segment_specs = segment_specs
     return module

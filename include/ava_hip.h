@@ -547,6 +547,14 @@ int ava_nn_merge(int64_t* best_idx, double* best_dist, const int64_t* idx, const
  * ava_pj_knn_query: rows [q0, q0 + nq) of the table of the k nearest of the n reference rows x [n][d] of each of the m
  *   query rows q [m][d] (one dtype for both), ordered by (distance, index), no row excluded; the distance arithmetic
  *   is that of ava_pj_knn.  1 <= k <= min(64, n), 1 <= d <= 65536.
+ * ava_pj_row_stats: stats [n][2] float64 (device): the fp64 mean and the centred sum of squares of every row of x, each a
+ *   fixed-order two-stage sum (csrc/corr_tile.h).  1 <= d <= 65536.
+ * ava_pj_knn_corr / ava_pj_knn_corr_query: ava_pj_knn / ava_pj_knn_query under umap-learn's correlation distance, with
+ *   the operands' statistics from ava_pj_row_stats (xstat [n][2], qstat [m][2]): dist = 1 - dot / sqrt(ss_q ss_r), the
+ *   dot product of the centred rows on the fp64 matrix cores, the cosine clipped to [-1, 1]; 0 when both rows have a
+ *   centred sum of squares of exactly 0, 1 when exactly one has.  Every distance is finite.  Same table layout, order
+ *   (distance, index), modes and limits; the dot products take k in one fixed order, so the table does not depend on
+ *   q0 / nq, and a pair of rows gets the bits ava_nn_argmin's correlation gives it.
  * ava_pj_smooth_bipartite: ava_pj_smooth for a table whose columns index another set than its rows: no weight is
  *   zeroed for idx == row.
  * ava_pj_transform_init: wn [m][k] = w / (row sum, left to right; a row of sum 0 stays 0) and y0 [m][2] =
@@ -574,6 +582,11 @@ int ava_pj_layout(double* y, double* y_tmp, const int64_t* indptr, const int* co
                   double learning_rate, double a, double b, double gamma, uint64_t salt, int* flag, ava_stream_t s);
 int ava_pj_knn_query(const void* q, const void* x, int dtype, int m, int n, int d, int k, int q0, int nq,
                      int64_t* out_idx, double* out_dist, ava_stream_t s);
+int ava_pj_row_stats(const void* x, int dtype, int n, int d, double* stats, ava_stream_t s);
+int ava_pj_knn_corr(const void* x, int dtype, const double* xstat, int n, int d, int k, int q0, int nq,
+                    int64_t* out_idx, double* out_dist, ava_stream_t s);
+int ava_pj_knn_corr_query(const void* q, const void* x, int dtype, const double* qstat, const double* xstat, int m,
+                          int n, int d, int k, int q0, int nq, int64_t* out_idx, double* out_dist, ava_stream_t s);
 int ava_pj_smooth_bipartite(const double* dist, const int64_t* idx, int n, int k, double local_connectivity,
                             double* mean_all, double* sigma, double* rho, double* w, ava_stream_t s);
 int ava_pj_transform_init(const double* w, const int64_t* idx, const double* emb, int m, int k, double* wn, double* y0,
