@@ -21,12 +21,24 @@
 // operations.  Sums run lane-sequentially and then through one xor-shuffle tree: a fixed order, no atomics.
 // LDS: (4 (T+1) + 4 T + 8 T) 8 + 8 T 4 bytes = 160 T + 32: 20.5 KB at T = 128 (7 workgroups / CU), 82 KB at the cap
 // T = 512, where one more row set no longer fits twice on a CU.
+//
+// The piecewise-linear warp (row f14): K = n_knots + 2 knots per motif, u[k] the source position of the template column
+// t_k = k (T-1) / (K-1).  Column j lies in segment k = min(j (K-1) / (T-1), K-2) (integers) and reads the source at
+// p(j) = u_k + s_k (j - t_k), s_k = (u_{k+1} - u_k) / (t_{k+1} - t_k), every operation rounded on its own; with K = 2 that
+// is wf_pos(u_0, s_0, j).  A candidate with some s_k <= 0 has loss +inf.
+//
+//   warpfit_pl_apply_kernel       warpfit_apply_kernel under knots [N][K]
+//   warpfit_pl_candidates_kernel  candidates [N][C][K] around u [N][K]: one knot, or all knots together, moved by 0, -h, +h, ...
+//   warpfit_pl_loss_kernel        warpfit_loss_kernel with the column tables made from knots: the same LDS, the same sums
+//                                 (wf_block_sums), + shift_l u_0^2 + slope_l mean_k (log s_k)^2
+//   warpfit_argmin_kernel         serves both fits: its parameter width is 2 or K
 #include "common.h"
 
 #define WF_CB 8          // candidates per workgroup (two per wave)
 #define WF_FR 4          // motif / target rows staged per pass
 #define WF_MAX_T 512
 #define WF_MAX_C 4096
+#define WF_MAX_K 16      // knots of a piecewise-linear warp, the two outer ones included
 
 struct WfTap { int lo; double w; };
 
@@ -47,6 +59,36 @@ __device__ __forceinline__ double wf_lerp(double a, double b, double w) {
 
 __device__ __forceinline__ double wf_pos(double shift, double slope, int j) {
   return __dadd_rn(shift, __dmul_rn(slope, (double)j));     // shifts[i] + slopes[i] * np.arange(T)
+}
+
+// template column of knot k: k (T-1) / (K-1), the product exact, one rounded division
+__device__ __forceinline__ double wf_knot_t(int k, int T, int K) { return __ddiv_rn((double)(k * (T - 1)), (double)(K - 1)); }
+
+// slope of segment k (0 <= k <= K-2) of the knots u[0 .. K-1]
+__device__ __forceinline__ double wf_pl_slope(const double* __restrict__ u, int k, int T, int K) {
+  return __ddiv_rn(__dsub_rn(u[k + 1], u[k]), __dsub_rn(wf_knot_t(k + 1, T, K), wf_knot_t(k, T, K)));
+}
+
+// source position of column j under the knots u[0 .. K-1]; T - 1 >= K - 1, so every segment holds a column
+__device__ __forceinline__ double wf_pl_pos(const double* __restrict__ u, int j, int T, int K) {
+  int k = j * (K - 1) / (T - 1);
+  k = k > K - 2 ? K - 2 : k;
+  return __dadd_rn(u[k], __dmul_rn(wf_pl_slope(u, k, T, K), __dsub_rn((double)j, wf_knot_t(k, T, K))));
+}
+
+template <typename T_>
+__global__ __launch_bounds__(256) void warpfit_pl_apply_kernel(const T_* __restrict__ spec, const double* __restrict__ knots,
+                                                               int F, int T, int K, T_* __restrict__ out) {
+  const int n = blockIdx.x;
+  const double* u = knots + (size_t)n * K;
+  for (int j = threadIdx.x; j < T; j += 256) {
+    const WfTap t = wf_tap(wf_pl_pos(u, j, T, K), T);
+    const int hi = t.lo + 1 < T ? t.lo + 1 : T - 1;
+    for (int f = blockIdx.y; f < F; f += gridDim.y) {
+      const T_* row = spec + ((size_t)n * F + f) * T;
+      out[((size_t)n * F + f) * T + j] = (T_)wf_lerp((double)row[t.lo], (double)row[hi], t.w);
+    }
+  }
 }
 
 template <typename T_>
@@ -96,6 +138,57 @@ __global__ __launch_bounds__(256) void warpfit_candidates_kernel(const double* _
   cand[2 * e + 1] = ls;
 }
 
+// Candidate c of motif n: the knots u[n][:] with knot `axis` (axis = -1: every knot) moved by o h, o = 0, -1, +1, -2, +2, ...
+// so that candidate 0 is u[n] itself.  C = 2 ks + 1.
+__global__ __launch_bounds__(256) void warpfit_pl_candidates_kernel(const double* __restrict__ u, int N, int K, int axis, int ks,
+                                                                    double h, double* __restrict__ cand) {
+  const int C = 2 * ks + 1;
+  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= (int64_t)N * C * K) return;
+  const int k = (int)(e % K);
+  const int64_t nc = e / K;
+  const int n = (int)(nc / C), c = (int)(nc - (int64_t)n * C);
+  const int o = (c & 1) ? -((c + 1) >> 1) : (c >> 1);
+  const double v = u[(size_t)n * K + k];
+  cand[e] = (o != 0 && (axis < 0 || axis == k)) ? __dadd_rn(v, __dmul_rn((double)o, h)) : v;
+}
+
+// The sums of the loss kernels: with the (lo, weight) tables of the workgroup's candidates in LDS (written by the wave
+// that owns the candidate; the first barrier below publishes them), acc[k] = this lane's share of
+// sum_{f,j} (interp - target)^2 for candidate c0 + wave + 4 k.
+template <typename T_>
+__device__ __forceinline__ void wf_block_sums(const T_* __restrict__ motif, const double* __restrict__ target, int F, int T,
+                                              int C, int c0, double* s_spec, double* s_tgt, const double* s_w,
+                                              const int* s_lo, double (&acc)[2]) {
+  const int TS = T + 1;
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  for (int f0 = 0; f0 < F; f0 += WF_FR) {
+    const int nr = F - f0 < WF_FR ? F - f0 : WF_FR;
+    __syncthreads();                                        // the previous rows are consumed (first pass: tables written)
+    for (int e = tid; e < nr * T; e += 256) {
+      const int r = e / T, j = e - r * T;
+      const double v = (double)motif[(size_t)f0 * T + e];
+      s_spec[r * TS + j] = v;
+      if (j == T - 1) s_spec[r * TS + T] = v;
+      s_tgt[r * T + j] = target[(size_t)f0 * T + e];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      const int cc = wave + 4 * k;
+      if (c0 + cc >= C) continue;
+      for (int j = lane; j < T; j += 64) {
+        const int lo = s_lo[cc * T + j];
+        const double w = s_w[cc * T + j];
+        for (int r = 0; r < nr; ++r) {
+          const double d = wf_lerp(s_spec[r * TS + lo], s_spec[r * TS + lo + 1], w) - s_tgt[r * T + j];
+          acc[k] += d * d;
+        }
+      }
+    }
+  }
+}
+
 template <typename T_>
 __global__ __launch_bounds__(256) void warpfit_loss_kernel(const T_* __restrict__ spec, const double* __restrict__ target,
                                                            const double* __restrict__ cand, int F, int T, int C,
@@ -128,32 +221,7 @@ __global__ __launch_bounds__(256) void warpfit_loss_kernel(const T_* __restrict_
   }
 
   double acc[2] = {0.0, 0.0};
-  const T_* motif = spec + (size_t)n * F * T;
-  for (int f0 = 0; f0 < F; f0 += WF_FR) {
-    const int nr = F - f0 < WF_FR ? F - f0 : WF_FR;
-    __syncthreads();                                        // the previous rows are consumed (first pass: tables written)
-    for (int e = tid; e < nr * T; e += 256) {
-      const int r = e / T, j = e - r * T;
-      const double v = (double)motif[(size_t)f0 * T + e];
-      s_spec[r * TS + j] = v;
-      if (j == T - 1) s_spec[r * TS + T] = v;
-      s_tgt[r * T + j] = target[(size_t)f0 * T + e];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-      const int cc = wave + 4 * k;
-      if (c0 + cc >= C) continue;
-      for (int j = lane; j < T; j += 64) {
-        const int lo = s_lo[cc * T + j];
-        const double w = s_w[cc * T + j];
-        for (int r = 0; r < nr; ++r) {
-          const double d = wf_lerp(s_spec[r * TS + lo], s_spec[r * TS + lo + 1], w) - s_tgt[r * T + j];
-          acc[k] += d * d;
-        }
-      }
-    }
-  }
+  wf_block_sums(spec + (size_t)n * F * T, target, F, T, C, c0, s_spec, s_tgt, s_w, s_lo, acc);
 #pragma unroll
   for (int k = 0; k < 2; ++k) {
     const int c = c0 + wave + 4 * k;
@@ -166,10 +234,67 @@ __global__ __launch_bounds__(256) void warpfit_loss_kernel(const T_* __restrict_
   }
 }
 
-// one wave per motif: lanes take candidates lane, lane + 64, ... in rising order, then a (loss, index) min over the wave
+// The loss kernel for candidates of K knots each, cand [N][C][K]: only the tables differ (a lane reads the two knots of
+// its column's segment from the candidate, K <= 16 doubles that stay in cache).  fixed_slope: every slope is 1 and the
+// positions are u_0 + j, the shift objective.  Crossed knots do not stop the sums -- wf_tap keeps every tap inside the
+// row -- and the total is replaced by +inf.
+template <typename T_>
+__global__ __launch_bounds__(256) void warpfit_pl_loss_kernel(const T_* __restrict__ spec, const double* __restrict__ target,
+                                                              const double* __restrict__ cand, int F, int T, int C, int K,
+                                                              double shift_lambda, double slope_lambda, int fixed_slope,
+                                                              double* __restrict__ loss) {
+  extern __shared__ __align__(16) double wf_sm[];
+  const int TS = T + 1;
+  double* s_spec = wf_sm;                                   // as in warpfit_loss_kernel
+  double* s_tgt = s_spec + WF_FR * TS;
+  double* s_w = s_tgt + WF_FR * T;
+  int* s_lo = reinterpret_cast<int*>(s_w + WF_CB * T);
+  const int n = blockIdx.x, c0 = blockIdx.y * WF_CB;
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+
+#pragma unroll
+  for (int k = 0; k < 2; ++k) {
+    const int cc = wave + 4 * k, c = c0 + cc;
+    if (c < C) {                                            // wave-uniform
+      const double* u = cand + ((size_t)n * C + c) * K;
+      for (int j = lane; j < T; j += 64) {
+        const WfTap t = wf_tap(fixed_slope ? wf_pos(u[0], 1.0, j) : wf_pl_pos(u, j, T, K), T);
+        s_lo[cc * T + j] = t.lo;
+        s_w[cc * T + j] = t.w;
+      }
+    }
+  }
+
+  double acc[2] = {0.0, 0.0};
+  wf_block_sums(spec + (size_t)n * F * T, target, F, T, C, c0, s_spec, s_tgt, s_w, s_lo, acc);
+#pragma unroll
+  for (int k = 0; k < 2; ++k) {
+    const int c = c0 + wave + 4 * k;
+    if (c >= C) continue;
+    const double* u = cand + ((size_t)n * C + c) * K;
+    double tot = wave_sum_d(acc[k]);
+    tot = __dadd_rn(tot, __dmul_rn(shift_lambda, __dmul_rn(u[0], u[0])));
+    if (!fixed_slope) {
+      double sq = 0.0;                                      // sum_k (log s_k)^2, k = 0, 1, ...
+      bool crossed = false;
+      for (int i = 0; i < K - 1; ++i) {
+        const double sl = wf_pl_slope(u, i, T, K);
+        crossed |= sl <= 0.0;
+        const double l = log(sl);
+        sq = __dadd_rn(sq, __dmul_rn(l, l));
+      }
+      tot = __dadd_rn(tot, __dmul_rn(slope_lambda, __ddiv_rn(sq, (double)(K - 1))));
+      if (crossed) tot = __builtin_inf();
+    }
+    if (lane == 0) loss[(size_t)n * C + c] = tot;
+  }
+}
+
+// one wave per motif: lanes take candidates lane, lane + 64, ... in rising order, then a (loss, index) min over the wave,
+// which leaves the result in every lane; W <= 64 parameters per candidate (2: shift and log slope; K: knots)
 __global__ __launch_bounds__(256) void warpfit_argmin_kernel(const double* __restrict__ loss, const double* __restrict__ cand,
-                                                             int N, int C, int* __restrict__ best, double* __restrict__ x,
-                                                             double* __restrict__ best_loss) {
+                                                             int N, int C, int W, int* __restrict__ best,
+                                                             double* __restrict__ x, double* __restrict__ best_loss) {
   const int n = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (n >= N) return;
   double bv = 0.0;
@@ -184,13 +309,10 @@ __global__ __launch_bounds__(256) void warpfit_argmin_kernel(const double* __res
     const int oi = __shfl_xor(bi, o, 64);
     if (oi >= 0 && (bi < 0 || ov < bv || (ov == bv && oi < bi))) { bv = ov; bi = oi; }
   }
+  const int c = bi < 0 ? 0 : bi;                            // all NaN: candidate 0 and its NaN
+  if (x != nullptr && lane < W) x[(size_t)W * n + lane] = cand[(size_t)W * ((size_t)n * C + c) + lane];
   if (lane == 0) {
-    const int c = bi < 0 ? 0 : bi;                          // all NaN: candidate 0 and its NaN
     best[n] = c;
-    if (x != nullptr) {
-      x[2 * (size_t)n] = cand[2 * ((size_t)n * C + c)];
-      x[2 * (size_t)n + 1] = cand[2 * ((size_t)n * C + c) + 1];
-    }
     if (best_loss != nullptr) best_loss[n] = loss[(size_t)n * C + c];
   }
 }
@@ -272,11 +394,82 @@ extern "C" int ava_warpfit_loss(const void* spec, int dtype, int N, int F, int T
   return wf_launch_loss(static_cast<const double*>(spec), N, F, T, target, cand, C, shift_lambda, slope_lambda, loss, to_stream(s));
 }
 
-extern "C" int ava_warpfit_argmin(const double* loss, const double* cand, int N, int C, int32_t* best, double* x,
-                                  double* best_loss, ava_stream_t s) {
+static int wf_launch_argmin(const double* loss, const double* cand, int N, int C, int W, int32_t* best, double* x,
+                            double* best_loss, ava_stream_t s) {
   if (loss == nullptr || best == nullptr || N < 1 || C < 1 || C > WF_MAX_C) return AVA_EINVAL;
   if (x != nullptr && cand == nullptr) return AVA_EINVAL;
-  hipLaunchKernelGGL(warpfit_argmin_kernel, dim3(ceil_div(N, 4)), dim3(256), 0, to_stream(s), loss, cand, N, C, best, x, best_loss);
+  hipLaunchKernelGGL(warpfit_argmin_kernel, dim3(ceil_div(N, 4)), dim3(256), 0, to_stream(s), loss, cand, N, C, W, best, x,
+                     best_loss);
   AVA_CHECK_LAUNCH();
   return AVA_OK;
+}
+
+extern "C" int ava_warpfit_argmin(const double* loss, const double* cand, int N, int C, int32_t* best, double* x,
+                                  double* best_loss, ava_stream_t s) {
+  return wf_launch_argmin(loss, cand, N, C, 2, best, x, best_loss, s);
+}
+
+// ---- the piecewise-linear warp (row f14) ------------------------------------------------------------------------------
+
+static bool wf_knots_ok(int T, int K) { return K >= 2 && K <= WF_MAX_K && T - 1 >= 2 * (K - 1); }
+
+extern "C" int ava_warpfit_max_knots(void) { return WF_MAX_K; }
+
+extern "C" int ava_warpfit_pl_apply(const void* spec, int dtype, int N, int F, int T, const double* knots, int K, void* out,
+                                    ava_stream_t s) {
+  if (spec == nullptr || knots == nullptr || out == nullptr || !wf_shape_ok(dtype, N, F, T) || !wf_knots_ok(T, K)) return AVA_EINVAL;
+  const dim3 grid(N, F < 64 ? F : 64);
+  if (dtype == 0)
+    hipLaunchKernelGGL(warpfit_pl_apply_kernel<float>, grid, dim3(256), 0, to_stream(s), static_cast<const float*>(spec), knots,
+                       F, T, K, static_cast<float*>(out));
+  else
+    hipLaunchKernelGGL(warpfit_pl_apply_kernel<double>, grid, dim3(256), 0, to_stream(s), static_cast<const double*>(spec),
+                       knots, F, T, K, static_cast<double*>(out));
+  AVA_CHECK_LAUNCH();
+  return AVA_OK;
+}
+
+extern "C" int ava_warpfit_pl_candidates(const double* u, int N, int K, int axis, int ks, double h, double* cand,
+                                         ava_stream_t s) {
+  if (u == nullptr || cand == nullptr || N < 1 || K < 2 || K > WF_MAX_K || axis < -1 || axis >= K) return AVA_EINVAL;
+  if (ks < 0 || ks > 31 || !(h >= 0.0)) return AVA_EINVAL;
+  const int64_t total = (int64_t)N * (2 * ks + 1) * K;
+  if (ceil_div64(total, 256) > 2147483647) return AVA_EINVAL;
+  hipLaunchKernelGGL(warpfit_pl_candidates_kernel, dim3((unsigned)ceil_div64(total, 256)), dim3(256), 0, to_stream(s), u, N, K,
+                     axis, ks, h, cand);
+  AVA_CHECK_LAUNCH();
+  return AVA_OK;
+}
+
+template <typename T_>
+static int wf_launch_pl_loss(const T_* spec, int N, int F, int T, const double* target, const double* cand, int C, int K,
+                             double shift_lambda, double slope_lambda, double* loss, hipStream_t st) {
+  // dynamic LDS over 64 KB (T > 409) has to be asked for, per device; asked whenever it is needed rather than once per
+  // process, so that neither a second device nor two threads' first calls can miss it
+  if (wf_loss_lds(T) > 65536 &&
+      hipFuncSetAttribute(reinterpret_cast<const void*>(&warpfit_pl_loss_kernel<T_>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                          (int)wf_loss_lds(WF_MAX_T)) != hipSuccess)
+    return AVA_ELAUNCH;
+  const int fixed = slope_lambda > 1.7976931348623157e308;  // +inf: the shift objective
+  hipLaunchKernelGGL(warpfit_pl_loss_kernel<T_>, dim3(N, ceil_div(C, WF_CB)), dim3(256), wf_loss_lds(T), st, spec, target, cand,
+                     F, T, C, K, shift_lambda, fixed ? 0.0 : slope_lambda, fixed, loss);
+  AVA_CHECK_LAUNCH();
+  return AVA_OK;
+}
+
+extern "C" int ava_warpfit_pl_loss(const void* spec, int dtype, int N, int F, int T, const double* target, const double* cand,
+                                   int C, int K, double shift_lambda, double slope_lambda, double* loss, ava_stream_t s) {
+  if (spec == nullptr || target == nullptr || cand == nullptr || loss == nullptr || !wf_shape_ok(dtype, N, F, T)) return AVA_EINVAL;
+  if (!wf_knots_ok(T, K) || C < 1 || C > WF_MAX_C || shift_lambda != shift_lambda || slope_lambda != slope_lambda) return AVA_EINVAL;
+  if (dtype == 0)
+    return wf_launch_pl_loss(static_cast<const float*>(spec), N, F, T, target, cand, C, K, shift_lambda, slope_lambda, loss,
+                             to_stream(s));
+  return wf_launch_pl_loss(static_cast<const double*>(spec), N, F, T, target, cand, C, K, shift_lambda, slope_lambda, loss,
+                           to_stream(s));
+}
+
+extern "C" int ava_warpfit_pl_argmin(const double* loss, const double* cand, int N, int C, int K, int32_t* best, double* u,
+                                     double* best_loss, ava_stream_t s) {
+  if (K < 2 || K > WF_MAX_K) return AVA_EINVAL;
+  return wf_launch_argmin(loss, cand, N, C, K, best, u, best_loss, s);
 }

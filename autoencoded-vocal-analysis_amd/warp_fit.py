@@ -1,4 +1,4 @@
-"""The shift-and-slope time-warp fit on the device.
+"""The time-warp fit on the device: shift and slope, piecewise linear (row f14).
 
 Mirror of the reference's own replacement for affinewarp, ``ava/preprocessing/warping.py``:
 
@@ -6,7 +6,8 @@ Mirror of the reference's own replacement for affinewarp, ``ava/preprocessing/wa
   ``align_specs``             warping.py:53-145    alternate a mean template with a per-spectrogram minimisation
   ``minimize_warp``           warping.py:121-131   the ``scipy.optimize.minimize(method='Powell')`` of every motif, batched
   ``warp_loss``               warping.py:148-163   both objectives, for a batch of candidates per motif
-  ``knots_from_warp_params``  the fitted shifts and slopes as the knots of ``DeviceWarpedWindowDataset``
+  ``knots_from_warp_params``  the fitted warps as the knots of ``DeviceWarpedWindowDataset``
+  ``pl_warp_loss``, ``pl_minimize_warp``, ``align_specs(..., n_knots=)``   the piecewise-linear warp, no reference code
   ``install``                 points the reference module's two public functions here
 
 Every number is made by the kernels of ``csrc/warp_fit.hip`` in fp64; there is no CPU fallback.  The functions take
@@ -30,6 +31,23 @@ side of its best point when it halves (5 points) was seen to settle in the cell 
 above it in loss; 15 points keep 3.5 cells on either side, 7 points 1.5.  The number of rounds depends on ``T`` alone,
 so nothing is read back: one ``align_specs`` iteration is enqueued without a host synchronisation.  The search always
 returns a result: the reference's ``(None, None)`` on an optimiser failure has no counterpart here.
+
+The piecewise-linear warp (``n_knots > 0``; what the reference's ``WarpedWindowDataset`` asks affinewarp for, which is no
+dependency here).  A motif has ``K = n_knots + 2`` knots ``u[k]``: the source position, in time bins, that the template
+column ``t_k = k (T - 1) / (K - 1)`` maps to.  Column ``j`` lies in segment ``k = min(j (K - 1) // (T - 1), K - 2)`` and
+reads the source at ``p(j) = u_k + s_k (j - t_k)`` with ``s_k = (u_{k+1} - u_k) / (t_{k+1} - t_k)``; the objective is
+``sum((interp(spec)(p) - target) ** 2) + shift_λ u_0 ** 2 + slope_λ mean_k(log(s_k) ** 2)``, ``+inf`` when some
+``s_k <= 0``.  With ``K = 2`` that is the objective above at ``shift = u_0``, ``slope = s_0``.  ``K`` is at most
+``ava_warpfit_max_knots()`` = 16 and ``T - 1 >= 2 (K - 1)`` (``ValueError``).  An iteration of ``align_specs`` searches in
+two stages.  Stage A is the search above for (shift, log slope), carried from iteration to iteration as before; its result
+gives the starting knots ``u_k = shift + slope t_k``: the knots of the iteration before are not kept, only the template
+made from them is.  Stage B (``pl_minimize_warp``) is a coordinate search: rounds with
+the knot step ``h`` halving from ``T * SHIFT_SPAN / (KNOT_KS (K - 1))`` until it is below ``XTOL``, every round sweeping
+the knots ``k = 0 .. K - 1`` in order, every knot trying ``u_k + o h`` for ``o = 0, -1, +1, ... ± KNOT_KS`` in one
+candidates, one loss and one argmin launch.  The first round reaches ``SHIFT_SPAN`` of a segment's length on either side
+of a knot.  Candidate 0 is the centre and wins ties, and crossed knots lose to any finite loss, so a motif's loss never
+rises and its knots stay in order.  An iteration with ``slope_λ = inf`` has no stage B: ``u_k = shift + t_k``.  The number of
+launches depends on ``T`` and ``K`` alone: nothing is read back here either.
 """
 import warnings
 
@@ -39,8 +57,9 @@ import torch
 from . import _lib
 
 __all__ = ["WARNING_MSG", "XTOL", "GRID_KS", "GRID_KL", "LINE_KS", "SHIFT_SPAN", "LOG_SLOPE_SPAN", "DEFAULT_SHIFT_LAMBDAS",
-           "DEFAULT_SLOPE_LAMBDAS", "apply_warp", "align_specs", "minimize_warp", "warp_loss", "search_rounds",
-           "check_schedule", "knots_from_warp_params", "install"]
+           "DEFAULT_SLOPE_LAMBDAS", "KNOT_KS", "apply_warp", "align_specs", "minimize_warp", "warp_loss", "search_rounds",
+           "check_schedule", "knots_from_warp_params", "install", "knot_columns", "knot_rounds", "pl_warp_loss",
+           "pl_minimize_warp"]
 
 WARNING_MSG = "ava.preprocessing.warping is experimental and may change in " + \
     "a future version of AVA!"                 # warping.py:20-21
@@ -50,6 +69,7 @@ GRID_KS, GRID_KL = 3, 2    # grid points on either side of the centre: shifts, l
 LINE_KS = 7                # the same for the line of shifts searched when slope_λ = inf
 SHIFT_SPAN = 0.125         # half-span of the first round's shifts, as a fraction of T
 LOG_SLOPE_SPAN = 0.25      # half-span of the first round's log slopes
+KNOT_KS = 3                # candidates on either side of a knot in the piecewise-linear coordinate search
 
 # the schedule fit='device' of DeviceWarpedWindowDataset uses when warp_params names none: shift-only first, then
 # decreasing penalties down to the maximum-likelihood fit (the advice of the reference's docstring, warping.py:67-72)
@@ -97,12 +117,49 @@ def _apply(specs, params):
     return out
 
 
+def knot_columns(T, K):
+    """the template columns ``t_k = k (T - 1) / (K - 1)`` of ``K`` knots: ``[K]`` float64"""
+    return np.arange(K) * (T - 1) / (K - 1)
+
+
+def _check_knots(T, K):
+    """``ValueError`` unless ``K`` knots fit ``T`` time bins; raised before any launch"""
+    cap = _lib.load().ava_warpfit_max_knots()
+    if K < 2 or K > cap:
+        raise ValueError("a warp has 2 to %d knots (n_knots = 0 to %d), got %d" % (cap, cap - 2, K))
+    if T - 1 < 2 * (K - 1):
+        raise ValueError("%d knots need at least %d time bins, got %d" % (K, 2 * (K - 1) + 1, T))
+
+
+def _knots_tensor(knots, dev, N, T):
+    t = knots if torch.is_tensor(knots) else torch.from_numpy(np.ascontiguousarray(np.asarray(knots, dtype=np.float64)))
+    if t.dim() != 2 or t.shape[0] != N:
+        raise ValueError("expected knots of shape [n_specs, n_knots + 2], got %s" % (tuple(t.shape),))
+    _check_knots(T, t.shape[1])
+    return t.to(device=dev, dtype=torch.float64).contiguous()
+
+
+def _apply_pl(specs, knots):
+    """``specs`` [N, F, T] under ``knots`` [N, K], device tensors; enqueued, nothing synchronises"""
+    N, F, T = specs.shape
+    out = torch.empty_like(specs)
+    rc = _lib.load().ava_warpfit_pl_apply(specs.data_ptr(), _DTYPES[specs.dtype], N, F, T, knots.data_ptr(), knots.shape[1],
+                                          out.data_ptr(), _lib.stream())
+    _lib.check(rc, "ava_warpfit_pl_apply")
+    return out
+
+
 def apply_warp(specs, warp_params):
     """``apply_warp`` (warping.py:25-50): ``warped[n, f, j] = interp1d(specs[n, f])(shifts[n] + slopes[n] * j)`` with the
     end columns held outside the spectrogram.  ``warp_params`` maps ``'shifts'`` and ``'slopes'`` to ``[n_specs]``
-    arrays or tensors.  Same shape, dtype and kind (numpy array or device tensor) as ``specs``."""
+    arrays or tensors.  With a key ``'knots'`` (``[n_specs, K]``, what ``align_specs(..., n_knots=K - 2)`` returns) the
+    positions are the piecewise-linear ``p(j)`` of the module docstring instead, and the other two keys are not read.
+    Same shape, dtype and kind (numpy array or device tensor) as ``specs``."""
     specs, is_numpy = _specs_tensor(specs)
     N = specs.shape[0]
+    if 'knots' in warp_params:
+        out = _apply_pl(specs, _knots_tensor(warp_params['knots'], specs.device, N, specs.shape[2]))
+        return out.cpu().numpy() if is_numpy else out
     params = torch.stack([_f64(warp_params['shifts'], specs.device, (N,)),
                           _f64(warp_params['slopes'], specs.device, (N,))], dim=1).contiguous()
     out = _apply(specs, params)
@@ -127,6 +184,26 @@ def warp_loss(specs, target, candidates, shift_λ, slope_λ):
     rc = _lib.load().ava_warpfit_loss(specs.data_ptr(), _DTYPES[specs.dtype], N, F, T, target.data_ptr(), cand.data_ptr(),
                                       cand.shape[1], shift_λ, slope_λ, loss.data_ptr(), _lib.stream())
     _lib.check(rc, "ava_warpfit_loss")
+    return loss.cpu().numpy() if is_numpy else loss
+
+
+def pl_warp_loss(specs, target, candidates, shift_λ, slope_λ):
+    """The piecewise-linear objective of the module docstring for ``candidates`` ``[N, C, K]``, ``K`` knots each:
+    ``[N, C]`` float64, ``+inf`` where knots cross.  With ``slope_λ = inf`` every slope is 1 (``p(j) = u_0 + j``), the
+    slope term is dropped and crossed knots go unnoticed.  Same sums, in the same order, as ``warp_loss``."""
+    specs, is_numpy = _specs_tensor(specs)
+    N, F, T = specs.shape
+    target = _f64(target, specs.device, (F, T))
+    cand = candidates if torch.is_tensor(candidates) else torch.from_numpy(np.asarray(candidates, dtype=np.float64))
+    if cand.dim() != 3 or cand.shape[0] != N or cand.shape[1] < 1:
+        raise ValueError("expected candidates of shape [n_specs, n_candidates, n_knots + 2]")
+    _check_knots(T, cand.shape[2])
+    cand = cand.to(device=specs.device, dtype=torch.float64).contiguous()
+    shift_λ, slope_λ = _check_lambdas(shift_λ, slope_λ)
+    loss = torch.empty((N, cand.shape[1]), dtype=torch.float64, device=specs.device)
+    rc = _lib.load().ava_warpfit_pl_loss(specs.data_ptr(), _DTYPES[specs.dtype], N, F, T, target.data_ptr(), cand.data_ptr(),
+                                         cand.shape[1], cand.shape[2], shift_λ, slope_λ, loss.data_ptr(), _lib.stream())
+    _lib.check(rc, "ava_warpfit_pl_loss")
     return loss.cpu().numpy() if is_numpy else loss
 
 
@@ -202,7 +279,58 @@ def minimize_warp(specs, target, x0, shift_λ, slope_λ):
     return (x.cpu().numpy(), best_loss.cpu().numpy()) if is_numpy else (x, best_loss)
 
 
-def align_specs(specs, shift_λs, slope_λs, verbose=True):
+def knot_rounds(T, K):
+    """the knot steps of every round of ``pl_minimize_warp`` for ``T`` time bins and ``K`` knots: halving from
+    ``T * SHIFT_SPAN / (KNOT_KS (K - 1))`` until below ``XTOL``"""
+    h, rounds = T * SHIFT_SPAN / (KNOT_KS * (K - 1)), []
+    while h >= XTOL:
+        rounds.append(h)
+        h = h / 2
+    return rounds
+
+
+def _minimize_pl(specs, target, u, shift_λ, slope_λ, best_loss):
+    """stage B on device tensors; ``u`` [N, K] and ``best_loss`` [N] are updated in place.  ``slope_λ = inf``: a line
+    search of one shift common to all knots, after which ``u_k = u_0 + t_k``."""
+    lib = _lib.load()
+    N, F, T = specs.shape
+    K = u.shape[1]
+    fixed = slope_λ == np.inf
+    ks = LINE_KS if fixed else KNOT_KS
+    steps = [(-1, hs) for hs, _ in search_rounds(T, True)[2]] if fixed else \
+        [(k, h) for h in knot_rounds(T, K) for k in range(K)]
+    C = 2 * ks + 1
+    dev, st = specs.device, _lib.stream()
+    cand = torch.empty((N, C, K), dtype=torch.float64, device=dev)
+    loss = torch.empty((N, C), dtype=torch.float64, device=dev)
+    best = torch.empty(N, dtype=torch.int32, device=dev)
+    for axis, h in steps:
+        _lib.check(lib.ava_warpfit_pl_candidates(u.data_ptr(), N, K, axis, ks, h, cand.data_ptr(), st),
+                   "ava_warpfit_pl_candidates")
+        _lib.check(lib.ava_warpfit_pl_loss(specs.data_ptr(), _DTYPES[specs.dtype], N, F, T, target.data_ptr(),
+                                           cand.data_ptr(), C, K, shift_λ, slope_λ, loss.data_ptr(), st), "ava_warpfit_pl_loss")
+        _lib.check(lib.ava_warpfit_pl_argmin(loss.data_ptr(), cand.data_ptr(), N, C, K, best.data_ptr(), u.data_ptr(),
+                                             best_loss.data_ptr(), st), "ava_warpfit_pl_argmin")
+    if fixed:
+        u.copy_(u[:, :1] + torch.from_numpy(knot_columns(T, K)).to(dev))
+
+
+def pl_minimize_warp(specs, target, u0, shift_λ, slope_λ):
+    """Stage B of the module docstring for all motifs at once: ``(u [N, K], loss [N])`` from the knots ``u0`` [N, K]
+    by the coordinate search over single knots.  The loss returned is never above ``pl_warp_loss`` at ``u0``, and
+    knots that start in order stay in order.  With ``slope_λ = inf`` one shift common to all knots is searched
+    instead (a line of ``2 LINE_KS + 1`` shifts, as ``minimize_warp`` does) and ``u_k = u_0 + t_k`` is returned."""
+    specs, is_numpy = _specs_tensor(specs)
+    N, F, T = specs.shape
+    target = _f64(target, specs.device, (F, T))
+    u = _knots_tensor(u0, specs.device, N, T).clone()
+    shift_λ, slope_λ = _check_lambdas(shift_λ, slope_λ)
+    best_loss = torch.empty(N, dtype=torch.float64, device=specs.device)
+    _minimize_pl(specs, target, u, shift_λ, slope_λ, best_loss)
+    return (u.cpu().numpy(), best_loss.cpu().numpy()) if is_numpy else (u, best_loss)
+
+
+def align_specs(specs, shift_λs, slope_λs, verbose=True, *, n_knots=0):
     """``align_specs`` (warping.py:53-145): align the spectrograms ``[n_specs, freq_bins, time_bins]`` by per-spectrogram
     shifts and slopes, alternating the mean warped spectrogram as the target with ``minimize_warp`` under
     ``shift_λs[i]``, ``slope_λs[i]`` (``slope_λ = inf``: a shift-only iteration, after which the log slope is 0), for
@@ -210,16 +338,29 @@ def align_specs(specs, shift_λs, slope_λs, verbose=True):
     in the shape, dtype and kind of ``specs``, and ``{'shifts': [n_specs], 'slopes': [n_specs]}`` in time bins, such that
     ``apply_warp(specs, warp_params)`` is ``warped_specs``.  Warns that the module is experimental, as the reference
     does.  The iterations are enqueued back to back; the ``verbose`` lines (the last spectrogram's loss per iteration,
-    warping.py:141-143) are printed once all of them are.  There is no ``(None, None)`` return."""
+    warping.py:141-143) are printed once all of them are.  There is no ``(None, None)`` return.
+
+    ``n_knots > 0`` (no counterpart in the reference): a piecewise-linear warp of ``n_knots + 2`` knots per spectrogram,
+    every iteration fitting stage A and then stage B of the module docstring.  Stage B does not warm-start: every
+    iteration rebuilds the knots from stage A's line ``shift + slope t_k`` and the previous iteration's knots reach it
+    only through the mean template.  ``warp_params`` then also holds
+    ``'knots'`` ``[n_specs, n_knots + 2]`` in time bins, which ``apply_warp`` uses; ``'shifts'`` and ``'slopes'`` are
+    stage A's last values."""
     warnings.warn(WARNING_MSG)
     specs, is_numpy = _specs_tensor(specs)
     N, F, T = specs.shape
+    n_knots = int(n_knots)
+    if n_knots != 0:
+        _check_knots(T, n_knots + 2)
     lib, dev = _lib.load(), specs.device
     total_iterations = min(len(shift_λs), len(slope_λs))
     schedule = [_check_lambdas(shift_λs[i], slope_λs[i]) for i in range(total_iterations)]
     warped = specs.clone()
     x = torch.zeros((N, 2), dtype=torch.float64, device=dev)
     params = torch.stack([x[:, 0], torch.exp(x[:, 1])], dim=1)
+    if n_knots != 0:
+        t_k = torch.from_numpy(knot_columns(T, n_knots + 2)).to(dev)
+        knots = (params[:, :1] + params[:, 1:] * t_k).contiguous()
     target = torch.empty((F, T), dtype=torch.float64, device=dev)
     best_loss = torch.empty(N, dtype=torch.float64, device=dev)
     last_losses = torch.zeros(max(total_iterations, 1), dtype=torch.float64, device=dev)
@@ -230,12 +371,20 @@ def align_specs(specs, shift_λs, slope_λs, verbose=True):
         if slope_λ == np.inf:
             x[:, 1] = 0.0                                   # slope = 1, log slope = 0 (warping.py:132-133)
         params = torch.stack([x[:, 0], torch.exp(x[:, 1])], dim=1)
-        warped = _apply(specs, params)
+        if n_knots == 0:
+            warped = _apply(specs, params)
+        else:
+            knots = (params[:, :1] + params[:, 1:] * t_k).contiguous()     # stage A's line: u_k = shift + slope t_k
+            if slope_λ != np.inf:
+                _minimize_pl(specs, target, knots, shift_λ, slope_λ, best_loss)
+            warped = _apply_pl(specs, knots)
         last_losses[warp_iter] = best_loss[-1]
     if verbose:
         for warp_iter, loss in enumerate(last_losses[:total_iterations].cpu().numpy()):
             print("Iteration {}, loss={}".format(warp_iter, round(float(loss), 3)))
     warp_params = {'shifts': params[:, 0].contiguous(), 'slopes': params[:, 1].contiguous()}
+    if n_knots != 0:
+        warp_params['knots'] = knots
     if is_numpy:
         return warped.cpu().numpy(), {k: v.cpu().numpy() for k, v in warp_params.items()}
     return warped, warp_params
@@ -246,14 +395,23 @@ def knots_from_warp_params(warp_params, num_time_bins):
     ``template_dur``.  Time bin ``j`` of the fit inputs is the STFT frame at ``j * frame_step`` seconds, i.e. at
     quantile ``j / num_time_bins`` of ``template_dur = num_time_bins * frame_step``; ``warped(j) = spec(shift + slope *
     j)`` therefore maps the template quantile ``y`` to the measured quantile ``x = shift / T + slope * y``:
-    ``y_knots = [0, 1]``, ``x_knots = [shift / T, shift / T + slope]``."""
+    ``y_knots = [0, 1]``, ``x_knots = [shift / T, shift / T + slope]``.  With a key ``'knots'`` (``[N, K]`` in time bins,
+    strictly increasing) the other two are not read: ``x_knots = knots / T``, ``y_knots = knot_columns(T, K) / T``
+    (``[N, K]`` each); the dataset extrapolates the outer segments beyond the outer knots."""
+    T = float(num_time_bins)
+    if 'knots' in warp_params:
+        u = np.asarray(_host(warp_params['knots']), dtype=np.float64)
+        if u.ndim != 2 or u.shape[1] < 2:
+            raise ValueError("'knots' must be [n_specs, n_knots + 2]")
+        if not (np.diff(u, axis=1) > 0).all():
+            raise ValueError("knots must be strictly increasing")
+        return u / T, np.tile(knot_columns(int(num_time_bins), u.shape[1]) / T, (len(u), 1))
     shifts = np.asarray(_host(warp_params['shifts']), dtype=np.float64).reshape(-1)
     slopes = np.asarray(_host(warp_params['slopes']), dtype=np.float64).reshape(-1)
     if shifts.shape != slopes.shape:
         raise ValueError("'shifts' and 'slopes' must have one entry per spectrogram each")
     if not (slopes > 0).all():
         raise ValueError("slopes must be positive")
-    T = float(num_time_bins)
     x_knots = np.stack([shifts / T, shifts / T + slopes], axis=1)
     y_knots = np.tile([0.0, 1.0], (len(shifts), 1))
     return x_knots, y_knots

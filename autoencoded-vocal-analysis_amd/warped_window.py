@@ -20,7 +20,8 @@ reference's batch), the inverse warp (``scipy.interpolate.interp1d`` on ``n x T`
 optional warp fit, which is ``affinewarp.PiecewiseWarping.fit`` exactly as the reference calls it when ``affinewarp``
 can be imported (``ImportError`` otherwise; ``warp_type='null'`` and ``load_warp=True`` need no fit).  ``fit='device'``
 fits the reference's own shift-and-slope warp (``ava/preprocessing/warping.py``) on the device instead
-(``ava_amd.warp_fit``, row f12) and needs no affinewarp.
+(``ava_amd.warp_fit``, row f12) and needs no affinewarp; with ``warp_params['n_knots'] > 0`` it fits that module's
+piecewise-linear warp of ``n_knots + 2`` knots per file (row f14).
 
 Not mirrored: ``write_hdf5_files`` (``h5py`` is no dependency of this package).  Limits as ``spec.get_spec_batch``:
 ``nperseg`` in 64..2048, at most 512 target times per window (``NotImplementedError``); the fit inputs need ``nperseg``
@@ -115,7 +116,7 @@ def _stack_specs_and_amps(spec, fsum, frame_off, dtype):
 class DeviceWarpedWindowDataset:
     """``WarpedWindowDataset`` (window_vae_dataset.py:358-701) with the audio and the log-spectrogram of every motif
     resident in HBM.  Same constructor arguments plus ``device`` and ``fit`` (``'affinewarp'``: the reference's fit;
-    ``'device'``: ``ava_amd.warp_fit.align_specs``, one linear segment per file) (``transform`` is accepted and ignored:
+    ``'device'``: ``ava_amd.warp_fit.align_specs``, ``warp_params['n_knots'] + 1`` linear segments per file) (``transform`` is accepted and ignored:
     the items already are fp32 device tensors); ``from_arrays`` builds one from in-memory recordings and knots.
 
     ``__getitem__(index, seed=None)``: for a list ``index`` one device tensor ``[len(index), F, T]`` (the reference
@@ -195,7 +196,9 @@ class DeviceWarpedWindowDataset:
 
     def _compute_warp(self, load_warp=False, save_warp=True, warp_type='spectrogram', fit='affinewarp'):
         """window_vae_dataset.py:480-586.  ``fit='device'``: where the reference fits affinewarp's ``PiecewiseWarping``,
-        fit the shift-and-slope warp of ``ava_amd.warp_fit`` instead (with ``n_knots: 0`` the same family of warps)."""
+        fit the warp of ``ava_amd.warp_fit`` with ``n_knots + 2`` knots instead (with ``n_knots: 0`` shift and slope, the
+        same family of warps; above that a piecewise-linear warp, but on fixed template knots and under that module's
+        penalties, not affinewarp's)."""
         if save_warp:
             assert self.warp_fn is not None, "``warp_fn`` must be specified to save warps!"
         if warp_type == 'null':
@@ -283,7 +286,9 @@ class DeviceWarpedWindowDataset:
         """The fit of ``fit='device'``: ``warp_fit.align_specs`` on the spectrograms (``warp_type='spectrogram'``) or the
         amplitude traces (``'amplitude'``) of ``get_specs_and_amplitude_traces`` as ``[files, bins, frames]``, under the
         schedule ``warp_params['shift_lambdas']`` / ``['slope_lambdas']`` (default: ``warp_fit.DEFAULT_*_LAMBDAS``);
-        the shifts and slopes become two knots per file.  The saved dict has the reference's keys."""
+        with ``warp_params['n_knots']`` inner knots: ``[files, n_knots + 2]`` knots, for ``n_knots: 0`` the shift and
+        slope as two knots per file.  ``warp_reg_scale``, ``smoothness_reg_scale`` and ``l2_reg_scale`` are not read.
+        The saved dict has the reference's keys."""
         from . import warp_fit
         shift_λs, slope_λs = warp_fit.check_schedule(self.warp_params.get('shift_lambdas', warp_fit.DEFAULT_SHIFT_LAMBDAS),
                                                      self.warp_params.get('slope_lambdas', warp_fit.DEFAULT_SLOPE_LAMBDAS))
@@ -298,7 +303,7 @@ class DeviceWarpedWindowDataset:
         else:
             raise NotImplementedError
         _, fitted = warp_fit.align_specs(np.ascontiguousarray(fit_input.transpose(0, 2, 1)), shift_λs, slope_λs,
-                                         verbose=False)
+                                         verbose=False, n_knots=int(self.warp_params.get('n_knots', 0)))
         self.x_knots, self.y_knots = warp_fit.knots_from_warp_params(fitted, fit_input.shape[1])
         if save_warp:
             print("Saving warp to:", self.warp_fn)

@@ -496,6 +496,34 @@ int ava_warpfit_loss(const void* spec, int dtype, int N, int F, int T, const dou
 int ava_warpfit_argmin(const double* loss, const double* cand, int N, int C, int32_t* best, double* x, double* best_loss,
                        ava_stream_t s);
 
+/* ---- the piecewise-linear time-warp fit --------------------------------------------
+ * The fit above with K = n_knots + 2 knots per motif, 2 <= K <= ava_warpfit_max_knots() (16), T - 1 >= 2 (K - 1).
+ * knots / u / a candidate: K float64, u_k = the source position (time bins) template column t_k = k (T-1) / (K-1) maps
+ * to.  Column j lies in segment k = min(j (K-1) / (T-1), K-2) (integer division) and reads the source at
+ * p(j) = u_k + s_k (j - t_k), s_k = (u_{k+1} - u_k) / (t_{k+1} - t_k), nothing fused; interpolation as above.  K = 2 is
+ * the warp above with shift = u_0, slope = s_0.
+ *
+ * ava_warpfit_pl_apply: out[n][f][j] = interp(spec[n][f][:])(p_n(j)) for knots [N][K], out of spec's dtype.
+ * ava_warpfit_pl_candidates: cand [N][C][K], C = 2 ks + 1, around u [N][K]: candidate c moves knot `axis` (axis = -1:
+ *   every knot) by o h, o = 0, -1, +1, -2, +2, ..., so candidate 0 is u itself.  -1 <= axis < K, 0 <= ks <= 31, h >= 0.
+ * ava_warpfit_pl_loss: loss [N][C] float64 = sum_{f,j} (interp(spec[n][f][:])(p(j)) - target[f][j])^2
+ *   + shift_lambda u_0^2 + slope_lambda (sum_k (log s_k)^2) / (K - 1) for every candidate of cand [N][C][K]; +inf for a
+ *   candidate with some s_k <= 0 (knots out of order).  slope_lambda = +inf: p(j) = u_0 + j whatever the other knots say,
+ *   the slope term is dropped and no candidate is out of order.  1 <= C <= 4096.  Same kernel structure, LDS and
+ *   summation order as ava_warpfit_loss.
+ * ava_warpfit_pl_argmin: ava_warpfit_argmin for candidates of K parameters: u [N][K] receives the best candidate.
+ *   +inf loses to every finite loss.
+ *
+ * All return AVA_EINVAL before any launch on the conditions of the entry points above, or for K outside the limits. */
+int ava_warpfit_max_knots(void);
+int ava_warpfit_pl_apply(const void* spec, int dtype, int N, int F, int T, const double* knots, int K, void* out,
+                         ava_stream_t s);
+int ava_warpfit_pl_candidates(const double* u, int N, int K, int axis, int ks, double h, double* cand, ava_stream_t s);
+int ava_warpfit_pl_loss(const void* spec, int dtype, int N, int F, int T, const double* target, const double* cand, int C,
+                        int K, double shift_lambda, double slope_lambda, double* loss, ava_stream_t s);
+int ava_warpfit_pl_argmin(const double* loss, const double* cand, int N, int C, int K, int32_t* best, double* u,
+                          double* best_loss, ava_stream_t s);
+
 /* ---- exact 1-nearest-neighbour search ------------------------------------------------
  * The searches of ava/plotting/shotgun_movie.py:shotgun_movie_DC: NearestNeighbors(n_neighbors=1,
  * metric='correlation') over spectrograms (:148-158) and argmin of scipy's euclidean over latent means (:126-133).

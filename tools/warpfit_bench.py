@@ -8,6 +8,12 @@ slopes), 10 iterations: three shift-only, then seven with decreasing penalties. 
                                                        35-candidate grid, and its bytes per second: every workgroup
                                                        reads its motif (F T 4 bytes) and the target (F T 8 bytes) once
                                                        per block of 8 candidates
+    python tools/warpfit_bench.py --n-knots 4          the same with the piecewise-linear warp of row f14 (6 knots per
+                                                       motif): every iteration that is not shift-only adds the
+                                                       coordinate search, (knot rounds x 6) x 3 small launches; the
+                                                       loss_kernel_* fields still time the shift-and-slope kernel
+                                                       (stage A of every iteration), pl_loss_kernel_* the knot
+                                                       search's kernel on its 7 candidates of 6 knots
     python tools/warpfit_bench.py --reference PATH     the reference's ava.preprocessing.warping.align_specs (numpy and
                                                        scipy's Powell) on the same workload, on this machine's CPU
 
@@ -49,7 +55,7 @@ def spread(w):
     return float(((w - w.mean(axis=0)) ** 2).sum())
 
 
-def device(specs, reps):
+def device(specs, reps, n_knots=0):
     import torch
     from ava_amd import _lib
     from ava_amd import warp_fit as wf
@@ -59,7 +65,7 @@ def device(specs, reps):
     def fit():
         with warnings.catch_warnings():
             warnings.simplefilter("ignore")
-            return wf.align_specs(d, SHIFT_LAMBDAS, SLOPE_LAMBDAS, verbose=False)
+            return wf.align_specs(d, SHIFT_LAMBDAS, SLOPE_LAMBDAS, verbose=False, n_knots=n_knots)
 
     fit()
     torch.cuda.synchronize()
@@ -82,25 +88,50 @@ def device(specs, reps):
         _lib.check(lib.ava_warpfit_loss(d.data_ptr(), 0, N, F, T, target.data_ptr(), cand.data_ptr(), C, 1e-3, 1.0,
                                         loss.data_ptr(), _lib.stream()), "ava_warpfit_loss")
 
-    run()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(reps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        run()
-        e1.record()
-        e1.synchronize()
-        ms.append(e0.elapsed_time(e1))
-    med = float(np.median(ms))
+    def median_ms(launch):
+        launch()
+        torch.cuda.synchronize()
+        ms = []
+        for _ in range(reps):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            launch()
+            e1.record()
+            e1.synchronize()
+            ms.append(e0.elapsed_time(e1))
+        return float(np.median(ms))
+
+    med = median_ms(run)
     blocks = N * ((C + 7) // 8)
     nbytes = blocks * F * T * (specs.dtype.itemsize + 8)
     launches = sum(len(wf.search_rounds(T, lam == np.inf)[2]) for lam in SLOPE_LAMBDAS)
-    return {"align_specs_wall_s": wall, "spread_before": spread(specs), "spread_after": spread(warped.cpu().numpy()),
+    knot_launches = 3 * (n_knots + 2) * len(wf.knot_rounds(T, n_knots + 2)) * sum(lam != np.inf for lam in SLOPE_LAMBDAS) \
+        if n_knots else 0
+    out = {"n_knots": n_knots, "knot_search_launches_per_fit": knot_launches, "loss_kernel": "warpfit_loss_kernel"}
+    if n_knots:
+        # the knot search's loss kernel alone: one knot of every motif moved, 2 KNOT_KS + 1 candidates of K knots
+        K, Cp = n_knots + 2, 2 * wf.KNOT_KS + 1
+        u = torch.from_numpy(np.tile(wf.knot_columns(T, K), (N, 1))).cuda()
+        pcand = torch.empty((N, Cp, K), dtype=torch.float64, device="cuda")
+        ploss = torch.empty((N, Cp), dtype=torch.float64, device="cuda")
+        _lib.check(lib.ava_warpfit_pl_candidates(u.data_ptr(), N, K, 1, wf.KNOT_KS, wf.knot_rounds(T, K)[3], pcand.data_ptr(),
+                                                 _lib.stream()), "ava_warpfit_pl_candidates")
+
+        def run_pl():
+            _lib.check(lib.ava_warpfit_pl_loss(d.data_ptr(), 0, N, F, T, target.data_ptr(), pcand.data_ptr(), Cp, K, 1e-3, 1.0,
+                                               ploss.data_ptr(), _lib.stream()), "ava_warpfit_pl_loss")
+
+        pmed = median_ms(run_pl)
+        pbytes = N * ((Cp + 7) // 8) * F * T * (specs.dtype.itemsize + 8)
+        out.update({"pl_loss_kernel": "warpfit_pl_loss_kernel", "pl_loss_kernel_ms": pmed, "pl_loss_kernel_candidates": Cp,
+                    "pl_loss_kernel_bytes": pbytes, "pl_loss_kernel_TB_per_s": pbytes / (pmed * 1e-3) / 1e12,
+                    "pl_loss_kernel_interp_per_s": N * Cp * F * T / (pmed * 1e-3), "pl_loss_launches_per_fit": knot_launches // 3})
+    out.update({"align_specs_wall_s": wall, "spread_before": spread(specs), "spread_after": spread(warped.cpu().numpy()),
             "loss_kernel_ms": med, "loss_kernel_candidates": C, "loss_kernel_bytes": nbytes,
             "loss_kernel_TB_per_s": nbytes / (med * 1e-3) / 1e12, "loss_kernel_fraction_of_8TBps": nbytes / (med * 1e-3) / 8e12,
             "loss_launches_per_fit": launches,
-            "loss_kernel_interp_per_s": N * C * F * T / (med * 1e-3)}
+            "loss_kernel_interp_per_s": N * C * F * T / (med * 1e-3)})
+    return out
 
 
 def reference(specs, path):
@@ -121,11 +152,12 @@ def main():
     ap.add_argument("--f", type=int, default=128)
     ap.add_argument("--t", type=int, default=128)
     ap.add_argument("--reps", type=int, default=9)
+    ap.add_argument("--n-knots", type=int, default=0, help="inner knots of the piecewise-linear warp (0: shift and slope)")
     ap.add_argument("--reference", default=None, help="path of the reference package: time its align_specs on the CPU")
     a = ap.parse_args()
     specs = workload(a.n, a.f, a.t)
     out = {"bench": "warpfit", "N": a.n, "F": a.f, "T": a.t, "iterations": len(SHIFT_LAMBDAS), "dtype": str(specs.dtype)}
-    out.update(reference(specs, a.reference) if a.reference else device(specs, a.reps))
+    out.update(reference(specs, a.reference) if a.reference else device(specs, a.reps, a.n_knots))
     print(json.dumps(out))
 
 
