@@ -131,6 +131,12 @@ SIGNATURES = {
     "ava_warpfit_pl_candidates": (_i, [_p, _i, _i, _i, _i, _d, _p, _p]),
     "ava_warpfit_pl_loss": (_i, [_p, _i, _i, _i, _i, _p, _p, _i, _i, _d, _d, _p, _p]),
     "ava_warpfit_pl_argmin": (_i, [_p, _p, _i, _i, _i, _p, _p, _p, _p]),
+    "ava_shiftfit_max_t": (_i, []),
+    "ava_shiftfit_workspace_bytes": (_sz, [_i, _i, _i]),
+    "ava_shiftfit_template": (_i, [_p, _i, _i, _i, _i, _p, _d, _d, _p, _p, _p, _sz, _p]),
+    "ava_shiftfit_loss": (_i, [_p, _i, _i, _i, _i, _p, _i, _p, _p]),
+    "ava_shiftfit_argmin": (_i, [_p, _i, _i, _p, _p, _p]),
+    "ava_shiftfit_apply": (_i, [_p, _i, _i, _i, _i, _p, _p, _p]),
     "ava_nn_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "ava_nn_argmin": (_i, [_p, _i, _i, _p, _i, _i, _i, _i, _p, _p, _p, _sz, _p]),
     "ava_nn_merge": (_i, [_p, _p, _p, _p, _i, _i64, _i, _p]),

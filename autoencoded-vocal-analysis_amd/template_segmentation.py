@@ -15,8 +15,12 @@ Mirror of the computational surface of ava/segmenting/template_segmentation.py, 
   ``clean_collected_segments`` lines 281-452   same signature, prints, prompts and picture; ``clean_collected_data`` is
                                its deprecated alias (lines 267-278)
   ``_in_region``               lines 817-827
+  ``segment_sylls_from_songs`` lines 455-627   same signature, prompts, prints and files; the alignment is
+                               ``shift_fit.ShiftWarping`` (row f15), this project's model in place of affinewarp's
+  ``segment_sylls_from_warped_songs``  lines 630-755   on a ``DeviceWarpedWindowDataset``; writes ``.npz``
   ``install``                  points the reference module's ``get_template``, ``segment_files``, ``_segment_file``,
-                               ``clean_collected_segments``, ``clean_collected_data`` here and adds ``segment_specs``
+                               ``clean_collected_segments``, ``clean_collected_data`` and the two ``segment_sylls_*``
+                               here and adds ``segment_specs``
 
 The band spectrogram of whole files (``_get_spec``, lines 758-790) and the correlation with the template run on the
 device in fp64 (the band kernel of ``csrc/segment.hip`` in sum mode, then ``csrc/template_seg.hip``); the host
@@ -44,7 +48,7 @@ from .spec import DeviceAudio, _is_wav_file, _read_wav, _stft_constants
 
 __all__ = ["EPSILON", "get_template", "get_template_from_audio", "segment_files", "read_segment_decisions",
            "xcorr_batch", "segment_batch", "segments_from_trace", "segment_specs", "clean_collected_segments",
-           "clean_collected_data", "_in_region", "install"]
+           "clean_collected_data", "_in_region", "segment_sylls_from_songs", "segment_sylls_from_warped_songs", "install"]
 
 EPSILON = 1e-9                       # template_segmentation.py:31
 DEFAULT_CHUNK_BYTES = 1 << 30        # audio bytes per batch of segment_files()
@@ -526,10 +530,310 @@ def clean_collected_data(result, audio_dirs, segment_dirs, p, max_num_specs=1000
                              img_fn=img_fn, tooltip_plot_dir=tooltip_plot_dir)
 
 
+# ---- song motifs into syllables ----------------------------------------------------
+
+def _song_slices(song_segs, shoulder, read):
+    """The host half of lines 487-512: for every song segment of ``song_segs`` (``{filename: [[onset, offset], ...]}``)
+    the samples ``audio[max(i1, 0):i2]`` with ``i = int(fs * t)`` (Python's truncation towards zero, not the ``round``
+    of ``segment_specs``) of the segment widened by ``shoulder`` on either side.  ``read(filename)`` returns ``(fs,
+    audio)``.  Returns a dict of equally long lists ``slices``, ``fns``, ``song_onsets`` (the widened onsets),
+    ``edge`` (does the segment reach outside the file?), ``pad_secs`` (``(-i1 / fs, (i2 - len(audio)) / fs)``: the
+    seconds missing in front and behind), and ``empty_audio_files``: the recordings without song."""
+    out = dict(slices=[], fns=[], song_onsets=[], edge=[], pad_secs=[], empty_audio_files=[])
+    for audio_fn in song_segs:
+        fs, audio = read(audio_fn)
+        for seg in np.asarray(song_segs[audio_fn]).reshape(-1, 2):
+            onset, offset = seg[0] - shoulder, seg[1] + shoulder
+            i1, i2 = int(fs * onset), int(fs * offset)
+            out['slices'].append(audio[max(i1, 0):i2])
+            out['fns'].append(audio_fn)
+            out['song_onsets'].append(onset)
+            out['edge'].append(i1 < 0 or i2 > len(audio))
+            out['pad_secs'].append((-i1 / fs, (i2 - len(audio)) / fs))
+        if len(song_segs[audio_fn]) == 0:
+            out['empty_audio_files'].append(audio_fn)
+    return out
+
+
+def _edge_bins(pad_secs, dt):
+    """``(pre_bins, post_bins)`` of lines 500-501 for a segment that misses ``pad_secs`` seconds in front and behind"""
+    return max(0, int(np.round(pad_secs[0] / dt))), max(0, int(np.round(pad_secs[1] / dt)))
+
+
+def _song_traces(audio_dirs, song_seg_dirs, p, shoulder=0.05, verbose=True):
+    """Lines 485-530 of ``segment_sylls_from_songs`` up to the fit: a dict with ``traces`` (device float64
+    ``[K, T]``: per segment the band spectrogram summed over frequency, minus its mean, divided by ``std + EPSILON``,
+    all on the device, then truncated to the shortest), ``specs`` (device ``[K, F, max_t]``, zero-padded), ``bins``
+    (time bins of every segment's spectrogram, edge padding included), ``dt`` and the lists of ``_song_slices``."""
+    song_segs = read_segment_decisions(audio_dirs, song_seg_dirs)
+
+    def read(fn):
+        fs, audio = _read_wav(fn)
+        return fs, audio
+
+    info = _song_slices(song_segs, shoulder, read)
+    assert len(info['slices']) > 0, "Found no spectrograms!"
+    for fn, piece in zip(info['fns'], info['slices']):
+        if len(piece) < p['nperseg']:
+            raise ValueError("a song segment of %s has %d samples, fewer than nperseg = %d" % (fn, len(piece), p['nperseg']))
+    specs, _, dt = _seg.padded_specs(info['slices'], p)
+    dev = specs.device
+    bins = _seg.frame_count([len(a) for a in info['slices']], int(p['nperseg']), int(p['noverlap']))
+    own = torch.from_numpy(bins).to(dev)                                  # columns the segment's own spectrogram has
+    edge = np.array(info['edge'], dtype=bool)
+    for k in np.flatnonzero(edge):                                        # lines 499-507: a constant, wider spectrogram
+        pre_bins, post_bins = _edge_bins(info['pad_secs'][k], dt)
+        bins[k] += pre_bins + post_bins
+    # amplitude traces (lines 516-520), every segment over its own columns
+    mask = (torch.arange(specs.shape[2], device=dev)[None, :] < own[:, None]).to(torch.float64)
+    amps = specs.sum(dim=1) * mask
+    mean = amps.sum(dim=1, keepdim=True) / own[:, None]
+    amps = (amps - mean) * mask
+    std = torch.sqrt((amps * amps).sum(dim=1, keepdim=True) / own[:, None])
+    amps = amps / (std + EPSILON)
+    amps[torch.from_numpy(edge).to(dev)] = 0.0                            # a constant spectrogram: an all-zero trace
+    min_time_bins, max_time_bins = int(bins.min()), int(bins.max())
+    if verbose and (min_time_bins != max_time_bins):
+        print("Found different numbers of time bins in segments!")
+        print("\tmin:" + str(min_time_bins) + ", max:", max_time_bins)
+        print("\tTruncating to minimum number of time bins.")
+    if min_time_bins > amps.shape[1]:                                     # every segment reaches outside its file
+        amps = torch.nn.functional.pad(amps, (0, min_time_bins - amps.shape[1]))
+    info.update(traces=amps[:, :min_time_bins].contiguous(), specs=specs, bins=bins, own_bins=own.cpu().numpy(), dt=dt)
+    return info
+
+
+def _write_syll_segments(fns, song_onsets, shifts, quantiles, num_time_bins, dt, audio_dirs, syll_seg_dirs,
+                         empty_audio_files):
+    """Lines 593-627: the syllable segment files.  Per song segment the onsets and offsets ``song_onset + duration *
+    quantile + shift * dt``, ``'%.5f'``, under a two-line header for a file's first segment (``'wb'``) and a one-line
+    header for the later ones (``'ab'``); an empty file with its header for every recording without song."""
+    duration = num_time_bins * dt
+    quantiles = np.array(quantiles)
+    quantiles.sort()
+    files_encountered = {}
+    for i, (fn, song_onset) in enumerate(zip(fns, song_onsets)):
+        onsets = song_onset + duration * quantiles[:-1] + shifts[i] * dt
+        offsets = song_onset + duration * quantiles[1:] + shifts[i] * dt
+        write_fn = _syll_filename(fn, audio_dirs, syll_seg_dirs)
+        segs = np.stack([onsets, offsets]).reshape(2, -1).T
+        header, mode = "", 'ab'
+        if fn not in files_encountered:
+            files_encountered[fn] = 1
+            mode = 'wb'
+            header += "Syllables from song: " + fn + "\n"
+        header += "Song onset: " + str(song_onset)
+        with open(write_fn, mode) as f:
+            np.savetxt(f, segs, fmt='%.5f', header=header)
+    for fn in empty_audio_files:
+        write_fn = _syll_filename(fn, audio_dirs, syll_seg_dirs)
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore", UserWarning)
+            np.savetxt(write_fn, np.array([]), header="Syllables from song: " + fn)
+
+
+def _syll_filename(fn, audio_dirs, syll_seg_dirs):
+    index = audio_dirs.index(os.path.split(fn)[0])
+    write_fn = os.path.join(syll_seg_dirs[index], os.path.split(fn)[-1])[:-4] + '.txt'
+    if not os.path.exists(os.path.split(write_fn)[0]):
+        os.makedirs(os.path.split(write_fn)[0])
+    return write_fn
+
+
+def _ask_quantile(quantiles, lo, hi, error_lines, blank_redraws=False):
+    """One round of the prompt of lines 571-587 / 688-705: ``True`` once the user stops"""
+    while True:
+        temp = input("Add or delete quantile or [s]top: ")
+        if blank_redraws and temp == '':
+            return False
+        if temp == 's':
+            return True
+        try:
+            temp = float(temp)
+            assert lo < temp and temp < hi
+        except (ValueError, AssertionError):
+            for line in error_lines:
+                print(line)
+            continue
+        if temp in quantiles:
+            quantiles.remove(temp)
+        else:
+            quantiles.append(temp)
+        return False
+
+
+def _check_quantiles(quantiles, lo, hi):
+    """the keyword-only ``quantiles`` as a list of floats strictly inside ``(lo, hi)``, at least two: ``ValueError``"""
+    quantiles = [float(q) for q in quantiles]
+    if len(quantiles) < 2:
+        raise ValueError("at least two quantiles are needed to cut a segment, got %d" % len(quantiles))
+    if not all(lo < q < hi for q in quantiles):
+        raise ValueError("quantiles must lie strictly between %s and %s" % (lo, hi))
+    return quantiles
+
+
+def segment_sylls_from_songs(audio_dirs, song_seg_dirs, syll_seg_dirs, p, shoulder=0.05, img_fn='temp.pdf', verbose=True,
+                             *, quantiles=None):
+    """Mirror of ``ava.segmenting.template_segmentation.segment_sylls_from_songs`` (lines 455-627; same arguments,
+    prompts, prints and files): split song renditions into syllables.  The band spectrograms of all song segments
+    (widened by ``shoulder``) are made in one batched pass, their amplitude traces are aligned by one integer shift each
+    with ``shift_fit.ShiftWarping(maxlag=0.2, smoothness_reg_scale=10.0)`` in 50 iterations on the device (this
+    project's own model in place of affinewarp's), the user enters quantiles of the aligned motif, and every
+    rendition's syllable segments are written to ``syll_seg_dirs``.  All song segments must be the same duration.
+
+    ``quantiles`` (keyword-only, no counterpart in the reference): cut at these quantiles without a picture or a prompt.
+    Fewer than two quantiles raise ``ValueError``, from the keyword before any device work; the reference would write
+    nothing useful there.
+
+    Edge behaviour, kept as the reference has it: a segment that reaches outside its file gets a constant spectrogram
+    of ``T + pre_bins + post_bins`` columns (line 506, which should paste the real one into it, is a no-op), hence an
+    all-zero amplitude trace and, by the tie rule of the fit, shift 0.  A segment of fewer than ``nperseg`` samples
+    raises ``ValueError``."""
+    from .shift_fit import ShiftWarping
+    if quantiles is not None:
+        quantiles = _check_quantiles(quantiles, 0.0, 1.0)
+    info = _song_traces(audio_dirs, song_seg_dirs, p, shoulder=shoulder, verbose=verbose)
+    amp_traces, dt = info['traces'], info['dt']
+    num_time_bins = int(amp_traces.shape[1])
+    max_t = num_time_bins * dt * 1e3
+    model = ShiftWarping(maxlag=0.2, smoothness_reg_scale=10.0)
+    model.fit(amp_traces[:, :, None], iterations=50)
+    shifts = model.shifts
+    if quantiles is None:
+        import matplotlib.pyplot as plt
+        plt.switch_backend('agg')
+        raw = amp_traces.cpu().numpy()
+        aligned = model.predict()[:, :, 0].cpu().numpy()
+        max_raw_val, max_aligned_val = np.max(raw), np.max(aligned)
+        quantiles = []
+        while True:
+            _, axarr = plt.subplots(3, 1, sharex=True)
+            k = np.random.randint(len(raw))
+            spec = info['specs'][k, :, :int(info['own_bins'][k])].cpu().numpy()
+            if info['edge'][k]:
+                spec = np.mean(spec) * np.ones((spec.shape[0], int(info['bins'][k])))
+            axarr[0].imshow(spec, origin='lower', aspect='auto', extent=[0, max_t, p['min_freq'] / 1e3, p['max_freq'] / 1e3])
+            temp = np.copy(raw)
+            for q in quantiles:
+                for i in range(len(temp)):
+                    try:
+                        temp[i, int(round(q * num_time_bins)) + shifts[i]] = max_raw_val
+                    except IndexError:
+                        pass
+            axarr[1].imshow(temp, origin='lower', aspect='auto', extent=[0, max_t, 0, len(raw)])
+            temp = np.copy(aligned)
+            for q in quantiles:
+                for i in range(len(temp)):
+                    temp[i, int(round(q * num_time_bins))] = max_aligned_val
+            axarr[2].imshow(temp, origin='lower', aspect='auto', extent=[0, max_t, 0, len(raw)])
+            axarr[0].set_ylabel("Frequency (kHz)")
+            axarr[1].set_ylabel('Amplitude')
+            axarr[2].set_ylabel('Shifted')
+            axarr[0].set_title('Enter segmenting quantiles:')
+            axarr[2].set_xlabel('Time (ms)')
+            plt.savefig(img_fn)
+            plt.close('all')
+            if _ask_quantile(quantiles, 0.0, 1.0, ["Invalid input!", "Must be \'s\' or a float between 0 and 1."]):
+                break
+        if len(quantiles) < 2:
+            raise ValueError("at least two quantiles are needed to cut a segment, got %d" % len(quantiles))
+    if verbose:
+        print("Writing syllable segments...")
+    _write_syll_segments(info['fns'], info['song_onsets'], shifts, quantiles, num_time_bins, dt, audio_dirs, syll_seg_dirs,
+                         info['empty_audio_files'])
+
+
+WARPED_BATCH = 1024                  # windows per launch of segment_sylls_from_warped_songs
+
+
+def _write_warped_sylls(dset, audio_dirs, spec_dirs, quantiles):
+    """Lines 712-752 on a dataset with ``audio_filenames``, ``p``, ``_target_times`` and ``windows``: one ``.npz`` per
+    recording, written as ``process_sylls`` writes its groups.  Returns the number of spectrograms saved."""
+    from .preprocess import iter_groups
+    audio_dir_to_spec_dir = dict(zip(audio_dirs, spec_dirs))
+    quantiles = sorted(quantiles)
+    segs = [[q1, q2] for q1, q2 in zip(quantiles[:-1], quantiles[1:])]
+    n_files, n_segs, T = len(dset.audio_filenames), len(segs), dset.p['num_time_bins']
+    file_index = np.repeat(np.arange(n_files), n_segs)
+    target_times = np.empty((n_files * n_segs, T))
+    for index in range(n_files):
+        for j, (q1, q2) in enumerate(segs):
+            target_times[index * n_segs + j] = dset._target_times(index, q1, q2, T)
+    specs = []
+    for lo in range(0, len(file_index), WARPED_BATCH):
+        specs.append(dset.windows(file_index[lo:lo + WARPED_BATCH], target_times[lo:lo + WARPED_BATCH]).cpu().numpy())
+    specs = np.concatenate(specs)
+    onsets, offsets = [q1 for q1, _ in segs], [q2 for _, q2 in segs]      # quantiles are saved, not times
+    for index, audio_fn in enumerate(dset.audio_filenames):
+        spec_dir = audio_dir_to_spec_dir[os.path.split(audio_fn)[0]]
+        if not os.path.exists(spec_dir):
+            os.makedirs(spec_dir)
+        write_fn = os.path.join(spec_dir, os.path.split(audio_fn)[-1][:-4] + '.npz')
+        rows = slice(index * n_segs, (index + 1) * n_segs)
+        for data in iter_groups(specs[rows], onsets, offsets, [audio_fn] * n_segs, n_segs):
+            np.savez(write_fn, **data)
+    return len(file_index)
+
+
+def segment_sylls_from_warped_songs(warped_window_dset, audio_dirs, spec_dirs, time_bins=512, num_specs=3,
+                                    img_fn='temp.pdf', verbose=True, *, quantiles=None):
+    """Mirror of ``ava.segmenting.template_segmentation.segment_sylls_from_warped_songs`` (lines 630-755; same
+    arguments, prompts and prints) on a ``warped_window.DeviceWarpedWindowDataset``: the user enters quantiles of the
+    warped motif, and for every recording the time-warped spectrogram between each pair of neighbouring quantiles is
+    saved.  All recordings x all quantile pairs go through ``windows()`` in batches of ``WARPED_BATCH``.  Per recording
+    one file ``<name>.npz`` in its ``spec_dir`` holds ``specs``, ``onsets``, ``offsets`` (the quantiles, as the reference
+    saves them) and ``audio_filenames``, written as ``preprocess.process_sylls`` writes (``.npz`` where the reference
+    writes ``.hdf5``), so ``get_syllable_partition`` / ``DeviceSyllableDataset`` read the directory.
+
+    ``quantiles`` (keyword-only, no counterpart in the reference): cut at these quantiles without a picture or a prompt.
+    Fewer than two quantiles raise ``ValueError`` (the reference asserts)."""
+    dset = warped_window_dset
+    for audio_fn in dset.audio_filenames:
+        assert os.path.split(audio_fn)[0] in audio_dirs, "Cannot find " + os.path.split(audio_fn)[0] + " in audio_dirs!"
+    start_q, stop_q = dset.start_q, dset.stop_q
+    p = dset.p
+    if quantiles is not None:
+        quantiles = _check_quantiles(quantiles, start_q, stop_q)
+    else:
+        import matplotlib.pyplot as plt
+        plt.switch_backend('agg')
+        error_msg = "Invalid input!\nMust be \'s\' or a float between " + "{0:.2f}".format(start_q) + " and " + \
+            "{0:.2f}".format(stop_q) + "."
+        quantiles = []
+        while True:
+            _, axarr = plt.subplots(nrows=num_specs, sharex=True)
+            if num_specs == 1:
+                axarr = [axarr]
+            axarr[0].set_title('Enter segmenting quantiles:')
+            for i in range(num_specs):
+                plt.sca(axarr[i])
+                index = np.random.randint(len(dset.audio_filenames))
+                warped_spec = dset.get_whole_warped_spectrogram(dset.audio_filenames[index], time_bins=time_bins)
+                plt.imshow(warped_spec, origin='lower', aspect='auto',
+                           extent=[start_q, stop_q, p['min_freq'] / 1e3, p['max_freq'] / 1e3])
+                for q in quantiles:
+                    plt.axvline(x=q, color='red')
+                plt.ylabel("Frequency (kHz)")
+            plt.xlabel('Warped Time Quantile')
+            plt.savefig(img_fn)
+            plt.close('all')
+            if _ask_quantile(quantiles, start_q, stop_q, [error_msg], blank_redraws=True):
+                break
+        if len(quantiles) < 2:
+            raise ValueError("Not enough quantiles to segment!")
+    if verbose:
+        print("Making and saving syllable spectrograms...")
+    num_saved = _write_warped_sylls(dset, audio_dirs, spec_dirs, quantiles)
+    if verbose:
+        print("\tSaved " + str(num_saved) + " spectrograms.")
+        print("\tDone.")
+
+
 def install(module=None):
-    """Point ``get_template``, ``segment_files``, ``_segment_file``, ``clean_collected_segments`` and
-    ``clean_collected_data`` of ``module`` (by default ``ava.segmenting.template_segmentation``, imported after the
-    reference package) at this module, and give it ``segment_specs``, the batch counterpart of its ``_get_spec``."""
+    """Point ``get_template``, ``segment_files``, ``_segment_file``, ``clean_collected_segments``,
+    ``clean_collected_data``, ``segment_sylls_from_songs`` and ``segment_sylls_from_warped_songs`` of ``module`` (by
+    default ``ava.segmenting.template_segmentation``, imported after the reference package) at this module, and give it
+    ``segment_specs``, the batch counterpart of its ``_get_spec``."""
     if module is None:
         import ava.segmenting.template_segmentation as module
     module.get_template = get_template
@@ -538,4 +842,6 @@ def install(module=None):
     module.clean_collected_segments = clean_collected_segments
     module.clean_collected_data = clean_collected_data
     module.segment_specs = segment_specs
+    module.segment_sylls_from_songs = segment_sylls_from_songs
+    module.segment_sylls_from_warped_songs = segment_sylls_from_warped_songs
     return module

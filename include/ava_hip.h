@@ -524,6 +524,35 @@ int ava_warpfit_pl_loss(const void* spec, int dtype, int N, int F, int T, const 
 int ava_warpfit_pl_argmin(const double* loss, const double* cand, int N, int C, int K, int32_t* best, double* u,
                           double* best_loss, ava_stream_t s);
 
+/* ---- the integer-shift time-warp fit -------------------------------------------------
+ * The alignment of ava/segmenting/template_segmentation.py:segment_sylls_from_songs (:531-539), this project's own model
+ * in place of affinewarp's ShiftWarping (ava_amd/shift_fit.py states it).  x / dtype: [K][F][T] contiguous on the
+ * device, 0 = float32, 1 = float64; 3 <= T <= ava_shiftfit_max_t() (2048), F T < 2^30.  All arithmetic is fp64.
+ * Template column t lies at raw column t + s_k, the end columns held.  Lags are ordered lag_c = 0, -1, +1, -2, +2, ...,
+ * -L, +L (c = 0 .. 2 L).
+ *
+ * ava_shiftfit_workspace_bytes: device scratch ava_shiftfit_template needs (0 for an unsupported shape).
+ * ava_shiftfit_template: mbar [F][T] (may be NULL) = sum_k x[k][f][clip(t + s_k, 0, T-1)] / K, summed in chunks of 128
+ *   renditions (within a chunk in rising k, then the chunks in rising order: the bits do not depend on the grid), and
+ *   tmpl [F][T] = the solution of A tmpl[f][:] = mbar[f][:], A = (1 + l2 / K) I + smoothness D2^T D2 (D2: the second
+ *   differences (1, -2, 1)), by a banded LDL^T.  shifts [K] int32; smoothness, l2 >= 0 and finite; K <= 65535 * 128.
+ * ava_shiftfit_loss: loss [K][2 L + 1] float64 = sum_{f,t} (x[k][f][clip(t + lag_c, 0, T-1)] - tmpl[f][t])^2 / (F T),
+ *   0 <= L <= T - 1.  Every term is one rounded subtraction and one rounded multiplication; the sum runs in a fixed
+ *   order (csrc/shift_fit.hip), no atomics: two calls give the same bits.
+ * ava_shiftfit_argmin: shifts [K] int32 = the lag of least loss; equal losses resolve to the lowest c (so 0 beats -1
+ *   beats +1 ...), NaN never wins (all NaN: shift 0).  best_loss [K] (may be NULL) = that loss.
+ * ava_shiftfit_apply: out[k][f][t] = x[k][f][clip(t + s_k, 0, T-1)], out of x's dtype: exact copies.
+ *
+ * All return AVA_EINVAL before any launch for null pointers, an unknown dtype, K or F < 1, T outside the limits, L
+ * outside its range or a negative, infinite or NaN penalty; ava_shiftfit_template AVA_EWORKSPACE for too little scratch. */
+int ava_shiftfit_max_t(void);
+size_t ava_shiftfit_workspace_bytes(int K, int F, int T);
+int ava_shiftfit_template(const void* x, int dtype, int K, int F, int T, const int32_t* shifts, double smoothness, double l2,
+                          double* mbar, double* tmpl, void* ws, size_t ws_bytes, ava_stream_t s);
+int ava_shiftfit_loss(const void* x, int dtype, int K, int F, int T, const double* tmpl, int L, double* loss, ava_stream_t s);
+int ava_shiftfit_argmin(const double* loss, int K, int L, int32_t* shifts, double* best_loss, ava_stream_t s);
+int ava_shiftfit_apply(const void* x, int dtype, int K, int F, int T, const int32_t* shifts, void* out, ava_stream_t s);
+
 /* ---- exact 1-nearest-neighbour search ------------------------------------------------
  * The searches of ava/plotting/shotgun_movie.py:shotgun_movie_DC: NearestNeighbors(n_neighbors=1,
  * metric='correlation') over spectrograms (:148-158) and argmin of scipy's euclidean over latent means (:126-133).
