@@ -11,10 +11,14 @@ reference (mmd_plots.py)       here                                        C ent
 ``_estimate_mmd2``             :func:`_estimate_mmd2`         (:255-296)   ``ava_mmd2``
 ``_estimate_mmd2_linear_time`` :func:`_estimate_mmd2_linear_time` (:299-312) ``ava_mmd2_linear``
 loop of ``_calculate_mmd2``    :func:`mmd2_matrix`            (:395-418)   the above per condition pair
+the same loop, in one pass     :func:`mmd2_matrix_one_pass`                ``ava_mmd2_matrix`` / ``_linear``
+``_calculate_mmd2``            :func:`_calculate_mmd2`        (:337-434)   the one-pass matrix
 =============================  ==========================================  =============================
 
 ``install()`` swaps the three estimator functions of an imported ``ava.plotting.mmd_plots`` for these, so the
-reference's plotting functions (``mmd_matrix_plot_DC`` ...) run unchanged on top of them.  There is no CPU fallback:
+reference's plotting functions (``mmd_matrix_plot_DC`` ...) run unchanged on top of them; ``install(matrix=True)`` also
+swaps ``_calculate_mmd2``, so that the whole condition-by-condition matrix is one launch sequence (every block sum of
+the sorted index list at once, each within-set term once) instead of a host loop over the pairs.  There is no CPU fallback:
 without the HIP library / a GPU every function raises ``AvaHipError``.
 """
 import numpy as np
@@ -24,7 +28,9 @@ from . import _lib
 
 EPSILON = 1e-8          # ava/plotting/mmd_plots.py:34
 
-__all__ = ["estimate_median_sigma", "_estimate_mmd2", "_estimate_mmd2_linear_time", "mmd2_matrix", "install", "EPSILON"]
+__all__ = ["estimate_median_sigma", "_estimate_mmd2", "_estimate_mmd2_linear_time", "mmd2_matrix", "mmd2_block_terms",
+           "mmd2_matrix_one_pass", "_calculate_mmd2", "install", "EPSILON"]
+TILE = 64               # rows of a tile of the pairwise kernel (SQD_T of csrc/sqdist_tile.h)
 
 
 def _device():
@@ -142,11 +148,177 @@ def mmd2_matrix(latent, condition, alg='quadratic', sigma=None, max_n=None):
     return result, all_conditions
 
 
-def install(module=None):
-    """Point ``ava.plotting.mmd_plots``'s estimators at this module (call after importing the reference package)."""
+def _group_plan(condition):
+    """Everything the one-pass launches need to know about the grouping, in numpy (no GPU): a dict with
+
+    ``all_conditions``  ``np.unique(condition)`` (sorted), ``C`` of them
+    ``index``           int64 ``[N]``: the rows of condition 0, then of condition 1, ...; within a condition ascending,
+                        i.e. ``np.argwhere(condition == c).flatten()`` (one stable argsort)
+    ``offsets``         int64 ``[C + 1]``: condition ``c`` owns ``index[offsets[c]:offsets[c + 1]]``
+    ``counts``, ``tiles``  rows and ``ceil(rows / 64)`` tiles per condition
+    ``blocks``          int64 ``[C (C + 1) / 2 + 1, 4]``: a row ``{first workgroup, first workspace slot, a, b}`` per
+                        block ``a <= b`` in row-major order, then the totals (the table of ``ava_mmd2_matrix``)
+    ``pairs``           the same for the pairs ``a < b`` of the linear estimator (``ava_mmd2_matrix_linear``)
+    """
+    condition = np.asarray(condition).reshape(-1)
+    order = np.argsort(condition, kind='stable').astype(np.int64)
+    ordered = condition[order]
+    starts = np.concatenate([[0], np.flatnonzero(ordered[1:] != ordered[:-1]) + 1]) if len(ordered) else np.zeros(0)
+    starts = starts.astype(np.int64)
+    offsets = np.concatenate([starts, [len(ordered)]]).astype(np.int64)
+    counts = np.diff(offsets)
+    tiles = (counts + TILE - 1) // TILE
+
+    def table(a, b, workgroups, slots):
+        out = np.zeros((len(a) + 1, 4), dtype=np.int64)
+        out[1:, 0], out[1:, 1] = np.cumsum(workgroups), np.cumsum(slots)
+        out[:-1, 2], out[:-1, 3] = a, b
+        return out
+    a, b = np.triu_indices(len(counts))
+    full = tiles[a] * tiles[b]
+    blocks = table(a, b, np.where(a == b, tiles[a] * (tiles[a] + 1) // 2, full), full)
+    a, b = np.triu_indices(len(counts), 1)
+    groups = np.minimum((np.minimum(counts[a], counts[b]) // 2 + 255) // 256, 1024)
+    return {"all_conditions": ordered[starts], "index": order, "offsets": offsets, "counts": counts, "tiles": tiles,
+            "blocks": blocks, "pairs": table(a, b, groups, groups)}
+
+
+def _launch_matrix(latent, plan, sigma, linear):
+    """One upload of the plan, one launch sequence, one download: ``(within [C] or None, cross / linear [C, C])``."""
+    L = _latent_dev(latent)
+    C = len(plan["counts"])
+    if len(L) != len(plan["index"]):
+        raise ValueError("latent has %d rows, condition %d" % (len(L), len(plan["index"])))
+    lib = _lib.load()
+    offsets = np.ascontiguousarray(plan["offsets"])
+    table = plan["pairs"] if linear else plan["blocks"]
+    host = np.concatenate([plan["index"], offsets, table.reshape(-1)])
+    dev = torch.from_numpy(host).to(L.device)
+    idx, off, tab = dev[:len(L)], dev[len(L):len(L) + C + 1], dev[len(L) + C + 1:]
+    nbytes = lib.ava_mmd2_matrix_workspace_bytes(offsets.ctypes.data, C, int(linear))
+    if nbytes == 0:
+        raise _lib.AvaHipError("ava_mmd2_matrix_workspace_bytes: unsupported grouping (%d conditions)" % C)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=L.device)
+    out = (torch.zeros if linear else torch.empty)(C * C + C, dtype=torch.float64, device=L.device)
+    if linear:
+        _lib.check(lib.ava_mmd2_matrix_linear(L.data_ptr(), L.shape[1], idx.data_ptr(), offsets.ctypes.data,
+                                              off.data_ptr(), C, tab.data_ptr(), int(table[-1, 0]), float(sigma),
+                                              out.data_ptr(), ws.data_ptr(), nbytes, _lib.stream()),
+                   "ava_mmd2_matrix_linear")
+    else:
+        _lib.check(lib.ava_mmd2_matrix(L.data_ptr(), L.shape[1], idx.data_ptr(), offsets.ctypes.data, off.data_ptr(), C,
+                                       tab.data_ptr(), int(table[-1, 0]), float(sigma), out[C * C:].data_ptr(),
+                                       out.data_ptr(), ws.data_ptr(), nbytes, _lib.stream()), "ava_mmd2_matrix")
+    host_out = out.cpu().numpy()
+    return (None if linear else host_out[C * C:]), host_out[:C * C].reshape(C, C)
+
+
+def mmd2_block_terms(latent, condition, sigma=None):
+    """The normalised block sums behind the whole MMD^2 matrix, from one launch sequence: ``(within [C], cross [C, C],
+    all_conditions)`` with ``within[a]`` the within-set term of condition ``a`` (``term_1`` / ``term_2`` of
+    mmd_plots.py:276-288) and ``cross[a, b] = cross[b, a]`` the cross term of the pair (``term_3``, :289-294);
+    ``cross[a, a] = 0``.  Bit for bit the terms :func:`_terms` gives pair by pair.  Needs two conditions or more, each
+    of two rows or more (``ZeroDivisionError`` otherwise, as the reference's ``2/(n*(n-1))``)."""
+    plan = _group_plan(condition)
+    if len(plan["counts"]) < 2:
+        raise ValueError("mmd2_block_terms needs at least two conditions")
+    if plan["counts"].min() < 2:
+        raise ZeroDivisionError("division by zero")
+    if sigma is None:
+        sigma = estimate_median_sigma(latent)
+    within, cross = _launch_matrix(latent, plan, sigma, False)
+    return within, cross, plan["all_conditions"]
+
+
+def mmd2_matrix_one_pass(latent, condition, alg='quadratic', sigma=None, max_n=None):
+    """:func:`mmd2_matrix` without the host loop: ``(result [C, C], all_conditions)``, the same values bit for bit.
+
+    The rows are grouped by condition once and every pair's sums come out of one launch sequence (``alg='quadratic'``:
+    ``result[i, j] = within[i] + within[j] - cross[i, j]`` of :func:`mmd2_block_terms`, each within-set term computed
+    once; ``alg='linear'``: every pair's linear-time estimate).  No conditions give a ``(0, 0)`` result, one gives
+    ``[[0.]]``; otherwise an unknown ``alg`` raises ``NotImplementedError`` and a condition of fewer than two rows
+    ``ZeroDivisionError`` (quadratic) or ``AssertionError`` (linear), like the reference's loop, before any launch.
+
+    ``max_n``: the reference draws a fresh, unseeded subsample of the larger conditions for every pair, which one pass
+    over fixed index lists cannot restate.  So when ``alg='quadratic'``, ``max_n`` is not ``None`` and some condition
+    has more than ``max_n`` rows, this calls the per-pair :func:`mmd2_matrix`; otherwise ``max_n`` has no effect (the
+    linear estimator never looks at it) and the one-pass path runs."""
+    plan = _group_plan(condition)
+    all_conditions, counts = plan["all_conditions"], plan["counts"]
+    n = len(counts)
+    result = np.zeros((n, n))
+    if n < 2:
+        return result, all_conditions
+    if alg not in ('linear', 'quadratic'):
+        raise NotImplementedError
+    if alg == 'linear':
+        assert counts.min() // 2 > 0
+    elif counts.min() < 2:
+        raise ZeroDivisionError("division by zero")
+    elif max_n is not None and counts.max() > max_n:
+        return mmd2_matrix(latent, condition, alg=alg, sigma=sigma, max_n=max_n)
+    if sigma is None:
+        sigma = estimate_median_sigma(latent)
+    within, cross = _launch_matrix(latent, plan, sigma, alg == 'linear')
+    i, j = np.triu_indices(n, 1)
+    upper = cross[i, j] if alg == 'linear' else within[i] + within[j] - cross[i, j]
+    result[i, j] = upper
+    result[j, i] = upper
+    return result, all_conditions
+
+
+def _calculate_mmd2(dc, condition_from_fn, mmd2_fn=None, condition_fn=None, parallel=False, alg='quadratic', max_n=None,
+                    sigma=None, verbose=True):
+    """``_calculate_mmd2`` of the reference (mmd_plots.py:337-434) on :func:`mmd2_matrix_one_pass`: same arguments,
+    asserts, messages, saved files and return value ``(mmd2 [C, C], conditions [C])``.  ``dc`` needs a
+    ``request(field)`` method for ``'latent_means'`` and ``'audio_filenames'`` (a ``DataContainer``).
+
+    ``parallel=True`` starts no joblib workers (each would open the GPU for a share of one launch sequence); the
+    ``i j mmd2`` lines the reference's workers print are printed once the matrix is there, in ``(i, j)`` order, so
+    ``_matrix_from_txt`` on the captured output still rebuilds the matrix."""
+    assert alg in ['linear', 'quadratic']
+    assert mmd2_fn is not None
+    if verbose:
+        print("Estimating an MMD matrix...")
+        print("\talg:", alg)
+        print("\tparallel:", parallel)
+        print("\tmax_n:", max_n)
+    latent = dc.request('latent_means')
+    audio_fns = dc.request('audio_filenames')
+    condition = np.array([condition_from_fn(str(i)) for i in audio_fns], dtype='int')
+    n = len(np.unique(condition))
+    if sigma is None:
+        sigma = estimate_median_sigma(latent)
+    if verbose:
+        print("\tconditions found:", n)
+        print("\tsigma:", sigma)
+    result, all_conditions = mmd2_matrix_one_pass(latent, condition, alg=alg, sigma=sigma, max_n=max_n)
+    if parallel:
+        for i in range(n - 1):
+            for j in range(i + 1, n):
+                print(i, j, float(result[i, j]), flush=True)
+    if mmd2_fn is not None:
+        if verbose:
+            print("\tSaving MMD^2 to:", mmd2_fn)
+        np.save(mmd2_fn, result)
+    if condition_fn is not None:
+        if verbose:
+            print("\tSaving conditions to:", condition_fn)
+        np.save(condition_fn, all_conditions)
+    if verbose:
+        print("\tDone.")
+    return result, all_conditions
+
+
+def install(module=None, matrix=False):
+    """Point ``ava.plotting.mmd_plots``'s estimators at this module (call after importing the reference package).
+    ``matrix=True`` also replaces its ``_calculate_mmd2``, the function behind ``mmd_matrix_plot_DC``, with the
+    one-pass :func:`_calculate_mmd2` of this module."""
     if module is None:
         import ava.plotting.mmd_plots as module
     module.estimate_median_sigma = estimate_median_sigma
     module._estimate_mmd2 = _estimate_mmd2
     module._estimate_mmd2_linear_time = _estimate_mmd2_linear_time
+    if matrix:
+        module._calculate_mmd2 = _calculate_mmd2
     return module

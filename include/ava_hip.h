@@ -293,6 +293,31 @@ int ava_mmd2(const double* latent, int z, const int64_t* i1, int n1, const int64
  * i1[2i+1], i2[2i+1]); out (device double) = sum h / m.  ws: (min(ceil(m/256), 1024) + 8) doubles. */
 int ava_mmd2_linear(const double* latent, int z, const int64_t* i1, const int64_t* i2, int m, double sigma,
                     double* out, void* ws, size_t ws_bytes, ava_stream_t s);
+/* The condition-by-condition loop of _calculate_mmd2 (mmd_plots.py:395-418) in one launch sequence (row f16).
+ * idx (device): the int64 index lists of the C conditions, concatenated in condition order; offsets (HOST) and
+ * offsets_dev (device): the same C + 1 int64 list starts, offsets[C] = len(idx).  2 <= C <= 4096, every condition has
+ * 2 .. 2^31 - 1 rows, 1 <= z <= 128, sigma > 0 (AVA_EINVAL otherwise).
+ * A table row is 4 int64 {first workgroup, first workspace slot, a, b}, followed by one sentinel row {total
+ * workgroups, total slots, 0, 0}; with t_c = ceil(n_c / 64):
+ *   blocks (ava_mmd2_matrix): the C (C + 1) / 2 blocks a <= b, row-major; block (a, b) has t_a t_b slots (its whole
+ *     row-major tile grid) and t_a t_b workgroups, a symmetric block (a, a) t_a (t_a + 1) / 2 workgroups (the tiles on
+ *     and above the diagonal);
+ *   pairs (ava_mmd2_matrix_linear): the C (C - 1) / 2 pairs a < b, row-major; pair (a, b) has
+ *     min(ceil(m / 256), 1024) workgroups and as many slots, m = min(n_a, n_b) / 2.
+ * total_tiles / total_workgroups: column 0 of the sentinel row; it is checked against the host offsets and must be
+ * below 2^31.  ws: ava_mmd2_matrix_workspace_bytes(offsets, C, linear) = (total slots + 8) doubles; returns 0 for
+ * arguments the entry points reject.
+ * ava_mmd2_matrix: within[a] (device, C doubles) = 2 / (n_a (n_a - 1)) sum_{i<j} k, cross (device, C x C doubles)
+ * [a][b] = [b][a] = 2 / (n_a n_b) sum k, cross[a][a] = 0: the terms ava_mmd2 gives pair by pair, bit for bit.
+ * ava_mmd2_matrix_linear: out (device, C x C doubles) [a][b] = [b][a] = what ava_mmd2_linear gives for the first 2 m
+ * indices of both lists, bit for bit; the diagonal is not written.  Neither allocates nor synchronises. */
+size_t ava_mmd2_matrix_workspace_bytes(const int64_t* offsets, int C, int linear);
+int ava_mmd2_matrix(const double* latent, int z, const int64_t* idx, const int64_t* offsets, const int64_t* offsets_dev,
+                    int C, const int64_t* blocks, int64_t total_tiles, double sigma, double* within, double* cross,
+                    void* ws, size_t ws_bytes, ava_stream_t s);
+int ava_mmd2_matrix_linear(const double* latent, int z, const int64_t* idx, const int64_t* offsets,
+                           const int64_t* offsets_dev, int C, const int64_t* pairs, int64_t total_workgroups,
+                           double sigma, double* out, void* ws, size_t ws_bytes, ava_stream_t s);
 /* squared distances of n index pairs, out[p] = |latent[a[p]] - latent[b[p]]|^2: the sampled pairs of
  * estimate_median_sigma (mmd_plots.py:450-474; the median itself is taken by the caller). */
 int ava_pair_sqdist(const double* latent, int z, const int64_t* a, const int64_t* b, int n, double* out,
