@@ -134,6 +134,10 @@ SIGNATURES = {
     "ava_warpfit_pl_candidates": (_i, [_p, _i, _i, _i, _i, _d, _p, _p]),
     "ava_warpfit_pl_loss": (_i, [_p, _i, _i, _i, _i, _p, _p, _i, _i, _d, _d, _p, _p]),
     "ava_warpfit_pl_argmin": (_i, [_p, _p, _i, _i, _i, _p, _p, _p, _p]),
+    "ava_warpfit_group_loss": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _p, _i, _p, _p, _i, _p, _p, _i, _i, _p, _p]),
+    "ava_warpfit_group_pl_loss": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _p, _i, _p, _p, _i, _i, _p, _p, _i, _i, _p, _p]),
+    "ava_warpfit_group_mean": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _p, _i, _i, _p, _i, _p, _p]),
+    "ava_warpfit_group_pl_mean": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _p, _i, _i, _p, _i, _i, _p, _p]),
     "ava_shiftfit_max_t": (_i, []),
     "ava_shiftfit_workspace_bytes": (_sz, [_i, _i, _i]),
     "ava_shiftfit_template": (_i, [_p, _i, _i, _i, _i, _p, _d, _d, _p, _p, _p, _sz, _p]),

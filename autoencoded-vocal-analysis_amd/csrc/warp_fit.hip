@@ -32,6 +32,17 @@
 //   warpfit_pl_loss_kernel        warpfit_loss_kernel with the column tables made from knots: the same LDS, the same sums
 //                                 (wf_block_sums), + shift_l u_0^2 + slope_l mean_k (log s_k)^2
 //   warpfit_argmin_kernel         serves both fits: its parameter width is 2 or K
+//
+// The grouped fits (row f17): many fit problems over the same spec in one launch.  A group is a sorted list of motifs, a
+// sorted list of bins and two lambdas of its own; a virtual row is one (motif, group) pair (struct WfPlan).
+//
+//   warpfit_group_loss_kernel     warpfit_loss_kernel per virtual row: the motif, the target, the bins and the lambdas come
+//   warpfit_group_pl_loss_kernel  through the plan, the bins are staged through their list in list order, and everything
+//                                 else is the plain kernel's body (wf_loss_body / wf_pl_loss_body over wf_block_sums), so a
+//                                 virtual row's losses have the bits of the plain kernel on the gathered tensor
+//   warpfit_group_mean_kernel     every group's mean warped motif without the warped motifs: the apply kernels' values,
+//                                 summed over the group's rows in rising order
+//   the candidates and argmin kernels serve virtual rows as they are
 #include "common.h"
 
 #define WF_CB 8          // candidates per workgroup (two per wave)
@@ -156,8 +167,11 @@ __global__ __launch_bounds__(256) void warpfit_pl_candidates_kernel(const double
 // The sums of the loss kernels: with the (lo, weight) tables of the workgroup's candidates in LDS (written by the wave
 // that owns the candidate; the first barrier below publishes them), acc[k] = this lane's share of
 // sum_{f,j} (interp - target)^2 for candidate c0 + wave + 4 k.
-template <typename T_>
-__device__ __forceinline__ void wf_block_sums(const T_* __restrict__ motif, const double* __restrict__ target, int F, int T,
+// G (the grouped fits, row f17): staged row f0 + r is row bins[f0 + r] of the motif, which has Fall rows; the target is
+// compact, [F][T] by list position.  The plain form reads rows 0 .. F-1 and never looks at bins.
+template <typename T_, bool G>
+__device__ __forceinline__ void wf_block_sums(const T_* __restrict__ motif, const double* __restrict__ target,
+                                              const int* __restrict__ bins, int Fall, int F, int T,
                                               int C, int c0, double* s_spec, double* s_tgt, const double* s_w,
                                               const int* s_lo, double (&acc)[2]) {
   const int TS = T + 1;
@@ -167,7 +181,13 @@ __device__ __forceinline__ void wf_block_sums(const T_* __restrict__ motif, cons
     __syncthreads();                                        // the previous rows are consumed (first pass: tables written)
     for (int e = tid; e < nr * T; e += 256) {
       const int r = e / T, j = e - r * T;
-      const double v = (double)motif[(size_t)f0 * T + e];
+      double v;
+      if constexpr (G) {
+        const int b = bins[f0 + r];                         // one coalesced read of T columns per staged row
+        v = (unsigned)b < (unsigned)Fall ? (double)motif[(size_t)b * T + j] : __builtin_nan("");
+      } else {
+        v = (double)motif[(size_t)f0 * T + e];
+      }
       s_spec[r * TS + j] = v;
       if (j == T - 1) s_spec[r * TS + T] = v;
       s_tgt[r * T + j] = target[(size_t)f0 * T + e];
@@ -189,18 +209,20 @@ __device__ __forceinline__ void wf_block_sums(const T_* __restrict__ motif, cons
   }
 }
 
-template <typename T_>
-__global__ __launch_bounds__(256) void warpfit_loss_kernel(const T_* __restrict__ spec, const double* __restrict__ target,
-                                                           const double* __restrict__ cand, int F, int T, int C,
-                                                           double shift_lambda, double slope_lambda, int fixed_slope,
-                                                           double* __restrict__ loss) {
+// The loss of one (motif, candidate block): the body of warpfit_loss_kernel and of its grouped form.  raw: the tables are
+// lo = j, w = 0, the unwarped row read exactly, no candidate is read and no penalty added.
+template <typename T_, bool G>
+__device__ __forceinline__ void wf_loss_body(const T_* __restrict__ motif, const double* __restrict__ target,
+                                             const int* __restrict__ bins, int Fall, const double* __restrict__ cand, int F,
+                                             int T, int C, double shift_lambda, double slope_lambda, int fixed_slope, int raw,
+                                             double* __restrict__ loss) {
   extern __shared__ __align__(16) double wf_sm[];
   const int TS = T + 1;
   double* s_spec = wf_sm;                                   // [WF_FR][T + 1], column T repeats column T-1
   double* s_tgt = s_spec + WF_FR * TS;                      // [WF_FR][T]
   double* s_w = s_tgt + WF_FR * T;                          // [WF_CB][T]
   int* s_lo = reinterpret_cast<int*>(s_w + WF_CB * T);      // [WF_CB][T]
-  const int n = blockIdx.x, c0 = blockIdx.y * WF_CB;
+  const int c0 = blockIdx.y * WF_CB;
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
 
   double shift[2], ls[2];
@@ -209,8 +231,15 @@ __global__ __launch_bounds__(256) void warpfit_loss_kernel(const T_* __restrict_
     const int cc = wave + 4 * k, c = c0 + cc;
     shift[k] = ls[k] = 0.0;
     if (c < C) {                                            // wave-uniform
-      shift[k] = cand[2 * ((size_t)n * C + c)];
-      ls[k] = cand[2 * ((size_t)n * C + c) + 1];
+      if (G && raw) {
+        for (int j = lane; j < T; j += 64) {
+          s_lo[cc * T + j] = j;
+          s_w[cc * T + j] = 0.0;
+        }
+        continue;
+      }
+      shift[k] = cand[2 * (size_t)c];
+      ls[k] = cand[2 * (size_t)c + 1];
       const double slope = fixed_slope ? 1.0 : exp(ls[k]);
       for (int j = lane; j < T; j += 64) {
         const WfTap t = wf_tap(wf_pos(shift[k], slope, j), T);
@@ -221,42 +250,90 @@ __global__ __launch_bounds__(256) void warpfit_loss_kernel(const T_* __restrict_
   }
 
   double acc[2] = {0.0, 0.0};
-  wf_block_sums(spec + (size_t)n * F * T, target, F, T, C, c0, s_spec, s_tgt, s_w, s_lo, acc);
+  wf_block_sums<T_, G>(motif, target, bins, Fall, F, T, C, c0, s_spec, s_tgt, s_w, s_lo, acc);
 #pragma unroll
   for (int k = 0; k < 2; ++k) {
     const int c = c0 + wave + 4 * k;
     if (c >= C) continue;
     double tot = wave_sum_d(acc[k]);
-    // loss + shift_l * x[0]**2 + slope_l * x[1]**2, left to right
-    tot = __dadd_rn(tot, __dmul_rn(shift_lambda, __dmul_rn(shift[k], shift[k])));
-    if (!fixed_slope) tot = __dadd_rn(tot, __dmul_rn(slope_lambda, __dmul_rn(ls[k], ls[k])));
-    if (lane == 0) loss[(size_t)n * C + c] = tot;
+    if (!(G && raw)) {
+      // loss + shift_l * x[0]**2 + slope_l * x[1]**2, left to right
+      tot = __dadd_rn(tot, __dmul_rn(shift_lambda, __dmul_rn(shift[k], shift[k])));
+      if (!fixed_slope) tot = __dadd_rn(tot, __dmul_rn(slope_lambda, __dmul_rn(ls[k], ls[k])));
+    }
+    if (lane == 0) loss[c] = tot;
   }
 }
 
-// The loss kernel for candidates of K knots each, cand [N][C][K]: only the tables differ (a lane reads the two knots of
-// its column's segment from the candidate, K <= 16 doubles that stay in cache).  fixed_slope: every slope is 1 and the
+template <typename T_>
+__global__ __launch_bounds__(256) void warpfit_loss_kernel(const T_* __restrict__ spec, const double* __restrict__ target,
+                                                           const double* __restrict__ cand, int F, int T, int C,
+                                                           double shift_lambda, double slope_lambda, int fixed_slope,
+                                                           double* __restrict__ loss) {
+  const int n = blockIdx.x;
+  wf_loss_body<T_, false>(spec + (size_t)n * F * T, target, nullptr, F, cand + 2 * (size_t)n * C, F, T, C, shift_lambda,
+                          slope_lambda, fixed_slope, 0, loss + (size_t)n * C);
+}
+
+// The plan of the grouped fits (row f17): V virtual rows, row v being motif row_src[v] of spec [N][Fall][T] seen by group
+// row_group[v]; group g owns the rows group_row_off[g] .. group_row_off[g+1] - 1 (rising source order), the bins
+// bins[bin_off[g] .. bin_off[g+1] - 1] (rising) and the compact target [F_g][T] at targets + bin_off[g] T.
+struct WfPlan {
+  const int* row_src;
+  const int* row_group;
+  const int* group_row_off;
+  const int* bin_off;
+  const int* bins;
+  int N, Fall;
+};
+
+// warpfit_loss_kernel over virtual rows: the motif, the target, the bins and both lambdas come through the plan, the rest
+// is the plain kernel's, operation for operation; cand [V][C][2], loss [V][C]
+template <typename T_>
+__global__ __launch_bounds__(256) void warpfit_group_loss_kernel(const T_* __restrict__ spec, WfPlan pl,
+                                                                 const double* __restrict__ targets,
+                                                                 const double* __restrict__ cand, int T, int C,
+                                                                 const double* __restrict__ shift_lambda,
+                                                                 const double* __restrict__ slope_lambda, int fixed_slope,
+                                                                 int raw, double* __restrict__ loss) {
+  const int v = blockIdx.x, g = pl.row_group[v], n = pl.row_src[v];
+  if ((unsigned)n >= (unsigned)pl.N) return;                // a broken plan reads nothing
+  const int b0 = pl.bin_off[g], F = pl.bin_off[g + 1] - b0;
+  wf_loss_body<T_, true>(spec + (size_t)n * pl.Fall * T, targets + (size_t)b0 * T, pl.bins + b0, pl.Fall,
+                         raw ? nullptr : cand + 2 * (size_t)v * C, F, T, C, raw ? 0.0 : shift_lambda[g],
+                         (raw || fixed_slope) ? 0.0 : slope_lambda[g], fixed_slope, raw, loss + (size_t)v * C);
+}
+
+// The loss body for candidates of K knots each, cand [C][K]: only the tables differ (a lane reads the two knots of its
+// column's segment from the candidate, K <= 16 doubles that stay in cache).  fixed_slope: every slope is 1 and the
 // positions are u_0 + j, the shift objective.  Crossed knots do not stop the sums -- wf_tap keeps every tap inside the
 // row -- and the total is replaced by +inf.
-template <typename T_>
-__global__ __launch_bounds__(256) void warpfit_pl_loss_kernel(const T_* __restrict__ spec, const double* __restrict__ target,
-                                                              const double* __restrict__ cand, int F, int T, int C, int K,
-                                                              double shift_lambda, double slope_lambda, int fixed_slope,
-                                                              double* __restrict__ loss) {
+template <typename T_, bool G>
+__device__ __forceinline__ void wf_pl_loss_body(const T_* __restrict__ motif, const double* __restrict__ target,
+                                                const int* __restrict__ bins, int Fall, const double* __restrict__ cand,
+                                                int F, int T, int C, int K, double shift_lambda, double slope_lambda,
+                                                int fixed_slope, int raw, double* __restrict__ loss) {
   extern __shared__ __align__(16) double wf_sm[];
   const int TS = T + 1;
-  double* s_spec = wf_sm;                                   // as in warpfit_loss_kernel
+  double* s_spec = wf_sm;                                   // as in wf_loss_body
   double* s_tgt = s_spec + WF_FR * TS;
   double* s_w = s_tgt + WF_FR * T;
   int* s_lo = reinterpret_cast<int*>(s_w + WF_CB * T);
-  const int n = blockIdx.x, c0 = blockIdx.y * WF_CB;
+  const int c0 = blockIdx.y * WF_CB;
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
 
 #pragma unroll
   for (int k = 0; k < 2; ++k) {
     const int cc = wave + 4 * k, c = c0 + cc;
     if (c < C) {                                            // wave-uniform
-      const double* u = cand + ((size_t)n * C + c) * K;
+      if (G && raw) {
+        for (int j = lane; j < T; j += 64) {
+          s_lo[cc * T + j] = j;
+          s_w[cc * T + j] = 0.0;
+        }
+        continue;
+      }
+      const double* u = cand + (size_t)c * K;
       for (int j = lane; j < T; j += 64) {
         const WfTap t = wf_tap(fixed_slope ? wf_pos(u[0], 1.0, j) : wf_pl_pos(u, j, T, K), T);
         s_lo[cc * T + j] = t.lo;
@@ -266,27 +343,117 @@ __global__ __launch_bounds__(256) void warpfit_pl_loss_kernel(const T_* __restri
   }
 
   double acc[2] = {0.0, 0.0};
-  wf_block_sums(spec + (size_t)n * F * T, target, F, T, C, c0, s_spec, s_tgt, s_w, s_lo, acc);
+  wf_block_sums<T_, G>(motif, target, bins, Fall, F, T, C, c0, s_spec, s_tgt, s_w, s_lo, acc);
 #pragma unroll
   for (int k = 0; k < 2; ++k) {
     const int c = c0 + wave + 4 * k;
     if (c >= C) continue;
-    const double* u = cand + ((size_t)n * C + c) * K;
     double tot = wave_sum_d(acc[k]);
-    tot = __dadd_rn(tot, __dmul_rn(shift_lambda, __dmul_rn(u[0], u[0])));
-    if (!fixed_slope) {
-      double sq = 0.0;                                      // sum_k (log s_k)^2, k = 0, 1, ...
-      bool crossed = false;
-      for (int i = 0; i < K - 1; ++i) {
-        const double sl = wf_pl_slope(u, i, T, K);
-        crossed |= sl <= 0.0;
-        const double l = log(sl);
-        sq = __dadd_rn(sq, __dmul_rn(l, l));
+    if (!(G && raw)) {
+      const double* u = cand + (size_t)c * K;
+      tot = __dadd_rn(tot, __dmul_rn(shift_lambda, __dmul_rn(u[0], u[0])));
+      if (!fixed_slope) {
+        double sq = 0.0;                                    // sum_k (log s_k)^2, k = 0, 1, ...
+        bool crossed = false;
+        for (int i = 0; i < K - 1; ++i) {
+          const double sl = wf_pl_slope(u, i, T, K);
+          crossed |= sl <= 0.0;
+          const double l = log(sl);
+          sq = __dadd_rn(sq, __dmul_rn(l, l));
+        }
+        tot = __dadd_rn(tot, __dmul_rn(slope_lambda, __ddiv_rn(sq, (double)(K - 1))));
+        if (crossed) tot = __builtin_inf();
       }
-      tot = __dadd_rn(tot, __dmul_rn(slope_lambda, __ddiv_rn(sq, (double)(K - 1))));
-      if (crossed) tot = __builtin_inf();
     }
-    if (lane == 0) loss[(size_t)n * C + c] = tot;
+    if (lane == 0) loss[c] = tot;
+  }
+}
+
+template <typename T_>
+__global__ __launch_bounds__(256) void warpfit_pl_loss_kernel(const T_* __restrict__ spec, const double* __restrict__ target,
+                                                              const double* __restrict__ cand, int F, int T, int C, int K,
+                                                              double shift_lambda, double slope_lambda, int fixed_slope,
+                                                              double* __restrict__ loss) {
+  const int n = blockIdx.x;
+  wf_pl_loss_body<T_, false>(spec + (size_t)n * F * T, target, nullptr, F, cand + (size_t)n * C * K, F, T, C, K, shift_lambda,
+                             slope_lambda, fixed_slope, 0, loss + (size_t)n * C);
+}
+
+// warpfit_pl_loss_kernel over virtual rows; cand [V][C][K]
+template <typename T_>
+__global__ __launch_bounds__(256) void warpfit_group_pl_loss_kernel(const T_* __restrict__ spec, WfPlan pl,
+                                                                    const double* __restrict__ targets,
+                                                                    const double* __restrict__ cand, int T, int C, int K,
+                                                                    const double* __restrict__ shift_lambda,
+                                                                    const double* __restrict__ slope_lambda, int fixed_slope,
+                                                                    int raw, double* __restrict__ loss) {
+  const int v = blockIdx.x, g = pl.row_group[v], n = pl.row_src[v];
+  if ((unsigned)n >= (unsigned)pl.N) return;
+  const int b0 = pl.bin_off[g], F = pl.bin_off[g + 1] - b0;
+  wf_pl_loss_body<T_, true>(spec + (size_t)n * pl.Fall * T, targets + (size_t)b0 * T, pl.bins + b0, pl.Fall,
+                            raw ? nullptr : cand + (size_t)v * C * K, F, T, C, K, raw ? 0.0 : shift_lambda[g],
+                            (raw || fixed_slope) ? 0.0 : slope_lambda[g], fixed_slope, raw, loss + (size_t)v * C);
+}
+
+// The grouped template (row f17): target_g[f][j] = sum over the group's rows, in rising order, of the value the apply
+// kernels would store for that row -- interpolated under the row's own parameters and rounded to spec's dtype -- divided
+// by the row count: warpfit_mean_kernel of warpfit_apply_kernel's output without that output.  One workgroup per (group,
+// WM_TJ columns, share of the bins): WM_TR rows at a time, a row's tap for a column is computed once into LDS and then
+// used for every bin of the workgroup's share; thread (column, bin lane) carries the running sum of its (bin, column)
+// cells from one row set to the next through the target itself, which only that thread touches.  fp64, a fixed order,
+// no atomics.  mode 0: params [V][2] = (shift, slope) through wf_pos; 1: knots [V][K] through wf_pl_pos; 2 (raw): the
+// unwarped value, which an identity warp does not reproduce bit for bit.
+#define WM_TJ 64
+#define WM_TR 16
+template <typename T_>
+__global__ __launch_bounds__(256) void warpfit_group_mean_kernel(const T_* __restrict__ spec, WfPlan pl,
+                                                                 const double* __restrict__ params, int T, int K, int mode,
+                                                                 double* __restrict__ targets) {
+  __shared__ int s_lo[WM_TR][WM_TJ];
+  __shared__ double s_w[WM_TR][WM_TJ];
+  const int g = blockIdx.x, j0 = blockIdx.y * WM_TJ;
+  const int v0 = pl.group_row_off[g], R = pl.group_row_off[g + 1] - v0;
+  const int b0 = pl.bin_off[g], F = pl.bin_off[g + 1] - b0;
+  const int jc = threadIdx.x & (WM_TJ - 1), bl = threadIdx.x >> 6, j = j0 + jc;
+  const int* bins = pl.bins + b0;
+  double* tgt = targets + (size_t)b0 * T;
+  for (int r0 = 0; r0 < R; r0 += WM_TR) {
+    const int nr = R - r0 < WM_TR ? R - r0 : WM_TR;
+    __syncthreads();                                        // the previous row set's taps are consumed
+    if (mode != 2) {
+      for (int e = threadIdx.x; e < nr * WM_TJ; e += 256) {
+        const int r = e >> 6, jj = j0 + (e & (WM_TJ - 1));
+        if (jj >= T) continue;
+        const size_t v = (size_t)(v0 + r0 + r);
+        const double p = mode == 0 ? wf_pos(params[2 * v], params[2 * v + 1], jj) : wf_pl_pos(params + v * K, jj, T, K);
+        const WfTap t = wf_tap(p, T);
+        s_lo[r][e & (WM_TJ - 1)] = t.lo;
+        s_w[r][e & (WM_TJ - 1)] = t.w;
+      }
+    }
+    __syncthreads();
+    if (j >= T) continue;                                   // no barrier depends on this thread's work below
+    for (int f = blockIdx.z * 4 + bl; f < F; f += 4 * gridDim.z) {
+      const int b = bins[f];
+      double acc = r0 == 0 ? 0.0 : tgt[(size_t)f * T + j];
+      for (int r = 0; r < nr; ++r) {
+        const int n = pl.row_src[v0 + r0 + r];
+        T_ val;
+        if ((unsigned)n >= (unsigned)pl.N || (unsigned)b >= (unsigned)pl.Fall) {
+          val = (T_)__builtin_nan("");
+        } else {
+          const T_* row = spec + ((size_t)n * pl.Fall + b) * T;
+          if (mode == 2) {
+            val = row[j];
+          } else {
+            const int lo = s_lo[r][jc], hi = lo + 1 < T ? lo + 1 : T - 1;
+            val = (T_)wf_lerp((double)row[lo], (double)row[hi], s_w[r][jc]);
+          }
+        }
+        acc += (double)val;
+      }
+      tgt[(size_t)f * T + j] = r0 + nr >= R ? acc / (double)R : acc;
+    }
   }
 }
 
@@ -472,4 +639,97 @@ extern "C" int ava_warpfit_pl_argmin(const double* loss, const double* cand, int
                                      double* best_loss, ava_stream_t s) {
   if (K < 2 || K > WF_MAX_K) return AVA_EINVAL;
   return wf_launch_argmin(loss, cand, N, C, K, best, u, best_loss, s);
+}
+
+// ---- the grouped fits (row f17) -----------------------------------------------------------------------------------------
+
+template <typename T_>
+static int wf_launch_group_loss(const T_* spec, const WfPlan& pl, int V, int T, const double* targets, const double* cand,
+                                int C, int K, const double* shift_lambda, const double* slope_lambda, int fixed_slope,
+                                int raw, double* loss, hipStream_t st) {
+  const void* fn = K == 0 ? reinterpret_cast<const void*>(&warpfit_group_loss_kernel<T_>)
+                          : reinterpret_cast<const void*>(&warpfit_group_pl_loss_kernel<T_>);
+  if (wf_loss_lds(T) > 65536 &&                             // as in wf_launch_pl_loss
+      hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)wf_loss_lds(WF_MAX_T)) != hipSuccess)
+    return AVA_ELAUNCH;
+  const dim3 grid(V, ceil_div(C, WF_CB));
+  if (K == 0)
+    hipLaunchKernelGGL(warpfit_group_loss_kernel<T_>, grid, dim3(256), wf_loss_lds(T), st, spec, pl, targets, cand, T, C,
+                       shift_lambda, slope_lambda, fixed_slope, raw, loss);
+  else
+    hipLaunchKernelGGL(warpfit_group_pl_loss_kernel<T_>, grid, dim3(256), wf_loss_lds(T), st, spec, pl, targets, cand, T, C, K,
+                       shift_lambda, slope_lambda, fixed_slope, raw, loss);
+  AVA_CHECK_LAUNCH();
+  return AVA_OK;
+}
+
+// K = 0: the shift-and-slope form
+static int wf_group_loss(const void* spec, int dtype, int N, int F, int T, const int32_t* row_src, const int32_t* row_group,
+                         const int32_t* bin_off, const int32_t* bins, int V, const double* targets, const double* cand, int C,
+                         int K, const double* shift_lambda, const double* slope_lambda, int fixed_slope, int raw, double* loss,
+                         ava_stream_t s) {
+  if (spec == nullptr || targets == nullptr || loss == nullptr || !wf_shape_ok(dtype, N, F, T)) return AVA_EINVAL;
+  if (row_src == nullptr || row_group == nullptr || bin_off == nullptr || bins == nullptr || V < 1) return AVA_EINVAL;
+  if (C < 1 || C > WF_MAX_C || (fixed_slope != 0 && fixed_slope != 1) || (raw != 0 && raw != 1)) return AVA_EINVAL;
+  if (!raw && (cand == nullptr || shift_lambda == nullptr || slope_lambda == nullptr)) return AVA_EINVAL;
+  const WfPlan pl{row_src, row_group, nullptr, bin_off, bins, N, F};
+  if (dtype == 0)
+    return wf_launch_group_loss(static_cast<const float*>(spec), pl, V, T, targets, cand, C, K, shift_lambda, slope_lambda,
+                                fixed_slope, raw, loss, to_stream(s));
+  return wf_launch_group_loss(static_cast<const double*>(spec), pl, V, T, targets, cand, C, K, shift_lambda, slope_lambda,
+                              fixed_slope, raw, loss, to_stream(s));
+}
+
+extern "C" int ava_warpfit_group_loss(const void* spec, int dtype, int N, int F, int T, const int32_t* row_src,
+                                      const int32_t* row_group, const int32_t* bin_off, const int32_t* bins, int V,
+                                      const double* targets, const double* cand, int C, const double* shift_lambda,
+                                      const double* slope_lambda, int fixed_slope, int raw, double* loss, ava_stream_t s) {
+  return wf_group_loss(spec, dtype, N, F, T, row_src, row_group, bin_off, bins, V, targets, cand, C, 0, shift_lambda,
+                       slope_lambda, fixed_slope, raw, loss, s);
+}
+
+extern "C" int ava_warpfit_group_pl_loss(const void* spec, int dtype, int N, int F, int T, const int32_t* row_src,
+                                         const int32_t* row_group, const int32_t* bin_off, const int32_t* bins, int V,
+                                         const double* targets, const double* cand, int C, int K, const double* shift_lambda,
+                                         const double* slope_lambda, int fixed_slope, int raw, double* loss, ava_stream_t s) {
+  if (!wf_knots_ok(T, K)) return AVA_EINVAL;
+  return wf_group_loss(spec, dtype, N, F, T, row_src, row_group, bin_off, bins, V, targets, cand, C, K, shift_lambda,
+                       slope_lambda, fixed_slope, raw, loss, s);
+}
+
+// mode as in warpfit_group_mean_kernel; max_bins: the longest bin list of the G groups (sizes the grid only)
+static int wf_group_mean(const void* spec, int dtype, int N, int F, int T, const int32_t* row_src, const int32_t* group_row_off,
+                         const int32_t* bin_off, const int32_t* bins, int G, int max_bins, const double* params, int K,
+                         int mode, double* targets, ava_stream_t s) {
+  if (spec == nullptr || targets == nullptr || !wf_shape_ok(dtype, N, F, T)) return AVA_EINVAL;
+  if (row_src == nullptr || group_row_off == nullptr || bin_off == nullptr || bins == nullptr) return AVA_EINVAL;
+  if (G < 1 || max_bins < 1 || (mode != 2 && params == nullptr)) return AVA_EINVAL;
+  const WfPlan pl{row_src, nullptr, group_row_off, bin_off, bins, N, F};
+  int z = ceil_div(max_bins, 4);
+  z = z > 32 ? 32 : z;
+  const dim3 grid(G, ceil_div(T, WM_TJ), z);
+  if (dtype == 0)
+    hipLaunchKernelGGL(warpfit_group_mean_kernel<float>, grid, dim3(256), 0, to_stream(s), static_cast<const float*>(spec), pl,
+                       params, T, K, mode, targets);
+  else
+    hipLaunchKernelGGL(warpfit_group_mean_kernel<double>, grid, dim3(256), 0, to_stream(s), static_cast<const double*>(spec),
+                       pl, params, T, K, mode, targets);
+  AVA_CHECK_LAUNCH();
+  return AVA_OK;
+}
+
+extern "C" int ava_warpfit_group_mean(const void* spec, int dtype, int N, int F, int T, const int32_t* row_src,
+                                      const int32_t* group_row_off, const int32_t* bin_off, const int32_t* bins, int G,
+                                      int max_bins, const double* params, int raw, double* targets, ava_stream_t s) {
+  if (raw != 0 && raw != 1) return AVA_EINVAL;
+  return wf_group_mean(spec, dtype, N, F, T, row_src, group_row_off, bin_off, bins, G, max_bins, params, 2, raw ? 2 : 0,
+                       targets, s);
+}
+
+extern "C" int ava_warpfit_group_pl_mean(const void* spec, int dtype, int N, int F, int T, const int32_t* row_src,
+                                         const int32_t* group_row_off, const int32_t* bin_off, const int32_t* bins, int G,
+                                         int max_bins, const double* knots, int K, int raw, double* targets, ava_stream_t s) {
+  if ((raw != 0 && raw != 1) || !wf_knots_ok(T, K)) return AVA_EINVAL;
+  return wf_group_mean(spec, dtype, N, F, T, row_src, group_row_off, bin_off, bins, G, max_bins, knots, K, raw ? 2 : 1,
+                       targets, s);
 }

@@ -8,6 +8,7 @@ Mirror of the reference's own replacement for affinewarp, ``ava/preprocessing/wa
   ``warp_loss``               warping.py:148-163   both objectives, for a batch of candidates per motif
   ``knots_from_warp_params``  the fitted warps as the knots of ``DeviceWarpedWindowDataset``
   ``pl_warp_loss``, ``pl_minimize_warp``, ``align_specs(..., n_knots=)``   the piecewise-linear warp, no reference code
+  ``align_specs_grouped``     many such fits over the same spectrograms in one launch sequence (row f17), for ``warp_search``
   ``install``                 points the reference module's two public functions here
 
 Every number is made by the kernels of ``csrc/warp_fit.hip`` in fp64; there is no CPU fallback.  The functions take
@@ -59,7 +60,7 @@ from . import _lib
 __all__ = ["WARNING_MSG", "XTOL", "GRID_KS", "GRID_KL", "LINE_KS", "SHIFT_SPAN", "LOG_SLOPE_SPAN", "DEFAULT_SHIFT_LAMBDAS",
            "DEFAULT_SLOPE_LAMBDAS", "KNOT_KS", "apply_warp", "align_specs", "minimize_warp", "warp_loss", "search_rounds",
            "check_schedule", "knots_from_warp_params", "install", "knot_columns", "knot_rounds", "pl_warp_loss",
-           "pl_minimize_warp"]
+           "pl_minimize_warp", "align_specs_grouped", "check_groups", "check_group_schedule", "GroupPlan"]
 
 WARNING_MSG = "ava.preprocessing.warping is experimental and may change in " + \
     "a future version of AVA!"                 # warping.py:20-21
@@ -388,6 +389,237 @@ def align_specs(specs, shift_λs, slope_λs, verbose=True, *, n_knots=0):
     if is_numpy:
         return warped.cpu().numpy(), {k: v.cpu().numpy() for k, v in warp_params.items()}
     return warped, warp_params
+
+
+# ---- grouped fits (row f17): many fit problems over the same spectrograms in one launch sequence ---------------------------
+
+def check_group_schedule(shift_λs, slope_λs, n_groups):
+    """The schedules of ``align_specs_grouped`` as float64 arrays ``[iterations, n_groups]``: the conditions of
+    ``check_schedule`` for every group, and within an iteration either every ``slope_λ`` is ``inf`` or none is (the
+    shift objective is one flag of a launch).  ``ValueError`` otherwise."""
+    a, b = np.asarray(shift_λs, dtype=np.float64), np.asarray(slope_λs, dtype=np.float64)
+    if a.ndim != 2 or a.shape != b.shape or a.shape[1] != n_groups:
+        raise ValueError("shift_λs and slope_λs must both be [iterations][%d groups], got %s and %s"
+                         % (n_groups, a.shape, b.shape))
+    if a.shape[0] == 0:
+        raise ValueError("an empty schedule fits nothing")
+    if not np.isfinite(a).all() or (a < 0).any():
+        raise ValueError("every shift_λ must be finite and not negative (only slope_λ may be inf)")
+    if np.isnan(b).any() or (b < 0).any():
+        raise ValueError("every slope_λ must be inf or not negative")
+    inf = np.isinf(b)
+    if (inf.any(axis=1) != inf.all(axis=1)).any():
+        raise ValueError("within an iteration slope_λ = inf (a shift-only iteration) must hold for every group or for none")
+    return np.ascontiguousarray(a), np.ascontiguousarray(b)
+
+
+def _index_list(idx, size, what):
+    """a sorted index list without repeats inside ``range(size)`` as int32; ``None``: all"""
+    if idx is None:
+        return np.arange(size, dtype=np.int32)
+    a = np.asarray(idx)
+    if a.ndim != 1 or a.size == 0:
+        raise ValueError("a group's %s must be a non-empty 1-D index list" % what)
+    if a.dtype.kind not in 'iu':
+        raise ValueError("a group's %s must be integers, got %s" % (what, a.dtype))
+    if a.min() < 0 or a.max() >= size:
+        raise ValueError("a group's %s must lie in [0, %d)" % (what, size))
+    if (np.diff(a.astype(np.int64)) <= 0).any():
+        raise ValueError("a group's %s must be sorted and without repeats" % what)
+    return a.astype(np.int32)
+
+
+def check_groups(groups, N, F):
+    """``[(rows, bins), ...]`` as int32 index arrays: every list sorted, without repeats, not empty and in range
+    (``None``: all rows / all bins).  ``ValueError`` otherwise, before anything is launched."""
+    groups = list(groups)
+    if len(groups) == 0:
+        raise ValueError("no groups to fit")
+    out = []
+    for g in groups:
+        if g is None:
+            g = (None, None)
+        if len(g) != 2:
+            raise ValueError("a group is a pair (rows, bins)")
+        out.append((_index_list(g[0], N, "rows"), _index_list(g[1], F, "bins")))
+    return out
+
+
+class GroupPlan:
+    """The device-side plan of a list of checked groups over ``specs`` [N, F, T] (a contiguous device tensor): the int32
+    arrays of include/ava_hip.h, the grouped template and the grouped losses.  Nothing here synchronises."""
+
+    def __init__(self, specs, groups):
+        self.specs = specs
+        self.N, self.F, self.T = specs.shape
+        self.G = len(groups)
+        rows = [g[0] for g in groups]
+        bins = [g[1] for g in groups]
+        self.row_off = np.concatenate([[0], np.cumsum([len(r) for r in rows])]).astype(np.int64)
+        self.bin_off = np.concatenate([[0], np.cumsum([len(b) for b in bins])]).astype(np.int64)
+        self.V, self.max_bins = int(self.row_off[-1]), int(max(len(b) for b in bins))
+        if self.V > 2 ** 31 - 1 or int(self.bin_off[-1]) * self.T > 2 ** 31 - 1:
+            raise ValueError("too many virtual rows or target cells for one plan: use max_rows")
+        dev = specs.device
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(dev)
+        self.row_src = up(np.concatenate(rows))
+        self.row_group_host = np.repeat(np.arange(self.G), np.diff(self.row_off))
+        self.row_group = up(self.row_group_host)
+        self.d_row_off, self.d_bin_off, self.bins = up(self.row_off), up(self.bin_off), up(np.concatenate(bins))
+        self.targets = torch.empty(int(self.bin_off[-1]) * self.T, dtype=torch.float64, device=dev)
+
+    def _head(self):
+        s = self.specs
+        return (s.data_ptr(), _DTYPES[s.dtype], self.N, self.F, self.T, self.row_src.data_ptr())
+
+    def mean(self, params=None, knots=None, out=None):
+        """the grouped template into ``out`` (default: the plan's own targets) under ``params`` [V, 2] = (shift, slope),
+        under ``knots`` [V, K], or of the unwarped rows when both are ``None``"""
+        lib, out = _lib.load(), self.targets if out is None else out
+        tail = (self.d_row_off.data_ptr(), self.d_bin_off.data_ptr(), self.bins.data_ptr(), self.G, self.max_bins)
+        if knots is not None:
+            rc = lib.ava_warpfit_group_pl_mean(*self._head(), *tail, knots.data_ptr(), knots.shape[1], 0, out.data_ptr(),
+                                               _lib.stream())
+        else:
+            rc = lib.ava_warpfit_group_mean(*self._head(), *tail, None if params is None else params.data_ptr(),
+                                            int(params is None), out.data_ptr(), _lib.stream())
+        _lib.check(rc, "ava_warpfit_group_mean")
+        return out
+
+    def _loss(self, pl, cand, C, K, shift_λ, slope_λ, fixed, loss, targets=None, raw=False):
+        lib = _lib.load()
+        targets = self.targets if targets is None else targets
+        ptr = lambda t: None if t is None else t.data_ptr()
+        head = self._head() + (self.row_group.data_ptr(), self.d_bin_off.data_ptr(), self.bins.data_ptr(), self.V,
+                               targets.data_ptr(), ptr(cand), C)
+        tail = (ptr(shift_λ), ptr(slope_λ), int(bool(fixed)), int(bool(raw)), loss.data_ptr(), _lib.stream())
+        if pl:
+            _lib.check(lib.ava_warpfit_group_pl_loss(*head, K, *tail), "ava_warpfit_group_pl_loss")
+        else:
+            _lib.check(lib.ava_warpfit_group_loss(*head, *tail), "ava_warpfit_group_loss")
+        return loss
+
+    def ss_loss(self, cand, shift_λ, slope_λ, fixed, loss, targets=None):
+        """``ava_warpfit_group_loss`` of ``cand`` [V, C, 2] = (shift, log slope) into ``loss`` [V, C]; λ: device [G]"""
+        return self._loss(False, cand, cand.shape[1], 0, shift_λ, slope_λ, fixed, loss, targets)
+
+    def pl_loss(self, cand, shift_λ, slope_λ, fixed, loss, targets=None):
+        """``ava_warpfit_group_pl_loss`` of ``cand`` [V, C, K] into ``loss`` [V, C]"""
+        return self._loss(True, cand, cand.shape[1], cand.shape[2], shift_λ, slope_λ, fixed, loss, targets)
+
+    def raw_loss(self, loss, targets=None):
+        """per virtual row the sum of squared differences of the unwarped row from its group's target, into ``loss`` [V]"""
+        return self._loss(False, None, 1, 0, None, None, False, loss, targets, raw=True)
+
+
+def _minimize_grouped(plan, x, shift_λ, slope_λ, fixed, best_loss):
+    """``_minimize`` over the virtual rows of ``plan``: ``x`` [V, 2] and ``best_loss`` [V] are updated in place"""
+    lib = _lib.load()
+    V, T = plan.V, plan.T
+    ks, kl, rounds = search_rounds(T, fixed)
+    C = (2 * ks + 1) * (2 * kl + 1)
+    dev, st = x.device, _lib.stream()
+    cand = torch.empty((V, C, 2), dtype=torch.float64, device=dev)
+    loss = torch.empty((V, C), dtype=torch.float64, device=dev)
+    best = torch.empty(V, dtype=torch.int32, device=dev)
+    for hs, hl in rounds:
+        _lib.check(lib.ava_warpfit_candidates(x.data_ptr(), V, T, ks, kl, hs, hl, cand.data_ptr(), st),
+                   "ava_warpfit_candidates")
+        plan.ss_loss(cand, shift_λ, slope_λ, fixed, loss)
+        _lib.check(lib.ava_warpfit_argmin(loss.data_ptr(), cand.data_ptr(), V, C, best.data_ptr(), x.data_ptr(),
+                                          best_loss.data_ptr(), st), "ava_warpfit_argmin")
+
+
+def _minimize_pl_grouped(plan, u, shift_λ, slope_λ, best_loss):
+    """stage B of ``_minimize_pl`` (never the shift objective: ``align_specs`` skips it then) over the virtual rows"""
+    lib = _lib.load()
+    V, T, K = plan.V, plan.T, u.shape[1]
+    C = 2 * KNOT_KS + 1
+    dev, st = u.device, _lib.stream()
+    cand = torch.empty((V, C, K), dtype=torch.float64, device=dev)
+    loss = torch.empty((V, C), dtype=torch.float64, device=dev)
+    best = torch.empty(V, dtype=torch.int32, device=dev)
+    for h in knot_rounds(T, K):
+        for k in range(K):
+            _lib.check(lib.ava_warpfit_pl_candidates(u.data_ptr(), V, K, k, KNOT_KS, h, cand.data_ptr(), st),
+                       "ava_warpfit_pl_candidates")
+            plan.pl_loss(cand, shift_λ, slope_λ, False, loss)
+            _lib.check(lib.ava_warpfit_pl_argmin(loss.data_ptr(), cand.data_ptr(), V, C, K, best.data_ptr(), u.data_ptr(),
+                                                 best_loss.data_ptr(), st), "ava_warpfit_pl_argmin")
+
+
+def _fit_plan(plan, shift_λs, slope_λs, n_knots):
+    """the iterations of ``align_specs`` over the virtual rows of ``plan``; ``shift_λs``, ``slope_λs``: numpy
+    [iterations, G].  Returns device tensors ``(params [V, 2] = (shift, slope), knots [V, K] or None)``."""
+    dev, V, T = plan.specs.device, plan.V, plan.T
+    d_shift, d_slope = torch.from_numpy(shift_λs).to(dev), torch.from_numpy(slope_λs).to(dev)
+    x = torch.zeros((V, 2), dtype=torch.float64, device=dev)
+    params = torch.stack([x[:, 0], torch.exp(x[:, 1])], dim=1)
+    knots = None
+    if n_knots != 0:
+        t_k = torch.from_numpy(knot_columns(T, n_knots + 2)).to(dev)
+    best_loss = torch.empty(V, dtype=torch.float64, device=dev)
+    for it in range(len(shift_λs)):
+        fixed = bool(np.isinf(slope_λs[it, 0]))
+        if it == 0:
+            plan.mean()                                     # the unwarped rows: an identity warp is not bit-exact
+        elif n_knots == 0:
+            plan.mean(params=params)
+        else:
+            plan.mean(knots=knots)
+        _minimize_grouped(plan, x, d_shift[it], d_slope[it], fixed, best_loss)
+        if fixed:
+            x[:, 1] = 0.0
+        params = torch.stack([x[:, 0], torch.exp(x[:, 1])], dim=1).contiguous()
+        if n_knots != 0:
+            knots = (params[:, :1] + params[:, 1:] * t_k).contiguous()
+            if not fixed:
+                _minimize_pl_grouped(plan, knots, d_shift[it], d_slope[it], best_loss)
+    return params, knots
+
+
+def align_specs_grouped(specs, groups, shift_λs, slope_λs, n_knots=0, max_rows=None):
+    """Many ``align_specs`` fits over the same spectrograms ``[N, F, T]`` in one launch sequence (row f17).  ``groups``
+    is a list of ``(rows, bins)``: sorted index lists without repeats (``None``: all) naming the motifs and the
+    frequency bins of one fit problem; ``shift_λs`` and ``slope_λs`` are ``[iterations][len(groups)]``, and within an
+    iteration ``slope_λ = inf`` holds for every group or for none.  Returns one dict per group, ``{'shifts', 'slopes'}``
+    and with ``n_knots > 0`` also ``'knots'``, numpy for numpy ``specs`` and device tensors otherwise: bit for bit the
+    ``warp_params`` that ``align_specs(specs[rows][:, bins], shift_λs[:, g], slope_λs[:, g], n_knots=n_knots)`` returns.
+    The spectrograms are read where they lie: no gathered copy is made and no warped spectrogram is stored; every
+    iteration's templates come from ``ava_warpfit_group_mean``.  All groups advance together, a launch covering
+    every (motif, group) pair -- ``V = sum(len(rows))`` virtual rows -- and nothing is read back inside the loop.
+    ``max_rows`` bounds ``V`` per launch sequence by running whole groups in chunks (a group larger than ``max_rows``
+    runs alone); the result does not depend on it.  ``ValueError`` before any launch for empty, unsorted, repeated or
+    out-of-range indices, a schedule of the wrong shape or with a mixed ``inf`` pattern, and unsupported ``n_knots``."""
+    specs, is_numpy = _specs_tensor(specs)
+    N, F, T = specs.shape
+    n_knots = int(n_knots)
+    if n_knots != 0:
+        _check_knots(T, n_knots + 2)
+    groups = check_groups(groups, N, F)
+    shift_λs, slope_λs = check_group_schedule(shift_λs, slope_λs, len(groups))
+    if max_rows is not None and int(max_rows) < 1:
+        raise ValueError("max_rows must be positive")
+    chunks, start, count = [], 0, 0
+    for g, (rows, _) in enumerate(groups):
+        if g > start and max_rows is not None and count + len(rows) > int(max_rows):
+            chunks.append((start, g))
+            start, count = g, 0
+        count += len(rows)
+    chunks.append((start, len(groups)))
+    out = []
+    for a, b in chunks:
+        plan = GroupPlan(specs, groups[a:b])
+        params, knots = _fit_plan(plan, np.ascontiguousarray(shift_λs[:, a:b]), np.ascontiguousarray(slope_λs[:, a:b]), n_knots)
+        for g in range(b - a):
+            lo, hi = int(plan.row_off[g]), int(plan.row_off[g + 1])
+            wp = {'shifts': params[lo:hi, 0].contiguous(), 'slopes': params[lo:hi, 1].contiguous()}
+            if knots is not None:
+                wp['knots'] = knots[lo:hi].contiguous()
+            out.append(wp)
+    if is_numpy:
+        return [{k: v.cpu().numpy() for k, v in wp.items()} for wp in out]
+    return out
 
 
 def knots_from_warp_params(warp_params, num_time_bins):

@@ -549,6 +549,46 @@ int ava_warpfit_pl_loss(const void* spec, int dtype, int N, int F, int T, const 
 int ava_warpfit_pl_argmin(const double* loss, const double* cand, int N, int C, int K, int32_t* best, double* u,
                           double* best_loss, ava_stream_t s);
 
+/* ---- the grouped time-warp fits ------------------------------------------------------
+ * Many fit problems ("groups") over one spec [N][F][T], advanced together by the kernels above.  A group is a sorted
+ * list of source rows (motifs), a sorted list of bins and its own two lambdas.  The plan, int32 on the device:
+ *   row_src [V], row_group [V]   virtual row v is motif row_src[v] as group row_group[v] sees it; a group's rows are
+ *                                contiguous, in rising source order
+ *   group_row_off [G+1]          group g owns the virtual rows group_row_off[g] .. group_row_off[g+1] - 1
+ *   bin_off [G+1], bins [sum F_g] group g owns bins[bin_off[g] .. bin_off[g+1] - 1], F_g of them, rising
+ *   targets                      float64, group g's [F_g][T] by list position at targets + bin_off[g] T
+ *   shift_lambda [G], slope_lambda [G]   float64
+ * ava_warpfit_candidates, _pl_candidates, _argmin and _pl_argmin serve the V virtual rows as they are (N = V).
+ *
+ * ava_warpfit_group_loss / ava_warpfit_group_pl_loss: loss [V][C] for cand [V][C][2] / [V][C][K]: for every virtual row
+ *   bit for bit what ava_warpfit_loss / ava_warpfit_pl_loss return on the gathered tensor spec[rows_g][:, bins_g] with
+ *   the group's target and lambdas: the bins are staged through the list, in list order, the sums are the plain
+ *   kernel's.  fixed_slope (0 / 1) is one flag for the launch: the shift objective, slope_lambda is not read.  raw = 1:
+ *   the sum of squared differences of the unwarped rows from the target, no penalty; cand and the lambdas are not read
+ *   and may be null.
+ * ava_warpfit_group_mean / ava_warpfit_group_pl_mean: targets = for every group the mean over its rows, in rising
+ *   order, of the values ava_warpfit_apply / ava_warpfit_pl_apply would store under params [V][2] = (shift, slope) /
+ *   knots [V][K] (rounded to spec's dtype first), bit for bit ava_warpfit_mean of that output on the gathered tensor,
+ *   without storing it.  raw = 1: the mean of the unwarped rows; params may be null.  max_bins: the largest F_g.
+ *
+ * The caller keeps every index of the plan in range and every list non-empty (ava_amd.warp_fit checks them on the
+ * host); a row or bin out of range reads nothing and yields NaN or leaves the loss unwritten.  AVA_EINVAL before any
+ * launch for null pointers, an unknown dtype, sizes < 1, T, C or K outside the caps above, or a flag that is not 0 / 1. */
+int ava_warpfit_group_loss(const void* spec, int dtype, int N, int F, int T, const int32_t* row_src, const int32_t* row_group,
+                           const int32_t* bin_off, const int32_t* bins, int V, const double* targets, const double* cand,
+                           int C, const double* shift_lambda, const double* slope_lambda, int fixed_slope, int raw,
+                           double* loss, ava_stream_t s);
+int ava_warpfit_group_pl_loss(const void* spec, int dtype, int N, int F, int T, const int32_t* row_src,
+                              const int32_t* row_group, const int32_t* bin_off, const int32_t* bins, int V,
+                              const double* targets, const double* cand, int C, int K, const double* shift_lambda,
+                              const double* slope_lambda, int fixed_slope, int raw, double* loss, ava_stream_t s);
+int ava_warpfit_group_mean(const void* spec, int dtype, int N, int F, int T, const int32_t* row_src,
+                           const int32_t* group_row_off, const int32_t* bin_off, const int32_t* bins, int G, int max_bins,
+                           const double* params, int raw, double* targets, ava_stream_t s);
+int ava_warpfit_group_pl_mean(const void* spec, int dtype, int N, int F, int T, const int32_t* row_src,
+                              const int32_t* group_row_off, const int32_t* bin_off, const int32_t* bins, int G, int max_bins,
+                              const double* knots, int K, int raw, double* targets, ava_stream_t s);
+
 /* ---- the integer-shift time-warp fit -------------------------------------------------
  * The alignment of ava/segmenting/template_segmentation.py:segment_sylls_from_songs (:531-539), this project's own model
  * in place of affinewarp's ShiftWarping (ava_amd/shift_fit.py states it).  x / dtype: [K][F][T] contiguous on the
