@@ -103,6 +103,10 @@ SIGNATURES = {
     "ava_mmd2_matrix_workspace_bytes": (_sz, [_p, _i, _i]),
     "ava_mmd2_matrix": (_i, [_p, _i, _p, _p, _p, _i, _p, _i64, _d, _p, _p, _p, _sz, _p]),
     "ava_mmd2_matrix_linear": (_i, [_p, _i, _p, _p, _p, _i, _p, _i64, _d, _p, _p, _sz, _p]),
+    "ava_mmd2_perm_tile": (_i, []),
+    "ava_mmd2_perm_workspace_bytes": (_sz, [_p, _i, _i]),
+    "ava_mmd2_perm_membership": (_i, [_p, _p, _i, _i64, _i64, C.c_uint64, _p, _p]),
+    "ava_mmd2_perm": (_i, [_p, _i, _p, _i64, _p, _p, _i, _i64, _i64, C.c_uint64, _d, _p, _p, _p, _p, _p, _p, _sz, _p]),
     "ava_pair_sqdist": (_i, [_p, _i, _p, _p, _i, _p, _p]),
     "ava_spec_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i, _i]),
     "ava_get_spec_batch": (_i, [_p, _i, _p, _p, _p, _p, _p, _p, _i, _i, _d, _i, _i, _p, _d, _p, _i, _i, _d, _d, _d, _i,

@@ -52,12 +52,16 @@ static inline char* ava_align256(const void* p) { return reinterpret_cast<char*>
 // Appendix E) so that injected and device-generated noise agree to float rounding when seeded alike.  Element i of a
 // stream depends on (i + offset, seed) only, never on the launch geometry.
 #ifdef __HIPCC__
-__device__ __forceinline__ double ava_u01_hash(uint64_t i, uint64_t salt) {
+// the 64 hashed bits of element i of stream salt (a bijection of i for a fixed salt: no two elements of a stream tie)
+__device__ __forceinline__ uint64_t ava_mix64(uint64_t i, uint64_t salt) {
   uint64_t x = i + salt * 0x9E3779B97F4A7C15ull;
   x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull;
   x ^= x >> 27; x *= 0x94D049BB133111EBull;
   x ^= x >> 31;
-  return (double)(x >> 11) * (1.0 / 9007199254740992.0);
+  return x;
+}
+__device__ __forceinline__ double ava_u01_hash(uint64_t i, uint64_t salt) {
+  return (double)(ava_mix64(i, salt) >> 11) * (1.0 / 9007199254740992.0);
 }
 __device__ __forceinline__ float ava_normal_hash(uint64_t i, uint64_t seed) {
   const double u1 = ava_u01_hash(i, seed), u2 = ava_u01_hash(i, seed + 7777);

@@ -13,6 +13,9 @@
 //   dot         every pair's sum starts at 0 and takes its k in one ascending walk of 4-wide MFMA steps from k = 0
 //               (stage after stage, step after step), whatever tile, stage or kernel the pair falls in
 // So both kernels give the same bits for the same pair of rows, and no result depends on the tiling.
+// mmd_perm_stat_kernel (mmd_perm.hip) uses corr_mfma_stage alone, for K0 S (kernel values times 0 / 1 membership
+// columns): the dot line above is what makes a column's value independent of its place in a tile and of the other
+// columns (the contract in the header of mmd_perm.hip).
 //
 // 256 threads.  A stage holds CORR_KC columns of ROWS rows (ROWS a multiple of 16) of each operand, row stride CORR_LD;
 // element t + 256 j of a stage is row (t >> 4) + 16 j, column t & 15.

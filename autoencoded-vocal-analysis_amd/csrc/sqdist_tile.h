@@ -5,6 +5,9 @@
 // Order contract: every pair's sum starts at 0 and takes one fma(x_k - y_k, x_k - y_k, sum) per k, k ascending from 0
 // to d - 1, whatever tile, stage or kernel the pair falls in.  So the three kernels give the same bits for the same
 // pair of rows (and the bits of the scalar loop of pair_sqdist_kernel), and no result depends on the tiling.
+// mmd_perm_stat_kernel (mmd_perm.hip) forms its tiles of exp(A d^2) from the same pieces (sqd_stage_rows), so its
+// kernel values have the bits of mmd_pair_kernel's; what it adds to the contract -- a column of K0 S depends on the
+// latent rows, sigma and its membership vector only -- is stated in the header of mmd_perm.hip.
 //
 // 256 threads; thread (ty, tx) = (t >> 4, t & 15) owns the pairs (ty + 16 i, tx + 16 j), i, j < 4.
 #pragma once
@@ -29,6 +32,21 @@ __device__ __forceinline__ void sqd_accumulate(const double* xs, const double* y
         const double df = x[i] - y[j];
         acc[i][j] = fma(df, df, acc[i][j]);
       }
+  }
+}
+
+// the same stage gathered through row lists: row r of xs is row xrow[r] of L, row r of ys row yrow[r] (64 entries each,
+// in LDS; a negative entry is a row that does not exist and is written as 0, like the columns from d on)
+__device__ __forceinline__ void sqd_stage_rows(double* xs, double* ys, const double* __restrict__ L,
+                                               const int64_t* xrow, const int64_t* yrow, int d, int k0, int t) {
+  const int sc = t & 31, sr = t >> 5;
+  const int k = k0 + sc;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const int r = sr + 8 * j;
+    const int64_t gx = xrow[r], gy = yrow[r];
+    xs[r * SQD_LD + sc] = (k < d && gx >= 0) ? L[(size_t)gx * d + k] : 0.0;
+    ys[r * SQD_LD + sc] = (k < d && gy >= 0) ? L[(size_t)gy * d + k] : 0.0;
   }
 }
 

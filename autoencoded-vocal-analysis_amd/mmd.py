@@ -13,12 +13,17 @@ reference (mmd_plots.py)       here                                        C ent
 loop of ``_calculate_mmd2``    :func:`mmd2_matrix`            (:395-418)   the above per condition pair
 the same loop, in one pass     :func:`mmd2_matrix_one_pass`                ``ava_mmd2_matrix`` / ``_linear``
 ``_calculate_mmd2``            :func:`_calculate_mmd2`        (:337-434)   the one-pass matrix
+(none: Gretton et al. 2012)    :func:`mmd2_permutation_test`, ``_matrix``  ``ava_mmd2_perm`` (row f18)
 =============================  ==========================================  =============================
 
 ``install()`` swaps the three estimator functions of an imported ``ava.plotting.mmd_plots`` for these, so the
 reference's plotting functions (``mmd_matrix_plot_DC`` ...) run unchanged on top of them; ``install(matrix=True)`` also
 swaps ``_calculate_mmd2``, so that the whole condition-by-condition matrix is one launch sequence (every block sum of
-the sorted index list at once, each within-set term once) instead of a host loop over the pairs.  There is no CPU fallback:
+the sorted index list at once, each within-set term once) instead of a host loop over the pairs.
+
+:func:`mmd2_permutation_test` and :func:`mmd2_permutation_matrix` add what the reference lacks, a measure of significance
+for the quadratic estimate: the one-sided permutation p-value of Gretton et al. 2012 (section 5), the null distribution
+computed on the device by ``csrc/mmd_perm.hip`` (model: DESIGN.md section 1, row f18).  There is no CPU fallback:
 without the HIP library / a GPU every function raises ``AvaHipError``.
 """
 import numpy as np
@@ -29,8 +34,12 @@ from . import _lib
 EPSILON = 1e-8          # ava/plotting/mmd_plots.py:34
 
 __all__ = ["estimate_median_sigma", "_estimate_mmd2", "_estimate_mmd2_linear_time", "mmd2_matrix", "mmd2_block_terms",
-           "mmd2_matrix_one_pass", "_calculate_mmd2", "install", "EPSILON"]
+           "mmd2_matrix_one_pass", "_calculate_mmd2", "mmd2_permutation_test", "mmd2_permutation_matrix",
+           "_calculate_mmd2_pvalues", "install", "EPSILON", "PERM_TILE", "PERM_MAX_BYTES"]
 TILE = 64               # rows of a tile of the pairwise kernel (SQD_T of csrc/sqdist_tile.h)
+PERM_TILE = 64          # columns (splits) of a workgroup of the statistic kernel (MP_COLS of csrc/mmd_perm.hip)
+PERM_MAX_BYTES = 256 << 20          # default bound on the membership bytes plus workspace of one chunk of splits
+PERM_MAX_CHUNK = 1 << 20            # splits per call of ava_mmd2_perm
 
 
 def _device():
@@ -310,10 +319,169 @@ def _calculate_mmd2(dc, condition_from_fn, mmd2_fn=None, condition_fn=None, para
     return result, all_conditions
 
 
-def install(module=None, matrix=False):
+def _perm_table(o1, o2, n1, n2, pair):
+    """The problem table of ``ava_mmd2_perm``: int64 ``[problems + 1, 8]`` rows ``{o1, o2, n1, n2, pair, first position,
+    first row tile, 0}`` and the sentinel ``{0, 0, 0, 0, 0, all positions, all row tiles, 0}``."""
+    n1, n2 = np.asarray(n1, dtype=np.int64).reshape(-1), np.asarray(n2, dtype=np.int64).reshape(-1)
+    table = np.zeros((len(n1) + 1, 8), dtype=np.int64)
+    table[:-1, 0], table[:-1, 1], table[:-1, 2], table[:-1, 3], table[:-1, 4] = o1, o2, n1, n2, pair
+    table[1:, 5] = np.cumsum(n1 + n2)
+    table[1:, 6] = np.cumsum((n1 + n2 + TILE - 1) // TILE)
+    return table
+
+
+def _perm_bytes(table, k):
+    """Device bytes of a chunk of ``k`` splits: ``k`` membership bytes per pool position plus the workspace of
+    ``ava_mmd2_perm_workspace_bytes`` (``k + 1`` columns of two doubles per row tile, and 256)."""
+    return int(k * table[-1, 5] + table[-1, 6] * (k + 1) * 16 + 256)
+
+
+def _perm_chunk(table, n_splits, max_bytes):
+    """The most splits (at least 1, at most ``n_splits``) whose chunk stays within ``max_bytes``."""
+    if max_bytes is None:
+        max_bytes = PERM_MAX_BYTES
+    per = int(table[-1, 5] + 16 * table[-1, 6])
+    k = (int(max_bytes) - _perm_bytes(table, 0)) // per
+    return int(max(1, min(k, n_splits, PERM_MAX_CHUNK, (2 ** 31 - 1) // max(len(table) - 1, 1))))
+
+
+def _perm_check(n_perm, counts):
+    if n_perm < 1:
+        raise ValueError("n_perm must be at least 1")
+    if n_perm > 2 ** 31 - 2:
+        raise ValueError("n_perm must be below 2^31 - 1")
+    if len(counts) and min(counts) < 2:
+        raise ZeroDivisionError("division by zero")                       # the reference's 2/(n*(n-1))
+
+
+def _run_perm(L, idx, table, n_perm, seed, sigma, max_bytes, want_null):
+    """Splits 0 .. n_perm of every problem of ``table`` in chunks: ``(stat_0 [problems], counts [problems], null
+    [problems, n_perm + 1, 4] or None)``, ``null[:, p]`` the three terms and the statistic of split ``p``.  ``idx``: the
+    device index list the table's offsets point into."""
+    lib = _lib.load()
+    n_prob = len(table) - 1
+    table = np.ascontiguousarray(table)
+    tab_dev = torch.from_numpy(table).to(L.device)
+    k = _perm_chunk(table, n_perm + 1, max_bytes)
+    nbytes = lib.ava_mmd2_perm_workspace_bytes(table.ctypes.data, n_prob, k)
+    if nbytes == 0:
+        raise _lib.AvaHipError("ava_mmd2_perm_workspace_bytes: unsupported problem table (%d problems)" % n_prob)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=L.device)
+    mem = torch.empty(k * int(table[-1, 5]), dtype=torch.uint8, device=L.device)
+    terms = torch.empty(n_prob * k * 3, dtype=torch.float64, device=L.device)
+    stats = torch.empty(n_prob * k, dtype=torch.float64, device=L.device)
+    stat0 = torch.empty(n_prob, dtype=torch.float64, device=L.device)
+    counts = torch.empty(n_prob, dtype=torch.int64, device=L.device)
+    null = np.empty((n_prob, n_perm + 1, 4)) if want_null else None
+    for p0 in range(0, n_perm + 1, k):
+        p1 = min(p0 + k, n_perm + 1)
+        _lib.check(lib.ava_mmd2_perm(L.data_ptr(), L.shape[1], idx.data_ptr(), idx.numel(), table.ctypes.data,
+                                     tab_dev.data_ptr(), n_prob, p0, p1, int(seed) & 0xffffffff, float(sigma),
+                                     mem.data_ptr(), terms.data_ptr(), stats.data_ptr(), stat0.data_ptr(),
+                                     counts.data_ptr(), ws.data_ptr(), nbytes, _lib.stream()), "ava_mmd2_perm")
+        if want_null:
+            null[:, p0:p1, :3] = terms[:n_prob * (p1 - p0) * 3].cpu().numpy().reshape(n_prob, p1 - p0, 3)
+            null[:, p0:p1, 3] = stats[:n_prob * (p1 - p0)].cpu().numpy().reshape(n_prob, p1 - p0)
+    return stat0.cpu().numpy(), counts.cpu().numpy(), null
+
+
+def _perm_terms(latent, i1, i2, n_perm, seed, sigma, max_bytes=None, pair=0):
+    """One problem: ``(terms [n_perm + 1, 4], count)``: the reference's three terms and their combination for splits
+    0 .. n_perm, and ``#{p >= 1 : stat_p >= stat_0}`` as the device counted it."""
+    n1, n2 = len(i1), len(i2)
+    L = _latent_dev(latent)
+    idx = torch.cat([_index_dev(i1, len(L)), _index_dev(i2, len(L))])
+    _, counts, null = _run_perm(L, idx, _perm_table(0, n1, n1, n2, pair), n_perm, seed, sigma, max_bytes, True)
+    return null[0], int(counts[0])
+
+
+def mmd2_permutation_test(latent, i1, i2, n_perm=1000, seed=0, sigma=None, return_null=False, max_bytes=None):
+    """Permutation test for the quadratic MMD^2 estimate (Gretton et al. 2012, section 5):
+    ``(mmd2, pvalue)``, or ``(mmd2, pvalue, null [n_perm])`` with ``return_null=True``.
+
+    The two sets are pooled and re-split ``n_perm`` times into ``len(i1)`` and ``len(i2)`` rows (the splits are a
+    function of ``seed`` alone); ``null`` holds the statistic of every re-split, ``mmd2`` that of the caller's own split
+    (from the same kernel; it agrees with :func:`_estimate_mmd2` to rounding) and ``pvalue = (1 + #{null >= mmd2}) /
+    (n_perm + 1)``: one-sided, never 0.  The splits go to the device in chunks whose membership bytes plus workspace
+    stay within ``max_bytes`` (default ``PERM_MAX_BYTES``, 256 MiB; never fewer than one split); no result depends on
+    it.  ``sigma=None`` is ``estimate_median_sigma(latent)``.  A set of fewer than two rows raises
+    ``ZeroDivisionError`` like :func:`_estimate_mmd2`, ``n_perm < 1`` ``ValueError``; both before the device is
+    touched."""
+    n1, n2 = len(i1), len(i2)
+    _perm_check(n_perm, [n1, n2])
+    if sigma is None:
+        sigma = estimate_median_sigma(latent)
+    L = _latent_dev(latent)
+    idx = torch.cat([_index_dev(i1, len(L)), _index_dev(i2, len(L))])
+    stat0, counts, null = _run_perm(L, idx, _perm_table(0, n1, n1, n2, 0), n_perm, seed, sigma, max_bytes, return_null)
+    out = (float(stat0[0]), (1 + int(counts[0])) / (n_perm + 1))
+    return out + (null[0, 1:, 3].copy(),) if return_null else out
+
+
+def mmd2_permutation_matrix(latent, condition, n_perm=1000, seed=0, sigma=None, max_bytes=None):
+    """:func:`mmd2_permutation_test` for every pair of conditions in one launch sequence per chunk of splits:
+    ``(mmd2 [C, C], pvalue [C, C], all_conditions)``, both symmetric, ``mmd2`` with a zero diagonal and ``pvalue`` with a
+    diagonal of ones.  Entry ``(i, j)``, ``i < j``, is bit for bit what ``mmd2_permutation_test(latent, rows of
+    condition i, rows of condition j, n_perm, seed + pair)`` gives, ``pair`` the index of ``(i, j)`` among the pairs in
+    row-major order.  The p-values are not corrected for the C (C - 1) / 2 comparisons."""
+    plan = _group_plan(condition)
+    all_conditions, counts = plan["all_conditions"], plan["counts"]
+    C = len(counts)
+    _perm_check(n_perm, counts if C > 1 else [])
+    mmd2, pvalue = np.zeros((C, C)), np.ones((C, C))
+    if C < 2:
+        return mmd2, pvalue, all_conditions
+    if sigma is None:
+        sigma = estimate_median_sigma(latent)
+    L = _latent_dev(latent)
+    if len(L) != len(plan["index"]):
+        raise ValueError("latent has %d rows, condition %d" % (len(L), len(plan["index"])))
+    a, b = np.triu_indices(C, 1)
+    table = _perm_table(plan["offsets"][a], plan["offsets"][b], counts[a], counts[b], np.arange(len(a)))
+    idx = torch.from_numpy(plan["index"]).to(L.device)
+    stat0, cnt, _ = _run_perm(L, idx, table, n_perm, seed, sigma, max_bytes, False)
+    mmd2[a, b] = mmd2[b, a] = stat0
+    pvalue[a, b] = pvalue[b, a] = (1 + cnt) / (n_perm + 1)
+    return mmd2, pvalue, all_conditions
+
+
+def _calculate_mmd2_pvalues(dc, condition_from_fn, pvalue_fn=None, condition_fn=None, n_perm=1000, seed=0, sigma=None,
+                            verbose=True):
+    """The companion of :func:`_calculate_mmd2` for :func:`mmd2_permutation_matrix`: the same two ``dc.request`` calls,
+    messages in the same style, ``np.save`` of the p-values (``pvalue_fn``, required) and of the conditions
+    (``condition_fn``); returns ``(mmd2 [C, C], pvalue [C, C], conditions [C])``."""
+    assert pvalue_fn is not None
+    if verbose:
+        print("Estimating an MMD p-value matrix...")
+        print("\tn_perm:", n_perm)
+        print("\tseed:", seed)
+    latent = dc.request('latent_means')
+    audio_fns = dc.request('audio_filenames')
+    condition = np.array([condition_from_fn(str(i)) for i in audio_fns], dtype='int')
+    n = len(np.unique(condition))
+    if sigma is None:
+        sigma = estimate_median_sigma(latent)
+    if verbose:
+        print("\tconditions found:", n)
+        print("\tsigma:", sigma)
+    mmd2, pvalue, all_conditions = mmd2_permutation_matrix(latent, condition, n_perm=n_perm, seed=seed, sigma=sigma)
+    if verbose:
+        print("\tSaving p-values to:", pvalue_fn)
+    np.save(pvalue_fn, pvalue)
+    if condition_fn is not None:
+        if verbose:
+            print("\tSaving conditions to:", condition_fn)
+        np.save(condition_fn, all_conditions)
+    if verbose:
+        print("\tDone.")
+    return mmd2, pvalue, all_conditions
+
+
+def install(module=None, matrix=False, pvalues=False):
     """Point ``ava.plotting.mmd_plots``'s estimators at this module (call after importing the reference package).
     ``matrix=True`` also replaces its ``_calculate_mmd2``, the function behind ``mmd_matrix_plot_DC``, with the
-    one-pass :func:`_calculate_mmd2` of this module."""
+    one-pass :func:`_calculate_mmd2` of this module; ``pvalues=True`` adds :func:`_calculate_mmd2_pvalues` (a name the
+    reference does not have) beside it."""
     if module is None:
         import ava.plotting.mmd_plots as module
     module.estimate_median_sigma = estimate_median_sigma
@@ -321,4 +489,6 @@ def install(module=None, matrix=False):
     module._estimate_mmd2_linear_time = _estimate_mmd2_linear_time
     if matrix:
         module._calculate_mmd2 = _calculate_mmd2
+    if pvalues:
+        module._calculate_mmd2_pvalues = _calculate_mmd2_pvalues
     return module

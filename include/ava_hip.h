@@ -318,6 +318,37 @@ int ava_mmd2_matrix(const double* latent, int z, const int64_t* idx, const int64
 int ava_mmd2_matrix_linear(const double* latent, int z, const int64_t* idx, const int64_t* offsets,
                            const int64_t* offsets_dev, int C, const int64_t* pairs, int64_t total_workgroups,
                            double sigma, double* out, void* ws, size_t ws_bytes, ava_stream_t s);
+/* Permutation test for MMD^2 (row f18; Gretton et al. 2012, section 5; the model is DESIGN.md section 1 row f18).
+ * A problem is a pair of index lists idx[o1 .. o1 + n1) and idx[o2 .. o2 + n2) (idx: device int64, n_idx entries); its
+ * pool is their concatenation, positions j = 0 .. n1 + n2 - 1.  Split 0 is the caller's own (set 1 = positions
+ * 0 .. n1 - 1); in split p >= 1 set 1 is the n1 positions with the smallest (key, j), key = the 64 hashed bits of
+ * ava_amd.synthetic.u01 for element j of stream salt = ((seed + pair) mod 2^32) 2^32 + p.
+ * table (HOST) and table_dev (device): n_problems + 1 rows of 8 int64 {o1, o2, n1, n2, pair, first position, first
+ * row tile, 0}; "first position" is the sum of n1 + n2 and "first row tile" the sum of ceil((n1 + n2) / 64) over the
+ * rows before; the last row is the sentinel {0, 0, 0, 0, 0, all positions, all row tiles, 0}.  A single test is a
+ * table of one problem with pair = 0.
+ * A call computes the splits p0 <= p < p1 of every problem:
+ *   membership (device, (p1 - p0) x all positions bytes): [p - p0][first position + j] = 1 if j is in set 1
+ *   terms (device, [n_problems][p1 - p0][3] doubles): term_1, term_2, term_3 of mmd_plots.py:277-295 for the split
+ *   stats (device, [n_problems][p1 - p0] doubles): term_1 + term_2 - term_3
+ *   stat0 (device, n_problems doubles), counts (device, n_problems int64): the call with p0 = 0 stores the statistic
+ *     of split 0 and sets counts = #{p >= 1 in the call : stat_p >= stat_0}; a call with p0 > 0 reads stat0 and adds
+ *     its count.  After the calls that cover 0 .. P, pvalue = (1 + counts) / (P + 1).
+ * A split's values do not depend on how 0 .. P is cut into calls, nor on the other problems of the table.
+ * ws: ava_mmd2_perm_workspace_bytes(table, n_problems, p1 - p0) = all row tiles x (p1 - p0 + 1) x 2 doubles + 256;
+ * returns 0 for arguments the entry points reject.  ava_mmd2_perm_membership writes the bytes only (what the tests
+ * compare); ava_mmd2_perm_tile() is the number of columns a workgroup of the statistic kernel owns.
+ * AVA_EINVAL: n1 or n2 < 2, n1 + n2 > 2^24, more than 2^23 problems, a list that leaves idx, z outside 1 .. 128,
+ * sigma not > 0, p0 < 0, p1 <= p0, p1 > 2^31 - 1, p1 - p0 > 2^20, n_problems (p1 - p0) > 2^31 - 1, a table whose sums
+ * disagree; AVA_EWORKSPACE: ws too small.  Neither allocates nor synchronises. */
+int ava_mmd2_perm_tile(void);
+size_t ava_mmd2_perm_workspace_bytes(const int64_t* table, int n_problems, int n_splits);
+int ava_mmd2_perm_membership(const int64_t* table, const int64_t* table_dev, int n_problems, int64_t p0, int64_t p1,
+                             uint64_t seed, uint8_t* membership, ava_stream_t s);
+int ava_mmd2_perm(const double* latent, int z, const int64_t* idx, int64_t n_idx, const int64_t* table,
+                  const int64_t* table_dev, int n_problems, int64_t p0, int64_t p1, uint64_t seed, double sigma,
+                  uint8_t* membership, double* terms, double* stats, double* stat0, int64_t* counts, void* ws,
+                  size_t ws_bytes, ava_stream_t s);
 /* squared distances of n index pairs, out[p] = |latent[a[p]] - latent[b[p]]|^2: the sampled pairs of
  * estimate_median_sigma (mmd_plots.py:450-474; the median itself is taken by the caller). */
 int ava_pair_sqdist(const double* latent, int z, const int64_t* a, const int64_t* b, int n, double* out,
