@@ -90,6 +90,7 @@ SIGNATURES = {
     "ava_bn_finalize_bwd": (_i, [_p, _i, _i64, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     "ava_gemm_workspace_bytes": (_sz, [_i, _i, _i]),
     "ava_gemm": (_i, [_p, _i, _p, _i, _p, _p, _i, _p, _p, _i, _i, _i, _i, _i, _i, _p, _sz, _p]),
+    "ava_gemm_path": (_i, [_p, _i, _p, _i, _p, _p, _i, _p, _p, _i, _i, _i, _i, _i, _i, C.POINTER(_i)]),
     "ava_latent_fwd": (_i, [_p] * 9 + [_i, _i, _p]),
     "ava_latent_bwd": (_i, [_p] * 9 + [_i, _i, _p]),
     "ava_elbo_finalize": (_i, [_p, _i, _p, _i, _i, _f, _p, _p]),

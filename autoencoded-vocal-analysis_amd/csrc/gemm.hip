@@ -502,16 +502,28 @@ int ava_gemm_defer2(const float* A, int lda, const float* B, int ldb, const floa
   return gemm_impl(A, lda, B, ldb, bias, C, ldc, mask, colsum, M, N, K, a_kmajor, b_kmajor, act, ws, ws_bytes, s, slabs);
 }
 
-static int gemm_impl(const float* A, int lda, const float* B, int ldb, const float* bias, float* C, int ldc,
-                     const float* mask, float* colsum, int M, int N, int K, int a_kmajor, int b_kmajor, int act,
-                     void* ws, size_t ws_bytes, ava_stream_t s, int* deferred_slabs) {
+// The one place where a product is given to a kernel.  Looks at shapes, flags, pointer values and nullness only (nothing
+// is dereferenced, nothing is launched): gemm_impl launches what this returns, ava_gemm_path reports it.
+enum { GEMM_PATH_LIMB = 1, GEMM_PATH_SKINNY = 2, GEMM_PATH_TILED = 3 };
+struct GemmChoice {
+  int path;
+  int tile;          // BN of the limb kernel, 16 for the skinny kernel, BM = BN of the tiled kernel
+  int bk;            // K step of the chosen instantiation
+  int vec;           // 16-byte operand loads
+  int splits, klen;  // of the chosen kernel (skinny: 1, K)
+  int threads;       // per workgroup
+  int plan_splits;   // splits of the tiled plan: the workspace gemm_impl insists on whichever kernel runs
+};
+
+static int gemm_select(const float* A, int lda, const float* B, int ldb, const float* bias, const float* C, int ldc,
+                       const float* mask, const float* colsum, int M, int N, int K, int a_kmajor, int b_kmajor, int act,
+                       GemmArgs* gp, GemmChoice* c) {
   if (A == nullptr || B == nullptr || C == nullptr || M <= 0 || N <= 0 || K <= 0) return AVA_EINVAL;
   int bm, splits, klen;
   plan(M, N, K, &bm, &splits, &klen);
-  if (splits > 1 && (ws == nullptr || ws_bytes < ava_gemm_workspace_bytes(M, N, K))) return AVA_EWORKSPACE;
-  GemmArgs g;
-  g.A = A; g.B = B; g.bias = bias; g.colsum = colsum; g.mask = mask;
-  g.C = splits > 1 ? reinterpret_cast<float*>(ws) : C;
+  GemmArgs& g = *gp;
+  g.A = A; g.B = B; g.bias = bias; g.colsum = const_cast<float*>(colsum); g.mask = mask;
+  g.C = const_cast<float*>(C);        // the caller's C: gemm_impl points it at the workspace once the splits are known
   g.M = M; g.N = N; g.K = K;
   g.lda = lda > 0 ? lda : (a_kmajor ? K : M);
   g.ldb = ldb > 0 ? ldb : (b_kmajor ? K : N);
@@ -522,16 +534,58 @@ static int gemm_impl(const float* A, int lda, const float* B, int ldb, const flo
   g.vec_a = (g.lda % 4 == 0) && ((reinterpret_cast<uintptr_t>(A) & 15) == 0) && (a_kmajor ? K % 4 == 0 && K >= 4 : M % 4 == 0 && M >= 4);
   g.vec_b = (g.ldb % 4 == 0) && ((reinterpret_cast<uintptr_t>(B) & 15) == 0) && (b_kmajor ? K % 4 == 0 && K >= 4 : N % 4 == 0 && N >= 4);
   const bool vec = g.vec_a && g.vec_b;
-  hipStream_t st = to_stream(s);
+  c->plan_splits = splits;
   if (ava_gemm_limb_ok(g, a_kmajor, b_kmajor)) {
     // the fc1 / fc8 products: three-limb bf16 matrix-core kernel (gemm_limb.hip), fp32-faithful
     int lbn;
     ava_gemm_limb_plan(M, N, K, a_kmajor, &lbn, &splits, &klen);
+    g.klen = klen; g.splits = splits;
+    c->path = GEMM_PATH_LIMB; c->tile = lbn; c->bk = 32; c->vec = 1; c->splits = splits; c->klen = klen; c->threads = 512;
+    return AVA_OK;
+  }
+  if (skinny_ok(g, a_kmajor, b_kmajor)) {
+    c->path = GEMM_PATH_SKINNY; c->tile = 16; c->bk = 16; c->vec = (a_kmajor || b_kmajor) ? 1 : 0;
+    c->splits = 1; c->klen = K;
+    c->threads = K >= 512 ? 512 : 256;              // long K: eight waves share the K range of a tile
+    return AVA_OK;
+  }
+  c->path = GEMM_PATH_TILED; c->tile = bm; c->vec = vec ? 1 : 0; c->splits = splits; c->klen = klen; c->threads = 256;
+  if (!vec) c->bk = 16;
+  else if (bm == 128) c->bk = klen % 32 == 0 ? 32 : 16;
+  else c->bk = (klen % 32 == 0 && klen >= 512) ? 32 : 16;      // BK 32: the long-K 64-tile shapes
+  return AVA_OK;
+}
+
+extern "C" int ava_gemm_path(const float* A, int lda, const float* B, int ldb, const float* bias, const float* C, int ldc,
+                             const float* mask, const float* colsum, int M, int N, int K, int a_kmajor, int b_kmajor,
+                             int act, int* info) {
+  GemmArgs g;
+  GemmChoice c;
+  const int rc = gemm_select(A, lda, B, ldb, bias, C, ldc, mask, colsum, M, N, K, a_kmajor, b_kmajor, act, &g, &c);
+  if (rc != AVA_OK) return rc;
+  if (info != nullptr) {
+    info[0] = c.tile; info[1] = c.bk; info[2] = c.vec; info[3] = c.splits; info[4] = c.klen; info[5] = c.threads;
+  }
+  return c.path;
+}
+
+static int gemm_impl(const float* A, int lda, const float* B, int ldb, const float* bias, float* C, int ldc,
+                     const float* mask, float* colsum, int M, int N, int K, int a_kmajor, int b_kmajor, int act,
+                     void* ws, size_t ws_bytes, ava_stream_t s, int* deferred_slabs) {
+  GemmArgs g;
+  GemmChoice c;
+  const int sel = gemm_select(A, lda, B, ldb, bias, C, ldc, mask, colsum, M, N, K, a_kmajor, b_kmajor, act, &g, &c);
+  if (sel != AVA_OK) return sel;
+  if (c.plan_splits > 1 && (ws == nullptr || ws_bytes < ava_gemm_workspace_bytes(M, N, K))) return AVA_EWORKSPACE;
+  // the slabs are written (and read back) as 16-byte quads
+  if (c.splits > 1 && (reinterpret_cast<uintptr_t>(ws) & 15) != 0) return AVA_EWORKSPACE;
+  const int splits = c.splits;
+  hipStream_t st = to_stream(s);
+  if (c.path == GEMM_PATH_LIMB) {
     if (splits > 1 && (ws == nullptr || ws_bytes < ((size_t)splits * M * N + (size_t)splits * M) * sizeof(float)))
       return AVA_EWORKSPACE;
-    g.klen = klen; g.splits = splits;
     g.C = splits > 1 ? reinterpret_cast<float*>(ws) : C;
-    const int rc = ava_gemm_limb_launch(g, a_kmajor, b_kmajor, lbn, st);
+    const int rc = ava_gemm_limb_launch(g, a_kmajor, b_kmajor, c.tile, st);
     if (rc != AVA_OK) return rc;
     if (splits == 2 && deferred_slabs != nullptr && mask == nullptr && colsum == nullptr && g.ldc == N) {
       *deferred_slabs = 2;                 // the consumer reduces
@@ -547,10 +601,10 @@ static int gemm_impl(const float* A, int lda, const float* B, int ldb, const flo
     }
     return AVA_OK;
   }
-  if (skinny_ok(g, a_kmajor, b_kmajor)) {
+  if (c.path == GEMM_PATH_SKINNY) {
     g.C = C;
     const dim3 sgrid(ceil_div(N, 16), ceil_div(M, 16));
-    const dim3 sblock(K >= 512 ? 512 : 256);          // long K: eight waves share the K range of a tile
+    const dim3 sblock(c.threads);
     if (a_kmajor && b_kmajor) hipLaunchKernelGGL((gemm_skinny_kernel<true, true>), sgrid, sblock, 0, st, g);
     else if (a_kmajor) hipLaunchKernelGGL((gemm_skinny_kernel<true, false>), sgrid, sblock, 0, st, g);
     else if (b_kmajor) hipLaunchKernelGGL((gemm_skinny_kernel<false, true>), sgrid, sblock, 0, st, g);
@@ -558,15 +612,17 @@ static int gemm_impl(const float* A, int lda, const float* B, int ldb, const flo
     AVA_CHECK_LAUNCH();
     return AVA_OK;
   }
+  g.C = splits > 1 ? reinterpret_cast<float*>(ws) : C;
+  const int bm = c.tile;
   dim3 grid(ceil_div(N, bm), ceil_div(M, bm), splits);
-  if (!vec) {
+  if (!c.vec) {
     if (bm == 128) launch_gemm<128, 16, false>(g, a_kmajor, b_kmajor, grid, st);
     else launch_gemm<64, 16, false>(g, a_kmajor, b_kmajor, grid, st);
   } else if (bm == 128) {
-    if (klen % 32 == 0) launch_gemm<128, 32, true>(g, a_kmajor, b_kmajor, grid, st);
+    if (c.bk == 32) launch_gemm<128, 32, true>(g, a_kmajor, b_kmajor, grid, st);
     else launch_gemm<128, 16, true>(g, a_kmajor, b_kmajor, grid, st);
   } else {
-    if (klen % 32 == 0 && klen >= 512) launch_gemm<64, 32, true>(g, a_kmajor, b_kmajor, grid, st);   // the long-K 64-tile shapes
+    if (c.bk == 32) launch_gemm<64, 32, true>(g, a_kmajor, b_kmajor, grid, st);
     else launch_gemm<64, 16, true>(g, a_kmajor, b_kmajor, grid, st);
   }
   AVA_CHECK_LAUNCH();

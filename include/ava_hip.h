@@ -240,6 +240,17 @@ size_t ava_gemm_workspace_bytes(int M, int N, int K);
 int ava_gemm(const float* A, int lda, const float* B, int ldb, const float* bias, float* C, int ldc,
              const float* mask, float* colsum, int M, int N, int K, int a_kmajor, int b_kmajor, int act,
              void* ws, size_t ws_bytes, ava_stream_t s);
+/* `ws` must be 16-byte aligned whenever the product is split (AVA_EWORKSPACE otherwise).
+ *
+ * Which kernel ava_gemm runs for these arguments: the dispatcher's own decision, taken on the host from shapes,
+ * flags, pointer values and nullness alone (nothing is dereferenced or launched, no device is needed).
+ * Returns 1 = three-limb bf16 kernel, 2 = skinny 16x16 kernel, 3 = LDS-tiled kernel, or AVA_EINVAL for arguments
+ * ava_gemm refuses.  info (may be NULL) receives {tile (BN of the limb kernel, 16 for the skinny one, BM = BN of
+ * the tiled one), K step of the instantiation, 16-byte operand loads (0/1; skinny: any k-major operand),
+ * splits, K elements per split, threads per workgroup}. */
+int ava_gemm_path(const float* A, int lda, const float* B, int ldb, const float* bias, const float* C, int ldc,
+                  const float* mask, const float* colsum, int M, int N, int K, int a_kmajor, int b_kmajor, int act,
+                  int* info);
 
 /* latent block: d = exp(a), z = mu + u*eps_w + sqrt(d)*eps_d, per-sample sum z^2 and entropy
  * (torch/distributions/lowrank_multivariate_normal.py:17-38,214-252).  sums: [B][2]. */

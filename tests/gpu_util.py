@@ -97,13 +97,23 @@ def bwd_fused(x, xa, xb, dy, Gb, mean, invstd, cin, cout, mode, dy_pro, B, hi, d
     return dx, bnp.double().sum(dim=0).cpu(), dw, dbias
 
 
-def gemm(A, B, M, N, K, a_k, b_k, bias=None, act=0, mask=None, colsum=False, lda=0, ldb=0, ldc=0, C=None):
+def gemm(A, B, M, N, K, a_k, b_k, bias=None, act=0, mask=None, colsum=False, lda=0, ldb=0, ldc=0, C=None,
+         guard_rows=0, fill=0.0, c_offset=0, path_info=None):
+    """guard_rows / fill: C and the column sums are allocated with that many rows behind them and pre-filled with `fill`
+    (C comes back with its guard rows and all ldc columns); c_offset: C starts that many floats into its allocation;
+    path_info: a list that receives ava_gemm_path's answer (path, info[6]) for exactly the arguments of this call."""
     lib = _lib.load()
     nbytes = lib.ava_gemm_workspace_bytes(M, N, K)
     ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device="cuda")
     if C is None:
-        C = torch.zeros(M, ldc if ldc else N, device="cuda")
-    cs = torch.zeros(M, device="cuda") if colsum else None
+        ld = ldc if ldc else N
+        flat = torch.full((c_offset + (M + guard_rows) * ld,), fill, device="cuda")
+        C = flat[c_offset:].view(M + guard_rows, ld)
+    cs = torch.full((M + guard_rows,), fill, device="cuda") if colsum else None
+    if path_info is not None:
+        info = (ctypes.c_int * 6)()
+        path = lib.ava_gemm_path(p(A), lda, p(B), ldb, p(bias), p(C), ldc, p(mask), p(cs), M, N, K, a_k, b_k, act, info)
+        path_info.append((path, tuple(info)))
     rc = lib.ava_gemm(p(A), lda, p(B), ldb, p(bias), p(C), ldc, p(mask), p(cs), M, N, K, a_k, b_k, act, p(ws), nbytes,
                       stream())
     _lib.check(rc, "ava_gemm")
