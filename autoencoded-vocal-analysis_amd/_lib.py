@@ -165,6 +165,14 @@ SIGNATURES = {
     "ava_pj_gram_workspace_bytes": (_sz, [_i, _i]),
     "ava_pj_gram": (_i, [_p, _i, _i, _i, _p, _p, _sz, _p]),
     "ava_pj_project": (_i, [_p, _i, _i, _i, _p, _p, _i, _p, _p]),
+    "ava_ts_max_n": (_i, []),
+    "ava_ts_col_chunks": (_i, [_i]),
+    "ava_ts_workspace_bytes": (_sz, [_i, _i]),
+    "ava_ts_sqdist": (_i, [_p, _i, _i, _i, _i, _p, _i, _p]),
+    "ava_ts_square": (_i, [_p, _i, _p, _i, _p]),
+    "ava_ts_joint": (_i, [_p, _i, _i, _d, _p, _sz, _p]),
+    "ava_ts_kl_gradient": (_i, [_p, _p, _i, _i, _d, _i, _p, _p, _p, _sz, _p]),
+    "ava_ts_descend": (_i, [_p, _p, _p, _p, _i, _i, _i, _d, _d, _d, _i, _p, _p, _sz, _p]),
 }
 
 _lib = None

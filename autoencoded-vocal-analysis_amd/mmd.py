@@ -477,11 +477,13 @@ def _calculate_mmd2_pvalues(dc, condition_from_fn, pvalue_fn=None, condition_fn=
     return mmd2, pvalue, all_conditions
 
 
-def install(module=None, matrix=False, pvalues=False):
+def install(module=None, matrix=False, pvalues=False, tsne=False):
     """Point ``ava.plotting.mmd_plots``'s estimators at this module (call after importing the reference package).
     ``matrix=True`` also replaces its ``_calculate_mmd2``, the function behind ``mmd_matrix_plot_DC``, with the
     one-pass :func:`_calculate_mmd2` of this module; ``pvalues=True`` adds :func:`_calculate_mmd2_pvalues` (a name the
-    reference does not have) beside it."""
+    reference does not have) beside it; ``tsne=True`` replaces its ``TSNE`` (sklearn's, whose exact fit of a
+    precomputed matrix raises with scikit-learn 1.7) with :class:`ava_amd.tsne.TSNE`, so that ``mmd_tsne_plot_DC``
+    runs unchanged (row f19)."""
     if module is None:
         import ava.plotting.mmd_plots as module
     module.estimate_median_sigma = estimate_median_sigma
@@ -491,4 +493,7 @@ def install(module=None, matrix=False, pvalues=False):
         module._calculate_mmd2 = _calculate_mmd2
     if pvalues:
         module._calculate_mmd2_pvalues = _calculate_mmd2_pvalues
+    if tsne:
+        from .tsne import TSNE
+        module.TSNE = TSNE
     return module

@@ -763,6 +763,38 @@ int ava_pj_gram(const void* x, int dtype, int n, int d, double* gram, void* ws, 
 int ava_pj_project(const void* x, int dtype, int n, int d, const double* V, const double* muv, int nc, double* out,
                    ava_stream_t s);
 
+/* ---- Exact t-SNE (row f19; sklearn 1.7 TSNE(method='exact', n_components=2); csrc/tsne.hip) -------------------------
+ * The N x N matrix m (squared distances, then joint probabilities) is float64 row-major on the device with a row
+ * stride ld >= n, ld even, on a 16-byte boundary; 2 <= n <= ava_ts_max_n() = 32768.  Everything is fp64 and free of
+ * atomics: the same inputs give the same bits on every run.  ws: ava_ts_workspace_bytes(n, col_chunks) bytes.
+ *
+ * ava_ts_col_chunks: the number of column chunks the descent kernels split the pairs into by default, a function of
+ *   n alone (0 for an unsupported n); col_chunks <= 0 in the calls below means this value, at most 64 may be passed.
+ * ava_ts_sqdist: out[i][j] = |x_i - x_j|^2 of the rows x [n][d] (dtype 0 = float32, 1 = float64; 1 <= d <= 65536)
+ *   with the bits of ava_pair_sqdist, rounded to the nearest float32 (and stored as float64) when round_f32 != 0.
+ * ava_ts_square: out[i][j] = float32(dist[i][j]^2) of a contiguous float64 [n][n] distance matrix.
+ * ava_ts_joint: in place, the squared distances become sklearn's joint probabilities P (_joint_probabilities with
+ *   _binary_search_perplexity; symmetric, zero diagonal, every other entry >= DBL_EPSILON).  0 < perplexity < n.
+ * ava_ts_kl_gradient: stats[0] = KL(e P || Q), stats[1] = |grad|_2 and grad [n][2] = dKL/dy at y [n][2] (sklearn's
+ *   _kl_divergence with P scaled by the exaggeration e).
+ * ava_ts_descend: n_iters iterations of sklearn's _gradient_descent on y, update, gains [n][2] (in / out), enqueued
+ *   without a host synchronisation; stats [n_iters][2] receives every iteration's {KL, |grad gains|_2}, the KL of
+ *   all but the last as NaN (not computed, like sklearn's compute_error=False: it costs more than the rest of the pass).
+ *
+ * All return AVA_EINVAL before any launch for null or misaligned pointers or an unsupported shape, AVA_EWORKSPACE for
+ * a workspace that is too small. */
+int ava_ts_max_n(void);
+int ava_ts_col_chunks(int n);
+size_t ava_ts_workspace_bytes(int n, int col_chunks);
+int ava_ts_sqdist(const void* x, int dtype, int n, int d, int round_f32, double* out, int ld, ava_stream_t s);
+int ava_ts_square(const double* dist, int n, double* out, int ld, ava_stream_t s);
+int ava_ts_joint(double* p, int ld, int n, double perplexity, void* ws, size_t ws_bytes, ava_stream_t s);
+int ava_ts_kl_gradient(const double* y, const double* p, int ld, int n, double exaggeration, int col_chunks,
+                       double* grad, double* stats, void* ws, size_t ws_bytes, ava_stream_t s);
+int ava_ts_descend(double* y, double* update, double* gains, const double* p, int ld, int n, int n_iters,
+                   double momentum, double lr, double exaggeration, int col_chunks, double* stats, void* ws,
+                   size_t ws_bytes, ava_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif
