@@ -173,6 +173,15 @@ SIGNATURES = {
     "ava_ts_joint": (_i, [_p, _i, _i, _d, _p, _sz, _p]),
     "ava_ts_kl_gradient": (_i, [_p, _p, _i, _i, _d, _i, _p, _p, _p, _sz, _p]),
     "ava_ts_descend": (_i, [_p, _p, _p, _p, _i, _i, _i, _d, _d, _d, _i, _p, _p, _sz, _p]),
+    "ava_gm_max_d": (_i, []),
+    "ava_gm_max_k": (_i, []),
+    "ava_gm_chunk_rows": (_i, []),
+    "ava_gm_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "ava_gm_e_step": (_i, [_p, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "ava_gm_means": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _p, _p, _sz, _p]),
+    "ava_gm_m_step": (_i, [_p, _i, _i, _i, _i, _i, _p, _d, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    "ava_gm_fit": (_i, [_p, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _d, _d, _i, _i, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    "ava_gm_onehot": (_i, [_p, _p, _i, _i, _p, _p, _p]),
 }
 
 _lib = None

@@ -795,6 +795,52 @@ int ava_ts_descend(double* y, double* update, double* gains, const double* p, in
                    double momentum, double lr, double exaggeration, int col_chunks, double* stats, void* ws,
                    size_t ws_bytes, ava_stream_t s);
 
+/* ---- Gaussian mixture models (row f20; sklearn 1.7 GaussianMixture, 'full' and 'diag'; csrc/mixture.hip) -----------
+ * x / dtype: [n][d] row-major on the device, 0 = float32, 1 = float64.  cov_type: 0 = 'full', 1 = 'diag'.  All other
+ * arrays are float64 on the device: weights [k], means [k][d], cov and prec_chol [k][d][d] ('full'; prec_chol is
+ * sklearn's precisions_cholesky_, upper triangular) or [k][d] ('diag'), log_det [k] = sum log diag prec_chol,
+ * log_prob_norm [n], log_resp and resp [n][k].  1 <= d <= ava_gm_max_d() = 128, 1 <= k <= ava_gm_max_k() = 64,
+ * k <= n.  Everything is fp64 in fixed orders (the contract at the head of mixture.hip): the same inputs give the same
+ * bits on every run.  Partial sums are taken over chunks of ava_gm_chunk_rows() = 2048 rows, a constant.
+ * ws: ava_gm_workspace_bytes(n, d, k, cov_type) bytes (0 for an unsupported shape).
+ *
+ * ava_gm_e_step: sklearn's _estimate_log_prob_resp at the given parameters, and resp = exp(log_resp).
+ * ava_gm_means:  nk [k] = sum_n resp + 10 DBL_EPSILON, means = sum_n resp x / nk, weights = nk / n normalised
+ *   (ws of cov_type 1).
+ * ava_gm_m_step: sklearn's _m_step from resp: ava_gm_means, then cov = sum_n resp (x - mean)(x - mean)^T / nk +
+ *   reg_covar I (exactly symmetric; 'diag': the diagonal), its Cholesky factor L, prec_chol = (L^-1)^T and log_det.
+ *   status [1] int is set to 1 when a covariance is not positive definite (nothing is read or written out of bounds;
+ *   prec_chol and log_det of that component are then undefined); the caller clears it.
+ * ava_gm_fit: iterations [it0, it0 + n_iters) of sklearn's EM loop (E-step, M-step, |lower bound - previous| < tol),
+ *   enqueued without a host synchronisation; the parameters advance in place.  lower_bounds [>= it0 + n_iters] receives
+ *   every iteration's bound; ctl [>= 3 + it0 + n_iters] int: ctl[0] the status word of ava_gm_m_step, ctl[1] the number
+ *   of iterations that ran, ctl[2 + i] whether the loop had stopped before iteration i (ctl[2 + it0 + n_iters] after
+ *   the call: whether it has stopped).  The caller zeroes ctl before iteration 0.  Once the loop has stopped, or
+ *   ctl[0] is set, every later launch returns at once, so the parameters are those of the stopping iteration.
+ *   log_prob_norm, log_resp and resp are scratch and hold the last E-step that ran.
+ * ava_gm_onehot: resp [n][k] = (labels[i] == j); changed [1] int += the number of rows with labels[i] != prev[i];
+ *   prev = labels (int64, device).
+ *
+ * All return AVA_EINVAL before any launch for null pointers, an unknown dtype or cov_type, negative tol or reg_covar or
+ * an unsupported shape, AVA_EWORKSPACE for a workspace that is too small. */
+int ava_gm_max_d(void);
+int ava_gm_max_k(void);
+int ava_gm_chunk_rows(void);
+size_t ava_gm_workspace_bytes(int n, int d, int k, int cov_type);
+int ava_gm_e_step(const void* x, int dtype, int n, int d, int k, int cov_type, const double* weights,
+                  const double* means, const double* prec_chol, const double* log_det, double* log_prob_norm,
+                  double* log_resp, double* resp, ava_stream_t s);
+int ava_gm_means(const void* x, int dtype, int n, int d, int k, const double* resp, double* weights, double* means,
+                 double* nk, void* ws, size_t ws_bytes, ava_stream_t s);
+int ava_gm_m_step(const void* x, int dtype, int n, int d, int k, int cov_type, const double* resp, double reg_covar,
+                  double* weights, double* means, double* cov, double* prec_chol, double* log_det, int* status,
+                  void* ws, size_t ws_bytes, ava_stream_t s);
+int ava_gm_fit(const void* x, int dtype, int n, int d, int k, int cov_type, double* weights, double* means,
+               double* cov, double* prec_chol, double* log_det, double tol, double reg_covar, int it0, int n_iters,
+               double* lower_bounds, int* ctl, double* log_prob_norm, double* log_resp, double* resp, void* ws,
+               size_t ws_bytes, ava_stream_t s);
+int ava_gm_onehot(const int64_t* labels, int64_t* prev, int n, int k, double* resp, int* changed, ava_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif
