@@ -182,6 +182,13 @@ SIGNATURES = {
     "ava_gm_m_step": (_i, [_p, _i, _i, _i, _i, _i, _p, _d, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
     "ava_gm_fit": (_i, [_p, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _d, _d, _i, _i, _p, _p, _p, _p, _p, _p, _sz, _p]),
     "ava_gm_onehot": (_i, [_p, _p, _i, _i, _p, _p, _p]),
+    "ava_sil_max_k": (_i, []),
+    "ava_sil_chunk_cols": (_i, []),
+    "ava_sil_workspace_bytes": (_sz, [_i, _i, _i]),
+    "ava_sil_cluster_sums": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _p, _sz, _p]),
+    "ava_sil_cluster_sums_pre": (_i, [_p, _i, _i, _i, _p, _p, _p, _p]),
+    "ava_sil_finish": (_i, [_p, _i, _i, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    "ava_sil_centroid_stats": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _p, _p, _sz, _p]),
 }
 
 _lib = None

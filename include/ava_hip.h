@@ -841,6 +841,40 @@ int ava_gm_fit(const void* x, int dtype, int n, int d, int k, int cov_type, doub
                size_t ws_bytes, ava_stream_t s);
 int ava_gm_onehot(const int64_t* labels, int64_t* prev, int n, int k, double* resp, int* changed, ava_stream_t s);
 
+/* ---- Silhouette and cluster-validity sums (row f21; sklearn 1.7 metrics/cluster/_unsupervised.py; csrc/silhouette.hip)
+ * x / dtype: [n][d] row-major on the device, 0 = float32, 1 = float64, d >= 1.  The labels are encoded by the caller as
+ * 0 .. k - 1 with 2 <= k <= min(n - 1, ava_sil_max_k() = 1024).  order [n] int64: the stable argsort of the encoded
+ * labels ("sorted row r" is the caller's row order[r]); off [k + 1] int64: cluster j owns the sorted rows
+ * [off[j], off[j + 1]).  Both on the device; entries out of range are clamped or skipped, never followed out of bounds.
+ * Everything is fp64 in fixed orders (the contract at the head of silhouette.hip): a cluster's columns are added in
+ * chunks of ava_sil_chunk_cols() = 2048 counted from the cluster's first column, so sums [.][j] depends on the rows of
+ * cluster j and on the row itself only.  ws: ava_sil_workspace_bytes(n, d, k) bytes (0 for an unsupported shape; the
+ * rows in cluster order and the chunk partials; the size for d serves every smaller d).
+ *
+ * ava_sil_cluster_sums: sums [n][k], row r = sorted row r: sums[r][j] = sum over the rows c of cluster j of
+ *   sqrt(sum_f (x_rf - x_cf)^2), direct differences, f ascending (the bits of ava_pair_sqdist), one fp64 sqrt.
+ * ava_sil_cluster_sums_pre: the same sums from dist [n][n] (dtype as x), distances in the caller's row order.
+ * ava_sil_finish: per sorted row r of cluster l: a = sums[r][l] / (n_l - 1), b = min_{j != l} sums[r][j] / n_j,
+ *   s = (b - a) / max(a, b), 0 where that is NaN; sil, a, b [n] in the caller's row order; score [1] = mean of sil
+ *   over chunks of 2048 rows added ascending.  ws: at least ava_sil_workspace_bytes(n, 1, k).
+ * ava_sil_centroid_stats: labels [n] int64 encoded labels in the caller's order, means [k][d] (ava_gm_onehot +
+ *   ava_gm_means); sum_dist [k] = sum over the rows of cluster j of ||x - means[j]||, sum_sq [k] of its square; chunks
+ *   of 2048 rows ascending.  d <= ava_gm_max_d(), k <= ava_gm_max_k().
+ *
+ * All return AVA_EINVAL before any launch for null pointers, an unknown dtype or an unsupported shape, AVA_EWORKSPACE
+ * for a workspace that is too small. */
+int ava_sil_max_k(void);
+int ava_sil_chunk_cols(void);
+size_t ava_sil_workspace_bytes(int n, int d, int k);
+int ava_sil_cluster_sums(const void* x, int dtype, int n, int d, int k, const int64_t* order, const int64_t* off,
+                         double* sums, void* ws, size_t ws_bytes, ava_stream_t s);
+int ava_sil_cluster_sums_pre(const void* dist, int dtype, int n, int k, const int64_t* order, const int64_t* off,
+                             double* sums, ava_stream_t s);
+int ava_sil_finish(const double* sums, int n, int k, const int64_t* order, const int64_t* off, double* sil, double* a,
+                   double* b, double* score, void* ws, size_t ws_bytes, ava_stream_t s);
+int ava_sil_centroid_stats(const void* x, int dtype, int n, int d, int k, const int64_t* labels, const double* means,
+                           double* sum_dist, double* sum_sq, void* ws, size_t ws_bytes, ava_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif
