@@ -25,23 +25,27 @@
 // The piecewise-linear warp (row f14): K = n_knots + 2 knots per motif, u[k] the source position of the template column
 // t_k = k (T-1) / (K-1).  Column j lies in segment k = min(j (K-1) / (T-1), K-2) (integers) and reads the source at
 // p(j) = u_k + s_k (j - t_k), s_k = (u_{k+1} - u_k) / (t_{k+1} - t_k), every operation rounded on its own; with K = 2 that
-// is wf_pos(u_0, s_0, j).  A candidate with some s_k <= 0 has loss +inf.
+// is wf_pos(u_0, s_0, j).  A candidate with some s_k <= 0 has loss +inf.  The penalties are shift_l u_0^2 + slope_l
+// mean_k (log s_k)^2.
 //
-//   warpfit_pl_apply_kernel       warpfit_apply_kernel under knots [N][K]
-//   warpfit_pl_candidates_kernel  candidates [N][C][K] around u [N][K]: one knot, or all knots together, moved by 0, -h, +h, ...
-//   warpfit_pl_loss_kernel        warpfit_loss_kernel with the column tables made from knots: the same LDS, the same sums
-//                                 (wf_block_sums), + shift_l u_0^2 + slope_l mean_k (log s_k)^2
-//   warpfit_argmin_kernel         serves both fits: its parameter width is 2 or K
+// The two warps are two models, WfAffine and WfKnots: how a candidate or a fitted warp is read, where column j reads the
+// source, what is added to a finished sum.  The apply, loss and grouped kernels are templates over the model and nothing
+// else in them knows which warp it is: the LDS, the staging, the sums (wf_block_sums) and their order exist once.
+//
+//   warpfit_apply_kernel<T, Model>   under (shift, slope) [N][2] or knots [N][K]
+//   warpfit_loss_kernel<T, Model>    candidates [N][C][2] or [N][C][K]
+//   warpfit_pl_candidates_kernel     candidates [N][C][K] around u [N][K]: one knot, or all knots together, moved by 0, -h, +h, ...
+//   warpfit_argmin_kernel            serves both fits: its parameter width is 2 or K
 //
 // The grouped fits (row f17): many fit problems over the same spec in one launch.  A group is a sorted list of motifs, a
 // sorted list of bins and two lambdas of its own; a virtual row is one (motif, group) pair (struct WfPlan).
 //
-//   warpfit_group_loss_kernel     warpfit_loss_kernel per virtual row: the motif, the target, the bins and the lambdas come
-//   warpfit_group_pl_loss_kernel  through the plan, the bins are staged through their list in list order, and everything
-//                                 else is the plain kernel's body (wf_loss_body / wf_pl_loss_body over wf_block_sums), so a
-//                                 virtual row's losses have the bits of the plain kernel on the gathered tensor
-//   warpfit_group_mean_kernel     every group's mean warped motif without the warped motifs: the apply kernels' values,
-//                                 summed over the group's rows in rising order
+//   warpfit_group_loss_kernel<T, Model>   warpfit_loss_kernel per virtual row: the motif, the target, the bins and the
+//                                         lambdas come through the plan, the bins are staged through their list in list
+//                                         order, and everything else is wf_loss_body, the plain kernel's body, so a virtual
+//                                         row's losses have the bits of the plain kernel on the gathered tensor
+//   warpfit_group_mean_kernel<T, Model>   every group's mean warped motif without the warped motifs: the apply kernel's
+//                                         values, summed over the group's rows in rising order
 //   the candidates and argmin kernels serve virtual rows as they are
 #include "common.h"
 
@@ -87,28 +91,73 @@ __device__ __forceinline__ double wf_pl_pos(const double* __restrict__ u, int j,
   return __dadd_rn(u[k], __dmul_rn(wf_pl_slope(u, k, T, K), __dsub_rn((double)j, wf_knot_t(k, T, K))));
 }
 
-template <typename T_>
-__global__ __launch_bounds__(256) void warpfit_pl_apply_kernel(const T_* __restrict__ spec, const double* __restrict__ knots,
-                                                               int F, int T, int K, T_* __restrict__ out) {
-  const int n = blockIdx.x;
-  const double* u = knots + (size_t)n * K;
-  for (int j = threadIdx.x; j < T; j += 256) {
-    const WfTap t = wf_tap(wf_pl_pos(u, j, T, K), T);
-    const int hi = t.lo + 1 < T ? t.lo + 1 : T - 1;
-    for (int f = blockIdx.y; f < F; f += gridDim.y) {
-      const T_* row = spec + ((size_t)n * F + f) * T;
-      out[((size_t)n * F + f) * T + j] = (T_)wf_lerp((double)row[t.lo], (double)row[hi], t.w);
-    }
+// The two warp models.  A model is one warp: warp(p, i, K) is warp i of the fitted parameters p, candidate(cand, c, K,
+// fixed_slope) is candidate c of a search; pos(j, T, K, fixed_slope) is the source position of column j (fixed_slope: the
+// shift objective, every slope 1) and penalised(tot, ...) the finished sum of squares plus the model's penalties.  Every
+// kernel below that warps is written once over the model; the operations inside a model, and their order, are the
+// objective's definition and the tests hold them to the bit.
+//
+// Shift and slope.  A candidate is (shift, log slope), a fitted warp (shift, slope).  The loss body holds shift and
+// log slope in registers across its sums for the penalties; the slope is dead once the tables are written.
+struct WfAffine {
+  double shift, ls, slope;
+  static __device__ __forceinline__ int width(int) { return 2; }
+  static __device__ __forceinline__ WfAffine warp(const double* __restrict__ p, size_t i, int) {
+    return {p[2 * i], 0.0, p[2 * i + 1]};
   }
-}
+  static __device__ __forceinline__ WfAffine candidate(const double* __restrict__ cand, size_t c, int, int fixed_slope) {
+    const double ls = cand[2 * c + 1];
+    return {cand[2 * c], ls, fixed_slope ? 1.0 : exp(ls)};
+  }
+  __device__ __forceinline__ double pos(int j, int, int, int) const { return wf_pos(shift, slope, j); }
+  // loss + shift_l * x[0]**2 + slope_l * x[1]**2, left to right
+  __device__ __forceinline__ double penalised(double tot, double shift_lambda, double slope_lambda, int fixed_slope, int,
+                                              int) const {
+    tot = __dadd_rn(tot, __dmul_rn(shift_lambda, __dmul_rn(shift, shift)));
+    if (!fixed_slope) tot = __dadd_rn(tot, __dmul_rn(slope_lambda, __dmul_rn(ls, ls)));
+    return tot;
+  }
+};
 
-template <typename T_>
+// K knots.  The model keeps a pointer: a lane reads the two knots of its column's segment from memory, K <= 16 doubles
+// that stay in cache, and the penalty re-reads them after the sums.  fixed_slope: the positions are u_0 + j.  Crossed
+// knots do not stop the sums -- wf_tap keeps every tap inside the row -- and the total is replaced by +inf.
+struct WfKnots {
+  const double* u;
+  static __device__ __forceinline__ int width(int K) { return K; }
+  static __device__ __forceinline__ WfKnots warp(const double* __restrict__ p, size_t i, int K) { return {p + i * K}; }
+  static __device__ __forceinline__ WfKnots candidate(const double* __restrict__ cand, size_t c, int K, int) {
+    return {cand + c * K};
+  }
+  __device__ __forceinline__ double pos(int j, int T, int K, int fixed_slope) const {
+    return fixed_slope ? wf_pos(u[0], 1.0, j) : wf_pl_pos(u, j, T, K);
+  }
+  // loss + shift_l u_0^2 + slope_l mean_k (log s_k)^2
+  __device__ __forceinline__ double penalised(double tot, double shift_lambda, double slope_lambda, int fixed_slope, int T,
+                                              int K) const {
+    tot = __dadd_rn(tot, __dmul_rn(shift_lambda, __dmul_rn(u[0], u[0])));
+    if (fixed_slope) return tot;
+    double sq = 0.0;                                        // sum_k (log s_k)^2, k = 0, 1, ...
+    bool crossed = false;
+    for (int i = 0; i < K - 1; ++i) {
+      const double sl = wf_pl_slope(u, i, T, K);
+      crossed |= sl <= 0.0;
+      const double l = log(sl);
+      sq = __dadd_rn(sq, __dmul_rn(l, l));
+    }
+    tot = __dadd_rn(tot, __dmul_rn(slope_lambda, __ddiv_rn(sq, (double)(K - 1))));
+    return crossed ? __builtin_inf() : tot;
+  }
+};
+
+// params: (shift, slope) [N][2] or knots [N][K]
+template <typename T_, typename Model>
 __global__ __launch_bounds__(256) void warpfit_apply_kernel(const T_* __restrict__ spec, const double* __restrict__ params,
-                                                            int F, int T, T_* __restrict__ out) {
+                                                            int F, int T, int K, T_* __restrict__ out) {
   const int n = blockIdx.x;
-  const double shift = params[2 * (size_t)n], slope = params[2 * (size_t)n + 1];
+  const Model m = Model::warp(params, n, K);
   for (int j = threadIdx.x; j < T; j += 256) {
-    const WfTap t = wf_tap(wf_pos(shift, slope, j), T);
+    const WfTap t = wf_tap(m.pos(j, T, K, 0), T);
     const int hi = t.lo + 1 < T ? t.lo + 1 : T - 1;
     for (int f = blockIdx.y; f < F; f += gridDim.y) {
       const T_* row = spec + ((size_t)n * F + f) * T;
@@ -209,13 +258,14 @@ __device__ __forceinline__ void wf_block_sums(const T_* __restrict__ motif, cons
   }
 }
 
-// The loss of one (motif, candidate block): the body of warpfit_loss_kernel and of its grouped form.  raw: the tables are
-// lo = j, w = 0, the unwarped row read exactly, no candidate is read and no penalty added.
-template <typename T_, bool G>
+// The loss of one (motif, candidate block) under either model: the body of warpfit_loss_kernel and of its grouped form.
+// cand: the motif's candidates [C][Model::width(K)].  raw (grouped only): the tables are lo = j, w = 0, the unwarped row
+// read exactly, no candidate is read (cand may be null) and no penalty added.
+template <typename T_, typename Model, bool G>
 __device__ __forceinline__ void wf_loss_body(const T_* __restrict__ motif, const double* __restrict__ target,
                                              const int* __restrict__ bins, int Fall, const double* __restrict__ cand, int F,
-                                             int T, int C, double shift_lambda, double slope_lambda, int fixed_slope, int raw,
-                                             double* __restrict__ loss) {
+                                             int T, int C, int K, double shift_lambda, double slope_lambda, int fixed_slope,
+                                             int raw, double* __restrict__ loss) {
   extern __shared__ __align__(16) double wf_sm[];
   const int TS = T + 1;
   double* s_spec = wf_sm;                                   // [WF_FR][T + 1], column T repeats column T-1
@@ -225,11 +275,10 @@ __device__ __forceinline__ void wf_loss_body(const T_* __restrict__ motif, const
   const int c0 = blockIdx.y * WF_CB;
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
 
-  double shift[2], ls[2];
+  Model m[2] = {};
 #pragma unroll
   for (int k = 0; k < 2; ++k) {
     const int cc = wave + 4 * k, c = c0 + cc;
-    shift[k] = ls[k] = 0.0;
     if (c < C) {                                            // wave-uniform
       if (G && raw) {
         for (int j = lane; j < T; j += 64) {
@@ -238,11 +287,9 @@ __device__ __forceinline__ void wf_loss_body(const T_* __restrict__ motif, const
         }
         continue;
       }
-      shift[k] = cand[2 * (size_t)c];
-      ls[k] = cand[2 * (size_t)c + 1];
-      const double slope = fixed_slope ? 1.0 : exp(ls[k]);
+      m[k] = Model::candidate(cand, c, K, fixed_slope);
       for (int j = lane; j < T; j += 64) {
-        const WfTap t = wf_tap(wf_pos(shift[k], slope, j), T);
+        const WfTap t = wf_tap(m[k].pos(j, T, K, fixed_slope), T);
         s_lo[cc * T + j] = t.lo;
         s_w[cc * T + j] = t.w;
       }
@@ -256,23 +303,20 @@ __device__ __forceinline__ void wf_loss_body(const T_* __restrict__ motif, const
     const int c = c0 + wave + 4 * k;
     if (c >= C) continue;
     double tot = wave_sum_d(acc[k]);
-    if (!(G && raw)) {
-      // loss + shift_l * x[0]**2 + slope_l * x[1]**2, left to right
-      tot = __dadd_rn(tot, __dmul_rn(shift_lambda, __dmul_rn(shift[k], shift[k])));
-      if (!fixed_slope) tot = __dadd_rn(tot, __dmul_rn(slope_lambda, __dmul_rn(ls[k], ls[k])));
-    }
+    if (!(G && raw)) tot = m[k].penalised(tot, shift_lambda, slope_lambda, fixed_slope, T, K);
     if (lane == 0) loss[c] = tot;
   }
 }
 
-template <typename T_>
+// loss[n][c] of spec [N][F][T] against one target [F][T]; cand [N][C][width]
+template <typename T_, typename Model>
 __global__ __launch_bounds__(256) void warpfit_loss_kernel(const T_* __restrict__ spec, const double* __restrict__ target,
-                                                           const double* __restrict__ cand, int F, int T, int C,
+                                                           const double* __restrict__ cand, int F, int T, int C, int K,
                                                            double shift_lambda, double slope_lambda, int fixed_slope,
                                                            double* __restrict__ loss) {
   const int n = blockIdx.x;
-  wf_loss_body<T_, false>(spec + (size_t)n * F * T, target, nullptr, F, cand + 2 * (size_t)n * C, F, T, C, shift_lambda,
-                          slope_lambda, fixed_slope, 0, loss + (size_t)n * C);
+  wf_loss_body<T_, Model, false>(spec + (size_t)n * F * T, target, nullptr, F, cand + (size_t)n * C * Model::width(K), F, T, C,
+                                 K, shift_lambda, slope_lambda, fixed_slope, 0, loss + (size_t)n * C);
 }
 
 // The plan of the grouped fits (row f17): V virtual rows, row v being motif row_src[v] of spec [N][Fall][T] seen by group
@@ -288,111 +332,21 @@ struct WfPlan {
 };
 
 // warpfit_loss_kernel over virtual rows: the motif, the target, the bins and both lambdas come through the plan, the rest
-// is the plain kernel's, operation for operation; cand [V][C][2], loss [V][C]
-template <typename T_>
+// is the plain kernel's, operation for operation; cand [V][C][width], loss [V][C]
+template <typename T_, typename Model>
 __global__ __launch_bounds__(256) void warpfit_group_loss_kernel(const T_* __restrict__ spec, WfPlan pl,
                                                                  const double* __restrict__ targets,
-                                                                 const double* __restrict__ cand, int T, int C,
+                                                                 const double* __restrict__ cand, int T, int C, int K,
                                                                  const double* __restrict__ shift_lambda,
                                                                  const double* __restrict__ slope_lambda, int fixed_slope,
                                                                  int raw, double* __restrict__ loss) {
   const int v = blockIdx.x, g = pl.row_group[v], n = pl.row_src[v];
   if ((unsigned)n >= (unsigned)pl.N) return;                // a broken plan reads nothing
   const int b0 = pl.bin_off[g], F = pl.bin_off[g + 1] - b0;
-  wf_loss_body<T_, true>(spec + (size_t)n * pl.Fall * T, targets + (size_t)b0 * T, pl.bins + b0, pl.Fall,
-                         raw ? nullptr : cand + 2 * (size_t)v * C, F, T, C, raw ? 0.0 : shift_lambda[g],
-                         (raw || fixed_slope) ? 0.0 : slope_lambda[g], fixed_slope, raw, loss + (size_t)v * C);
-}
-
-// The loss body for candidates of K knots each, cand [C][K]: only the tables differ (a lane reads the two knots of its
-// column's segment from the candidate, K <= 16 doubles that stay in cache).  fixed_slope: every slope is 1 and the
-// positions are u_0 + j, the shift objective.  Crossed knots do not stop the sums -- wf_tap keeps every tap inside the
-// row -- and the total is replaced by +inf.
-template <typename T_, bool G>
-__device__ __forceinline__ void wf_pl_loss_body(const T_* __restrict__ motif, const double* __restrict__ target,
-                                                const int* __restrict__ bins, int Fall, const double* __restrict__ cand,
-                                                int F, int T, int C, int K, double shift_lambda, double slope_lambda,
-                                                int fixed_slope, int raw, double* __restrict__ loss) {
-  extern __shared__ __align__(16) double wf_sm[];
-  const int TS = T + 1;
-  double* s_spec = wf_sm;                                   // as in wf_loss_body
-  double* s_tgt = s_spec + WF_FR * TS;
-  double* s_w = s_tgt + WF_FR * T;
-  int* s_lo = reinterpret_cast<int*>(s_w + WF_CB * T);
-  const int c0 = blockIdx.y * WF_CB;
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-
-#pragma unroll
-  for (int k = 0; k < 2; ++k) {
-    const int cc = wave + 4 * k, c = c0 + cc;
-    if (c < C) {                                            // wave-uniform
-      if (G && raw) {
-        for (int j = lane; j < T; j += 64) {
-          s_lo[cc * T + j] = j;
-          s_w[cc * T + j] = 0.0;
-        }
-        continue;
-      }
-      const double* u = cand + (size_t)c * K;
-      for (int j = lane; j < T; j += 64) {
-        const WfTap t = wf_tap(fixed_slope ? wf_pos(u[0], 1.0, j) : wf_pl_pos(u, j, T, K), T);
-        s_lo[cc * T + j] = t.lo;
-        s_w[cc * T + j] = t.w;
-      }
-    }
-  }
-
-  double acc[2] = {0.0, 0.0};
-  wf_block_sums<T_, G>(motif, target, bins, Fall, F, T, C, c0, s_spec, s_tgt, s_w, s_lo, acc);
-#pragma unroll
-  for (int k = 0; k < 2; ++k) {
-    const int c = c0 + wave + 4 * k;
-    if (c >= C) continue;
-    double tot = wave_sum_d(acc[k]);
-    if (!(G && raw)) {
-      const double* u = cand + (size_t)c * K;
-      tot = __dadd_rn(tot, __dmul_rn(shift_lambda, __dmul_rn(u[0], u[0])));
-      if (!fixed_slope) {
-        double sq = 0.0;                                    // sum_k (log s_k)^2, k = 0, 1, ...
-        bool crossed = false;
-        for (int i = 0; i < K - 1; ++i) {
-          const double sl = wf_pl_slope(u, i, T, K);
-          crossed |= sl <= 0.0;
-          const double l = log(sl);
-          sq = __dadd_rn(sq, __dmul_rn(l, l));
-        }
-        tot = __dadd_rn(tot, __dmul_rn(slope_lambda, __ddiv_rn(sq, (double)(K - 1))));
-        if (crossed) tot = __builtin_inf();
-      }
-    }
-    if (lane == 0) loss[c] = tot;
-  }
-}
-
-template <typename T_>
-__global__ __launch_bounds__(256) void warpfit_pl_loss_kernel(const T_* __restrict__ spec, const double* __restrict__ target,
-                                                              const double* __restrict__ cand, int F, int T, int C, int K,
-                                                              double shift_lambda, double slope_lambda, int fixed_slope,
-                                                              double* __restrict__ loss) {
-  const int n = blockIdx.x;
-  wf_pl_loss_body<T_, false>(spec + (size_t)n * F * T, target, nullptr, F, cand + (size_t)n * C * K, F, T, C, K, shift_lambda,
-                             slope_lambda, fixed_slope, 0, loss + (size_t)n * C);
-}
-
-// warpfit_pl_loss_kernel over virtual rows; cand [V][C][K]
-template <typename T_>
-__global__ __launch_bounds__(256) void warpfit_group_pl_loss_kernel(const T_* __restrict__ spec, WfPlan pl,
-                                                                    const double* __restrict__ targets,
-                                                                    const double* __restrict__ cand, int T, int C, int K,
-                                                                    const double* __restrict__ shift_lambda,
-                                                                    const double* __restrict__ slope_lambda, int fixed_slope,
-                                                                    int raw, double* __restrict__ loss) {
-  const int v = blockIdx.x, g = pl.row_group[v], n = pl.row_src[v];
-  if ((unsigned)n >= (unsigned)pl.N) return;
-  const int b0 = pl.bin_off[g], F = pl.bin_off[g + 1] - b0;
-  wf_pl_loss_body<T_, true>(spec + (size_t)n * pl.Fall * T, targets + (size_t)b0 * T, pl.bins + b0, pl.Fall,
-                            raw ? nullptr : cand + (size_t)v * C * K, F, T, C, K, raw ? 0.0 : shift_lambda[g],
-                            (raw || fixed_slope) ? 0.0 : slope_lambda[g], fixed_slope, raw, loss + (size_t)v * C);
+  wf_loss_body<T_, Model, true>(spec + (size_t)n * pl.Fall * T, targets + (size_t)b0 * T, pl.bins + b0, pl.Fall,
+                                raw ? nullptr : cand + (size_t)v * C * Model::width(K), F, T, C, K,
+                                raw ? 0.0 : shift_lambda[g], (raw || fixed_slope) ? 0.0 : slope_lambda[g], fixed_slope, raw,
+                                loss + (size_t)v * C);
 }
 
 // The grouped template (row f17): target_g[f][j] = sum over the group's rows, in rising order, of the value the apply
@@ -401,13 +355,13 @@ __global__ __launch_bounds__(256) void warpfit_group_pl_loss_kernel(const T_* __
 // WM_TJ columns, share of the bins): WM_TR rows at a time, a row's tap for a column is computed once into LDS and then
 // used for every bin of the workgroup's share; thread (column, bin lane) carries the running sum of its (bin, column)
 // cells from one row set to the next through the target itself, which only that thread touches.  fp64, a fixed order,
-// no atomics.  mode 0: params [V][2] = (shift, slope) through wf_pos; 1: knots [V][K] through wf_pl_pos; 2 (raw): the
-// unwarped value, which an identity warp does not reproduce bit for bit.
+// no atomics.  params [V][2] = (shift, slope) or knots [V][K], by the model; raw: no warp at all but the unwarped value,
+// which an identity warp does not reproduce bit for bit, and params is not read.
 #define WM_TJ 64
 #define WM_TR 16
-template <typename T_>
+template <typename T_, typename Model>
 __global__ __launch_bounds__(256) void warpfit_group_mean_kernel(const T_* __restrict__ spec, WfPlan pl,
-                                                                 const double* __restrict__ params, int T, int K, int mode,
+                                                                 const double* __restrict__ params, int T, int K, int raw,
                                                                  double* __restrict__ targets) {
   __shared__ int s_lo[WM_TR][WM_TJ];
   __shared__ double s_w[WM_TR][WM_TJ];
@@ -420,13 +374,11 @@ __global__ __launch_bounds__(256) void warpfit_group_mean_kernel(const T_* __res
   for (int r0 = 0; r0 < R; r0 += WM_TR) {
     const int nr = R - r0 < WM_TR ? R - r0 : WM_TR;
     __syncthreads();                                        // the previous row set's taps are consumed
-    if (mode != 2) {
+    if (!raw) {
       for (int e = threadIdx.x; e < nr * WM_TJ; e += 256) {
         const int r = e >> 6, jj = j0 + (e & (WM_TJ - 1));
         if (jj >= T) continue;
-        const size_t v = (size_t)(v0 + r0 + r);
-        const double p = mode == 0 ? wf_pos(params[2 * v], params[2 * v + 1], jj) : wf_pl_pos(params + v * K, jj, T, K);
-        const WfTap t = wf_tap(p, T);
+        const WfTap t = wf_tap(Model::warp(params, (size_t)(v0 + r0 + r), K).pos(jj, T, K, 0), T);
         s_lo[r][e & (WM_TJ - 1)] = t.lo;
         s_w[r][e & (WM_TJ - 1)] = t.w;
       }
@@ -443,7 +395,7 @@ __global__ __launch_bounds__(256) void warpfit_group_mean_kernel(const T_* __res
           val = (T_)__builtin_nan("");
         } else {
           const T_* row = spec + ((size_t)n * pl.Fall + b) * T;
-          if (mode == 2) {
+          if (raw) {
             val = row[j];
           } else {
             const int lo = s_lo[r][jc], hi = lo + 1 < T ? lo + 1 : T - 1;
@@ -488,24 +440,40 @@ static bool wf_shape_ok(int dtype, int N, int F, int T) {
   return (dtype == 0 || dtype == 1) && N >= 1 && F >= 1 && T >= 2 && T <= WF_MAX_T;
 }
 
+static bool wf_knots_ok(int T, int K) { return K >= 2 && K <= WF_MAX_K && T - 1 >= 2 * (K - 1); }
+
 static size_t wf_loss_lds(int T) {
   return ((size_t)WF_FR * (T + 1) + (size_t)WF_FR * T + (size_t)WF_CB * T) * sizeof(double) + (size_t)WF_CB * T * sizeof(int);
 }
 
 extern "C" int ava_warpfit_max_t(void) { return WF_MAX_T; }
+extern "C" int ava_warpfit_max_knots(void) { return WF_MAX_K; }
+
+// ---- apply, mean, candidates, argmin -------------------------------------------------------------------------------------
+
+template <typename Model>
+static int wf_apply(const void* spec, int dtype, int N, int F, int T, const double* params, int K, void* out, ava_stream_t s) {
+  const dim3 grid(N, F < 64 ? F : 64);
+  if (dtype == 0)
+    hipLaunchKernelGGL((warpfit_apply_kernel<float, Model>), grid, dim3(256), 0, to_stream(s), static_cast<const float*>(spec),
+                       params, F, T, K, static_cast<float*>(out));
+  else
+    hipLaunchKernelGGL((warpfit_apply_kernel<double, Model>), grid, dim3(256), 0, to_stream(s),
+                       static_cast<const double*>(spec), params, F, T, K, static_cast<double*>(out));
+  AVA_CHECK_LAUNCH();
+  return AVA_OK;
+}
 
 extern "C" int ava_warpfit_apply(const void* spec, int dtype, int N, int F, int T, const double* params, void* out,
                                  ava_stream_t s) {
   if (spec == nullptr || params == nullptr || out == nullptr || !wf_shape_ok(dtype, N, F, T)) return AVA_EINVAL;
-  const dim3 grid(N, F < 64 ? F : 64);
-  if (dtype == 0)
-    hipLaunchKernelGGL(warpfit_apply_kernel<float>, grid, dim3(256), 0, to_stream(s), static_cast<const float*>(spec), params,
-                       F, T, static_cast<float*>(out));
-  else
-    hipLaunchKernelGGL(warpfit_apply_kernel<double>, grid, dim3(256), 0, to_stream(s), static_cast<const double*>(spec),
-                       params, F, T, static_cast<double*>(out));
-  AVA_CHECK_LAUNCH();
-  return AVA_OK;
+  return wf_apply<WfAffine>(spec, dtype, N, F, T, params, 2, out, s);
+}
+
+extern "C" int ava_warpfit_pl_apply(const void* spec, int dtype, int N, int F, int T, const double* knots, int K, void* out,
+                                    ava_stream_t s) {
+  if (spec == nullptr || knots == nullptr || out == nullptr || !wf_shape_ok(dtype, N, F, T) || !wf_knots_ok(T, K)) return AVA_EINVAL;
+  return wf_apply<WfKnots>(spec, dtype, N, F, T, knots, K, out, s);
 }
 
 extern "C" int ava_warpfit_mean(const void* spec, int dtype, int N, int F, int T, double* target, ava_stream_t s) {
@@ -535,30 +503,16 @@ extern "C" int ava_warpfit_candidates(const double* x, int N, int T, int ks, int
   return AVA_OK;
 }
 
-template <typename T_>
-static int wf_launch_loss(const T_* spec, int N, int F, int T, const double* target, const double* cand, int C,
-                          double shift_lambda, double slope_lambda, double* loss, hipStream_t st) {
-  static bool attr = false;
-  if (!attr) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&warpfit_loss_kernel<T_>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)wf_loss_lds(WF_MAX_T)) != hipSuccess)
-      return AVA_ELAUNCH;
-    attr = true;
-  }
-  const int fixed = slope_lambda > 1.7976931348623157e308;  // +inf: the shift objective
-  hipLaunchKernelGGL(warpfit_loss_kernel<T_>, dim3(N, ceil_div(C, WF_CB)), dim3(256), wf_loss_lds(T), st, spec, target, cand, F,
-                     T, C, shift_lambda, fixed ? 0.0 : slope_lambda, fixed, loss);
+extern "C" int ava_warpfit_pl_candidates(const double* u, int N, int K, int axis, int ks, double h, double* cand,
+                                         ava_stream_t s) {
+  if (u == nullptr || cand == nullptr || N < 1 || K < 2 || K > WF_MAX_K || axis < -1 || axis >= K) return AVA_EINVAL;
+  if (ks < 0 || ks > 31 || !(h >= 0.0)) return AVA_EINVAL;
+  const int64_t total = (int64_t)N * (2 * ks + 1) * K;
+  if (ceil_div64(total, 256) > 2147483647) return AVA_EINVAL;
+  hipLaunchKernelGGL(warpfit_pl_candidates_kernel, dim3((unsigned)ceil_div64(total, 256)), dim3(256), 0, to_stream(s), u, N, K,
+                     axis, ks, h, cand);
   AVA_CHECK_LAUNCH();
   return AVA_OK;
-}
-
-extern "C" int ava_warpfit_loss(const void* spec, int dtype, int N, int F, int T, const double* target, const double* cand,
-                                int C, double shift_lambda, double slope_lambda, double* loss, ava_stream_t s) {
-  if (spec == nullptr || target == nullptr || cand == nullptr || loss == nullptr || !wf_shape_ok(dtype, N, F, T)) return AVA_EINVAL;
-  if (C < 1 || C > WF_MAX_C || shift_lambda != shift_lambda || slope_lambda != slope_lambda) return AVA_EINVAL;
-  if (dtype == 0)
-    return wf_launch_loss(static_cast<const float*>(spec), N, F, T, target, cand, C, shift_lambda, slope_lambda, loss, to_stream(s));
-  return wf_launch_loss(static_cast<const double*>(spec), N, F, T, target, cand, C, shift_lambda, slope_lambda, loss, to_stream(s));
 }
 
 static int wf_launch_argmin(const double* loss, const double* cand, int N, int C, int W, int32_t* best, double* x,
@@ -576,94 +530,56 @@ extern "C" int ava_warpfit_argmin(const double* loss, const double* cand, int N,
   return wf_launch_argmin(loss, cand, N, C, 2, best, x, best_loss, s);
 }
 
-// ---- the piecewise-linear warp (row f14) ------------------------------------------------------------------------------
-
-static bool wf_knots_ok(int T, int K) { return K >= 2 && K <= WF_MAX_K && T - 1 >= 2 * (K - 1); }
-
-extern "C" int ava_warpfit_max_knots(void) { return WF_MAX_K; }
-
-extern "C" int ava_warpfit_pl_apply(const void* spec, int dtype, int N, int F, int T, const double* knots, int K, void* out,
-                                    ava_stream_t s) {
-  if (spec == nullptr || knots == nullptr || out == nullptr || !wf_shape_ok(dtype, N, F, T) || !wf_knots_ok(T, K)) return AVA_EINVAL;
-  const dim3 grid(N, F < 64 ? F : 64);
-  if (dtype == 0)
-    hipLaunchKernelGGL(warpfit_pl_apply_kernel<float>, grid, dim3(256), 0, to_stream(s), static_cast<const float*>(spec), knots,
-                       F, T, K, static_cast<float*>(out));
-  else
-    hipLaunchKernelGGL(warpfit_pl_apply_kernel<double>, grid, dim3(256), 0, to_stream(s), static_cast<const double*>(spec),
-                       knots, F, T, K, static_cast<double*>(out));
-  AVA_CHECK_LAUNCH();
-  return AVA_OK;
-}
-
-extern "C" int ava_warpfit_pl_candidates(const double* u, int N, int K, int axis, int ks, double h, double* cand,
-                                         ava_stream_t s) {
-  if (u == nullptr || cand == nullptr || N < 1 || K < 2 || K > WF_MAX_K || axis < -1 || axis >= K) return AVA_EINVAL;
-  if (ks < 0 || ks > 31 || !(h >= 0.0)) return AVA_EINVAL;
-  const int64_t total = (int64_t)N * (2 * ks + 1) * K;
-  if (ceil_div64(total, 256) > 2147483647) return AVA_EINVAL;
-  hipLaunchKernelGGL(warpfit_pl_candidates_kernel, dim3((unsigned)ceil_div64(total, 256)), dim3(256), 0, to_stream(s), u, N, K,
-                     axis, ks, h, cand);
-  AVA_CHECK_LAUNCH();
-  return AVA_OK;
-}
-
-template <typename T_>
-static int wf_launch_pl_loss(const T_* spec, int N, int F, int T, const double* target, const double* cand, int C, int K,
-                             double shift_lambda, double slope_lambda, double* loss, hipStream_t st) {
-  // dynamic LDS over 64 KB (T > 409) has to be asked for, per device; asked whenever it is needed rather than once per
-  // process, so that neither a second device nor two threads' first calls can miss it
-  if (wf_loss_lds(T) > 65536 &&
-      hipFuncSetAttribute(reinterpret_cast<const void*>(&warpfit_pl_loss_kernel<T_>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                          (int)wf_loss_lds(WF_MAX_T)) != hipSuccess)
-    return AVA_ELAUNCH;
-  const int fixed = slope_lambda > 1.7976931348623157e308;  // +inf: the shift objective
-  hipLaunchKernelGGL(warpfit_pl_loss_kernel<T_>, dim3(N, ceil_div(C, WF_CB)), dim3(256), wf_loss_lds(T), st, spec, target, cand,
-                     F, T, C, K, shift_lambda, fixed ? 0.0 : slope_lambda, fixed, loss);
-  AVA_CHECK_LAUNCH();
-  return AVA_OK;
-}
-
-extern "C" int ava_warpfit_pl_loss(const void* spec, int dtype, int N, int F, int T, const double* target, const double* cand,
-                                   int C, int K, double shift_lambda, double slope_lambda, double* loss, ava_stream_t s) {
-  if (spec == nullptr || target == nullptr || cand == nullptr || loss == nullptr || !wf_shape_ok(dtype, N, F, T)) return AVA_EINVAL;
-  if (!wf_knots_ok(T, K) || C < 1 || C > WF_MAX_C || shift_lambda != shift_lambda || slope_lambda != slope_lambda) return AVA_EINVAL;
-  if (dtype == 0)
-    return wf_launch_pl_loss(static_cast<const float*>(spec), N, F, T, target, cand, C, K, shift_lambda, slope_lambda, loss,
-                             to_stream(s));
-  return wf_launch_pl_loss(static_cast<const double*>(spec), N, F, T, target, cand, C, K, shift_lambda, slope_lambda, loss,
-                           to_stream(s));
-}
-
 extern "C" int ava_warpfit_pl_argmin(const double* loss, const double* cand, int N, int C, int K, int32_t* best, double* u,
                                      double* best_loss, ava_stream_t s) {
   if (K < 2 || K > WF_MAX_K) return AVA_EINVAL;
   return wf_launch_argmin(loss, cand, N, C, K, best, u, best_loss, s);
 }
 
-// ---- the grouped fits (row f17) -----------------------------------------------------------------------------------------
+// ---- the losses ----------------------------------------------------------------------------------------------------------
 
-template <typename T_>
-static int wf_launch_group_loss(const T_* spec, const WfPlan& pl, int V, int T, const double* targets, const double* cand,
-                                int C, int K, const double* shift_lambda, const double* slope_lambda, int fixed_slope,
-                                int raw, double* loss, hipStream_t st) {
-  const void* fn = K == 0 ? reinterpret_cast<const void*>(&warpfit_group_loss_kernel<T_>)
-                          : reinterpret_cast<const void*>(&warpfit_group_pl_loss_kernel<T_>);
-  if (wf_loss_lds(T) > 65536 &&                             // as in wf_launch_pl_loss
-      hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)wf_loss_lds(WF_MAX_T)) != hipSuccess)
+// Every loss launch: `kernel` over (rows, blocks of WF_CB candidates).  Dynamic LDS over 64 KB (T > 409) has to be asked
+// for, per device; asked whenever it is needed rather than once per process, so that neither a second device nor two
+// threads' first calls can miss it.
+template <typename... P, typename... A>
+static int wf_launch_loss(void (*kernel)(P...), int rows, int T, int C, ava_stream_t s, A... args) {
+  if (wf_loss_lds(T) > 65536 &&
+      hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                          (int)wf_loss_lds(WF_MAX_T)) != hipSuccess)
     return AVA_ELAUNCH;
-  const dim3 grid(V, ceil_div(C, WF_CB));
-  if (K == 0)
-    hipLaunchKernelGGL(warpfit_group_loss_kernel<T_>, grid, dim3(256), wf_loss_lds(T), st, spec, pl, targets, cand, T, C,
-                       shift_lambda, slope_lambda, fixed_slope, raw, loss);
-  else
-    hipLaunchKernelGGL(warpfit_group_pl_loss_kernel<T_>, grid, dim3(256), wf_loss_lds(T), st, spec, pl, targets, cand, T, C, K,
-                       shift_lambda, slope_lambda, fixed_slope, raw, loss);
+  hipLaunchKernelGGL(kernel, dim3(rows, ceil_div(C, WF_CB)), dim3(256), wf_loss_lds(T), to_stream(s), args...);
   AVA_CHECK_LAUNCH();
   return AVA_OK;
 }
 
-// K = 0: the shift-and-slope form
+template <typename Model>
+static int wf_loss(const void* spec, int dtype, int N, int F, int T, const double* target, const double* cand, int C, int K,
+                   double shift_lambda, double slope_lambda, double* loss, ava_stream_t s) {
+  if (spec == nullptr || target == nullptr || cand == nullptr || loss == nullptr || !wf_shape_ok(dtype, N, F, T)) return AVA_EINVAL;
+  if (C < 1 || C > WF_MAX_C || shift_lambda != shift_lambda || slope_lambda != slope_lambda) return AVA_EINVAL;
+  const int fixed = slope_lambda > 1.7976931348623157e308;  // +inf: the shift objective
+  if (fixed) slope_lambda = 0.0;
+  if (dtype == 0)
+    return wf_launch_loss(&warpfit_loss_kernel<float, Model>, N, T, C, s, static_cast<const float*>(spec), target, cand, F, T, C,
+                          K, shift_lambda, slope_lambda, fixed, loss);
+  return wf_launch_loss(&warpfit_loss_kernel<double, Model>, N, T, C, s, static_cast<const double*>(spec), target, cand, F, T, C,
+                        K, shift_lambda, slope_lambda, fixed, loss);
+}
+
+extern "C" int ava_warpfit_loss(const void* spec, int dtype, int N, int F, int T, const double* target, const double* cand,
+                                int C, double shift_lambda, double slope_lambda, double* loss, ava_stream_t s) {
+  return wf_loss<WfAffine>(spec, dtype, N, F, T, target, cand, C, 2, shift_lambda, slope_lambda, loss, s);
+}
+
+extern "C" int ava_warpfit_pl_loss(const void* spec, int dtype, int N, int F, int T, const double* target, const double* cand,
+                                   int C, int K, double shift_lambda, double slope_lambda, double* loss, ava_stream_t s) {
+  if (!wf_knots_ok(T, K)) return AVA_EINVAL;
+  return wf_loss<WfKnots>(spec, dtype, N, F, T, target, cand, C, K, shift_lambda, slope_lambda, loss, s);
+}
+
+// ---- the grouped fits (row f17) -----------------------------------------------------------------------------------------
+
+template <typename Model>
 static int wf_group_loss(const void* spec, int dtype, int N, int F, int T, const int32_t* row_src, const int32_t* row_group,
                          const int32_t* bin_off, const int32_t* bins, int V, const double* targets, const double* cand, int C,
                          int K, const double* shift_lambda, const double* slope_lambda, int fixed_slope, int raw, double* loss,
@@ -674,18 +590,18 @@ static int wf_group_loss(const void* spec, int dtype, int N, int F, int T, const
   if (!raw && (cand == nullptr || shift_lambda == nullptr || slope_lambda == nullptr)) return AVA_EINVAL;
   const WfPlan pl{row_src, row_group, nullptr, bin_off, bins, N, F};
   if (dtype == 0)
-    return wf_launch_group_loss(static_cast<const float*>(spec), pl, V, T, targets, cand, C, K, shift_lambda, slope_lambda,
-                                fixed_slope, raw, loss, to_stream(s));
-  return wf_launch_group_loss(static_cast<const double*>(spec), pl, V, T, targets, cand, C, K, shift_lambda, slope_lambda,
-                              fixed_slope, raw, loss, to_stream(s));
+    return wf_launch_loss(&warpfit_group_loss_kernel<float, Model>, V, T, C, s, static_cast<const float*>(spec), pl, targets,
+                          cand, T, C, K, shift_lambda, slope_lambda, fixed_slope, raw, loss);
+  return wf_launch_loss(&warpfit_group_loss_kernel<double, Model>, V, T, C, s, static_cast<const double*>(spec), pl, targets,
+                        cand, T, C, K, shift_lambda, slope_lambda, fixed_slope, raw, loss);
 }
 
 extern "C" int ava_warpfit_group_loss(const void* spec, int dtype, int N, int F, int T, const int32_t* row_src,
                                       const int32_t* row_group, const int32_t* bin_off, const int32_t* bins, int V,
                                       const double* targets, const double* cand, int C, const double* shift_lambda,
                                       const double* slope_lambda, int fixed_slope, int raw, double* loss, ava_stream_t s) {
-  return wf_group_loss(spec, dtype, N, F, T, row_src, row_group, bin_off, bins, V, targets, cand, C, 0, shift_lambda,
-                       slope_lambda, fixed_slope, raw, loss, s);
+  return wf_group_loss<WfAffine>(spec, dtype, N, F, T, row_src, row_group, bin_off, bins, V, targets, cand, C, 2, shift_lambda,
+                                 slope_lambda, fixed_slope, raw, loss, s);
 }
 
 extern "C" int ava_warpfit_group_pl_loss(const void* spec, int dtype, int N, int F, int T, const int32_t* row_src,
@@ -693,27 +609,28 @@ extern "C" int ava_warpfit_group_pl_loss(const void* spec, int dtype, int N, int
                                          const double* targets, const double* cand, int C, int K, const double* shift_lambda,
                                          const double* slope_lambda, int fixed_slope, int raw, double* loss, ava_stream_t s) {
   if (!wf_knots_ok(T, K)) return AVA_EINVAL;
-  return wf_group_loss(spec, dtype, N, F, T, row_src, row_group, bin_off, bins, V, targets, cand, C, K, shift_lambda,
-                       slope_lambda, fixed_slope, raw, loss, s);
+  return wf_group_loss<WfKnots>(spec, dtype, N, F, T, row_src, row_group, bin_off, bins, V, targets, cand, C, K, shift_lambda,
+                                slope_lambda, fixed_slope, raw, loss, s);
 }
 
-// mode as in warpfit_group_mean_kernel; max_bins: the longest bin list of the G groups (sizes the grid only)
+// max_bins: the longest bin list of the G groups (sizes the grid only)
+template <typename Model>
 static int wf_group_mean(const void* spec, int dtype, int N, int F, int T, const int32_t* row_src, const int32_t* group_row_off,
                          const int32_t* bin_off, const int32_t* bins, int G, int max_bins, const double* params, int K,
-                         int mode, double* targets, ava_stream_t s) {
-  if (spec == nullptr || targets == nullptr || !wf_shape_ok(dtype, N, F, T)) return AVA_EINVAL;
+                         int raw, double* targets, ava_stream_t s) {
+  if (spec == nullptr || targets == nullptr || !wf_shape_ok(dtype, N, F, T) || (raw != 0 && raw != 1)) return AVA_EINVAL;
   if (row_src == nullptr || group_row_off == nullptr || bin_off == nullptr || bins == nullptr) return AVA_EINVAL;
-  if (G < 1 || max_bins < 1 || (mode != 2 && params == nullptr)) return AVA_EINVAL;
+  if (G < 1 || max_bins < 1 || (!raw && params == nullptr)) return AVA_EINVAL;
   const WfPlan pl{row_src, nullptr, group_row_off, bin_off, bins, N, F};
   int z = ceil_div(max_bins, 4);
   z = z > 32 ? 32 : z;
   const dim3 grid(G, ceil_div(T, WM_TJ), z);
   if (dtype == 0)
-    hipLaunchKernelGGL(warpfit_group_mean_kernel<float>, grid, dim3(256), 0, to_stream(s), static_cast<const float*>(spec), pl,
-                       params, T, K, mode, targets);
+    hipLaunchKernelGGL((warpfit_group_mean_kernel<float, Model>), grid, dim3(256), 0, to_stream(s),
+                       static_cast<const float*>(spec), pl, params, T, K, raw, targets);
   else
-    hipLaunchKernelGGL(warpfit_group_mean_kernel<double>, grid, dim3(256), 0, to_stream(s), static_cast<const double*>(spec),
-                       pl, params, T, K, mode, targets);
+    hipLaunchKernelGGL((warpfit_group_mean_kernel<double, Model>), grid, dim3(256), 0, to_stream(s),
+                       static_cast<const double*>(spec), pl, params, T, K, raw, targets);
   AVA_CHECK_LAUNCH();
   return AVA_OK;
 }
@@ -721,15 +638,14 @@ static int wf_group_mean(const void* spec, int dtype, int N, int F, int T, const
 extern "C" int ava_warpfit_group_mean(const void* spec, int dtype, int N, int F, int T, const int32_t* row_src,
                                       const int32_t* group_row_off, const int32_t* bin_off, const int32_t* bins, int G,
                                       int max_bins, const double* params, int raw, double* targets, ava_stream_t s) {
-  if (raw != 0 && raw != 1) return AVA_EINVAL;
-  return wf_group_mean(spec, dtype, N, F, T, row_src, group_row_off, bin_off, bins, G, max_bins, params, 2, raw ? 2 : 0,
-                       targets, s);
+  return wf_group_mean<WfAffine>(spec, dtype, N, F, T, row_src, group_row_off, bin_off, bins, G, max_bins, params, 2, raw,
+                                 targets, s);
 }
 
 extern "C" int ava_warpfit_group_pl_mean(const void* spec, int dtype, int N, int F, int T, const int32_t* row_src,
                                          const int32_t* group_row_off, const int32_t* bin_off, const int32_t* bins, int G,
                                          int max_bins, const double* knots, int K, int raw, double* targets, ava_stream_t s) {
-  if ((raw != 0 && raw != 1) || !wf_knots_ok(T, K)) return AVA_EINVAL;
-  return wf_group_mean(spec, dtype, N, F, T, row_src, group_row_off, bin_off, bins, G, max_bins, knots, K, raw ? 2 : 1,
-                       targets, s);
+  if (!wf_knots_ok(T, K)) return AVA_EINVAL;
+  return wf_group_mean<WfKnots>(spec, dtype, N, F, T, row_src, group_row_off, bin_off, bins, G, max_bins, knots, K, raw,
+                                targets, s);
 }

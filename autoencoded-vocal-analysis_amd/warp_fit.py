@@ -108,13 +108,21 @@ def _f64(a, dev, shape):
     return t
 
 
-def _apply(specs, params):
-    """``specs`` [N, F, T] under ``params`` [N, 2] = (shift, slope), device tensors; enqueued, nothing synchronises"""
+def _entry(stem, pl, *args):
+    """Call the entry point ``ava_warpfit_<stem>``, the ``%s`` of ``stem`` standing for ``pl_`` with knots (``pl``) and for
+    nothing with shift and slope; a failure names the entry point that was called.  ``pl`` is always said by the caller,
+    never read off a tensor's last dimension: two knots and (shift, log slope) are both two wide."""
+    name = "ava_warpfit_" + stem % ("pl_" if pl else "")
+    _lib.check(getattr(_lib.load(), name)(*args), name)
+
+
+def _apply(specs, params, pl):
+    """``specs`` [N, F, T] under ``params`` [N, 2] = (shift, slope) or, with ``pl``, under knots [N, K]; device tensors;
+    enqueued, nothing synchronises"""
     N, F, T = specs.shape
     out = torch.empty_like(specs)
-    rc = _lib.load().ava_warpfit_apply(specs.data_ptr(), _DTYPES[specs.dtype], N, F, T, params.data_ptr(), out.data_ptr(),
-                                       _lib.stream())
-    _lib.check(rc, "ava_warpfit_apply")
+    k = (params.shape[1],) if pl else ()
+    _entry("%sapply", pl, specs.data_ptr(), _DTYPES[specs.dtype], N, F, T, params.data_ptr(), *k, out.data_ptr(), _lib.stream())
     return out
 
 
@@ -140,16 +148,6 @@ def _knots_tensor(knots, dev, N, T):
     return t.to(device=dev, dtype=torch.float64).contiguous()
 
 
-def _apply_pl(specs, knots):
-    """``specs`` [N, F, T] under ``knots`` [N, K], device tensors; enqueued, nothing synchronises"""
-    N, F, T = specs.shape
-    out = torch.empty_like(specs)
-    rc = _lib.load().ava_warpfit_pl_apply(specs.data_ptr(), _DTYPES[specs.dtype], N, F, T, knots.data_ptr(), knots.shape[1],
-                                          out.data_ptr(), _lib.stream())
-    _lib.check(rc, "ava_warpfit_pl_apply")
-    return out
-
-
 def apply_warp(specs, warp_params):
     """``apply_warp`` (warping.py:25-50): ``warped[n, f, j] = interp1d(specs[n, f])(shifts[n] + slopes[n] * j)`` with the
     end columns held outside the spectrogram.  ``warp_params`` maps ``'shifts'`` and ``'slopes'`` to ``[n_specs]``
@@ -159,12 +157,46 @@ def apply_warp(specs, warp_params):
     specs, is_numpy = _specs_tensor(specs)
     N = specs.shape[0]
     if 'knots' in warp_params:
-        out = _apply_pl(specs, _knots_tensor(warp_params['knots'], specs.device, N, specs.shape[2]))
+        out = _apply(specs, _knots_tensor(warp_params['knots'], specs.device, N, specs.shape[2]), True)
         return out.cpu().numpy() if is_numpy else out
     params = torch.stack([_f64(warp_params['shifts'], specs.device, (N,)),
                           _f64(warp_params['slopes'], specs.device, (N,))], dim=1).contiguous()
-    out = _apply(specs, params)
+    out = _apply(specs, params, False)
     return out.cpu().numpy() if is_numpy else out
+
+
+class _Problem:
+    """One plain fit problem as the searches see it: ``specs`` [N, F, T] against one ``target`` [F, T] (device tensors),
+    with what a ``GroupPlan`` offers them: the row count ``V``, ``T`` and ``loss``.  Its λ are host floats."""
+
+    def __init__(self, specs, target):
+        self.specs, self.target = specs, target
+        self.V, self.T = specs.shape[0], specs.shape[2]
+
+    def loss(self, pl, cand, shift_λ, slope_λ, fixed, loss):
+        """``ava_warpfit_loss`` of ``cand`` [N, C, 2] or, with ``pl``, ``ava_warpfit_pl_loss`` of ``cand`` [N, C, K] into
+        ``loss`` [N, C]; the entry points read ``fixed`` off ``slope_λ = inf`` themselves"""
+        N, F, T = self.specs.shape
+        k = (cand.shape[2],) if pl else ()
+        _entry("%sloss", pl, self.specs.data_ptr(), _DTYPES[self.specs.dtype], N, F, T, self.target.data_ptr(), cand.data_ptr(),
+               cand.shape[1], *k, shift_λ, slope_λ, loss.data_ptr(), _lib.stream())
+        return loss
+
+
+def _warp_loss(specs, target, candidates, shift_λ, slope_λ, pl):
+    specs, is_numpy = _specs_tensor(specs)
+    N, F, T = specs.shape
+    target = _f64(target, specs.device, (F, T))
+    cand = candidates if torch.is_tensor(candidates) else torch.from_numpy(np.asarray(candidates, dtype=np.float64))
+    if cand.dim() != 3 or cand.shape[0] != N or cand.shape[1] < 1 or (not pl and cand.shape[2] != 2):
+        raise ValueError("expected candidates of shape [n_specs, n_candidates, %s]" % ("n_knots + 2" if pl else "2"))
+    if pl:
+        _check_knots(T, cand.shape[2])
+    cand = cand.to(device=specs.device, dtype=torch.float64).contiguous()
+    shift_λ, slope_λ = _check_lambdas(shift_λ, slope_λ)
+    loss = torch.empty((N, cand.shape[1]), dtype=torch.float64, device=specs.device)
+    _Problem(specs, target).loss(pl, cand, shift_λ, slope_λ, slope_λ == np.inf, loss)
+    return loss.cpu().numpy() if is_numpy else loss
 
 
 def warp_loss(specs, target, candidates, shift_λ, slope_λ):
@@ -173,39 +205,14 @@ def warp_loss(specs, target, candidates, shift_λ, slope_λ):
     ``[N, C, 2]`` = (shift, log_slope).  With ``slope_λ = inf`` the slope is 1 and the slope term is dropped
     (``_get_shift_objective``).  Sums run in a fixed order: two calls give the same bits.  Returns ``[N, C]`` float64
     (numpy for numpy ``specs``)."""
-    specs, is_numpy = _specs_tensor(specs)
-    N, F, T = specs.shape
-    target = _f64(target, specs.device, (F, T))
-    cand = candidates if torch.is_tensor(candidates) else torch.from_numpy(np.asarray(candidates, dtype=np.float64))
-    if cand.dim() != 3 or cand.shape[0] != N or cand.shape[1] < 1 or cand.shape[2] != 2:
-        raise ValueError("expected candidates of shape [n_specs, n_candidates, 2]")
-    cand = cand.to(device=specs.device, dtype=torch.float64).contiguous()
-    shift_λ, slope_λ = _check_lambdas(shift_λ, slope_λ)
-    loss = torch.empty((N, cand.shape[1]), dtype=torch.float64, device=specs.device)
-    rc = _lib.load().ava_warpfit_loss(specs.data_ptr(), _DTYPES[specs.dtype], N, F, T, target.data_ptr(), cand.data_ptr(),
-                                      cand.shape[1], shift_λ, slope_λ, loss.data_ptr(), _lib.stream())
-    _lib.check(rc, "ava_warpfit_loss")
-    return loss.cpu().numpy() if is_numpy else loss
+    return _warp_loss(specs, target, candidates, shift_λ, slope_λ, False)
 
 
 def pl_warp_loss(specs, target, candidates, shift_λ, slope_λ):
     """The piecewise-linear objective of the module docstring for ``candidates`` ``[N, C, K]``, ``K`` knots each:
     ``[N, C]`` float64, ``+inf`` where knots cross.  With ``slope_λ = inf`` every slope is 1 (``p(j) = u_0 + j``), the
     slope term is dropped and crossed knots go unnoticed.  Same sums, in the same order, as ``warp_loss``."""
-    specs, is_numpy = _specs_tensor(specs)
-    N, F, T = specs.shape
-    target = _f64(target, specs.device, (F, T))
-    cand = candidates if torch.is_tensor(candidates) else torch.from_numpy(np.asarray(candidates, dtype=np.float64))
-    if cand.dim() != 3 or cand.shape[0] != N or cand.shape[1] < 1:
-        raise ValueError("expected candidates of shape [n_specs, n_candidates, n_knots + 2]")
-    _check_knots(T, cand.shape[2])
-    cand = cand.to(device=specs.device, dtype=torch.float64).contiguous()
-    shift_λ, slope_λ = _check_lambdas(shift_λ, slope_λ)
-    loss = torch.empty((N, cand.shape[1]), dtype=torch.float64, device=specs.device)
-    rc = _lib.load().ava_warpfit_pl_loss(specs.data_ptr(), _DTYPES[specs.dtype], N, F, T, target.data_ptr(), cand.data_ptr(),
-                                         cand.shape[1], cand.shape[2], shift_λ, slope_λ, loss.data_ptr(), _lib.stream())
-    _lib.check(rc, "ava_warpfit_pl_loss")
-    return loss.cpu().numpy() if is_numpy else loss
+    return _warp_loss(specs, target, candidates, shift_λ, slope_λ, True)
 
 
 def _check_lambdas(shift_λ, slope_λ):
@@ -243,24 +250,20 @@ def search_rounds(T, fixed_slope):
     return ks, kl, rounds
 
 
-def _minimize(specs, target, x, shift_λ, slope_λ, best_loss):
-    """the search of ``minimize_warp`` on device tensors; ``x`` [N, 2] and ``best_loss`` [N] are updated in place"""
-    lib = _lib.load()
-    N, F, T = specs.shape
-    fixed = slope_λ == np.inf
+def _minimize(prob, x, shift_λ, slope_λ, fixed, best_loss):
+    """the search of ``minimize_warp`` over the rows of ``prob``, a ``_Problem`` (λ: floats) or a ``GroupPlan`` (λ: device
+    [G]); ``x`` [V, 2] and ``best_loss`` [V] are updated in place"""
+    V, T = prob.V, prob.T
     ks, kl, rounds = search_rounds(T, fixed)
     C = (2 * ks + 1) * (2 * kl + 1)
-    dev, st = specs.device, _lib.stream()
-    cand = torch.empty((N, C, 2), dtype=torch.float64, device=dev)
-    loss = torch.empty((N, C), dtype=torch.float64, device=dev)
-    best = torch.empty(N, dtype=torch.int32, device=dev)
+    dev, st = x.device, _lib.stream()
+    cand = torch.empty((V, C, 2), dtype=torch.float64, device=dev)
+    loss = torch.empty((V, C), dtype=torch.float64, device=dev)
+    best = torch.empty(V, dtype=torch.int32, device=dev)
     for hs, hl in rounds:
-        _lib.check(lib.ava_warpfit_candidates(x.data_ptr(), N, T, ks, kl, hs, hl, cand.data_ptr(), st),
-                   "ava_warpfit_candidates")
-        _lib.check(lib.ava_warpfit_loss(specs.data_ptr(), _DTYPES[specs.dtype], N, F, T, target.data_ptr(), cand.data_ptr(),
-                                        C, shift_λ, slope_λ, loss.data_ptr(), st), "ava_warpfit_loss")
-        _lib.check(lib.ava_warpfit_argmin(loss.data_ptr(), cand.data_ptr(), N, C, best.data_ptr(), x.data_ptr(),
-                                          best_loss.data_ptr(), st), "ava_warpfit_argmin")
+        _entry("%scandidates", False, x.data_ptr(), V, T, ks, kl, hs, hl, cand.data_ptr(), st)
+        prob.loss(False, cand, shift_λ, slope_λ, fixed, loss)
+        _entry("%sargmin", False, loss.data_ptr(), cand.data_ptr(), V, C, best.data_ptr(), x.data_ptr(), best_loss.data_ptr(), st)
 
 
 def minimize_warp(specs, target, x0, shift_λ, slope_λ):
@@ -276,7 +279,7 @@ def minimize_warp(specs, target, x0, shift_λ, slope_λ):
     x = _f64(x0, specs.device, (N, 2)).clone()
     shift_λ, slope_λ = _check_lambdas(shift_λ, slope_λ)
     best_loss = torch.empty(N, dtype=torch.float64, device=specs.device)
-    _minimize(specs, target, x, shift_λ, slope_λ, best_loss)
+    _minimize(_Problem(specs, target), x, shift_λ, slope_λ, slope_λ == np.inf, best_loss)
     return (x.cpu().numpy(), best_loss.cpu().numpy()) if is_numpy else (x, best_loss)
 
 
@@ -290,28 +293,22 @@ def knot_rounds(T, K):
     return rounds
 
 
-def _minimize_pl(specs, target, u, shift_λ, slope_λ, best_loss):
-    """stage B on device tensors; ``u`` [N, K] and ``best_loss`` [N] are updated in place.  ``slope_λ = inf``: a line
-    search of one shift common to all knots, after which ``u_k = u_0 + t_k``."""
-    lib = _lib.load()
-    N, F, T = specs.shape
-    K = u.shape[1]
-    fixed = slope_λ == np.inf
+def _minimize_pl(prob, u, shift_λ, slope_λ, fixed, best_loss):
+    """stage B over the rows of ``prob`` (as in ``_minimize``); ``u`` [V, K] and ``best_loss`` [V] are updated in place.
+    ``fixed``: a line search of one shift common to all knots, after which ``u_k = u_0 + t_k``."""
+    V, T, K = prob.V, prob.T, u.shape[1]
     ks = LINE_KS if fixed else KNOT_KS
     steps = [(-1, hs) for hs, _ in search_rounds(T, True)[2]] if fixed else \
         [(k, h) for h in knot_rounds(T, K) for k in range(K)]
     C = 2 * ks + 1
-    dev, st = specs.device, _lib.stream()
-    cand = torch.empty((N, C, K), dtype=torch.float64, device=dev)
-    loss = torch.empty((N, C), dtype=torch.float64, device=dev)
-    best = torch.empty(N, dtype=torch.int32, device=dev)
+    dev, st = u.device, _lib.stream()
+    cand = torch.empty((V, C, K), dtype=torch.float64, device=dev)
+    loss = torch.empty((V, C), dtype=torch.float64, device=dev)
+    best = torch.empty(V, dtype=torch.int32, device=dev)
     for axis, h in steps:
-        _lib.check(lib.ava_warpfit_pl_candidates(u.data_ptr(), N, K, axis, ks, h, cand.data_ptr(), st),
-                   "ava_warpfit_pl_candidates")
-        _lib.check(lib.ava_warpfit_pl_loss(specs.data_ptr(), _DTYPES[specs.dtype], N, F, T, target.data_ptr(),
-                                           cand.data_ptr(), C, K, shift_λ, slope_λ, loss.data_ptr(), st), "ava_warpfit_pl_loss")
-        _lib.check(lib.ava_warpfit_pl_argmin(loss.data_ptr(), cand.data_ptr(), N, C, K, best.data_ptr(), u.data_ptr(),
-                                             best_loss.data_ptr(), st), "ava_warpfit_pl_argmin")
+        _entry("%scandidates", True, u.data_ptr(), V, K, axis, ks, h, cand.data_ptr(), st)
+        prob.loss(True, cand, shift_λ, slope_λ, fixed, loss)
+        _entry("%sargmin", True, loss.data_ptr(), cand.data_ptr(), V, C, K, best.data_ptr(), u.data_ptr(), best_loss.data_ptr(), st)
     if fixed:
         u.copy_(u[:, :1] + torch.from_numpy(knot_columns(T, K)).to(dev))
 
@@ -327,7 +324,7 @@ def pl_minimize_warp(specs, target, u0, shift_λ, slope_λ):
     u = _knots_tensor(u0, specs.device, N, T).clone()
     shift_λ, slope_λ = _check_lambdas(shift_λ, slope_λ)
     best_loss = torch.empty(N, dtype=torch.float64, device=specs.device)
-    _minimize_pl(specs, target, u, shift_λ, slope_λ, best_loss)
+    _minimize_pl(_Problem(specs, target), u, shift_λ, slope_λ, slope_λ == np.inf, best_loss)
     return (u.cpu().numpy(), best_loss.cpu().numpy()) if is_numpy else (u, best_loss)
 
 
@@ -353,7 +350,7 @@ def align_specs(specs, shift_λs, slope_λs, verbose=True, *, n_knots=0):
     n_knots = int(n_knots)
     if n_knots != 0:
         _check_knots(T, n_knots + 2)
-    lib, dev = _lib.load(), specs.device
+    dev = specs.device
     total_iterations = min(len(shift_λs), len(slope_λs))
     schedule = [_check_lambdas(shift_λs[i], slope_λs[i]) for i in range(total_iterations)]
     warped = specs.clone()
@@ -362,23 +359,24 @@ def align_specs(specs, shift_λs, slope_λs, verbose=True, *, n_knots=0):
     if n_knots != 0:
         t_k = torch.from_numpy(knot_columns(T, n_knots + 2)).to(dev)
         knots = (params[:, :1] + params[:, 1:] * t_k).contiguous()
-    target = torch.empty((F, T), dtype=torch.float64, device=dev)
+    prob = _Problem(specs, torch.empty((F, T), dtype=torch.float64, device=dev))
     best_loss = torch.empty(N, dtype=torch.float64, device=dev)
     last_losses = torch.zeros(max(total_iterations, 1), dtype=torch.float64, device=dev)
     for warp_iter, (shift_λ, slope_λ) in enumerate(schedule):
-        _lib.check(lib.ava_warpfit_mean(warped.data_ptr(), _DTYPES[warped.dtype], N, F, T, target.data_ptr(),
-                                        _lib.stream()), "ava_warpfit_mean")
-        _minimize(specs, target, x, shift_λ, slope_λ, best_loss)
-        if slope_λ == np.inf:
+        fixed = slope_λ == np.inf
+        _lib.check(_lib.load().ava_warpfit_mean(warped.data_ptr(), _DTYPES[warped.dtype], N, F, T, prob.target.data_ptr(),
+                                                _lib.stream()), "ava_warpfit_mean")
+        _minimize(prob, x, shift_λ, slope_λ, fixed, best_loss)
+        if fixed:
             x[:, 1] = 0.0                                   # slope = 1, log slope = 0 (warping.py:132-133)
         params = torch.stack([x[:, 0], torch.exp(x[:, 1])], dim=1)
         if n_knots == 0:
-            warped = _apply(specs, params)
+            warped = _apply(specs, params, False)
         else:
             knots = (params[:, :1] + params[:, 1:] * t_k).contiguous()     # stage A's line: u_k = shift + slope t_k
-            if slope_λ != np.inf:
-                _minimize_pl(specs, target, knots, shift_λ, slope_λ, best_loss)
-            warped = _apply_pl(specs, knots)
+            if not fixed:
+                _minimize_pl(prob, knots, shift_λ, slope_λ, False, best_loss)
+            warped = _apply(specs, knots, True)
         last_losses[warp_iter] = best_loss[-1]
     if verbose:
         for warp_iter, loss in enumerate(last_losses[:total_iterations].cpu().numpy()):
@@ -475,77 +473,38 @@ class GroupPlan:
     def mean(self, params=None, knots=None, out=None):
         """the grouped template into ``out`` (default: the plan's own targets) under ``params`` [V, 2] = (shift, slope),
         under ``knots`` [V, K], or of the unwarped rows when both are ``None``"""
-        lib, out = _lib.load(), self.targets if out is None else out
+        out = self.targets if out is None else out
         tail = (self.d_row_off.data_ptr(), self.d_bin_off.data_ptr(), self.bins.data_ptr(), self.G, self.max_bins)
         if knots is not None:
-            rc = lib.ava_warpfit_group_pl_mean(*self._head(), *tail, knots.data_ptr(), knots.shape[1], 0, out.data_ptr(),
-                                               _lib.stream())
+            warp = (knots.data_ptr(), knots.shape[1], 0)
         else:
-            rc = lib.ava_warpfit_group_mean(*self._head(), *tail, None if params is None else params.data_ptr(),
-                                            int(params is None), out.data_ptr(), _lib.stream())
-        _lib.check(rc, "ava_warpfit_group_mean")
+            warp = (None if params is None else params.data_ptr(), int(params is None))
+        _entry("group_%smean", knots is not None, *self._head(), *tail, *warp, out.data_ptr(), _lib.stream())
         return out
 
-    def _loss(self, pl, cand, C, K, shift_λ, slope_λ, fixed, loss, targets=None, raw=False):
-        lib = _lib.load()
+    def loss(self, pl, cand, shift_λ, slope_λ, fixed, loss, targets=None, raw=False):
+        """``ava_warpfit_group_loss`` of ``cand`` [V, C, 2] = (shift, log slope) or, with ``pl``,
+        ``ava_warpfit_group_pl_loss`` of ``cand`` [V, C, K] into ``loss`` [V, C] against ``targets`` (default: the plan's
+        own); λ: device [G].  ``raw``: no warp, no candidates, no λ, ``loss`` [V]."""
         targets = self.targets if targets is None else targets
         ptr = lambda t: None if t is None else t.data_ptr()
-        head = self._head() + (self.row_group.data_ptr(), self.d_bin_off.data_ptr(), self.bins.data_ptr(), self.V,
-                               targets.data_ptr(), ptr(cand), C)
-        tail = (ptr(shift_λ), ptr(slope_λ), int(bool(fixed)), int(bool(raw)), loss.data_ptr(), _lib.stream())
-        if pl:
-            _lib.check(lib.ava_warpfit_group_pl_loss(*head, K, *tail), "ava_warpfit_group_pl_loss")
-        else:
-            _lib.check(lib.ava_warpfit_group_loss(*head, *tail), "ava_warpfit_group_loss")
+        k = (cand.shape[2],) if pl else ()
+        _entry("group_%sloss", pl, *self._head(), self.row_group.data_ptr(), self.d_bin_off.data_ptr(), self.bins.data_ptr(),
+               self.V, targets.data_ptr(), ptr(cand), 1 if cand is None else cand.shape[1], *k, ptr(shift_λ), ptr(slope_λ),
+               int(bool(fixed)), int(bool(raw)), loss.data_ptr(), _lib.stream())
         return loss
 
     def ss_loss(self, cand, shift_λ, slope_λ, fixed, loss, targets=None):
-        """``ava_warpfit_group_loss`` of ``cand`` [V, C, 2] = (shift, log slope) into ``loss`` [V, C]; λ: device [G]"""
-        return self._loss(False, cand, cand.shape[1], 0, shift_λ, slope_λ, fixed, loss, targets)
+        """``loss`` of ``cand`` [V, C, 2] = (shift, log slope)"""
+        return self.loss(False, cand, shift_λ, slope_λ, fixed, loss, targets)
 
     def pl_loss(self, cand, shift_λ, slope_λ, fixed, loss, targets=None):
-        """``ava_warpfit_group_pl_loss`` of ``cand`` [V, C, K] into ``loss`` [V, C]"""
-        return self._loss(True, cand, cand.shape[1], cand.shape[2], shift_λ, slope_λ, fixed, loss, targets)
+        """``loss`` of ``cand`` [V, C, K]"""
+        return self.loss(True, cand, shift_λ, slope_λ, fixed, loss, targets)
 
     def raw_loss(self, loss, targets=None):
         """per virtual row the sum of squared differences of the unwarped row from its group's target, into ``loss`` [V]"""
-        return self._loss(False, None, 1, 0, None, None, False, loss, targets, raw=True)
-
-
-def _minimize_grouped(plan, x, shift_λ, slope_λ, fixed, best_loss):
-    """``_minimize`` over the virtual rows of ``plan``: ``x`` [V, 2] and ``best_loss`` [V] are updated in place"""
-    lib = _lib.load()
-    V, T = plan.V, plan.T
-    ks, kl, rounds = search_rounds(T, fixed)
-    C = (2 * ks + 1) * (2 * kl + 1)
-    dev, st = x.device, _lib.stream()
-    cand = torch.empty((V, C, 2), dtype=torch.float64, device=dev)
-    loss = torch.empty((V, C), dtype=torch.float64, device=dev)
-    best = torch.empty(V, dtype=torch.int32, device=dev)
-    for hs, hl in rounds:
-        _lib.check(lib.ava_warpfit_candidates(x.data_ptr(), V, T, ks, kl, hs, hl, cand.data_ptr(), st),
-                   "ava_warpfit_candidates")
-        plan.ss_loss(cand, shift_λ, slope_λ, fixed, loss)
-        _lib.check(lib.ava_warpfit_argmin(loss.data_ptr(), cand.data_ptr(), V, C, best.data_ptr(), x.data_ptr(),
-                                          best_loss.data_ptr(), st), "ava_warpfit_argmin")
-
-
-def _minimize_pl_grouped(plan, u, shift_λ, slope_λ, best_loss):
-    """stage B of ``_minimize_pl`` (never the shift objective: ``align_specs`` skips it then) over the virtual rows"""
-    lib = _lib.load()
-    V, T, K = plan.V, plan.T, u.shape[1]
-    C = 2 * KNOT_KS + 1
-    dev, st = u.device, _lib.stream()
-    cand = torch.empty((V, C, K), dtype=torch.float64, device=dev)
-    loss = torch.empty((V, C), dtype=torch.float64, device=dev)
-    best = torch.empty(V, dtype=torch.int32, device=dev)
-    for h in knot_rounds(T, K):
-        for k in range(K):
-            _lib.check(lib.ava_warpfit_pl_candidates(u.data_ptr(), V, K, k, KNOT_KS, h, cand.data_ptr(), st),
-                       "ava_warpfit_pl_candidates")
-            plan.pl_loss(cand, shift_λ, slope_λ, False, loss)
-            _lib.check(lib.ava_warpfit_pl_argmin(loss.data_ptr(), cand.data_ptr(), V, C, K, best.data_ptr(), u.data_ptr(),
-                                                 best_loss.data_ptr(), st), "ava_warpfit_pl_argmin")
+        return self.loss(False, None, None, None, False, loss, targets, raw=True)
 
 
 def _fit_plan(plan, shift_λs, slope_λs, n_knots):
@@ -567,14 +526,14 @@ def _fit_plan(plan, shift_λs, slope_λs, n_knots):
             plan.mean(params=params)
         else:
             plan.mean(knots=knots)
-        _minimize_grouped(plan, x, d_shift[it], d_slope[it], fixed, best_loss)
+        _minimize(plan, x, d_shift[it], d_slope[it], fixed, best_loss)
         if fixed:
             x[:, 1] = 0.0
         params = torch.stack([x[:, 0], torch.exp(x[:, 1])], dim=1).contiguous()
         if n_knots != 0:
             knots = (params[:, :1] + params[:, 1:] * t_k).contiguous()
             if not fixed:
-                _minimize_pl_grouped(plan, knots, d_shift[it], d_slope[it], best_loss)
+                _minimize_pl(plan, knots, d_shift[it], d_slope[it], False, best_loss)
     return params, knots
 
 

@@ -90,6 +90,24 @@ def test_warp_loss_at_shapes_with_several_row_passes_and_candidate_blocks(shape,
         assert rel <= bound
 
 
+def test_kernel_bits_are_the_recorded_ones():
+    """The loss, apply and grouped-mean entry points against tests/golden/warpfit_bits.npz, recorded on the device before
+    the loss bodies, kernels and launch paths of the two warp forms were folded into one of each: an equality of bit
+    patterns.  The grouped-equals-plain tests compare two outputs of one body and would move together with it."""
+    from conftest import load_golden
+    want, got = load_golden("warpfit_bits.npz"), FC.bits_record()
+    assert sorted(got) == sorted(want)
+    inf = int(np.array([np.inf]).view(np.int64)[0])
+    for key in sorted(want):
+        assert got[key].dtype == want[key].dtype == np.int64 and got[key].shape == want[key].shape, key
+        differ = int((got[key] != want[key]).sum())
+        assert differ == 0, "%s: %d of %d bit patterns differ" % (key, differ, want[key].size)
+        if key.endswith("pl_loss.finite"):                                                # the crossed candidate
+            assert want[key][0, 1] == inf and int((want[key] == inf).sum()) == 1, key
+        elif "loss" in key:
+            assert not (want[key] == inf).any(), key
+
+
 def _lib_and_stream():
     from ava_amd import _lib
     return _lib.load(), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)

@@ -124,6 +124,108 @@ def lam_key(shift_λ, slope_λ):
     return "l%g_%g" % (shift_λ, slope_λ)
 
 
+# ---- the bits of the loss, apply and grouped-mean kernels (tests/golden/warpfit_bits.npz) ---------------------------------
+# main: three row passes 4 + 4 + 1, three candidate blocks (the last holds 3 of 8), columns past one 64-lane stride;
+# grouped: the shape and groups of the grouped-kernel tests; cap: T and K at their caps, the loss kernels' LDS over 64 KB.
+# A group is (rows, bins); every shape has three, so that the per-group λ below serve all of them.
+BITS_SHAPES = {
+    'main': (dict(N=3, F=9, T=200, C=19, K=4), [([1], [4]), ([0, 2], [0, 2, 3, 5, 8]), (None, None)], 7101),
+    'grouped': (None, None, 7201),                           # warpsearch_cases.KERNEL_SHAPE / KERNEL_GROUPS
+    'cap': (dict(N=2, F=2, T=512, C=9, K=16), [([1], [1]), ([0], None), (None, None)], 7301),
+}
+BITS_LAMBDAS = {'finite': (0.01, 0.5), 'inf': (0.01, np.inf)}        # the plain entry points' (shift_λ, slope_λ)
+
+
+def bits_record():
+    """``{key: int64 bit patterns}`` of what the loss, apply and grouped-mean entry points of csrc/warp_fit.hip give,
+    called through the C ABI alone, on hashed inputs: for every shape of ``BITS_SHAPES`` and both dtypes the plain and
+    grouped losses of both forms under a finite ``slope_λ`` and under ``inf``, the grouped ones also with ``raw = 1``;
+    at the cap shape both apply kernels; at the grouped shape the three modes of the grouped mean.  Candidate [0, 1] of
+    every knots batch has knots 1 and 2 swapped: crossed, ``+inf`` unless ``slope_λ = inf``.  A float32 output's 32 bits
+    are widened to int64.  Needs the device."""
+    import ctypes
+
+    import torch
+
+    import warpsearch_cases as SC
+    from ava_amd import _lib
+    from ava_amd.warp_fit import check_groups
+
+    lib, st = _lib.load(), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()                          # noqa: E731
+    new = lambda *shape: torch.full(shape, -123.0, dtype=torch.float64, device="cuda")       # noqa: E731
+    out = {}
+
+    def keep(key, t):
+        bits = t.view(torch.int32 if t.dtype == torch.float32 else torch.int64)
+        out[key] = bits.cpu().numpy().astype(np.int64)
+
+    for name, (shape, groups, salt) in BITS_SHAPES.items():
+        if shape is None:
+            shape, groups = SC.KERNEL_SHAPE, SC.KERNEL_GROUPS
+        N, F, T, C, K = (shape[k] for k in 'NFTCK')
+        groups = check_groups(groups, N, F)
+        rows, bins = [g[0] for g in groups], [g[1] for g in groups]
+        row_off = np.concatenate([[0], np.cumsum([len(r) for r in rows])]).astype(np.int32)
+        bin_off = np.concatenate([[0], np.cumsum([len(b) for b in bins])]).astype(np.int32)
+        G, V, max_bins = len(groups), int(row_off[-1]), max(len(b) for b in bins)
+        row_src, all_bins = dev(np.concatenate(rows)), dev(np.concatenate(bins))
+        row_group = dev(np.repeat(np.arange(G, dtype=np.int32), np.diff(row_off)))
+        d_row_off, d_bin_off = dev(row_off), dev(bin_off)
+        target = dev(syn.u01(F * T, salt + 1))
+        targets = dev(syn.u01(int(bin_off[-1]) * T, salt + 2))
+        knots = SC.hashed_knots(max(N, V), C, T, K, salt + 4)
+        knots[0, 1, [1, 2]] = knots[0, 1, [2, 1]]
+        cands = {'ss': dev(SC.hashed_params(max(N, V), C, T, salt + 3)), 'pl': dev(knots)}
+        x = SC.hashed_params(max(N, V), 1, T, salt + 5)[:, 0, :]
+        params = dev(np.stack([x[:, 0], np.exp(x[:, 1])], axis=1))                            # (shift, slope)
+        one_knots = dev(SC.hashed_knots(max(N, V), 1, T, K, salt + 6)[:, 0, :] * 1.0)
+        for code, dtype in enumerate(('float32', 'float64')):
+            specs = dev(syn.u01(N * F * T, salt).reshape(N, F, T).astype(dtype))
+            head = (specs.data_ptr(), code, N, F, T)
+            plan = head + (row_src.data_ptr(), row_group.data_ptr(), d_bin_off.data_ptr(), all_bins.data_ptr(), V,
+                           targets.data_ptr())
+            for form, cand in cands.items():
+                k = (K,) if form == 'pl' else ()
+                plain = lib.ava_warpfit_pl_loss if form == 'pl' else lib.ava_warpfit_loss
+                grouped = lib.ava_warpfit_group_pl_loss if form == 'pl' else lib.ava_warpfit_group_loss
+                for lam, (shift_λ, slope_λ) in BITS_LAMBDAS.items():
+                    loss = new(N, C)
+                    assert plain(*head, target.data_ptr(), cand.data_ptr(), C, *k, shift_λ, slope_λ, loss.data_ptr(), st) == 0
+                    keep("%s.%s.%s_loss.%s" % (name, dtype, form, lam), loss)
+                    fixed = slope_λ == np.inf
+                    d_shift = dev(np.array(SC.KERNEL_SHIFT_LAMBDAS))
+                    d_slope = dev(np.array([np.inf] * G if fixed else SC.KERNEL_SLOPE_LAMBDAS))
+                    loss = new(V, C)
+                    assert grouped(*plan, cand.data_ptr(), C, *k, d_shift.data_ptr(), d_slope.data_ptr(), int(fixed), 0,
+                                   loss.data_ptr(), st) == 0
+                    keep("%s.%s.group_%s_loss.%s" % (name, dtype, form, lam), loss)
+                loss = new(V)
+                assert grouped(*plan, None, 1, *k, None, None, 0, 1, loss.data_ptr(), st) == 0
+                keep("%s.%s.group_%s_loss.raw" % (name, dtype, form), loss)
+            if name == 'cap':                                # columns over the apply kernels' stride of 256, K = 16
+                warped = torch.full_like(specs, -123.0)
+                assert lib.ava_warpfit_apply(*head, params.data_ptr(), warped.data_ptr(), st) == 0
+                keep("%s.%s.ss_apply" % (name, dtype), warped)
+                warped = torch.full_like(specs, -123.0)
+                assert lib.ava_warpfit_pl_apply(*head, one_knots.data_ptr(), K, warped.data_ptr(), st) == 0
+                keep("%s.%s.pl_apply" % (name, dtype), warped)
+            if name != 'grouped':
+                continue
+            mean = head + (row_src.data_ptr(), d_row_off.data_ptr(), d_bin_off.data_ptr(), all_bins.data_ptr(), G, max_bins)
+            for mode in ('ss', 'pl', 'raw'):
+                tgt = torch.full_like(targets, -123.0)
+                if mode == 'pl':
+                    rc = lib.ava_warpfit_group_pl_mean(*mean, one_knots.data_ptr(), K, 0, tgt.data_ptr(), st)
+                else:
+                    rc = lib.ava_warpfit_group_mean(*mean, params.data_ptr() if mode == 'ss' else None, int(mode == 'raw'),
+                                                    tgt.data_ptr(), st)
+                assert rc == 0
+                keep("%s.%s.group_mean.%s" % (name, dtype, mode), tgt)
+    torch.cuda.synchronize()
+    return out
+
+
 def load():
     """the golden as a dict, JSON entries decoded"""
     from conftest import load_golden

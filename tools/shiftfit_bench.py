@@ -100,7 +100,7 @@ def one_shape(K, F, T, reps, rounds):
             "loss_hist_last": model.loss_hist[-1], "shifts_equal_planted_up_to_one_offset": bool(len(set(offsets.tolist())) == 1),
             "loss_kernel": "shiftfit_loss_kernel", "loss_kernel_ms": float(np.median(new_ms)), "loss_kernel_ms_rounds": new_ms,
             "loss_kernel_terms_per_s": terms / (float(np.median(new_ms)) * 1e-3),
-            "baseline_kernel": "warpfit_loss_kernel", "baseline_ms": float(np.median(base_ms)), "baseline_ms_rounds": base_ms,
+            "baseline_kernel": "warpfit_loss_kernel<float, WfAffine>", "baseline_ms": float(np.median(base_ms)), "baseline_ms_rounds": base_ms,
             "baseline_spread_ms": max(base_ms) - min(base_ms), "speedup": float(np.median(base_ms) / np.median(new_ms)),
             "faster_beyond_spread": bool(max(new_ms) < min(base_ms)), "max_rel_diff": rel}
 

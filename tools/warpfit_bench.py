@@ -107,7 +107,7 @@ def device(specs, reps, n_knots=0):
     launches = sum(len(wf.search_rounds(T, lam == np.inf)[2]) for lam in SLOPE_LAMBDAS)
     knot_launches = 3 * (n_knots + 2) * len(wf.knot_rounds(T, n_knots + 2)) * sum(lam != np.inf for lam in SLOPE_LAMBDAS) \
         if n_knots else 0
-    out = {"n_knots": n_knots, "knot_search_launches_per_fit": knot_launches, "loss_kernel": "warpfit_loss_kernel"}
+    out = {"n_knots": n_knots, "knot_search_launches_per_fit": knot_launches, "loss_kernel": "warpfit_loss_kernel<float, WfAffine>"}
     if n_knots:
         # the knot search's loss kernel alone: one knot of every motif moved, 2 KNOT_KS + 1 candidates of K knots
         K, Cp = n_knots + 2, 2 * wf.KNOT_KS + 1
@@ -123,7 +123,7 @@ def device(specs, reps, n_knots=0):
 
         pmed = median_ms(run_pl)
         pbytes = N * ((Cp + 7) // 8) * F * T * (specs.dtype.itemsize + 8)
-        out.update({"pl_loss_kernel": "warpfit_pl_loss_kernel", "pl_loss_kernel_ms": pmed, "pl_loss_kernel_candidates": Cp,
+        out.update({"pl_loss_kernel": "warpfit_loss_kernel<float, WfKnots>", "pl_loss_kernel_ms": pmed, "pl_loss_kernel_candidates": Cp,
                     "pl_loss_kernel_bytes": pbytes, "pl_loss_kernel_TB_per_s": pbytes / (pmed * 1e-3) / 1e12,
                     "pl_loss_kernel_interp_per_s": N * Cp * F * T / (pmed * 1e-3), "pl_loss_launches_per_fit": knot_launches // 3})
     out.update({"align_specs_wall_s": wall, "spread_before": spread(specs), "spread_after": spread(warped.cpu().numpy()),
