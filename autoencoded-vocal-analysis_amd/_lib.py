@@ -189,6 +189,16 @@ SIGNATURES = {
     "ava_sil_cluster_sums_pre": (_i, [_p, _i, _i, _i, _p, _p, _p, _p]),
     "ava_sil_finish": (_i, [_p, _i, _i, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
     "ava_sil_centroid_stats": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _p, _p, _sz, _p]),
+    "ava_db_max_eps": (_i, []),
+    "ava_db_workspace_bytes": (_sz, [_i, _i, _i]),
+    "ava_db_counts": (_i, [_p, _i, _i, _i, _p, _i, _p, _p]),
+    "ava_db_counts_pre": (_i, [_p, _i, _i, _p, _i, _p, _p]),
+    "ava_db_union": (_i, [_p, _i, _i, _i, _p, _i, _i, _p, _p, _sz, _p]),
+    "ava_db_union_pre": (_i, [_p, _i, _i, _p, _i, _i, _p, _p, _sz, _p]),
+    "ava_db_assign": (_i, [_p, _i, _i, _i, _p, _i, _i, _p, _p, _p, _p, _p, _sz, _p]),
+    "ava_db_assign_pre": (_i, [_p, _i, _i, _p, _i, _i, _p, _p, _p, _p, _p, _sz, _p]),
+    "ava_db_labels": (_i, [_p, _i, _i, _i, _p, _i, _i, _p, _p, _p, _p, _p, _sz, _p]),
+    "ava_db_labels_pre": (_i, [_p, _i, _i, _p, _i, _i, _p, _p, _p, _p, _p, _sz, _p]),
 }
 
 _lib = None

@@ -875,6 +875,49 @@ int ava_sil_finish(const double* sums, int n, int k, const int64_t* order, const
 int ava_sil_centroid_stats(const void* x, int dtype, int n, int d, int k, const int64_t* labels, const double* means,
                            double* sum_dist, double* sum_sq, void* ws, size_t ws_bytes, ava_stream_t s);
 
+/* ---- DBSCAN (row f22; sklearn 1.7 cluster/_dbscan.py and _dbscan_inner.pyx; csrc/dbscan.hip) -------------------------
+ * x / dtype: [n][d] row-major on the device, 0 = float32, 1 = float64, 1 <= d <= 65536, 1 <= n <= 2^21.  The _pre forms
+ * take dist [n][n] (dtype as x), a SYMMETRIC matrix of distances, in its place.  eps [n_eps]: HOST array of the radii,
+ * each positive and finite, 1 <= n_eps <= ava_db_max_eps() = 8; a pass forms every pair's distance once and compares it
+ * n_eps times, and all per-radius arrays are laid out [n_eps][n].  A pair is within radius e when d2 <= eps[e] * eps[e]
+ * (the product rounded once in fp64, d2 the direct-difference sum of ava_pair_sqdist, no square root), or when
+ * (double)dist[i][j] <= eps[e], i < j.  Only integer atomics whose outcome does not depend on their order are used: the
+ * same inputs give the same output on every run.  ws: ava_db_workspace_bytes(n, d, n_eps) bytes (0 for an unsupported
+ * shape).
+ *
+ * ava_db_counts: counts [n_eps][n] int (device) = the number of rows within the radius of each row, itself included.
+ * ava_db_union: row i is a core row of radius e when counts[e][i] >= min_samples (>= 1).  The connected components of
+ *   the core rows under "within the radius" by a lock-free union-find that hooks the larger root under the smaller;
+ *   leaves in ws every core row's root = the smallest row of its component.
+ * ava_db_assign: after ava_db_union on the same ws and arguments: core [n_eps][n] bytes (1 = core row), labels
+ *   [n_eps][n] int64 and n_clusters [n_eps] int (all device).  The components are numbered 0, 1, .. in ascending order
+ *   of their smallest row; a non-core row with core rows within the radius takes the smallest cluster number among
+ *   them; every other row is -1.
+ * ava_db_labels: ava_db_union, then ava_db_assign.
+ *
+ * All return AVA_EINVAL before any HIP call for null pointers, an unknown dtype, an unsupported shape, a bad radius or
+ * min_samples < 1, AVA_EWORKSPACE for a workspace that is too small. */
+int ava_db_max_eps(void);
+size_t ava_db_workspace_bytes(int n, int d, int n_eps);
+int ava_db_counts(const void* x, int dtype, int n, int d, const double* eps, int n_eps, int* counts, ava_stream_t s);
+int ava_db_counts_pre(const void* dist, int dtype, int n, const double* eps, int n_eps, int* counts, ava_stream_t s);
+int ava_db_union(const void* x, int dtype, int n, int d, const double* eps, int n_eps, int min_samples,
+                 const int* counts, void* ws, size_t ws_bytes, ava_stream_t s);
+int ava_db_union_pre(const void* dist, int dtype, int n, const double* eps, int n_eps, int min_samples,
+                     const int* counts, void* ws, size_t ws_bytes, ava_stream_t s);
+int ava_db_assign(const void* x, int dtype, int n, int d, const double* eps, int n_eps, int min_samples,
+                  const int* counts, unsigned char* core, int64_t* labels, int* n_clusters, void* ws, size_t ws_bytes,
+                  ava_stream_t s);
+int ava_db_assign_pre(const void* dist, int dtype, int n, const double* eps, int n_eps, int min_samples,
+                      const int* counts, unsigned char* core, int64_t* labels, int* n_clusters, void* ws,
+                      size_t ws_bytes, ava_stream_t s);
+int ava_db_labels(const void* x, int dtype, int n, int d, const double* eps, int n_eps, int min_samples,
+                  const int* counts, unsigned char* core, int64_t* labels, int* n_clusters, void* ws, size_t ws_bytes,
+                  ava_stream_t s);
+int ava_db_labels_pre(const void* dist, int dtype, int n, const double* eps, int n_eps, int min_samples,
+                      const int* counts, unsigned char* core, int64_t* labels, int* n_clusters, void* ws,
+                      size_t ws_bytes, ava_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif
