@@ -215,13 +215,16 @@ def fit(X, params, cov_type, tol=1e-3, reg_covar=1e-6, max_iter=100, check_margi
                 n_iter=n_iter, lower_bound=lower_bound, lower_bounds=np.array(bounds))
 
 
-def predict(X, fitted, cov_type, margin=1e-6):
-    """labels of the fitted model; asserts a posterior margin between the two best components"""
+def predict(X, fitted, cov_type, margin=1e-6, near_ties=0.0):
+    """labels of the fitted model; asserts a posterior margin between the two best components.  ``near_ties`` > 0: at
+    most that share of the rows may be within the margin, and the mask of the other rows is returned as well."""
     _, log_resp, _ = e_step(X, fitted["weights"], fitted["means"], fitted["precisions_cholesky"], cov_type)
+    clear = np.ones(len(log_resp), dtype=bool)
     if log_resp.shape[1] > 1:
         two = -np.partition(-log_resp, 1, axis=1)[:, :2]
-        assert np.all(two[:, 0] - two[:, 1] > margin), "a predict case is near a tie"
-    return log_resp.argmax(axis=1)
+        clear = two[:, 0] - two[:, 1] > margin
+        assert np.mean(~clear) <= near_ties, "a predict case is near a tie"
+    return (log_resp.argmax(axis=1), clear) if near_ties > 0.0 else log_resp.argmax(axis=1)
 
 
 def n_parameters(k, d, cov_type):
@@ -289,6 +292,83 @@ def threshold_case(n):
     return _frozen(X, resp / resp.sum(axis=1, keepdims=True))
 
 
+# name -> (N, d, K, dtype) at the library's limits K <= 64, d <= 128: the fourth pass of the 'diag' E-step's component
+# loop (K = 25); K d below, at and above one 256-output slice of the chunk-sum kernel with K = 64; eight feature blocks of
+# which three are empty (d = 65) under 33 components; one below both limits with three chunks and a ragged last slice;
+# the corner itself (32 slices, 3 x 64 covariance partials of 128 x 128) as float32 and as float64 rows
+LIMIT_CASES = {
+    "k25_d3": (600, 3, 25, np.float64),
+    "k64_d1": (300, 1, 64, np.float32),
+    "k64_d4": (2049, 4, 64, np.float32),
+    "k33_d65": (2049, 65, 33, np.float64),
+    "k63_d127": (4100, 127, 63, np.float32),
+    "k64_d128": (4100, 128, 64, np.float32),
+    "k64_d128_f64": (4100, 128, 64, np.float64),
+}
+# name -> (salt, spread of the blob centres): small spreads, so that the components overlap and the E-step is no one-hot
+# exercise (tests/test_cpu_gmm.py holds the share of soft rows and the conditioning)
+LIMIT_ROWS = {
+    "k25_d3": (10100, 0.25),
+    "k64_d1": (10110, 0.25),
+    "k64_d4": (10120, 0.25),
+    "k33_d65": (10130, 0.2),
+    "k63_d127": (10140, 0.2),
+    "k64_d128": (10150, 0.2),
+    "k64_d128_f64": (10150, 0.2),
+}
+LIMIT_GOLDEN = ("k63_d127", "k64_d128")        # the device against sklearn's values (the CPU test takes every case)
+LIMIT_QUANTITIES = ("m_weights", "m_means_k", "m_means_j", "m_var_k", "m_var_j", "m_log_det")
+
+
+def limit_key(name, cov_type):
+    """the key of a limit case in tests/golden/gmm.npz: the float64 copy of the corner shares the float32 one's"""
+    return "limit_%s_%s_" % (name[:-4] if name.endswith("_f64") else name, cov_type)
+
+
+def limit_reduced(weights, means, cov, pchol, cov_type):
+    """what tests/golden/gmm.npz keeps of an M-step at the limits, where the covariances alone are 8 MB: the weights,
+    log det P_k, and the sums over the features and over the components of the means and of the variances (the
+    covariances' diagonals), in the order of LIMIT_QUANTITIES.  One wrong entry (k, j) moves the sums k and j."""
+    var = np.diagonal(cov, axis1=1, axis2=2) if cov_type == "full" else cov
+    return (weights, means.sum(axis=1), means.sum(axis=0), var.sum(axis=1), var.sum(axis=0), log_det(pchol, cov_type))
+
+
+@functools.lru_cache(maxsize=None)
+def limit_resp(name):
+    """the M-step input of a limit case: normalised hash noise [N, K], every component owning a share of every row (at
+    fitted responsibilities a component of the corner would own fewer rows than it has features)"""
+    n, _, k, _ = LIMIT_CASES[name]
+    resp = syn.u01(n * k, LIMIT_ROWS[name][0] + 4).reshape(n, k) + 1e-3
+    return _frozen(resp / resp.sum(axis=1, keepdims=True))[0]
+
+
+@functools.lru_cache(maxsize=None)
+def limit_case(name, cov_type):
+    """(X, weights, means, covariances, precisions_cholesky, the E-step there) with explicit parameters: blob-wise means,
+    hash weights in [0.5, 1.5) / sum and covariances I + A A^T / 8 (A: d x 4 normals; 'diag': 1 + mean(A^2) / 2).
+    Parameters fitted at these sizes overfit their own rows and leave a one-hot E-step; these do not."""
+    n, d, k, dtype = LIMIT_CASES[name]
+    salt, spread = LIMIT_ROWS[name]
+    X = blobs(n, d, k, salt, dtype, spread=spread)
+    X64 = X.astype(np.float64)
+    means = np.stack([X64[j::k].mean(axis=0) for j in range(k)])
+    weights = syn.u01(k, salt + 2) + 0.5
+    weights = weights / weights.sum()
+    A = syn.gauss(k * d * 4, salt + 3).reshape(k, d, 4)
+    if cov_type == "full":
+        cov = np.eye(d) + 0.5 * (A @ np.swapaxes(A, 1, 2)) / 4.0
+    else:
+        cov = 1.0 + 0.5 * (A * A).mean(axis=2)
+    pchol = precision_cholesky(cov, cov_type)
+    est = e_step(X, weights, means, pchol, cov_type)
+    return _frozen(X, weights, means, cov, pchol, *est)
+
+
+def limit_m_case(name, cov_type):
+    """the limit case with the M-step's input (``limit_resp``) in the place of the E-step's responsibilities"""
+    return limit_case(name, cov_type)[:7] + (limit_resp(name),)
+
+
 SPECIAL_ROWS = {"duplicates": duplicates, "offset": offset_rows}
 
 
@@ -302,21 +382,29 @@ def special_case(name, cov_type):
     return _frozen(X, *params, *est)
 
 
+# the fit at the limit of 64 components: 60 rows per blob in two chunks, K d = 320 outputs of the chunk sums (two slices,
+# the second ragged).  Rows and salt are chosen on the CPU: the 64 seeds leave 20 blobs without one and put up to four
+# into one blob; with these the k-means start ends after 17 assignments and its smallest cluster still has 15 rows for a
+# 5 x 5 covariance (tests/test_cpu_gmm.py holds cond < 1e3 for the fitted covariances)
+K64_ROWS, K64_SALT = 3840, 10250
+
 # whole fits: name -> (rows, K)
 FIT_ROWS = {
     "blobs300": lambda: (blobs(300, 5, 3, 9900), 3),
     "chunks2100": lambda: (blobs(2100, 17, 4, 9910), 4),
     "offset300": lambda: (offset_rows(), 3),
+    "k64_d5": lambda: (blobs(K64_ROWS, 5, 64, K64_SALT), 64),
 }
 FIT_RUNS = (("tol0_1", 0.0, 1), ("tol0_20", 0.0, 20), ("tol0_100", 0.0, 100), ("tol1e-3", 1e-3, 100))
 FIT_INITS = ("explicit", "random_from_data", "kmeans")
 FIT_QUANTITIES = ("weights", "means", "covariances", "precisions_cholesky", "lower_bound")
 # (rows, covariance type, init, run): every init and run on the small case; the first step after a 'random_from_data'
 # start on rows far from the origin (variances = reg_covar: sklearn's 'diag' expansion is at its worst there); several
-# chunks from an explicit and from the k-means start
+# chunks from an explicit and from the k-means start; the same at the limit of 64 components (two chunks)
 FIT_CASES = [("blobs300", c, i, r[0]) for c in COV_TYPES for i in FIT_INITS for r in FIT_RUNS] + \
             [("offset300", c, "random_from_data", r) for c in COV_TYPES for r in ("tol0_1", "tol1e-3")] + \
-            [("chunks2100", c, i, r) for c in COV_TYPES for i in ("explicit", "kmeans") for r in ("tol0_20", "tol1e-3")]
+            [("chunks2100", c, i, r) for c in COV_TYPES for i in ("explicit", "kmeans") for r in ("tol0_20", "tol1e-3")] + \
+            [("k64_d5", c, i, r) for c in COV_TYPES for i in ("explicit", "kmeans") for r in ("tol0_20", "tol1e-3")]
 
 
 def fit_id(case):
@@ -324,10 +412,10 @@ def fit_id(case):
 
 
 def explicit_init(X, k, cov_type):
-    """the explicit ``*_init`` arrays of a fit case: blob-wise means of the first rows, unit precisions"""
+    """the explicit ``*_init`` arrays of a fit case: blob-wise means of the first max(60, 4 K) rows, unit precisions"""
     X = np.asarray(X, dtype=np.float64)
     d = X.shape[1]
-    means = np.stack([X[j:60:k].mean(axis=0) for j in range(k)])
+    means = np.stack([X[j:max(60, 4 * k):k].mean(axis=0) for j in range(k)])
     weights = np.full(k, 1.0 / k)
     precisions = np.ones((k, d, d)) * np.eye(d) if cov_type == "full" else np.ones((k, d))
     return weights, means, precisions

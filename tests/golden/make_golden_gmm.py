@@ -8,7 +8,12 @@ as ``weights_init`` / ``means_init`` / ``precisions_init``).  sklearn always get
 
 Beside every quantity ``q`` the file stores ``floor_q``: the larger of |sklearn - restatement| and |sklearn - sklearn on
 rows perturbed by 1e-15 relative|, relative to max |sklearn|.  That is the reference-side noise the tests scale their
-bounds with."""
+bounds with.
+
+Per limit case (``GC.LIMIT_CASES``; the covariances of 64 components in 128 dimensions are 8 MB, so neither parameters
+nor covariances are stored): sklearn's ``log_prob_norm`` at the case's explicit parameters and ``GC.limit_reduced`` of
+sklearn's ``_m_step`` at ``GC.limit_resp``, each with its floor.  The float64 copy of the corner shares the float32
+copy's entries."""
 import os
 import sys
 import warnings
@@ -103,6 +108,28 @@ def main():
                 out[key + "floor_" + q] = np.float64(max(rel(a, got), rel(a, b)))
                 floors.append(out[key + "floor_" + q])
             print("%-14s %-4s floors: %s" % (name, cov_type, " ".join("%.1e" % f for f in floors)))
+    before = sum(np.asarray(v).nbytes for v in out.values())
+    for name in GC.LIMIT_CASES:
+        for cov_type in GC.COV_TYPES:
+            key = GC.limit_key(name, cov_type)
+            if key + "lpn" in out:
+                continue
+            X, weights, means, cov, pchol, lpn, _, _ = GC.limit_case(name, cov_type)
+            sk = sk_e_step(X, weights, means, pchol, cov_type)[0]
+            sp = sk_e_step(perturbed(X, 1), weights, means, pchol, cov_type)[0]
+            out[key + "lpn"] = sk
+            out[key + "floor_lpn"] = np.float64(max(rel(sk, lpn), rel(sk, sp)))
+            floors = [out[key + "floor_lpn"]]
+            resp = GC.limit_resp(name)
+            skm = GC.limit_reduced(*sk_m_step(X, resp, cov_type), cov_type)
+            spm = GC.limit_reduced(*sk_m_step(perturbed(X, 2), resp, cov_type), cov_type)
+            mine = GC.limit_reduced(*GC.m_step(X, resp, 1e-6, cov_type), cov_type)
+            for q, got, a, b in zip(GC.LIMIT_QUANTITIES, mine, skm, spm):
+                out[key + q] = a
+                out[key + "floor_" + q] = np.float64(max(rel(a, got), rel(a, b)))
+                floors.append(out[key + "floor_" + q])
+            print("%-14s %-4s floors: %s" % (name, cov_type, " ".join("%.1e" % f for f in floors)))
+    print("limit cases: %d bytes of arrays" % (sum(np.asarray(v).nbytes for v in out.values()) - before))
     for case in GC.FIT_CASES:
         name, cov_type, init, run = case
         tol, max_iter = {r[0]: r[1:] for r in GC.FIT_RUNS}[run]

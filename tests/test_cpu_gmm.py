@@ -77,6 +77,21 @@ def test_restatement_fits_and_stopping_rule(golden, case):
     assert len(fitted["lower_bounds"]) == fitted["n_iter"] and fitted["lower_bounds"][-1] == fitted["lower_bound"]
 
 
+@pytest.mark.parametrize("cov_type", GC.COV_TYPES)
+def test_fits_at_64_components_are_well_conditioned_and_decided(cov_type):
+    """the fitted covariances of the 64-component fits keep cond < 1e3 like the step cases, and the model the statistics
+    test predicts with leaves at most 1 % of the rows within the 1e-6 posterior margin"""
+    for case in GC.FIT_CASES:
+        if case[0] == "k64_d5" and case[1] == cov_type:
+            cond = worst_cond(GC.fit_case(*case)["covariances"], cov_type)
+            print("%s: cond %.1f" % (GC.fit_id(case), cond))
+            assert cond < 1e3, case
+    X = GC.fit_start("k64_d5", cov_type, "kmeans")[0]
+    labels, clear = GC.predict(X, GC.fit_case("k64_d5", cov_type, "kmeans", "tol1e-3"), cov_type, near_ties=0.01)
+    print("rows within the margin: %d of %d" % ((~clear).sum(), len(clear)))
+    assert len(set(labels)) == 64
+
+
 def test_empty_component():
     """a component that owns no sample: nk = 10 eps, mean 0, covariance reg_covar I, nothing is NaN"""
     for cov_type in GC.COV_TYPES:
@@ -89,12 +104,70 @@ def test_empty_component():
         assert all(np.isfinite(a).all() for a in (weights, means, cov, pchol))
 
 
+def worst_cond(cov, cov_type):
+    return max(np.linalg.cond(c) for c in cov) if cov_type == "full" else (cov.max(axis=1) / cov.min(axis=1)).max()
+
+
 def test_step_cases_are_well_conditioned():
     """the GPU tests hold precisions_cholesky within 1e-12 of its largest entry; two factorisations of the same matrix
-    differ by a small multiple of cond(C) eps, so the cases keep cond(C) below 1e3 (1e3 eps = 2.2e-13)"""
+    differ by a small multiple of cond(C) eps, so the cases keep cond(C) below 1e3 (1e3 eps = 2.2e-13).  At the limits
+    that covers the explicit covariances of the E-step and the ones the M-step returns, 'diag' as max / min."""
     for name in GC.STEP_CASES:
         cov = GC.step_case(name, "full")[3]
         assert max(np.linalg.cond(c) for c in cov) < 1e3, name
+    for name in GC.LIMIT_CASES:
+        for cov_type in GC.COV_TYPES:
+            X, _, _, cov, _, _, _, _ = GC.limit_case(name, cov_type)
+            given = worst_cond(cov, cov_type)
+            returned = worst_cond(GC.m_step(X, GC.limit_resp(name), 1e-6, cov_type)[2], cov_type)
+            print("%s %s: cond %.1f (E-step), %.1f (M-step)" % (name, cov_type, given, returned))
+            assert given < 1e3 and returned < 1e3, (name, cov_type)
+
+
+@pytest.mark.parametrize("cov_type", GC.COV_TYPES)
+@pytest.mark.parametrize("name", sorted(GC.LIMIT_CASES))
+def test_limit_cases_are_soft(name, cov_type):
+    """fitted parameters at 64 components in 128 dimensions leave a one-hot E-step; the explicit ones of the limit
+    cases must not: in at least half the rows the second-largest responsibility is above 1e-3, and the M-step's input
+    gives every component a share of every row"""
+    resp = GC.limit_case(name, cov_type)[7]
+    share = float((np.partition(resp, -2, axis=1)[:, -2] > 1e-3).mean())
+    print("%s %s: second-largest responsibility above 1e-3 in %.3f of the rows" % (name, cov_type, share))
+    assert share >= 0.5
+    given = GC.limit_resp(name)
+    assert given.shape == resp.shape and given.min() > 0.0
+    np.testing.assert_allclose(given.sum(axis=1), 1.0, rtol=0, atol=1e-14)
+
+
+@pytest.mark.parametrize("cov_type", GC.COV_TYPES)
+@pytest.mark.parametrize("name", sorted(GC.LIMIT_CASES))
+def test_restatement_steps_at_limits(golden, name, cov_type):
+    """the restatement against sklearn at up to 64 components in 128 dimensions, through the reduced quantities of
+    ``GC.limit_reduced`` (the covariances themselves are 8 MB at the corner)"""
+    X, _, _, _, _, lpn, _, resp = GC.limit_case(name, cov_type)
+    key = GC.limit_key(name, cov_type)
+    close(lpn, golden[key + "lpn"], golden[key + "floor_lpn"], "log_prob_norm")
+    # log_prob_norm is near -d: its rounding, eps |lpn| / 2 and as much again for the logarithm, scales the row's sum
+    np.testing.assert_allclose(resp.sum(axis=1), 1.0, rtol=0, atol=np.finfo(np.float64).eps * max(1.0, np.abs(lpn).max()))
+    got = GC.m_step(X, GC.limit_resp(name), 1e-6, cov_type)
+    for q, g in zip(GC.LIMIT_QUANTITIES, GC.limit_reduced(*got, cov_type)):
+        close(g, golden[key + q], golden[key + "floor_" + q], q)
+    if cov_type == "full":
+        np.testing.assert_array_equal(got[2], np.swapaxes(got[2], 1, 2))
+        np.testing.assert_array_equal(np.tril(got[3], -1), 0.0)
+
+
+def test_limit_reduced_sees_one_wrong_entry():
+    """the reduced quantities move when a single mean or variance does"""
+    X = GC.limit_case("k25_d3", "diag")[0]
+    weights, means, cov, pchol = GC.m_step(X, GC.limit_resp("k25_d3"), 1e-6, "diag")
+    want = GC.limit_reduced(weights, means, cov, pchol, "diag")
+    for which, slots in ((1, (1, 2)), (2, (3, 4))):
+        arrays = [weights, means.copy(), cov.copy(), pchol]
+        arrays[which][7, 2] *= 1.0 + 1e-9
+        got = GC.limit_reduced(*arrays, "diag")
+        for i, (g, w) in enumerate(zip(got, want)):
+            assert (np.abs(g - w).max() > 1e-11 * np.abs(w).max()) == (i in slots), (which, i)
 
 
 def test_kmeans_restatement():
@@ -107,6 +180,10 @@ def test_kmeans_restatement():
     X, k = GC.FIT_ROWS["chunks2100"]()
     labels, rounds = GC.kmeans(X, GC.seeds(len(X), k))
     assert rounds < GC.KMEANS_MAX_ITER and len(set(labels)) == k
+    # 64 centres: some blobs hold several seeds and some none, so clusters split and merge, but none runs empty or small
+    X, k = GC.FIT_ROWS["k64_d5"]()
+    labels, rounds = GC.kmeans(X, GC.seeds(len(X), k))
+    assert k == 64 and 2 <= rounds < GC.KMEANS_MAX_ITER and np.bincount(labels, minlength=k).min() >= 15
     # an empty cluster keeps its centre: two seeds on the same duplicated row
     X, rows = GC.empty_cluster_rows()
     labels, rounds = GC.kmeans(X, rows, check_margin=False)

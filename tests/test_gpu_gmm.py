@@ -1,7 +1,8 @@
 """The kernels of csrc/mixture.hip and ava_amd.mixture.GaussianMixture on the MI355X: the E-step and the M-step against
 the numpy restatement of tests/gmm_cases.py at chunk, stage and block edges, whole fits against the restatement and
-against scikit-learn's own values (tests/golden/gmm.npz), the run shapes that must not change a bit, the k-means start,
-the statistics and the error paths.  tests/test_cpu_gmm.py shows that the restatement is sklearn's arithmetic and that
+against scikit-learn's own values (tests/golden/gmm.npz), both again at the library's limits of 64 components and 128
+features, the run shapes that must not change a bit, the k-means start, the statistics and the error paths.
+tests/test_cpu_gmm.py shows that the restatement is sklearn's arithmetic and that
 the cases are away from the discontinuous rules.
 
 Bounds: a step is held within 1e-12 of the largest wanted entry of each quantity (the project's bound for fp64 sums of
@@ -137,6 +138,36 @@ def test_steps_against_sklearn(golden, name, cov_type):
         close(g, golden[key + q], STEP_TOL + 4 * golden[key + "floor_" + q], q)
 
 
+# ---- steps at the library's limits: up to 64 components in 128 dimensions ----------------------------------------------
+# STEP_TOL holds unchanged: no sum of these cases is longer than one of the cases above (a chunk is 2048 rows, d = 128
+# and 63 chunks are among them); only the number of sums grows.
+@pytest.mark.parametrize("cov_type", GC.COV_TYPES)
+@pytest.mark.parametrize("name", sorted(GC.LIMIT_CASES))
+def test_e_step_at_limits(name, cov_type):
+    check_e_step(GC.limit_case(name, cov_type), cov_type)
+
+
+@pytest.mark.parametrize("cov_type", GC.COV_TYPES)
+@pytest.mark.parametrize("name", sorted(GC.LIMIT_CASES))
+def test_m_step_at_limits(name, cov_type):
+    check_m_step(GC.limit_m_case(name, cov_type), cov_type)
+
+
+@pytest.mark.parametrize("cov_type", GC.COV_TYPES)
+@pytest.mark.parametrize("name", GC.LIMIT_GOLDEN)
+def test_steps_at_limits_against_sklearn(golden, name, cov_type):
+    """the device against sklearn's own values through the reduced quantities of ``GC.limit_reduced``: the step bound
+    plus 4 x the reference-side floor"""
+    X, weights, means, _, pchol, _, _, _ = GC.limit_case(name, cov_type)
+    key = GC.limit_key(name, cov_type)
+    got = _np(M.e_step(X, weights, means, pchol, cov_type)[0])
+    close(got, golden[key + "lpn"], STEP_TOL + 4 * golden[key + "floor_lpn"], "log_prob_norm")
+    got = [_np(t) for t in M.m_step(X, GC.limit_resp(name), 1e-6, cov_type)]
+    close(got[4], GC.log_det(got[3], cov_type), STEP_TOL, "log_det of the returned factors")
+    for q, g in zip(GC.LIMIT_QUANTITIES, GC.limit_reduced(*got[:4], cov_type)):
+        close(g, golden[key + q], STEP_TOL + 4 * golden[key + "floor_" + q], q)
+
+
 # ---- whole fits ------------------------------------------------------------------------------------------------------
 def device_fit(case, **kw):
     name, cov_type, init, run = case
@@ -202,6 +233,31 @@ def test_predict_and_statistics(cov_type):
     n_par = GC.n_parameters(3, d, cov_type)
     np.testing.assert_allclose(g.bic(X), -2.0 * lpn.mean() * n + n_par * np.log(n), rtol=1e-12)
     np.testing.assert_allclose(g.aic(X), -2.0 * lpn.mean() * n + 2.0 * n_par, rtol=1e-12)
+
+
+@pytest.mark.parametrize("cov_type", GC.COV_TYPES)
+def test_predict_and_statistics_at_k64(cov_type):
+    """the fitted 64-component model: labels wherever the restatement's posterior margin decides them (the CPU test
+    holds that it does in 99 % of the rows), sklearn's formulas on the fitted parameters"""
+    case = ("k64_d5", cov_type, "kmeans", "tol1e-3")
+    want = GC.fit_case(*case)
+    g, X = device_fit(case)
+    labels, clear = GC.predict(X, want, cov_type, near_ties=0.01)
+    got = g.predict(X)
+    assert got.dtype == np.int64 and got.shape == labels.shape
+    np.testing.assert_array_equal(got[clear], labels[clear])
+    assert len(set(got)) == 64
+    lpn, _, resp = GC.e_step(X, g.weights_, g.means_, g.precisions_cholesky_, cov_type)
+    n, d = X.shape
+    close(g.score_samples(X), lpn, FIT_TOL, "score_samples")
+    proba = g.predict_proba(X)
+    close(proba, resp, FIT_TOL, "predict_proba")
+    assert np.abs(proba.sum(axis=1) - 1.0).max() <= 1e-12
+    np.testing.assert_allclose(g.score(X), lpn.mean(), rtol=FIT_TOL)
+    n_par = GC.n_parameters(64, d, cov_type)
+    assert g._n_parameters(d) == n_par
+    np.testing.assert_allclose(g.bic(X), -2.0 * lpn.mean() * n + n_par * np.log(n), rtol=FIT_TOL)
+    np.testing.assert_allclose(g.aic(X), -2.0 * lpn.mean() * n + 2.0 * n_par, rtol=FIT_TOL)
 
 
 # ---- run shapes that change no bit -------------------------------------------------------------------------------------
