@@ -199,6 +199,13 @@ SIGNATURES = {
     "ava_db_assign_pre": (_i, [_p, _i, _i, _p, _i, _i, _p, _p, _p, _p, _p, _sz, _p]),
     "ava_db_labels": (_i, [_p, _i, _i, _i, _p, _i, _i, _p, _p, _p, _p, _p, _sz, _p]),
     "ava_db_labels_pre": (_i, [_p, _i, _i, _p, _i, _i, _p, _p, _p, _p, _p, _sz, _p]),
+    "ava_hd_workspace_bytes": (_sz, [_i, _i]),
+    "ava_hd_max_rounds": (_i, [_i]),
+    "ava_hd_core": (_i, [_p, _i, _i, _i, _p, _p, _p]),
+    "ava_hd_core_pre": (_i, [_p, _i, _i, _i, _p, _p]),
+    "ava_hd_mst": (_i, [_p, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    "ava_hd_mst_pre": (_i, [_p, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    "ava_hd_tree": (_i, [_p, _p, _p, _i, _i, _i, _p, _p, _p, _p]),
 }
 
 _lib = None

@@ -918,6 +918,44 @@ int ava_db_labels_pre(const void* dist, int dtype, int n, const double* eps, int
                       const int* counts, unsigned char* core, int64_t* labels, int* n_clusters, void* ws,
                       size_t ws_bytes, ava_stream_t s);
 
+/* ---- HDBSCAN (row f23; sklearn 1.7 cluster/_hdbscan: hdbscan.py, _reachability.pyx, _linkage.pyx, _tree.pyx;
+ * csrc/hdbscan.hip) ------------------------------------------------------------------------------------------------------
+ * x / dtype: [n][d] row-major on the device, 0 = float32, 1 = float64, 1 <= d <= 65536, 2 <= n <= 2^21.  The _pre forms
+ * take dist [n][n] (dtype as x), a SYMMETRIC matrix of distances, in its place.  The pair measure m(i, j) is the
+ * direct-difference sum d2 of ava_pair_sqdist (no square root) or (double)dist[i][j]; core [n] (device, float64) is the
+ * min_samples-th smallest m(i, .), the row itself (as 0) counted first; w(i, j) = max(core[i], core[j], m(i, j)).  Edges
+ * are ordered by the key (w, m, min(i, j), max(i, j)), a strict total order: the minimum spanning tree is unique.
+ *
+ * ava_hd_core: kth [n] int64 (device) = the row of each row's min_samples-th neighbour (column min_samples - 1 of
+ *   ava_pj_knn's table); core[i] = d2(i, kth[i]) in the fma order of the distance tile.
+ * ava_hd_core_pre: core[i] = the k-th smallest of row i of dist, its diagonal entry read as 0; 1 <= k <= min(64, n).
+ * ava_hd_mst: Boruvka rounds on the device.  ei, ej [n - 1] int, ew, em [n - 1] float64 (device): the n - 1 tree edges
+ *   (ei < ej) with their w and m, in NO particular order (sort them by the key).  rounds (HOST int): the rounds taken,
+ *   at most ava_hd_max_rounds(n) = ceil(log2 n); rowmin_ms (HOST float [ava_hd_max_rounds(n)], may be NULL): the time
+ *   of each round's row-minimum launch, by device events.  The call reads one word per round back and returns with the
+ *   stream idle.  AVA_ELAUNCH also when a round leaves more than half of its components (impossible for finite input).
+ *   ws: ava_hd_workspace_bytes(n, d) bytes (0 for an unsupported shape; d = 1 for the _pre form).
+ * ava_hd_tree: HOST code, no HIP call, every pointer a host pointer.  ei, ej int64 and dist float64 [n - 1]: the tree's
+ *   edges in ascending key order with the distances to report (sqrt(w) or w).  sklearn's make_single_linkage,
+ *   _condense_tree, _compute_stability, _get_clusters (method 0 = 'eom', 1 = 'leaf'; allow_single_cluster = False,
+ *   cluster_selection_epsilon = 0, max_cluster_size = None), _do_labelling and get_probabilities: labels [n] int64
+ *   (noise -1, clusters numbered in ascending order of their smallest row), prob [n] float64, *n_clusters, linkage
+ *   [n - 1][4] float64 (scipy's format: the cluster of ei, the cluster of ej, the distance, the size).  AVA_EINVAL
+ *   for edges that are no spanning tree, a NaN distance, min_cluster_size < 2 or an unknown method.
+ *
+ * All return AVA_EINVAL before any HIP call for null pointers, an unknown dtype or an unsupported shape, AVA_EWORKSPACE
+ * for a workspace that is too small. */
+size_t ava_hd_workspace_bytes(int n, int d);
+int ava_hd_max_rounds(int n);
+int ava_hd_core(const void* x, int dtype, int n, int d, const int64_t* kth, double* core, ava_stream_t s);
+int ava_hd_core_pre(const void* dist, int dtype, int n, int k, double* core, ava_stream_t s);
+int ava_hd_mst(const void* x, int dtype, int n, int d, const double* core, int* ei, int* ej, double* ew, double* em,
+               int* rounds, float* rowmin_ms, void* ws, size_t ws_bytes, ava_stream_t s);
+int ava_hd_mst_pre(const void* dist, int dtype, int n, const double* core, int* ei, int* ej, double* ew, double* em,
+                   int* rounds, float* rowmin_ms, void* ws, size_t ws_bytes, ava_stream_t s);
+int ava_hd_tree(const int64_t* ei, const int64_t* ej, const double* dist, int n, int min_cluster_size, int method,
+                int64_t* labels, double* prob, int* n_clusters, double* linkage);
+
 #ifdef __cplusplus
 }
 #endif
