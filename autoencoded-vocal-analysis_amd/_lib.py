@@ -243,3 +243,11 @@ def ptr(t):
 def stream():
     import torch
     return torch.cuda.current_stream().cuda_stream
+
+
+def device(what):
+    """the current GPU as a ``torch.device``; ``what`` names the caller's kernels in the error raised without one"""
+    import torch
+    if not torch.cuda.is_available():
+        raise AvaHipError("the %s kernels only run on an MI355X: there is no CPU fallback in this package" % what)
+    return torch.device("cuda", torch.cuda.current_device())

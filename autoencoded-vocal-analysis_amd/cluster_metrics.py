@@ -39,6 +39,7 @@ import torch
 
 from . import _lib
 from . import mixture as _mx
+from . import projection as _pj
 
 __all__ = ["silhouette_samples", "silhouette_score", "calinski_harabasz_score", "davies_bouldin_score", "cluster_sums",
            "select_n_components", "MAX_K", "CHUNK_COLS"]
@@ -49,10 +50,7 @@ _CRITERIA = ('bic', 'aic', 'silhouette', 'calinski_harabasz', 'davies_bouldin')
 
 
 def _device():
-    if not torch.cuda.is_available():
-        raise _lib.AvaHipError("the cluster-metric kernels only run on an MI355X: there is no CPU fallback in this "
-                               "package")
-    return torch.device("cuda", torch.cuda.current_device())
+    return _lib.device("cluster-metric")
 
 
 def _check_metric(metric):
@@ -95,6 +93,25 @@ def _check_rows(X, metric='euclidean'):
         if float(diag) > atol:
             raise ValueError(_DIAGONAL)
     return X
+
+
+def _check_pair_rows(X, metric, max_n):
+    """the host checks that ``dbscan`` and ``hdbscan`` share: the metric, the rows, and the shape their tile walks hold"""
+    _check_metric(metric)
+    X = _check_rows(X, metric)
+    if X.shape[0] > max_n:
+        raise ValueError("unsupported shape: N = %d rows, at most %d" % (X.shape[0], max_n))
+    if metric == 'euclidean' and X.shape[1] > _pj.MAX_DIM:
+        raise ValueError("unsupported shape: d = %d features, at most %d" % (X.shape[1], _pj.MAX_DIM))
+    return X
+
+
+def _upload_pair_rows(X, metric, dev):
+    """checked rows on the device; a precomputed matrix must be symmetric (its tiles are formed above the diagonal)"""
+    Xd = _mx._upload(X, dev)
+    if metric == 'precomputed' and not bool((Xd == Xd.T).all()):
+        raise ValueError("The precomputed distance matrix must be symmetric")
+    return Xd
 
 
 def _encode(labels, n, max_k=None):

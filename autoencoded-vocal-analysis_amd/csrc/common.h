@@ -47,6 +47,20 @@ static inline int64_t ceil_div64(int64_t a, int64_t b) { return (a + b - 1) / b;
 // boundary (every *_workspace_bytes reserves 256 bytes of slack for that)
 static inline size_t ava_up256(size_t x) { return (x + 255) & ~(size_t)255; }
 static inline char* ava_align256(const void* p) { return reinterpret_cast<char*>(ava_up256(reinterpret_cast<uintptr_t>(p))); }
+// The carving of a workspace: regions in the order of the take calls, from the aligned base; bytes() is what the
+// caller's buffer must hold, slack included.  A null base hands out null pointers and gives the sizes only.
+struct ava_ws_cursor {
+  char* p;
+  size_t o = 0;
+  explicit ava_ws_cursor(void* base) : p(base ? ava_align256(base) : nullptr) {}
+  template <typename T>
+  T* take(size_t count) {
+    T* r = p ? reinterpret_cast<T*>(p + o) : nullptr;
+    o += ava_up256(count * sizeof(T));
+    return r;
+  }
+  size_t bytes() const { return o + 256; }
+};
 
 // Counter-based standard normal: splitmix64 finaliser + Box-Muller; matches ava_amd.synthetic.u01 / gauss (SURVEY
 // Appendix E) so that injected and device-generated noise agree to float rounding when seeded alike.  Element i of a

@@ -63,41 +63,28 @@ __device__ __forceinline__ void db_decode_tile(int64_t p, int tiles, int& bi, in
   bj = (int)(r + (p - db_row_start(r, tiles)));
 }
 
-// acc[i][j] = the distance measure of the pair (q0 + ty + 16 i, r0 + tx + 16 j); rows and columns from n on are not to
-// be used by the caller.  Ends with every thread past the last read of xs / ys.
-template <typename T, bool PRE>
-__device__ __forceinline__ void db_tile(const T* __restrict__ X, int n, int d, int q0, int r0, double* xs, double* ys,
-                                        int t, double (&acc)[4][4]) {
-  const int ty = t >> 4, tx = t & 15;
-  if (PRE) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int r = q0 + ty + 16 * i, c = r0 + tx + 16 * j;
-        acc[i][j] = (r < n && c < n) ? (double)X[(size_t)r * n + c] : INFINITY;
-      }
-  } else {
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) acc[i][j] = 0.0;
-    for (int k0 = 0; k0 < d; k0 += SQD_KC) {
-      __syncthreads();                                               // the stage before is consumed
-      sqd_stage(xs, ys, X, q0, n, X, r0, n, d, k0, t);
-      __syncthreads();
-      sqd_accumulate(xs, ys, SQD_LD, d - k0 < SQD_KC ? d - k0 : SQD_KC, ty, tx, acc);
-    }
+// The core bits of the tile's rows (side 0, from q0) and columns (side 1, from r0) into LDS: bit e of bits[side][l] is
+// set when counts[e][row] >= min_samples, and any[side] is the OR over the side.  A row from n on has no bit set.  With
+// BORDER it has all n_eps bits set instead (a row that does not exist is never a border row), and any[2 + side] is the
+// OR of the complements over the rows that exist: the radii at which the side has a non-core row.  Every thread calls;
+// opens with a barrier after zeroing `any` (which also publishes what the caller initialised) and ends with one.
+template <bool BORDER>
+__device__ __forceinline__ void db_stage_core_bits(const int* __restrict__ counts, int n, int n_eps, int min_samples,
+                                                   int q0, int r0, int t, unsigned (*bits)[SQD_T], unsigned* any) {
+  const unsigned all = (1u << n_eps) - 1u;
+  if (t < (BORDER ? 4 : 2)) any[t] = 0;
+  __syncthreads();
+  if (t < 2 * SQD_T) {
+    const int side = t >> 6, l = t & 63;
+    const int row = (side ? r0 : q0) + l;
+    unsigned m = 0;
+    if (row < n)
+      for (int e = 0; e < n_eps; ++e) m |= (counts[(size_t)e * n + row] >= min_samples ? 1u : 0u) << e;
+    bits[side][l] = (BORDER && row >= n) ? all : m;
+    if (m) atomicOr(&any[side], m);
+    if (BORDER && row < n && (~m & all)) atomicOr(&any[2 + side], ~m & all);
   }
-}
-
-// the core bits of a row: bit e is set when counts[e][row] >= min_samples; `valid` is 0 for a row from n on
-__device__ __forceinline__ unsigned db_core_bits(const int* __restrict__ counts, int n, int n_eps, int min_samples,
-                                                 int row) {
-  unsigned m = 0;
-  if (row < n)
-    for (int e = 0; e < n_eps; ++e) m |= (counts[(size_t)e * n + row] >= min_samples ? 1u : 0u) << e;
-  return m;
+  __syncthreads();
 }
 
 // ---- 1. neighbour counts ------------------------------------------------------------------------------------------------
@@ -119,7 +106,7 @@ __global__ __launch_bounds__(256) void db_count_kernel(const T* __restrict__ X, 
     (&csum[0][0])[p] = 0;
   }
   double acc[4][4];
-  db_tile<T, PRE>(X, n, d, q0, r0, xs, ys, t, acc);                  // its barriers also publish the zeros (d >= 1)
+  sqd_pair_tile<T, PRE>(X, n, d, q0, r0, xs, ys, t, acc);            // its barriers also publish the zeros (d >= 1)
   if (PRE) __syncthreads();
   for (int e = 0; e < n_eps; ++e) {
     const double lim = thr.v[e];
@@ -189,19 +176,11 @@ __global__ __launch_bounds__(256) void db_union_kernel(const T* __restrict__ X, 
   db_decode_tile(blockIdx.x, tiles, bi, bj);
   const int q0 = bi * SQD_T, r0 = bj * SQD_T;
   const bool diag = bi == bj;
-  if (t < 2) any[t] = 0;
-  __syncthreads();
-  if (t < 2 * SQD_T) {
-    const int side = t >> 6, l = t & 63;
-    const unsigned m = db_core_bits(counts, n, n_eps, min_samples, (side ? r0 : q0) + l);
-    bits[side][l] = m;
-    if (m) atomicOr(&any[side], m);
-  }
-  __syncthreads();
+  db_stage_core_bits<false>(counts, n, n_eps, min_samples, q0, r0, t, bits, any);
   const unsigned live = any[0] & any[1];
   if (!live) return;                                                 // uniform: no radius has core rows on both sides
   double acc[4][4];
-  db_tile<T, PRE>(X, n, d, q0, r0, xs, ys, t, acc);
+  sqd_pair_tile<T, PRE>(X, n, d, q0, r0, xs, ys, t, acc);
   unsigned rb[4], cb[4];
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
@@ -250,27 +229,16 @@ __global__ __launch_bounds__(256) void db_border_kernel(const T* __restrict__ X,
   db_decode_tile(blockIdx.x, tiles, bi, bj);
   const int q0 = bi * SQD_T, r0 = bj * SQD_T;
   const bool diag = bi == bj;
-  const unsigned all = (1u << n_eps) - 1u;
-  if (t < 4) any[t] = 0;
   for (int p = t; p < DB_MAX_EPS * SQD_T; p += 256) {
     (&rmin[0][0])[p] = INT_MAX;
     (&cmin[0][0])[p] = INT_MAX;
   }
-  __syncthreads();
-  if (t < 2 * SQD_T) {
-    const int side = t >> 6, l = t & 63;
-    const int row = (side ? r0 : q0) + l;
-    const unsigned m = db_core_bits(counts, n, n_eps, min_samples, row);
-    bits[side][l] = row < n ? m : all;                               // a row that does not exist is never a border row
-    if (m) atomicOr(&any[side], m);
-    if (row < n && (~m & all)) atomicOr(&any[2 + side], ~m & all);
-  }
-  __syncthreads();
+  db_stage_core_bits<true>(counts, n, n_eps, min_samples, q0, r0, t, bits, any);
   const unsigned live_r = any[2] & any[1];                           // non-core rows facing core columns
   const unsigned live_c = diag ? 0u : any[3] & any[0];
   if (!(live_r | live_c)) return;                                    // uniform
   double acc[4][4];
-  db_tile<T, PRE>(X, n, d, q0, r0, xs, ys, t, acc);
+  sqd_pair_tile<T, PRE>(X, n, d, q0, r0, xs, ys, t, acc);
   unsigned rb[4], cb[4];
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
@@ -393,22 +361,15 @@ struct db_ws {
   int *parent, *root, *cand, *scan, *csum;
 };
 static size_t db_ws_layout(int n, int n_eps, void* base, db_ws* out) {
-  const size_t chunks = ceil_div(n, DB_CHUNK);
-  size_t o = 0;
-  char* p = base ? ava_align256(base) : nullptr;
-  auto take = [&](size_t bytes) {
-    int* r = p ? reinterpret_cast<int*>(p + o) : nullptr;
-    o += ava_up256(bytes);
-    return r;
-  };
-  const size_t rows = (size_t)n_eps * n * sizeof(int);
-  int* parent = take(rows);
-  int* root = take(rows);
-  int* cand = take(rows);
-  int* scan = take(rows);
-  int* csum = take((size_t)n_eps * chunks * sizeof(int));
+  const size_t chunks = ceil_div(n, DB_CHUNK), rows = (size_t)n_eps * n;
+  ava_ws_cursor c(base);
+  int* parent = c.take<int>(rows);
+  int* root = c.take<int>(rows);
+  int* cand = c.take<int>(rows);
+  int* scan = c.take<int>(rows);
+  int* csum = c.take<int>((size_t)n_eps * chunks);
   if (out) *out = db_ws{parent, root, cand, scan, csum};
-  return o + 256;
+  return c.bytes();
 }
 
 // eps2 (or eps) per radius; false for a radius that is not a positive finite number

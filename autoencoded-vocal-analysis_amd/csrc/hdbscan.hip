@@ -53,33 +53,6 @@ __device__ __forceinline__ double hd_unord(hd_u64 k) {
   return __longlong_as_double((long long)((k >> 63) ? (k & 0x7FFFFFFFFFFFFFFFull) : ~k));
 }
 
-// acc[i][j] = m(q0 + ty + 16 i, r0 + tx + 16 j); rows and columns from n on are not to be used by the caller
-template <typename T, bool PRE>
-__device__ __forceinline__ void hd_tile(const T* __restrict__ X, int n, int d, int q0, int r0, double* xs, double* ys,
-                                        int t, double (&acc)[4][4]) {
-  const int ty = t >> 4, tx = t & 15;
-  if (PRE) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int r = q0 + ty + 16 * i, c = r0 + tx + 16 * j;
-        acc[i][j] = (r < n && c < n) ? (double)X[(size_t)r * n + c] : INFINITY;
-      }
-  } else {
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) acc[i][j] = 0.0;
-    for (int k0 = 0; k0 < d; k0 += SQD_KC) {
-      __syncthreads();                                               // the stage before is consumed
-      sqd_stage(xs, ys, X, q0, n, X, r0, n, d, k0, t);
-      __syncthreads();
-      sqd_accumulate(xs, ys, SQD_LD, d - k0 < SQD_KC ? d - k0 : SQD_KC, ty, tx, acc);
-    }
-  }
-}
-
 // ---- core measures -------------------------------------------------------------------------------------------------------
 // euclidean: kth[i] is the row of the min_samples-th neighbour (ava_pj_knn); its d2 again in the tile's fma order
 template <typename T>
@@ -209,7 +182,7 @@ __global__ __launch_bounds__(256) void hd_rowmin_kernel(const T* __restrict__ X,
       ccore[t] = c < n ? core[c] : 0.0;
     }
     double acc[4][4];
-    hd_tile<T, PRE>(X, n, d, q0, r0, xs, ys, t, acc);               // its barriers also publish ccomp (d >= 1)
+    sqd_pair_tile<T, PRE>(X, n, d, q0, r0, xs, ys, t, acc);         // its barriers also publish ccomp (d >= 1)
     if (PRE) __syncthreads();
 #pragma unroll
     for (int j = 0; j < 4; ++j) {                                    // columns ascending: only a smaller (w, m) replaces
@@ -364,26 +337,20 @@ struct hd_ws {
 };
 static size_t hd_ws_layout(int n, void* base, hd_ws* out) {
   const size_t segs = hd_segs(n), tiles = ceil_div(n, SQD_T);
-  size_t o = 0;
-  char* p = base ? ava_align256(base) : nullptr;
-  auto take = [&](size_t bytes) {
-    char* r = p ? p + o : nullptr;
-    o += ava_up256(bytes);
-    return r;
-  };
+  ava_ws_cursor c(base);
   hd_ws w;
-  w.comp = reinterpret_cast<int*>(take((size_t)n * sizeof(int)));
-  w.parent = reinterpret_cast<int*>(take((size_t)n * sizeof(int)));
-  w.cand_j = reinterpret_cast<int*>(take(segs * n * sizeof(int)));
-  w.cursor = reinterpret_cast<int*>(take(sizeof(int)));
-  w.brange = reinterpret_cast<int2*>(take(tiles * sizeof(int2)));
-  w.bw = reinterpret_cast<hd_u64*>(take((size_t)n * sizeof(hd_u64)));
-  w.bm = reinterpret_cast<hd_u64*>(take((size_t)n * sizeof(hd_u64)));
-  w.be = reinterpret_cast<hd_u64*>(take((size_t)n * sizeof(hd_u64)));
-  w.cand_w = reinterpret_cast<double*>(take(segs * n * sizeof(double)));
-  w.cand_m = reinterpret_cast<double*>(take(segs * n * sizeof(double)));
+  w.comp = c.take<int>(n);
+  w.parent = c.take<int>(n);
+  w.cand_j = c.take<int>(segs * n);
+  w.cursor = c.take<int>(1);
+  w.brange = c.take<int2>(tiles);
+  w.bw = c.take<hd_u64>(n);
+  w.bm = c.take<hd_u64>(n);
+  w.be = c.take<hd_u64>(n);
+  w.cand_w = c.take<double>(segs * n);
+  w.cand_m = c.take<double>(segs * n);
   if (out) *out = w;
-  return o + 256;
+  return c.bytes();
 }
 
 extern "C" size_t ava_hd_workspace_bytes(int n, int d) {

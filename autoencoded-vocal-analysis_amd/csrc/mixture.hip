@@ -524,20 +524,14 @@ struct gm_ws {
 };
 static size_t gm_ws_layout(int n, int d, int K, int cov_type, void* base, gm_ws* out) {
   const size_t chunks = gm_chunks(n), dp = 16 * (size_t)gm_nb(d);
-  size_t off = 0;
-  char* p = base ? ava_align256(base) : nullptr;
-  auto take = [&](size_t doubles) {
-    double* r = p ? reinterpret_cast<double*>(p + off) : nullptr;
-    off += ava_up256(doubles * sizeof(double));
-    return r;
-  };
-  double* s0 = take(chunks * K);
-  double* s1 = take(chunks * K * d);
-  double* ll = take(chunks);
-  double* nk = take(K);
-  double* cpart = take(cov_type == 0 ? chunks * K * dp * dp : 0);
+  ava_ws_cursor c(base);
+  double* s0 = c.take<double>(chunks * K);
+  double* s1 = c.take<double>(chunks * K * d);
+  double* ll = c.take<double>(chunks);
+  double* nk = c.take<double>(K);
+  double* cpart = c.take<double>(cov_type == 0 ? chunks * K * dp * dp : 0);
   if (out) *out = gm_ws{s0, s1, ll, nk, cpart};
-  return off + 256;
+  return c.bytes();
 }
 
 extern "C" int ava_gm_max_d(void) { return GM_MAX_D; }

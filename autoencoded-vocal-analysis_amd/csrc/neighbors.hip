@@ -147,16 +147,7 @@ __global__ __launch_bounds__(256) void nn_eucl_kernel(const TQ* __restrict__ Q, 
   const int rt = blockIdx.x;
   const int q0 = blockIdx.y * SQD_T, r0 = rt * SQD_T;
   double acc[4][4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = 0.0;
-  for (int k0 = 0; k0 < d; k0 += SQD_KC) {
-    sqd_stage(xs, ys, Q, q0, nq, R, r0, nr, d, k0, t);
-    __syncthreads();
-    sqd_accumulate(xs, ys, SQD_LD, d - k0 < SQD_KC ? d - k0 : SQD_KC, ty, tx, acc);
-    __syncthreads();
-  }
+  sqd_tile(xs, ys, Q, q0, nq, R, r0, nr, d, t, acc);
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     double best = 0.0;

@@ -101,16 +101,7 @@ __global__ __launch_bounds__(256) void pj_knn_kernel(const T* __restrict__ Q, co
   }
   for (int r0 = 0; r0 < n; r0 += SQD_T) {
     double acc[4][4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) acc[i][j] = 0.0;
-    for (int k0 = 0; k0 < d; k0 += SQD_KC) {
-      __syncthreads();                               // previous stage / distance tile consumed
-      sqd_stage(xs, ys, Q, qb, qe, X, r0, n, d, k0, t);
-      __syncthreads();
-      sqd_accumulate(xs, ys, SQD_LD, d - k0 < SQD_KC ? d - k0 : SQD_KC, ty, tx, acc);
-    }
+    sqd_tile(xs, ys, Q, qb, qe, X, r0, n, d, t, acc);  // opens with a barrier: the distance tile before is folded
     __syncthreads();                                 // staging reads done: the tile reuses the buffer
 #pragma unroll
     for (int i = 0; i < 4; ++i)

@@ -82,6 +82,8 @@ __global__ __launch_bounds__(256) void sil_sums_kernel(const T* __restrict__ X, 
     const int he = h0 + SIL_CHUNK < ce ? h0 + SIL_CHUNK : ce;
     double part[4] = {0.0, 0.0, 0.0, 0.0};
     for (int r0 = h0; r0 < he; r0 += SQD_T) {
+      // sqd_tile's loop, written out: called through sqd_tile this kernel's stage addressing compiles to a 64-bit
+      // multiply with sign fix-ups and the pass measured 0.17 % slower at N = 1e5 (profiles/NOTES.md (61))
       double acc[4][4];
 #pragma unroll
       for (int i = 0; i < 4; ++i)
@@ -281,18 +283,12 @@ struct sil_ws {
 };
 static size_t sil_ws_layout(int n, int d, int K, void* base, sil_ws* out) {
   const size_t chunks = ceil_div(n, SIL_CHUNK);
-  size_t o = 0;
-  char* p = base ? ava_align256(base) : nullptr;
-  auto take = [&](size_t bytes) {
-    void* r = p ? static_cast<void*>(p + o) : nullptr;
-    o += ava_up256(bytes);
-    return r;
-  };
-  void* rows = take((size_t)n * d * sizeof(double));
-  double* mean_part = static_cast<double*>(take(chunks * sizeof(double)));
-  double* cent_part = static_cast<double*>(take(chunks * K * 2 * sizeof(double)));
+  ava_ws_cursor c(base);
+  void* rows = c.take<double>((size_t)n * d);                         // float32 rows use the first half
+  double* mean_part = c.take<double>(chunks);
+  double* cent_part = c.take<double>(chunks * K * 2);
   if (out) *out = sil_ws{rows, mean_part, cent_part};
-  return o + 256;
+  return c.bytes();
 }
 
 extern "C" int ava_sil_max_k(void) { return SIL_MAX_K; }

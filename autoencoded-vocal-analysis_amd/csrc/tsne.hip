@@ -91,16 +91,7 @@ __global__ __launch_bounds__(256) void ts_sqdist_kernel(const T* __restrict__ X,
   const int t = threadIdx.x, ty = t >> 4, tx = t & 15;
   const int i0 = blockIdx.y * SQD_T, j0 = blockIdx.x * SQD_T;
   double acc[4][4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = 0.0;
-  for (int k0 = 0; k0 < d; k0 += SQD_KC) {
-    __syncthreads();                                 // previous stage consumed
-    sqd_stage(xs, ys, X, i0, n, X, j0, n, d, k0, t);
-    __syncthreads();
-    sqd_accumulate(xs, ys, SQD_LD, d - k0 < SQD_KC ? d - k0 : SQD_KC, ty, tx, acc);
-  }
+  sqd_tile(xs, ys, X, i0, n, X, j0, n, d, t, acc);
 #pragma unroll
   for (int i = 0; i < 4; ++i)
 #pragma unroll

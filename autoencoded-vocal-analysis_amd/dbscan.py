@@ -53,9 +53,7 @@ MAX_N = 2 ** 21                 # rows (the list of the upper triangle's tiles s
 
 
 def _device():
-    if not torch.cuda.is_available():
-        raise _lib.AvaHipError("the DBSCAN kernels only run on an MI355X: there is no CPU fallback in this package")
-    return torch.device("cuda", torch.cuda.current_device())
+    return _lib.device("DBSCAN")
 
 
 def _check_eps(eps):
@@ -83,16 +81,7 @@ def _eps_list(eps_list):
 
 def _rows(X, metric):
     """the checks that need no device, then the rows on the device"""
-    _cm._check_metric(metric)
-    X = _cm._check_rows(X, metric)
-    if X.shape[0] > MAX_N:
-        raise ValueError("unsupported shape: N = %d rows, at most %d" % (X.shape[0], MAX_N))
-    if metric == 'euclidean' and X.shape[1] > _pj.MAX_DIM:
-        raise ValueError("unsupported shape: d = %d features, at most %d" % (X.shape[1], _pj.MAX_DIM))
-    Xd = _mx._upload(X, _device())
-    if metric == 'precomputed' and not bool((Xd == Xd.T).all()):
-        raise ValueError("The precomputed distance matrix must be symmetric")
-    return Xd
+    return _cm._upload_pair_rows(_cm._check_pair_rows(X, metric, MAX_N), metric, _device())
 
 
 def _counts_group(Xd, radii, metric):

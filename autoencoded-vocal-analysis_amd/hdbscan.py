@@ -53,9 +53,7 @@ _METHODS = ('eom', 'leaf')
 
 
 def _device():
-    if not torch.cuda.is_available():
-        raise _lib.AvaHipError("the HDBSCAN kernels only run on an MI355X: there is no CPU fallback in this package")
-    return torch.device("cuda", torch.cuda.current_device())
+    return _lib.device("HDBSCAN")
 
 
 def _check_int(value, name, low, none_ok=False):
@@ -76,24 +74,6 @@ def _check_min_samples(min_samples, n):
     if min_samples > _pj.MAX_K:
         raise ValueError("min_samples (%d) must be at most %d (projection.MAX_K, the neighbours the kNN kernel keeps)"
                          % (min_samples, _pj.MAX_K))
-
-
-def _rows(X, metric):
-    """the checks of the rows that need no device"""
-    _cm._check_metric(metric)
-    X = _cm._check_rows(X, metric)
-    if X.shape[0] > MAX_N:
-        raise ValueError("unsupported shape: N = %d rows, at most %d" % (X.shape[0], MAX_N))
-    if metric == 'euclidean' and X.shape[1] > _pj.MAX_DIM:
-        raise ValueError("unsupported shape: d = %d features, at most %d" % (X.shape[1], _pj.MAX_DIM))
-    return X
-
-
-def _upload(X, metric):
-    Xd = _mx._upload(X, _device())
-    if metric == 'precomputed' and not bool((Xd == Xd.T).all()):
-        raise ValueError("The precomputed distance matrix must be symmetric")
-    return Xd
 
 
 def _core_device(Xd, min_samples, metric):
@@ -183,9 +163,9 @@ def mutual_reachability_mst(X, min_samples, metric='euclidean'):
     ``i < j``, in key order, and ``core_distances`` float64 ``[N]`` (both square-rooted for ``'euclidean'``).  ``X`` and
     ``metric`` as for :class:`HDBSCAN`; ``1 <= min_samples <= min(projection.MAX_K, N)``."""
     min_samples = _check_int(min_samples, "min_samples", 1)
-    X = _rows(X, metric)
+    X = _cm._check_pair_rows(X, metric, MAX_N)
     _check_min_samples(min_samples, X.shape[0])
-    mst, core, _ = _mst_host(_upload(X, metric), min_samples, metric)
+    mst, core, _ = _mst_host(_cm._upload_pair_rows(X, metric, _device()), min_samples, metric)
     return mst, core
 
 
@@ -211,12 +191,12 @@ class HDBSCAN:
         if self.cluster_selection_method not in _METHODS:
             raise ValueError("The 'cluster_selection_method' parameter of HDBSCAN must be a str among {'eom', 'leaf'}. "
                              "Got %r instead." % (self.cluster_selection_method,))
-        X = _rows(X, self.metric)
+        X = _cm._check_pair_rows(X, self.metric, MAX_N)
         n = int(X.shape[0])
         min_samples = min_cluster_size if min_samples is None else min_samples
         _check_min_samples(min_samples, n)
         min_cluster_size = min(min_cluster_size, 2 ** 31 - 1)
-        Xd = _upload(X, self.metric)
+        Xd = _cm._upload_pair_rows(X, self.metric, _device())
         mst, core, rounds = _mst_host(Xd, min_samples, self.metric)
         labels, prob, count, linkage = _tree_host(mst, n, min_cluster_size, self.cluster_selection_method)
         self.labels_ = labels

@@ -45,9 +45,7 @@ _ILL_DEFINED = ("Fitting the mixture model failed because some components have i
 
 
 def _device():
-    if not torch.cuda.is_available():
-        raise _lib.AvaHipError("the mixture kernels only run on an MI355X: there is no CPU fallback in this package")
-    return torch.device("cuda", torch.cuda.current_device())
+    return _lib.device("mixture")
 
 
 def _cov_code(covariance_type):

@@ -43,9 +43,7 @@ PERM_MAX_CHUNK = 1 << 20            # splits per call of ava_mmd2_perm
 
 
 def _device():
-    if not torch.cuda.is_available():
-        raise _lib.AvaHipError("the MMD kernels only run on an MI355X: there is no CPU fallback in this package")
-    return torch.device("cuda", torch.cuda.current_device())
+    return _lib.device("MMD")
 
 
 def _latent_dev(latent):

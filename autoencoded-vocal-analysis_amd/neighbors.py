@@ -25,9 +25,7 @@ _DTYPE_CODES = {np.dtype(np.float32): 0, np.dtype(np.float64): 1}
 
 
 def _device():
-    if not torch.cuda.is_available():
-        raise _lib.AvaHipError("the nearest-neighbour kernels only run on an MI355X: there is no CPU fallback")
-    return torch.device("cuda", torch.cuda.current_device())
+    return _lib.device("nearest-neighbour")
 
 
 def _rows(x, d, what):

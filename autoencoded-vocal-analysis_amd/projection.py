@@ -62,9 +62,7 @@ MAX_NEGATIVE_SAMPLE_RATE = 7   # keeps n_neg <= 2 rate + 1 <= 16
 
 
 def _device():
-    if not torch.cuda.is_available():
-        raise _lib.AvaHipError("the projection kernels only run on an MI355X: there is no CPU fallback")
-    return torch.device("cuda", torch.cuda.current_device())
+    return _lib.device("projection")
 
 
 def _as_rows(X, dtype):

@@ -40,9 +40,7 @@ EXPLORATION_MAX_ITER = 250      # TSNE._EXPLORATION_MAX_ITER
 
 
 def _device():
-    if not torch.cuda.is_available():
-        raise _lib.AvaHipError("the t-SNE kernels only run on an MI355X: there is no CPU fallback in this package")
-    return torch.device("cuda", torch.cuda.current_device())
+    return _lib.device("t-SNE")
 
 
 def _matrix(n, dev):
