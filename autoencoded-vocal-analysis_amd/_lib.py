@@ -206,6 +206,13 @@ SIGNATURES = {
     "ava_hd_mst": (_i, [_p, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
     "ava_hd_mst_pre": (_i, [_p, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
     "ava_hd_tree": (_i, [_p, _p, _p, _i, _i, _i, _p, _p, _p, _p]),
+    "ava_kp_max_sweep": (_i, []),
+    "ava_kp_max_classes": (_i, []),
+    "ava_kp_max_outputs": (_i, []),
+    "ava_kp_knn_masked": (_i, [_p, _i, _i, _i, _i, _p, _i, _i, _p, _p, _p]),
+    "ava_kp_vote": (_i, [_p, _p, _i, _i, _p, _p, _i, _i, _p, _p]),
+    "ava_kp_proba": (_i, [_p, _p, _i, _i, _p, _i, _i, _p, _p]),
+    "ava_kp_regress": (_i, [_p, _p, _i, _i, _p, _i, _p, _i, _i, _p, _p]),
 }
 
 _lib = None

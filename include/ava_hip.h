@@ -956,6 +956,38 @@ int ava_hd_mst_pre(const void* dist, int dtype, int n, const double* core, int* 
 int ava_hd_tree(const int64_t* ei, const int64_t* ej, const double* dist, int n, int min_cluster_size, int method,
                 int64_t* labels, double* prob, int* n_clusters, double* linkage);
 
+/* ---- cross-validated k-nearest-neighbour prediction (row f24; sklearn 1.7 neighbors/_classification.py, _regression.py,
+ * _base.py::_get_weights under cross_val_predict with a PredefinedSplit; csrc/knn_predict.hip) ---------------------------
+ * ava_kp_knn_masked: rows [q0, q0 + nq) of the table of the k nearest rows of every row of x [n][d] (dtype 0 = float32,
+ *   1 = float64; device) among the rows of OTHER folds: reference r is a candidate of query q unless
+ *   fold[r] == fold[q] (fold [n] int, device).  out_idx [nq][k] int64, out_dist [nq][k] float64 (device), ordered by
+ *   (distance, index); the distance arithmetic is that of ava_pj_knn, bit for bit.  A row is in its own fold, so it is
+ *   never its own neighbour.  1 <= k <= min(64, n), n <= 2^30, 1 <= d <= 65536.  The caller guarantees that every row has k
+ *   candidates (n minus the largest fold >= k); a slot without one is written as index -1 at distance 0.
+ * The three below read a [nq][kmax] table of that form (kmax <= 64; every index a row of y / Y) and a sweep ks (HOST int
+ *   [n_k], 1 <= n_k <= ava_kp_max_sweep() = 16, strictly ascending, 1 <= ks[a] <= kmax): the list for ks[a] is the first
+ *   ks[a] slots.  The weight of a slot is 1 (weighted = 0) or 1 / distance (weighted = 1), except in a row whose slot 0
+ *   is at distance 0, where it is 1 for the slots at distance 0 and 0 for the others.
+ * ava_kp_vote: y [n] int (device): the class codes of the reference rows.  out_pred [n_k][nq] int (device): the class
+ *   with the largest sum of weights, the smallest such class on a tie.  The sums run in slot order from 0.
+ * ava_kp_proba: the table is [nq][k]; out [nq][n_classes] float64 (device): the sums of weights of the classes
+ *   0 .. n_classes - 1, in slot order, divided by the sum of all k weights (a sum of 0 counts as 1).
+ *   1 <= n_classes <= ava_kp_max_classes() = 4096; a class code outside that range is counted in the divisor only.
+ * ava_kp_regress: Y [n][n_out] float64 (device), 1 <= n_out <= ava_kp_max_outputs() = 256.  out [n_k][nq][n_out] float64
+ *   (device): num / den with num = fma(w_s, Y[idx_s][t], num) and den += w_s over the slots in ascending order.
+ * All return AVA_EINVAL before any launch for null pointers, an unknown dtype, a bad sweep or an unsupported shape. */
+int ava_kp_max_sweep(void);
+int ava_kp_max_classes(void);
+int ava_kp_max_outputs(void);
+int ava_kp_knn_masked(const void* x, int dtype, int n, int d, int k, const int* fold, int q0, int nq, int64_t* out_idx,
+                      double* out_dist, ava_stream_t s);
+int ava_kp_vote(const int64_t* idx, const double* dist, int nq, int kmax, const int* y, const int* ks, int n_k,
+                int weighted, int* out_pred, ava_stream_t s);
+int ava_kp_proba(const int64_t* idx, const double* dist, int nq, int k, const int* y, int n_classes, int weighted,
+                 double* out, ava_stream_t s);
+int ava_kp_regress(const int64_t* idx, const double* dist, int nq, int kmax, const double* Y, int n_out, const int* ks,
+                   int n_k, int weighted, double* out, ava_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif
