@@ -252,6 +252,24 @@ def stream():
     return torch.cuda.current_stream().cuda_stream
 
 
+def dtype_code(t):
+    """the ABI's dtype argument of a tensor, an array, or a torch or numpy dtype: 0 for float32, 1 for float64"""
+    dtype = getattr(t, "dtype", t)
+    code = {"float32": 0, "float64": 1}.get(str(dtype).replace("torch.", ""))
+    if code is None:
+        raise AvaHipError("the kernels read float32 or float64 rows, got %s" % (dtype,))
+    return code
+
+
+def workspace(nbytes, dev, what):
+    """``nbytes`` of device scratch (uint8), as an ``ava_*_workspace_bytes`` call sized it; that call answers 0 for a
+    shape the entry points reject, which ``what`` describes in the error"""
+    import torch
+    if nbytes == 0:
+        raise ValueError("unsupported shape: " + what)
+    return torch.empty(nbytes, dtype=torch.uint8, device=dev)
+
+
 def device(what):
     """the current GPU as a ``torch.device``; ``what`` names the caller's kernels in the error raised without one"""
     import torch

@@ -37,7 +37,7 @@ without the HIP library / a GPU every device function raises ``AvaHipError``.
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, _rows
 from . import mixture as _mx
 from . import projection as _pj
 
@@ -60,15 +60,8 @@ def _check_metric(metric):
 
 def _check_rows(X, metric='euclidean'):
     """sklearn's check_X_y for the rows, on the host or the device; returns float32 or float64 rows as they are"""
-    if torch.is_tensor(X):
-        if X.dtype not in (torch.float32, torch.float64):
-            X = X.to(torch.float64)
-        shape = tuple(X.shape)
-    else:
-        X = np.asarray(X)
-        if X.dtype not in (np.float32, np.float64):
-            X = X.astype(np.float64)
-        shape = X.shape
+    X = _rows.native(X)
+    shape = tuple(X.shape)
     if len(shape) != 2:
         raise ValueError("Expected 2D array, got %dD array instead" % len(shape))
     if shape[0] < 1 or shape[1] < 1:
@@ -76,13 +69,9 @@ def _check_rows(X, metric='euclidean'):
                          % (shape[0], shape[1]))
     if shape[0] > 2 ** 30:
         raise ValueError("at most 2**30 rows")
-    if torch.is_tensor(X):
-        nan, finite = bool(torch.isnan(X).any()), bool(torch.isfinite(X).all())
-    else:
-        nan, finite = bool(np.isnan(X).any()), bool(np.isfinite(X).all())
-    if nan:
+    if _rows.has_nan(X):
         raise ValueError("Input X contains NaN.")
-    if not finite:
+    if not _rows.is_finite(X):
         raise ValueError("Input X contains infinity or a value too large for dtype('float64').")
     if metric == 'precomputed':
         if shape[0] != shape[1]:
@@ -108,7 +97,7 @@ def _check_pair_rows(X, metric, max_n):
 
 def _upload_pair_rows(X, metric, dev):
     """checked rows on the device; a precomputed matrix must be symmetric (its tiles are formed above the diagonal)"""
-    Xd = _mx._upload(X, dev)
+    Xd = _rows.upload(X, dev)
     if metric == 'precomputed' and not bool((Xd == Xd.T).all()):
         raise ValueError("The precomputed distance matrix must be symmetric")
     return Xd
@@ -145,9 +134,7 @@ def _tables(enc, k):
 
 def _workspace(n, d, k, dev):
     nbytes = _lib.load().ava_sil_workspace_bytes(n, d, k)
-    if nbytes == 0:
-        raise ValueError("unsupported shape: N = %d, d = %d, %d labels" % (n, d, k))
-    return torch.empty(nbytes, dtype=torch.uint8, device=dev), nbytes
+    return _lib.workspace(nbytes, dev, "N = %d, d = %d, %d labels" % (n, d, k)), nbytes
 
 
 def _sums(Xd, order, off, k, metric):
@@ -157,12 +144,12 @@ def _sums(Xd, order, off, k, metric):
     d = Xd.shape[1] if metric == 'euclidean' else 1
     ws, nbytes = _workspace(n, d, k, Xd.device)                       # raises before any launch
     S = torch.empty((n, k), dtype=torch.float64, device=Xd.device)
+    code = _lib.dtype_code(Xd)
     if metric == 'euclidean':
-        _lib.check(lib.ava_sil_cluster_sums(Xd.data_ptr(), _mx._code(Xd), n, d, k, order.data_ptr(), off.data_ptr(),
-                                            S.data_ptr(), ws.data_ptr(), nbytes, _lib.stream()),
-                   "ava_sil_cluster_sums")
+        _lib.check(lib.ava_sil_cluster_sums(Xd.data_ptr(), code, n, d, k, order.data_ptr(), off.data_ptr(), S.data_ptr(),
+                                            ws.data_ptr(), nbytes, _lib.stream()), "ava_sil_cluster_sums")
     else:
-        _lib.check(lib.ava_sil_cluster_sums_pre(Xd.data_ptr(), _mx._code(Xd), n, k, order.data_ptr(), off.data_ptr(),
+        _lib.check(lib.ava_sil_cluster_sums_pre(Xd.data_ptr(), code, n, k, order.data_ptr(), off.data_ptr(),
                                                 S.data_ptr(), _lib.stream()), "ava_sil_cluster_sums_pre")
     return S, (ws, nbytes)
 
@@ -173,7 +160,7 @@ def _prepare(X, labels, metric):
     enc, k = _encode(labels, X.shape[0], MAX_K)
     order, off = _tables(enc, k)
     dev = _device()
-    Xd = _mx._upload(X, dev)
+    Xd = _rows.upload(X, dev)
     return Xd, torch.from_numpy(order).to(dev), torch.from_numpy(off).to(dev), k
 
 
@@ -243,7 +230,7 @@ def _centroid_stats(X, labels):
                          % (d, k, _mx.MAX_D, _mx.MAX_K))
     lib = _lib.load()
     dev = _device()
-    Xd = _mx._upload(X, dev)
+    Xd = _rows.upload(X, dev)
     lab = torch.from_numpy(enc).to(dev)
     ws, nbytes = _workspace(n, d, k, dev)
     gws, gbytes = _mx._workspace(n, d, k, 1, dev)
@@ -255,9 +242,9 @@ def _centroid_stats(X, labels):
     st = _lib.stream()
     _lib.check(lib.ava_gm_onehot(lab.data_ptr(), prev.data_ptr(), n, k, resp.data_ptr(), changed.data_ptr(), st),
                "ava_gm_onehot")
-    _lib.check(lib.ava_gm_means(Xd.data_ptr(), _mx._code(Xd), n, d, k, resp.data_ptr(), out[0].data_ptr(),
+    _lib.check(lib.ava_gm_means(Xd.data_ptr(), _lib.dtype_code(Xd), n, d, k, resp.data_ptr(), out[0].data_ptr(),
                                 means.data_ptr(), out[1].data_ptr(), gws.data_ptr(), gbytes, st), "ava_gm_means")
-    _lib.check(lib.ava_sil_centroid_stats(Xd.data_ptr(), _mx._code(Xd), n, d, k, lab.data_ptr(), means.data_ptr(),
+    _lib.check(lib.ava_sil_centroid_stats(Xd.data_ptr(), _lib.dtype_code(Xd), n, d, k, lab.data_ptr(), means.data_ptr(),
                                           out[2].data_ptr(), out[3].data_ptr(), ws.data_ptr(), nbytes, st),
                "ava_sil_centroid_stats")
     host = out.cpu().numpy()
@@ -311,7 +298,7 @@ def select_n_components(X, n_components, *, covariance_type='full', criteria=_CR
         raise ValueError("n_components is empty")
     X = _mx._check_rows(X, max(counts))
     models = [_mx.GaussianMixture(c, covariance_type=covariance_type, **gmm_kwargs) for c in counts]
-    Xd = _mx._upload(X, _device())
+    Xd = _rows.upload(X, _device())
     out = {c: np.full(len(counts), np.nan) for c in criteria}
     labels = np.empty((len(counts), Xd.shape[0]), dtype=np.int64)
     for i, g in enumerate(models):

@@ -42,9 +42,8 @@ import numbers
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, _rows
 from . import cluster_metrics as _cm
-from . import mixture as _mx
 from . import projection as _pj
 
 __all__ = ["DBSCAN", "neighbor_counts", "dbscan_sweep", "k_distances", "MAX_EPS", "MAX_N"]
@@ -79,7 +78,7 @@ def _eps_list(eps_list):
     return radii
 
 
-def _rows(X, metric):
+def _device_rows(X, metric):
     """the checks that need no device, then the rows on the device"""
     return _cm._upload_pair_rows(_cm._check_pair_rows(X, metric, MAX_N), metric, _device())
 
@@ -90,12 +89,13 @@ def _counts_group(Xd, radii, metric):
     n = Xd.shape[0]
     eps = np.asarray(radii, dtype=np.float64)
     counts = torch.empty((len(radii), n), dtype=torch.int32, device=Xd.device)
+    code = _lib.dtype_code(Xd)
     if metric == 'euclidean':
-        _lib.check(lib.ava_db_counts(Xd.data_ptr(), _mx._code(Xd), n, Xd.shape[1], eps.ctypes.data, len(radii),
+        _lib.check(lib.ava_db_counts(Xd.data_ptr(), code, n, Xd.shape[1], eps.ctypes.data, len(radii),
                                      counts.data_ptr(), _lib.stream()), "ava_db_counts")
     else:
-        _lib.check(lib.ava_db_counts_pre(Xd.data_ptr(), _mx._code(Xd), n, eps.ctypes.data, len(radii),
-                                         counts.data_ptr(), _lib.stream()), "ava_db_counts_pre")
+        _lib.check(lib.ava_db_counts_pre(Xd.data_ptr(), code, n, eps.ctypes.data, len(radii), counts.data_ptr(),
+                                         _lib.stream()), "ava_db_counts_pre")
     return counts
 
 
@@ -105,10 +105,8 @@ def _labels_group(Xd, radii, min_samples, metric):
     n, e = Xd.shape[0], len(radii)
     d = Xd.shape[1] if metric == 'euclidean' else 1
     nbytes = lib.ava_db_workspace_bytes(n, d, e)
-    if nbytes == 0:
-        raise ValueError("unsupported shape: N = %d, d = %d, %d radii" % (n, d, e))
+    ws = _lib.workspace(nbytes, Xd.device, "N = %d, d = %d, %d radii" % (n, d, e))       # raises before any launch
     counts = _counts_group(Xd, radii, metric)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=Xd.device)
     eps = np.asarray(radii, dtype=np.float64)
     labels = torch.empty((e, n), dtype=torch.int64, device=Xd.device)
     core = torch.empty((e, n), dtype=torch.uint8, device=Xd.device)
@@ -116,9 +114,9 @@ def _labels_group(Xd, radii, min_samples, metric):
     tail = (eps.ctypes.data, e, min_samples, counts.data_ptr(), core.data_ptr(), labels.data_ptr(), ncl.data_ptr(),
             ws.data_ptr(), nbytes, _lib.stream())
     if metric == 'euclidean':
-        _lib.check(lib.ava_db_labels(Xd.data_ptr(), _mx._code(Xd), n, d, *tail), "ava_db_labels")
+        _lib.check(lib.ava_db_labels(Xd.data_ptr(), _lib.dtype_code(Xd), n, d, *tail), "ava_db_labels")
     else:
-        _lib.check(lib.ava_db_labels_pre(Xd.data_ptr(), _mx._code(Xd), n, *tail), "ava_db_labels_pre")
+        _lib.check(lib.ava_db_labels_pre(Xd.data_ptr(), _lib.dtype_code(Xd), n, *tail), "ava_db_labels_pre")
     return labels, core.bool(), ncl
 
 
@@ -134,7 +132,7 @@ def neighbor_counts(X, eps, metric='euclidean'):
     ``E`` radii (which share the distance passes in groups of ``MAX_EPS``).  ``X`` as for :class:`DBSCAN`."""
     single = isinstance(eps, numbers.Real) or (isinstance(eps, np.ndarray) and eps.ndim == 0)
     radii = [_check_eps(float(eps) if isinstance(eps, np.ndarray) else eps)] if single else _eps_list(eps)
-    Xd = _rows(X, metric)
+    Xd = _device_rows(X, metric)
     if _lib.load().ava_db_workspace_bytes(Xd.shape[0], Xd.shape[1] if metric == 'euclidean' else 1, 1) == 0:
         raise ValueError("unsupported shape %s" % (tuple(Xd.shape),))
     parts = [_counts_group(Xd, radii[g:g + MAX_EPS], metric) for g in range(0, len(radii), MAX_EPS)]
@@ -158,7 +156,7 @@ class DBSCAN:
 
     def fit(self, X, y=None):
         eps, min_samples = _check_eps(self.eps), _check_min_samples(self.min_samples)
-        Xd = _rows(X, self.metric)
+        Xd = _device_rows(X, self.metric)
         labels, core, ncl = _sweep_device(Xd, [eps], min_samples, self.metric)
         self.labels_ = labels[0]
         self.core_sample_indices_ = np.flatnonzero(core[0]).astype(np.int64)
@@ -194,7 +192,7 @@ def dbscan_sweep(X, eps_list, min_samples=5, metric='euclidean', scores=False):
     when there are more than ``cluster_metrics.MAX_K`` or when every remaining row is alone in its cluster."""
     radii = _eps_list(eps_list)
     min_samples = _check_min_samples(min_samples)
-    Xd = _rows(X, metric)
+    Xd = _device_rows(X, metric)
     labels, core, ncl = _sweep_device(Xd, radii, min_samples, metric)
     out = {'eps': np.asarray(radii, dtype=np.float64), 'labels': labels, 'n_clusters': ncl,
            'n_noise': (labels == -1).sum(axis=1).astype(np.int64), 'core': core}
@@ -212,6 +210,6 @@ def k_distances(X, k):
     X = _cm._check_rows(X)
     if not 1 <= k <= min(_pj.MAX_K, X.shape[0]):
         raise ValueError("k must be in [1, min(%d, n)], got %d" % (_pj.MAX_K, k))
-    Xd = _mx._upload(X, _device())
+    Xd = _rows.upload(X, _device())
     dist = _pj._knn_device(Xd, int(k))[1]
     return torch.sort(dist[:, int(k) - 1].contiguous())[0].cpu().numpy()

@@ -43,7 +43,6 @@ import torch
 
 from . import _lib
 from . import cluster_metrics as _cm
-from . import mixture as _mx
 from . import projection as _pj
 
 __all__ = ["HDBSCAN", "mutual_reachability_mst", "MAX_N"]
@@ -81,8 +80,9 @@ def _core_device(Xd, min_samples, metric):
     lib = _lib.load()
     n = int(Xd.shape[0])
     core = torch.empty(n, dtype=torch.float64, device=Xd.device)
+    code = _lib.dtype_code(Xd)
     if metric == 'precomputed':
-        _lib.check(lib.ava_hd_core_pre(Xd.data_ptr(), _mx._code(Xd), n, min_samples, core.data_ptr(), _lib.stream()),
+        _lib.check(lib.ava_hd_core_pre(Xd.data_ptr(), code, n, min_samples, core.data_ptr(), _lib.stream()),
                    "ava_hd_core_pre")
         return core
     kth = torch.empty(n, dtype=torch.int64, device=Xd.device)
@@ -90,10 +90,10 @@ def _core_device(Xd, min_samples, metric):
         q1 = min(q0 + _KNN_CHUNK, n)
         idx = torch.empty((q1 - q0, min_samples), dtype=torch.int64, device=Xd.device)
         dist = torch.empty((q1 - q0, min_samples), dtype=torch.float64, device=Xd.device)
-        _lib.check(lib.ava_pj_knn(Xd.data_ptr(), _mx._code(Xd), n, int(Xd.shape[1]), min_samples, q0, q1 - q0,
+        _lib.check(lib.ava_pj_knn(Xd.data_ptr(), code, n, int(Xd.shape[1]), min_samples, q0, q1 - q0,
                                   idx.data_ptr(), dist.data_ptr(), _lib.stream()), "ava_pj_knn")
         kth[q0:q1] = idx[:, min_samples - 1]
-    _lib.check(lib.ava_hd_core(Xd.data_ptr(), _mx._code(Xd), n, int(Xd.shape[1]), kth.data_ptr(), core.data_ptr(),
+    _lib.check(lib.ava_hd_core(Xd.data_ptr(), code, n, int(Xd.shape[1]), kth.data_ptr(), core.data_ptr(),
                                _lib.stream()), "ava_hd_core")
     return core
 
@@ -105,10 +105,8 @@ def _mst_device(Xd, core, metric, timings=None):
     n = int(Xd.shape[0])
     d = int(Xd.shape[1]) if metric == 'euclidean' else 1
     nbytes = lib.ava_hd_workspace_bytes(n, d)
-    if nbytes == 0:
-        raise ValueError("unsupported shape: N = %d, d = %d" % (n, d))
     dev = Xd.device
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    ws = _lib.workspace(nbytes, dev, "N = %d, d = %d" % (n, d))
     ei = torch.empty(n - 1, dtype=torch.int32, device=dev)
     ej = torch.empty(n - 1, dtype=torch.int32, device=dev)
     ew = torch.empty(n - 1, dtype=torch.float64, device=dev)
@@ -118,9 +116,9 @@ def _mst_device(Xd, core, metric, timings=None):
     tail = (core.data_ptr(), ei.data_ptr(), ej.data_ptr(), ew.data_ptr(), em.data_ptr(), ctypes.addressof(rounds),
             ctypes.addressof(ms) if timings is not None else None, ws.data_ptr(), nbytes, _lib.stream())
     if metric == 'euclidean':
-        _lib.check(lib.ava_hd_mst(Xd.data_ptr(), _mx._code(Xd), n, d, *tail), "ava_hd_mst")
+        _lib.check(lib.ava_hd_mst(Xd.data_ptr(), _lib.dtype_code(Xd), n, d, *tail), "ava_hd_mst")
     else:
-        _lib.check(lib.ava_hd_mst_pre(Xd.data_ptr(), _mx._code(Xd), n, *tail), "ava_hd_mst_pre")
+        _lib.check(lib.ava_hd_mst_pre(Xd.data_ptr(), _lib.dtype_code(Xd), n, *tail), "ava_hd_mst_pre")
     if timings is not None:
         timings.extend(float(ms[r]) for r in range(rounds.value))
     cols = [ew, em, ei.long(), ej.long()]

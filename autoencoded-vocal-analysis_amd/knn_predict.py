@@ -45,9 +45,8 @@ import numbers
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, _rows
 from . import cluster_metrics as _cm
-from . import mixture as _mx
 from . import projection as _pj
 
 __all__ = ["masked_kneighbors", "kfold", "group_folds", "cross_val_predict", "cross_val_score", "KNeighborsClassifier",
@@ -210,7 +209,7 @@ def _masked_device(Xd, fold_d, k):
     dist = torch.empty((n, k), dtype=torch.float64, device=Xd.device)
     for q0 in range(0, n, _KNN_CHUNK):
         nq = min(_KNN_CHUNK, n - q0)
-        _lib.check(lib.ava_kp_knn_masked(Xd.data_ptr(), _mx._code(Xd), n, d, k, fold_d.data_ptr(), q0, nq,
+        _lib.check(lib.ava_kp_knn_masked(Xd.data_ptr(), _lib.dtype_code(Xd), n, d, k, fold_d.data_ptr(), q0, nq,
                                          idx[q0:].data_ptr(), dist[q0:].data_ptr(), _lib.stream()), "ava_kp_knn_masked")
     return idx, dist
 
@@ -254,7 +253,7 @@ def masked_kneighbors(X, fold, k):
     X = _check_x(X)
     codes, _ = _check_fold(fold, int(X.shape[0]), int(k))
     dev = _device()
-    idx, dist = _masked_device(_mx._upload(X, dev), torch.from_numpy(codes).to(dev), int(k))
+    idx, dist = _masked_device(_rows.upload(X, dev), torch.from_numpy(codes).to(dev), int(k))
     return dist.cpu().numpy(), idx.cpu().numpy()
 
 
@@ -277,7 +276,7 @@ def _cross_val_device(X, y, fold, n_neighbors, weights, task):
     dev = _device()
     fold_d = torch.from_numpy(codes).to(dev)
     target_d = torch.from_numpy(target).to(dev)
-    idx, dist = _masked_device(_mx._upload(X, dev), fold_d, int(ks[-1]))
+    idx, dist = _masked_device(_rows.upload(X, dev), fold_d, int(ks[-1]))
     if task == 'classify':
         pred = _vote_device(idx, dist, target_d, ks, weighted)
     else:
@@ -402,7 +401,7 @@ class _KNeighbors:
         if int(Xq.shape[1]) != self.n_features_in_:
             raise ValueError("X has %d features, but %s is expecting %d features as input."
                              % (int(Xq.shape[1]), type(self).__name__, self.n_features_in_))
-        qd = _mx._upload(Xq, self._Xd.device).to(self._Xd.dtype)
+        qd = _rows.upload(Xq, self._Xd.device).to(self._Xd.dtype)
         return _pj._knn_query_device(qd, self._Xd, k, _KNN_CHUNK)
 
     def kneighbors(self, X=None, n_neighbors=None, return_distance=True):
@@ -423,7 +422,7 @@ class KNeighborsClassifier(_KNeighbors):
         X = self._fit_rows(X)
         self.classes_, codes = _check_classes(y, self.n_samples_fit_)
         dev = _device()
-        self._Xd = _mx._upload(X, dev)
+        self._Xd = _rows.upload(X, dev)
         self._yd = torch.from_numpy(codes).to(dev)
         return self
 
@@ -455,7 +454,7 @@ class KNeighborsRegressor(_KNeighbors):
         X = self._fit_rows(X)
         Y, self._flat = _check_targets(y, self.n_samples_fit_)
         dev = _device()
-        self._Xd = _mx._upload(X, dev)
+        self._Xd = _rows.upload(X, dev)
         self._yd = torch.from_numpy(Y).to(dev)
         return self
 

@@ -31,7 +31,7 @@ function raises ``AvaHipError``.
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, _rows
 
 __all__ = ["GaussianMixture", "e_step", "m_step", "kmeans_labels", "MAX_D", "MAX_K", "CHUNK_ROWS", "KMEANS_MAX_ITER"]
 MAX_D = 128                     # ava_gm_max_d
@@ -58,15 +58,8 @@ def _cov_code(covariance_type):
 
 def _check_rows(X, n_components=1):
     """host-side checks of the rows; returns them as they go to the device (numpy or tensor, float32 or float64)"""
-    if torch.is_tensor(X):
-        if X.dtype not in (torch.float32, torch.float64):
-            X = X.to(torch.float64)
-        shape = tuple(X.shape)
-    else:
-        X = np.asarray(X)
-        if X.dtype not in (np.float32, np.float64):
-            X = X.astype(np.float64)
-        shape = X.shape
+    X = _rows.native(X)
+    shape = tuple(X.shape)
     if len(shape) != 2 or shape[0] < 1 or shape[1] < 1:
         raise ValueError("expected a non-empty 2-D array of rows, got shape %s" % (shape,))
     n, d = shape
@@ -78,15 +71,9 @@ def _check_rows(X, n_components=1):
         raise ValueError("n_samples = %d must be at least n_components = %d" % (n, n_components))
     if n >= 2 ** 31:
         raise ValueError("at most 2**31 - 1 rows")
-    finite = bool(torch.isfinite(X).all()) if torch.is_tensor(X) else bool(np.isfinite(X).all())
-    if not finite:
+    if not _rows.is_finite(X):
         raise ValueError("the input contains NaN or infinity")
     return X
-
-
-def _upload(X, dev):
-    t = X if torch.is_tensor(X) else torch.from_numpy(np.ascontiguousarray(X))
-    return t.to(dev).contiguous()
 
 
 def _f64(a, dev, shape, what):
@@ -96,15 +83,9 @@ def _f64(a, dev, shape, what):
     return t.to(device=dev, dtype=torch.float64).contiguous()
 
 
-def _code(t):
-    return 0 if t.dtype == torch.float32 else 1
-
-
 def _workspace(n, d, k, code, dev):
     nbytes = _lib.load().ava_gm_workspace_bytes(n, d, k, code)
-    if nbytes == 0:
-        raise ValueError("unsupported shape: N = %d, d = %d, n_components = %d" % (n, d, k))
-    return torch.empty(nbytes, dtype=torch.uint8, device=dev), nbytes
+    return _lib.workspace(nbytes, dev, "N = %d, d = %d, n_components = %d" % (n, d, k)), nbytes
 
 
 def _param_shape(k, d, code):
@@ -124,9 +105,9 @@ def _e_step(Xd, weights, means, pchol, log_det, code):
     lpn = torch.empty(n, dtype=torch.float64, device=dev)
     log_resp = torch.empty((n, k), dtype=torch.float64, device=dev)
     resp = torch.empty((n, k), dtype=torch.float64, device=dev)
-    _lib.check(_lib.load().ava_gm_e_step(Xd.data_ptr(), _code(Xd), n, d, k, code, weights.data_ptr(), means.data_ptr(),
-                                         pchol.data_ptr(), log_det.data_ptr(), lpn.data_ptr(), log_resp.data_ptr(),
-                                         resp.data_ptr(), _lib.stream()), "ava_gm_e_step")
+    _lib.check(_lib.load().ava_gm_e_step(Xd.data_ptr(), _lib.dtype_code(Xd), n, d, k, code, weights.data_ptr(),
+                                         means.data_ptr(), pchol.data_ptr(), log_det.data_ptr(), lpn.data_ptr(),
+                                         log_resp.data_ptr(), resp.data_ptr(), _lib.stream()), "ava_gm_e_step")
     return lpn, log_resp, resp
 
 
@@ -139,7 +120,7 @@ def e_step(X, weights, means, precisions_cholesky, covariance_type='full'):
     k = int(np.shape(weights)[0])
     X = _check_rows(X, k)
     dev = _device()
-    Xd = _upload(X, dev)
+    Xd = _rows.upload(X, dev)
     d = Xd.shape[1]
     w = _f64(weights, dev, (k,), "weights")
     mu = _f64(means, dev, (k, d), "means")
@@ -159,10 +140,10 @@ def _m_step(Xd, resp, reg_covar, code, ws=None):
     pchol = torch.zeros(_param_shape(k, d, code), dtype=torch.float64, device=dev)
     log_det = torch.zeros(k, dtype=torch.float64, device=dev)
     status = torch.zeros(1, dtype=torch.int32, device=dev)
-    _lib.check(_lib.load().ava_gm_m_step(Xd.data_ptr(), _code(Xd), n, d, k, code, resp.data_ptr(), float(reg_covar),
-                                         weights.data_ptr(), means.data_ptr(), cov.data_ptr(), pchol.data_ptr(),
-                                         log_det.data_ptr(), status.data_ptr(), ws.data_ptr(), nbytes, _lib.stream()),
-               "ava_gm_m_step")
+    _lib.check(_lib.load().ava_gm_m_step(Xd.data_ptr(), _lib.dtype_code(Xd), n, d, k, code, resp.data_ptr(),
+                                         float(reg_covar), weights.data_ptr(), means.data_ptr(), cov.data_ptr(),
+                                         pchol.data_ptr(), log_det.data_ptr(), status.data_ptr(), ws.data_ptr(), nbytes,
+                                         _lib.stream()), "ava_gm_m_step")
     if int(status.item()) != 0:
         raise ValueError(_ILL_DEFINED)
     return weights, means, cov, pchol, log_det
@@ -181,7 +162,7 @@ def m_step(X, resp, reg_covar=1e-6, covariance_type='full'):
     k = int(np.shape(resp)[1])
     X = _check_rows(X, k)
     dev = _device()
-    Xd = _upload(X, dev)
+    Xd = _rows.upload(X, dev)
     r = _f64(resp, dev, (Xd.shape[0], k), "resp")
     return _m_step(Xd, r, reg_covar, code)
 
@@ -194,9 +175,7 @@ def _kmeans(Xd, seeds):
     k = len(seeds)
     centres = Xd[torch.as_tensor(np.asarray(seeds, dtype=np.int64), device=dev)].to(torch.float64).contiguous()
     nn_bytes = lib.ava_nn_workspace_bytes(n, k, d, 1)
-    if nn_bytes == 0:
-        raise ValueError("unsupported shape: N = %d, d = %d, n_components = %d" % (n, d, k))
-    nn_ws = torch.empty(nn_bytes, dtype=torch.uint8, device=dev)
+    nn_ws = _lib.workspace(nn_bytes, dev, "N = %d, d = %d, n_components = %d" % (n, d, k))
     ws, nbytes = _workspace(n, d, k, 1, dev)
     labels = torch.empty(n, dtype=torch.int64, device=dev)
     dist = torch.empty(n, dtype=torch.float64, device=dev)
@@ -209,15 +188,16 @@ def _kmeans(Xd, seeds):
     st = _lib.stream()
     rounds = 0
     for _ in range(KMEANS_MAX_ITER):
-        _lib.check(lib.ava_nn_argmin(Xd.data_ptr(), _code(Xd), n, centres.data_ptr(), 1, k, d, 1, labels.data_ptr(),
-                                     dist.data_ptr(), nn_ws.data_ptr(), nn_bytes, st), "ava_nn_argmin")
+        _lib.check(lib.ava_nn_argmin(Xd.data_ptr(), _lib.dtype_code(Xd), n, centres.data_ptr(), 1, k, d, 1,
+                                     labels.data_ptr(), dist.data_ptr(), nn_ws.data_ptr(), nn_bytes, st),
+                   "ava_nn_argmin")
         changed.zero_()
         _lib.check(lib.ava_gm_onehot(labels.data_ptr(), prev.data_ptr(), n, k, resp.data_ptr(), changed.data_ptr(), st),
                    "ava_gm_onehot")
         rounds += 1
         if int(changed.item()) == 0:
             break
-        _lib.check(lib.ava_gm_means(Xd.data_ptr(), _code(Xd), n, d, k, resp.data_ptr(), weights.data_ptr(),
+        _lib.check(lib.ava_gm_means(Xd.data_ptr(), _lib.dtype_code(Xd), n, d, k, resp.data_ptr(), weights.data_ptr(),
                                     means.data_ptr(), nk.data_ptr(), ws.data_ptr(), nbytes, st), "ava_gm_means")
         centres = torch.where(nk[:, None] > 0.5, means, centres).contiguous()       # an empty cluster keeps its centre
     return labels, resp, rounds
@@ -232,7 +212,7 @@ def kmeans_labels(X, seeds):
     X = _check_rows(X, len(seeds))
     if seeds.ndim != 1 or len(seeds) < 1 or seeds.min() < 0 or seeds.max() >= X.shape[0]:
         raise ValueError("seeds must be row indices")
-    labels, _, rounds = _kmeans(_upload(X, _device()), seeds)
+    labels, _, rounds = _kmeans(_rows.upload(X, _device()), seeds)
     return labels.cpu().numpy(), rounds
 
 
@@ -347,7 +327,7 @@ class GaussianMixture:
                 means = torch.empty((k, d), dtype=torch.float64, device=dev)
                 nk = torch.empty(k, dtype=torch.float64, device=dev)
                 ws1 = _workspace(n, d, k, 1, dev)
-                _lib.check(_lib.load().ava_gm_means(Xd.data_ptr(), _code(Xd), n, d, k, resp.data_ptr(),
+                _lib.check(_lib.load().ava_gm_means(Xd.data_ptr(), _lib.dtype_code(Xd), n, d, k, resp.data_ptr(),
                                                     weights.data_ptr(), means.data_ptr(), nk.data_ptr(),
                                                     ws1[0].data_ptr(), ws1[1], _lib.stream()), "ava_gm_means")
         if w0 is not None:
@@ -379,9 +359,9 @@ class GaussianMixture:
         stopped = False
         for it0 in range(0, self.max_iter, self.iter_block):
             n_iters = min(self.iter_block, self.max_iter - it0)
-            _lib.check(lib.ava_gm_fit(Xd.data_ptr(), _code(Xd), n, d, k, code, weights.data_ptr(), means.data_ptr(),
-                                      cov.data_ptr(), pchol.data_ptr(), log_det.data_ptr(), self.tol, self.reg_covar,
-                                      it0, n_iters, bounds.data_ptr(), ctl.data_ptr(), lpn.data_ptr(),
+            _lib.check(lib.ava_gm_fit(Xd.data_ptr(), _lib.dtype_code(Xd), n, d, k, code, weights.data_ptr(),
+                                      means.data_ptr(), cov.data_ptr(), pchol.data_ptr(), log_det.data_ptr(), self.tol,
+                                      self.reg_covar, it0, n_iters, bounds.data_ptr(), ctl.data_ptr(), lpn.data_ptr(),
                                       log_resp.data_ptr(), resp.data_ptr(), ws[0].data_ptr(), ws[1], _lib.stream()),
                        "ava_gm_fit")
             host = ctl.cpu().numpy()                       # the only host read of a block
@@ -399,7 +379,7 @@ class GaussianMixture:
         n, d = X.shape
         w0, mu0, prec0 = self._check_init(d)
         dev = _device()
-        Xd = _upload(X, dev)
+        Xd = _rows.upload(X, dev)
         code = _COV[self.covariance_type]
         ws = _workspace(n, d, self.n_components, code, dev)
         rs = _random_state(self.random_state)
@@ -427,7 +407,7 @@ class GaussianMixture:
         X = _check_rows(X, 1)
         if X.shape[1] != self.n_features_in_:
             raise ValueError("X has %d features, the model was fitted with %d" % (X.shape[1], self.n_features_in_))
-        Xd = _upload(X, self._params[0].device)
+        Xd = _rows.upload(X, self._params[0].device)
         weights, means, _, pchol, log_det = self._params
         return _e_step(Xd, weights, means, pchol, log_det, _COV[self.covariance_type])
 

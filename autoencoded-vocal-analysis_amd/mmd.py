@@ -29,7 +29,7 @@ without the HIP library / a GPU every function raises ``AvaHipError``.
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, _rows
 
 EPSILON = 1e-8          # ava/plotting/mmd_plots.py:34
 
@@ -48,9 +48,7 @@ def _device():
 
 def _latent_dev(latent):
     """[N, z] float64 on the device (accepts the numpy array VAE.get_latent returns, or a tensor already there)."""
-    dev = _device()
-    t = latent if torch.is_tensor(latent) else torch.from_numpy(np.ascontiguousarray(latent, dtype=np.float64))
-    t = t.to(device=dev, dtype=torch.float64).contiguous()
+    t = _rows.upload(latent, _device(), torch.float64)
     if t.dim() != 2 or t.shape[1] < 1 or t.shape[1] > 128:
         raise ValueError("latent must be [N, z] with 1 <= z <= 128")
     return t
@@ -86,7 +84,7 @@ def _terms(L, i1, i2, sigma):
     lib = _lib.load()
     d1, d2 = _index_dev(i1, len(L)), _index_dev(i2, len(L))
     nbytes = lib.ava_mmd2_workspace_bytes(n1, n2)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=L.device)
+    ws = _lib.workspace(nbytes, L.device, "%d and %d rows" % (n1, n2))
     out = torch.empty(4, dtype=torch.float64, device=L.device)
     _lib.check(lib.ava_mmd2(L.data_ptr(), L.shape[1], d1.data_ptr(), n1, d2.data_ptr(), n2, float(sigma),
                             out.data_ptr(), ws.data_ptr(), nbytes, _lib.stream()), "ava_mmd2")
@@ -205,7 +203,7 @@ def _launch_matrix(latent, plan, sigma, linear):
     nbytes = lib.ava_mmd2_matrix_workspace_bytes(offsets.ctypes.data, C, int(linear))
     if nbytes == 0:
         raise _lib.AvaHipError("ava_mmd2_matrix_workspace_bytes: unsupported grouping (%d conditions)" % C)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=L.device)
+    ws = _lib.workspace(nbytes, L.device, "MMD matrix")
     out = (torch.zeros if linear else torch.empty)(C * C + C, dtype=torch.float64, device=L.device)
     if linear:
         _lib.check(lib.ava_mmd2_matrix_linear(L.data_ptr(), L.shape[1], idx.data_ptr(), offsets.ctypes.data,
@@ -364,7 +362,7 @@ def _run_perm(L, idx, table, n_perm, seed, sigma, max_bytes, want_null):
     nbytes = lib.ava_mmd2_perm_workspace_bytes(table.ctypes.data, n_prob, k)
     if nbytes == 0:
         raise _lib.AvaHipError("ava_mmd2_perm_workspace_bytes: unsupported problem table (%d problems)" % n_prob)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=L.device)
+    ws = _lib.workspace(nbytes, L.device, "MMD permutations")
     mem = torch.empty(k * int(table[-1, 5]), dtype=torch.uint8, device=L.device)
     terms = torch.empty(n_prob * k * 3, dtype=torch.float64, device=L.device)
     stats = torch.empty(n_prob * k, dtype=torch.float64, device=L.device)

@@ -15,13 +15,13 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._rows import native, upload       # by name: ``_rows`` here is this module's reshaping function
 
 __all__ = ["nearest", "METRICS", "MAX_DIM", "DEFAULT_CHUNK_BYTES"]
 
 METRICS = {'correlation': 0, 'euclidean': 1}
 MAX_DIM = 65536
 DEFAULT_CHUNK_BYTES = 1 << 30        # host references uploaded per launch when chunk_rows is not given
-_DTYPE_CODES = {np.dtype(np.float32): 0, np.dtype(np.float64): 1}
 
 
 def _device():
@@ -33,14 +33,7 @@ def _rows(x, d, what):
     takes the row length from ``x`` itself: a 1-D ``x`` is one row, otherwise ``reshape(-1, prod(shape[1:]))``."""
     if torch.is_tensor(x) and x.device.type != "cuda":
         x = x.detach().numpy()
-    if torch.is_tensor(x):
-        x = x.detach()
-        if x.dtype not in (torch.float32, torch.float64):
-            x = x.double()
-    else:
-        x = np.asarray(x)
-        if x.dtype not in _DTYPE_CODES:
-            x = x.astype(np.float64)
+    x = native(x.detach() if torch.is_tensor(x) else x)
     shape = tuple(x.shape)
     n_el = int(np.prod(shape, dtype=np.int64))
     if d is None:
@@ -50,16 +43,6 @@ def _rows(x, d, what):
     if d < 1 or n_el == 0 or n_el % d:
         raise ValueError("%s of shape %s cannot be reshaped to [-1, %d]" % (what, shape, d))
     return x.reshape(-1, d)
-
-
-def _code(x):
-    return 0 if x.dtype in (torch.float32, np.float32) else 1
-
-
-def _upload(x, dev):
-    if torch.is_tensor(x):
-        return x.contiguous()
-    return torch.from_numpy(np.ascontiguousarray(x)).to(dev)
 
 
 def nearest(queries, refs, metric='correlation', chunk_rows=None):
@@ -89,22 +72,22 @@ def nearest(queries, refs, metric='correlation', chunk_rows=None):
     code = METRICS[metric]
     lib = _lib.load()
     nbytes = lib.ava_nn_workspace_bytes(nq, chunk_rows, d, code)
-    if nbytes == 0:
+    if nbytes == 0:                                     # refused here, before the device is asked for
         raise ValueError("unsupported shape: %d queries, %d references of length %d" % (nq, chunk_rows, d))
     dev = _device()
-    qd = _upload(q, dev)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    qd = upload(q, dev)
+    ws = _lib.workspace(nbytes, dev, "nearest")
     best_idx = torch.empty(nq, dtype=torch.int64, device=dev)
     best_dist = torch.empty(nq, dtype=torch.float64, device=dev)
     idx = torch.empty_like(best_idx) if chunk_rows < nr else best_idx
     dist = torch.empty_like(best_dist) if chunk_rows < nr else best_dist
     st = _lib.stream()
     for start in range(0, nr, chunk_rows):
-        rd = _upload(r[start:start + chunk_rows], dev)
+        rd = upload(r[start:start + chunk_rows], dev)
         n = int(rd.shape[0])
         oi, od = (best_idx, best_dist) if start == 0 else (idx, dist)
-        _lib.check(lib.ava_nn_argmin(qd.data_ptr(), _code(qd), nq, rd.data_ptr(), _code(rd), n, d, code, oi.data_ptr(),
-                                     od.data_ptr(), ws.data_ptr(), nbytes, st), "ava_nn_argmin")
+        _lib.check(lib.ava_nn_argmin(qd.data_ptr(), _lib.dtype_code(qd), nq, rd.data_ptr(), _lib.dtype_code(rd), n, d,
+                                     code, oi.data_ptr(), od.data_ptr(), ws.data_ptr(), nbytes, st), "ava_nn_argmin")
         if start:
             _lib.check(lib.ava_nn_merge(best_idx.data_ptr(), best_dist.data_ptr(), idx.data_ptr(), dist.data_ptr(), nq,
                                         start, code, st), "ava_nn_merge")

@@ -48,7 +48,7 @@ import numpy as np
 import scipy.sparse
 import torch
 
-from . import _lib
+from . import _lib, _rows
 
 __all__ = ["UMAP", "TransformableUMAP", "pca_projection", "install", "knn", "knn_query", "smooth_knn",
            "smooth_knn_bipartite", "transform_init", "transform_layout", "fuzzy_union", "find_ab_params",
@@ -65,28 +65,18 @@ def _device():
     return _lib.device("projection")
 
 
-def _as_rows(X, dtype):
-    """``X`` as a contiguous 2-D device tensor of ``dtype`` (numpy arrays and host tensors are uploaded)."""
-    if torch.is_tensor(X):
-        t = X.detach()
-    else:
-        t = torch.from_numpy(np.ascontiguousarray(np.asarray(X)))
-    if t.dim() != 2 or t.shape[0] < 1 or t.shape[1] < 1:
+def _as_rows(X, dtype=None):
+    """``X`` as a contiguous 2-D device tensor of ``dtype`` (numpy arrays and host tensors are uploaded); without
+    ``dtype`` float32 / float64 inputs are read as they are, everything else as float64."""
+    t = X.detach() if torch.is_tensor(X) else np.asarray(X)
+    if dtype is None:
+        t = _rows.native(t)
+    if t.ndim != 2 or t.shape[0] < 1 or t.shape[1] < 1:
         raise ValueError("expected a non-empty 2-D array, got shape %s" % (tuple(t.shape),))
-    t = t.to(device=_device(), dtype=dtype).contiguous()
-    if not bool(torch.isfinite(t).all()):
+    t = _rows.upload(t, _device(), dtype)
+    if not _rows.is_finite(t):
         raise ValueError("input contains NaN or infinity")
     return t
-
-
-def _native_dtype(X):
-    """float32 / float64 inputs are read as they are, everything else as float64"""
-    dt = X.dtype if torch.is_tensor(X) else torch.from_numpy(np.zeros(0, dtype=np.asarray(X).dtype)).dtype
-    return dt if dt in (torch.float32, torch.float64) else torch.float64
-
-
-def _code(t):
-    return 0 if t.dtype == torch.float32 else 1
 
 
 METRICS = ('euclidean', 'correlation')     # of knn / knn_query
@@ -104,7 +94,7 @@ def _row_stats_device(xd):
     if d > MAX_DIM or n >= 2 ** 31:
         raise ValueError("unsupported shape [%d, %d]" % (n, d))
     stats = torch.empty((n, 2), dtype=torch.float64, device=xd.device)
-    _lib.check(_lib.load().ava_pj_row_stats(xd.data_ptr(), _code(xd), n, d, stats.data_ptr(), _lib.stream()),
+    _lib.check(_lib.load().ava_pj_row_stats(xd.data_ptr(), _lib.dtype_code(xd), n, d, stats.data_ptr(), _lib.stream()),
                "ava_pj_row_stats")
     return stats
 
@@ -133,7 +123,7 @@ def _knn_device(xd, k, chunk_rows=None, qd=None, metric='euclidean', xstat=None)
     idx = torch.empty((m, k), dtype=torch.int64, device=xd.device)
     dist = torch.empty((m, k), dtype=torch.float64, device=xd.device)
     st = _lib.stream()
-    corr = metric == 'correlation'
+    corr, code = metric == 'correlation', _lib.dtype_code(xd)
     if corr:
         if xstat is None:
             xstat = _row_stats_device(xd)
@@ -144,14 +134,14 @@ def _knn_device(xd, k, chunk_rows=None, qd=None, metric='euclidean', xstat=None)
         nq = min(chunk_rows, m - q0)
         out = (k, q0, nq, idx[q0:].data_ptr(), dist[q0:].data_ptr(), st)
         if corr and qd is None:
-            _lib.check(lib.ava_pj_knn_corr(xd.data_ptr(), _code(xd), xstat.data_ptr(), n, d, *out), "ava_pj_knn_corr")
+            _lib.check(lib.ava_pj_knn_corr(xd.data_ptr(), code, xstat.data_ptr(), n, d, *out), "ava_pj_knn_corr")
         elif corr:
-            _lib.check(lib.ava_pj_knn_corr_query(qd.data_ptr(), xd.data_ptr(), _code(xd), qstat.data_ptr(),
-                                                 xstat.data_ptr(), m, n, d, *out), "ava_pj_knn_corr_query")
+            _lib.check(lib.ava_pj_knn_corr_query(qd.data_ptr(), xd.data_ptr(), code, qstat.data_ptr(), xstat.data_ptr(),
+                                                 m, n, d, *out), "ava_pj_knn_corr_query")
         elif qd is None:
-            _lib.check(lib.ava_pj_knn(xd.data_ptr(), _code(xd), n, d, *out), "ava_pj_knn")
+            _lib.check(lib.ava_pj_knn(xd.data_ptr(), code, n, d, *out), "ava_pj_knn")
         else:
-            _lib.check(lib.ava_pj_knn_query(qd.data_ptr(), xd.data_ptr(), _code(xd), m, n, d, *out), "ava_pj_knn_query")
+            _lib.check(lib.ava_pj_knn_query(qd.data_ptr(), xd.data_ptr(), code, m, n, d, *out), "ava_pj_knn_query")
     return idx, dist
 
 
@@ -169,7 +159,7 @@ def knn(X, k, chunk_rows=None, metric='euclidean'):
     centred sum of squares is exactly 0, and then the distance is 0 to another constant row and 1 to any other, so
     every distance is finite."""
     _check_metric(metric)
-    xd = _as_rows(X, _native_dtype(X))
+    xd = _as_rows(X)
     idx, dist = _knn_device(xd, int(k), chunk_rows, metric=metric)
     return idx.cpu().numpy(), dist.cpu().numpy()
 
@@ -180,7 +170,7 @@ def knn_query(Q, X, k, chunk_rows=None, metric='euclidean'):
     excluded: under the euclidean metric a query that is a copy of reference row ``r`` gets ``(r, 0.0)`` first.  ``Q``
     is read in the dtype of ``X``.  ``chunk_rows`` query rows go to one launch; the result does not depend on it."""
     _check_metric(metric)
-    xd = _as_rows(X, _native_dtype(X))
+    xd = _as_rows(X)
     qd = _as_rows(Q, xd.dtype)
     idx, dist = _knn_query_device(qd, xd, int(k), chunk_rows, metric)
     return idx.cpu().numpy(), dist.cpu().numpy()
@@ -621,7 +611,7 @@ def pca_projection(X, n_components=2):
     ``[N, n_components]``) through sklearn 1.7's ``covariance_eigh`` path: the device sums the columns and ``X^T X``,
     the host forms the covariance, runs ``eigh`` and fixes the signs as ``svd_flip(u_based_decision=False)``, and the
     device projects ``X V^T - mu V^T``."""
-    xd = _as_rows(X, _native_dtype(X))
+    xd = _as_rows(X)
     n, d = int(xd.shape[0]), int(xd.shape[1])
     if int(n_components) != n_components or not 1 <= n_components <= min(n, d):
         raise ValueError("n_components must be an integer in [1, min(n, d)] = [1, %d], got %r"
@@ -632,10 +622,10 @@ def pca_projection(X, n_components=2):
         raise ValueError("row length %d exceeds %d" % (d, MAX_PCA_DIM))
     lib = _lib.load()
     nbytes = lib.ava_pj_gram_workspace_bytes(n, d)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=xd.device)
+    ws = _lib.workspace(nbytes, xd.device, "[%d, %d]" % (n, d))
     gram = torch.empty((d + 1, d + 1), dtype=torch.float64, device=xd.device)
     st = _lib.stream()
-    _lib.check(lib.ava_pj_gram(xd.data_ptr(), _code(xd), n, d, gram.data_ptr(), ws.data_ptr(), nbytes, st),
+    _lib.check(lib.ava_pj_gram(xd.data_ptr(), _lib.dtype_code(xd), n, d, gram.data_ptr(), ws.data_ptr(), nbytes, st),
                "ava_pj_gram")
     g = gram.cpu().numpy()
     mean = g[:d, d] / n
@@ -649,7 +639,7 @@ def pca_projection(X, n_components=2):
     Vd = torch.from_numpy(V).to(xd.device)
     mud = torch.from_numpy(np.ascontiguousarray(muv.ravel())).to(xd.device)
     out = torch.empty((n, n_components), dtype=torch.float64, device=xd.device)
-    _lib.check(lib.ava_pj_project(xd.data_ptr(), _code(xd), n, d, Vd.data_ptr(), mud.data_ptr(), n_components,
+    _lib.check(lib.ava_pj_project(xd.data_ptr(), _lib.dtype_code(xd), n, d, Vd.data_ptr(), mud.data_ptr(), n_components,
                                   out.data_ptr(), st), "ava_pj_project")
     return out.cpu().numpy()
 

@@ -157,8 +157,7 @@ def _trace(audio, frame_off, p, dt, want_spec=False):
     gw = torch.from_numpy(w).to(dev)
     trace = torch.empty(frames, dtype=torch.float64 if tdt == np.float64 else torch.float32, device=dev)
     spec = torch.empty((i2 - i1, frames), dtype=torch.float64, device=dev) if want_spec else None
-    nbytes = lib.ava_amp_workspace_bytes(frames)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    ws = _lib.workspace(lib.ava_amp_workspace_bytes(frames), dev, "%d frames" % frames)
     rc = lib.ava_amp_trace(audio.samples.data_ptr(), audio.code, audio.file_off.data_ptr(), audio.file_len.data_ptr(),
                            fo.data_ptr(), len(audio), frames, nperseg, noverlap, window.data_ptr(), scale, i1, i2,
                            float(p['spec_min_val']), float(p['spec_max_val']), 1 if softmax else 0, temperature,

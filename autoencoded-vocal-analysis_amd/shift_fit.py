@@ -107,7 +107,7 @@ def _template(x, shifts, lam, l2, mbar, template, ws):
 
 def _workspace(x):
     K, F, T = x.shape
-    return torch.empty(_lib.load().ava_shiftfit_workspace_bytes(K, F, T), dtype=torch.uint8, device=x.device)
+    return _lib.workspace(_lib.load().ava_shiftfit_workspace_bytes(K, F, T), x.device, "[%d, %d, %d]" % (K, F, T))
 
 
 def _apply(x, shifts):

@@ -100,8 +100,7 @@ def _xcorr(band, template, keep):
     offs = torch.from_numpy(np.stack([lag_off, tile_off])).to(dev)
     tm = torch.from_numpy(np.ascontiguousarray(template, dtype=np.float64)).to(dev)
     trace = torch.empty(lags, dtype=torch.float64, device=dev)
-    nbytes = lib.ava_tpl_workspace_bytes(lags)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    ws = _lib.workspace(lib.ava_tpl_workspace_bytes(lags), dev, "%d lags" % lags)
     rc = lib.ava_tpl_xcorr(spec.data_ptr(), fsum.data_ptr(), spec.shape[0], spec.shape[1], fo.data_ptr(),
                            offs[0].data_ptr(), offs[1].data_ptr(), len(T), lags, int(tile_off[-1]), tm.data_ptr(), F, L,
                            trace.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream())

@@ -30,7 +30,7 @@ There is no CPU fallback: without the HIP library / a GPU every device function 
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, _rows
 
 __all__ = ["TSNE", "squared_distances", "joint_probabilities", "kl_gradient", "descend", "schedule", "MAX_N",
            "N_ITER_CHECK", "EXPLORATION_MAX_ITER"]
@@ -69,7 +69,7 @@ def _workspace(n, col_chunks, dev):
     nbytes = _lib.load().ava_ts_workspace_bytes(n, 0 if col_chunks is None else int(col_chunks))
     if nbytes == 0:
         raise ValueError("unsupported N = %d or col_chunks = %r" % (n, col_chunks))
-    return torch.empty(nbytes, dtype=torch.uint8, device=dev), nbytes
+    return _lib.workspace(nbytes, dev, "t-SNE"), nbytes
 
 
 def _pairs(t, n, what):
@@ -91,27 +91,24 @@ def squared_distances(X, metric='euclidean', round_float32=True):
     dev = _device()
     lib = _lib.load()
     if metric == 'euclidean':
-        t = X if torch.is_tensor(X) else torch.from_numpy(np.ascontiguousarray(X))
-        if t.dtype not in (torch.float32, torch.float64):
-            t = t.to(torch.float64)
-        t = t.to(dev).contiguous()
+        t = _rows.upload(_rows.native(X), dev)
         if t.dim() != 2 or not 1 <= t.shape[1] <= 65536:
             raise ValueError("X must be [N, d] with 1 <= d <= 65536")
         n, d = t.shape
         if not 2 <= n <= MAX_N:
             raise ValueError("t-SNE needs 2 <= N <= %d rows, got %d" % (MAX_N, n))
         out = _matrix(n, dev)
-        _lib.check(lib.ava_ts_sqdist(t.data_ptr(), 0 if t.dtype == torch.float32 else 1, n, d, int(bool(round_float32)),
-                                     out.data_ptr(), out.stride(0), _lib.stream()), "ava_ts_sqdist")
+        _lib.check(lib.ava_ts_sqdist(t.data_ptr(), _lib.dtype_code(t), n, d, int(bool(round_float32)), out.data_ptr(),
+                                     out.stride(0), _lib.stream()), "ava_ts_sqdist")
         return out
     if metric == 'precomputed':
-        t = X if torch.is_tensor(X) else torch.from_numpy(np.ascontiguousarray(X, dtype=np.float64))
-        if t.dim() != 2 or t.shape[0] != t.shape[1]:
+        t = X if torch.is_tensor(X) else np.asarray(X)
+        if t.ndim != 2 or t.shape[0] != t.shape[1]:
             raise ValueError("a precomputed distance matrix must be square, got shape %s" % (tuple(t.shape),))
         n = t.shape[0]
         if not 2 <= n <= MAX_N:
             raise ValueError("t-SNE needs 2 <= N <= %d rows, got %d" % (MAX_N, n))
-        t = t.to(device=dev, dtype=torch.float64).contiguous()
+        t = _rows.upload(t, dev, torch.float64)
         out = _matrix(n, dev)
         _lib.check(lib.ava_ts_square(t.data_ptr(), n, out.data_ptr(), out.stride(0), _lib.stream()), "ava_ts_square")
         return out
@@ -256,15 +253,9 @@ class TSNE:
 
     def _check(self, X):
         """host-side checks of the input; returns it as it goes to the device"""
-        if torch.is_tensor(X):
-            shape, finite = tuple(X.shape), bool(torch.isfinite(X).all())
-            negative = self.metric == 'precomputed' and bool((X < 0).any())
-        else:
-            X = np.asarray(X)
-            if X.dtype not in (np.float32, np.float64):
-                X = X.astype(np.float64)
-            shape, finite = X.shape, bool(np.isfinite(X).all())
-            negative = self.metric == 'precomputed' and bool((X < 0).any())
+        X = _rows.native(X)
+        shape, finite = tuple(X.shape), _rows.is_finite(X)
+        negative = self.metric == 'precomputed' and bool((X < 0).any())
         if len(shape) != 2:
             raise ValueError("expected a 2-D array, got shape %s" % (shape,))
         if self.metric == 'precomputed' and shape[0] != shape[1]:

@@ -361,7 +361,7 @@ class DeviceWarpedWindowDataset:
             raise _lib.AvaHipError("ava_warp_cache_bytes: unsupported shape")
         window, scale = _stft_constants(geo[3], self.device)
         cache = torch.zeros(nbytes, dtype=torch.uint8, device=self.device)       # padding included: two builds are equal bytes
-        ws = torch.empty(wbytes, dtype=torch.uint8, device=self.device)
+        ws = _lib.workspace(wbytes, self.device, "warp cache")
         rc = lib.ava_warp_cache_build(audio.samples.data_ptr(), audio.code, audio.file_off.data_ptr(),
                                       audio.file_len.data_ptr(), *geo, window.data_ptr(), scale, *band, 1,
                                       cache.data_ptr(), cache.numel(), ws.data_ptr(), ws.numel(), _lib.stream())

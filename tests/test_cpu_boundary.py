@@ -25,6 +25,41 @@ def test_library_exports_every_declared_symbol():
     assert lib.ava_version() >= 100
 
 
+def test_header_mirror():
+    """every declaration of include/ava_hip.h has its ctypes mirror in _lib.SIGNATURES: the return type and every
+    argument.  A pointer, an ava_stream_t or an array parameter may be mirrored by c_void_p, by c_char_p where it points
+    to char, or by POINTER of the pointee's own mirror; a scalar has exactly one mirror."""
+    import ctypes
+    scalar = {"int": ctypes.c_int, "float": ctypes.c_float, "double": ctypes.c_double, "size_t": ctypes.c_size_t,
+              "int64_t": ctypes.c_int64, "uint64_t": ctypes.c_uint64}
+    header = open(os.path.join(ROOT, "include", "ava_hip.h")).read()
+    decls = re.findall(r"^((?:const )?\w+\s*\*?)\s*(ava_[a-z0-9_]+)\(([^;{]*)\);", header, flags=re.M)
+    assert sorted(d[1] for d in decls) == sorted(_lib.SIGNATURES) and len(decls) == 167
+    families = {"ava_gm_": 9, "ava_sil_": 7, "ava_db_": 10, "ava_hd_": 7, "ava_kp_": 7}
+    assert {p: sum(d[1].startswith(p) for d in decls) for p in families} == families
+
+    def mirrors(ctype, got):
+        """whether ``got`` mirrors the C type ``ctype`` (a parameter's, its name removed, or a return type)"""
+        ctype = ctype.replace("const ", "").strip()
+        if ctype == "ava_stream_t":
+            return got is ctypes.c_void_p
+        if ctype.endswith("*"):
+            pointee = ctype[:-1].strip()
+            return (got is ctypes.c_void_p or (pointee == "char" and got is ctypes.c_char_p)
+                    or (pointee in scalar and got is ctypes.POINTER(scalar[pointee]))
+                    or (pointee.endswith("*") and got is ctypes.POINTER(ctypes.c_void_p)))
+        return got is (None if ctype == "void" else scalar[ctype])
+
+    for res, name, args in decls:
+        got_res, got_args = _lib.SIGNATURES[name]
+        assert mirrors(" ".join(res.split()), got_res), name
+        want = [] if args.strip() == "void" else [" ".join(a.split()) for a in args.split(",")]
+        assert len(got_args) == len(want), name
+        for arg, got in zip(want, got_args):
+            m = re.fullmatch(r"(.*?)\s*\b\w+(\[\d*\])?", arg)          # the type, the name, an array suffix
+            assert mirrors(m.group(1) + ("*" if m.group(2) else ""), got), (name, arg)
+
+
 @pytest.mark.parametrize("z", [8, 32, 64, 100])
 def test_arena_layout_mirror(z):
     lib = _lib.load()

@@ -6,16 +6,13 @@ Bounds: the golden file stores, per case and quantity, the reference-side noise 
 restatement| where the file was written and |sklearn - sklearn on the rows in reversed order|, relative to
 max |sklearn|).  The restatement is held within 4 x that floor plus the rounding bound derived in silhouette_cases.py,
 relative to the largest wanted value."""
-import ctypes
-import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
 import silhouette_cases as SC
-from conftest import ROOT, load_golden
+from conftest import load_golden
 from ava_amd import _lib
 from ava_amd import cluster_metrics as CM
 from ava_amd import mixture as M
@@ -185,26 +182,6 @@ def test_host_formulas_from_exact_sums():
 
 
 # ---- the C ABI ---------------------------------------------------------------------------------------------------------
-def test_header_mirror():
-    """every ava_sil_* declaration of include/ava_hip.h has its ctypes mirror, argument by argument"""
-    header = open(os.path.join(ROOT, "include", "ava_hip.h")).read()
-    decls = re.findall(r"^(int|size_t) (ava_sil_[a-z_]+)\(([^;]*)\);", header, flags=re.M)
-    assert sorted(d[1] for d in decls) == sorted(n for n in _lib.SIGNATURES if n.startswith("ava_sil_"))
-    assert len(decls) == 7
-
-    def ctype(arg):
-        arg = " ".join(arg.split())
-        if "*" in arg or arg.startswith("ava_stream_t"):
-            return ctypes.c_void_p
-        return {"int": ctypes.c_int, "double": ctypes.c_double, "size_t": ctypes.c_size_t}[arg.rsplit(" ", 1)[0]]
-
-    for res, name, args in decls:
-        want = [] if args.strip() == "void" else [ctype(a) for a in args.split(",")]
-        got_res, got_args = _lib.SIGNATURES[name]
-        assert got_res is (ctypes.c_int if res == "int" else ctypes.c_size_t), name
-        assert got_args == want, name
-
-
 def up256(x):
     return (x + 255) // 256 * 256
 

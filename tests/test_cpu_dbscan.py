@@ -3,16 +3,13 @@
 argument checks that need no device and the C ABI's mirror and refusals.
 
 All label comparisons are exact: the labels are determined by the data (dbscan_cases.py), so there is no tolerance."""
-import ctypes
-import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
 import dbscan_cases as DC
-from conftest import ROOT, load_golden
+from conftest import load_golden
 from ava_amd import _lib
 from ava_amd import dbscan as DB
 
@@ -188,26 +185,6 @@ def test_constructor_keeps_its_parameters():
 
 
 # ---- the C ABI ---------------------------------------------------------------------------------------------------------
-def test_header_mirror():
-    """every ava_db_* declaration of include/ava_hip.h has its ctypes mirror, argument by argument"""
-    header = open(os.path.join(ROOT, "include", "ava_hip.h")).read()
-    decls = re.findall(r"^(int|size_t) (ava_db_[a-z_]+)\(([^;]*)\);", header, flags=re.M)
-    assert sorted(d[1] for d in decls) == sorted(n for n in _lib.SIGNATURES if n.startswith("ava_db_"))
-    assert len(decls) == 10
-
-    def ctype(arg):
-        arg = " ".join(arg.split())
-        if "*" in arg or arg.startswith("ava_stream_t"):
-            return ctypes.c_void_p
-        return {"int": ctypes.c_int, "double": ctypes.c_double, "size_t": ctypes.c_size_t}[arg.rsplit(" ", 1)[0]]
-
-    for res, name, args in decls:
-        want = [] if args.strip() == "void" else [ctype(a) for a in args.split(",")]
-        got_res, got_args = _lib.SIGNATURES[name]
-        assert got_res is (ctypes.c_int if res == "int" else ctypes.c_size_t), name
-        assert got_args == want, name
-
-
 def up256(x):
     return (x + 255) // 256 * 256
 

@@ -7,15 +7,12 @@ restatement| where the file was written and |sklearn - sklearn on rows perturbed
 max |sklearn|).  The restatement is held within 4 x that floor, the project's usual margin over reference-side noise;
 a floor below 1e-15 (4.5 ulp, the resolution of a stored fp64 result of a few operations) counts as 1e-15, because
 another BLAS build may round a sum that happened to agree bit for bit here differently."""
-import ctypes
-import os
-import re
 
 import numpy as np
 import pytest
 
 import gmm_cases as GC
-from conftest import ROOT, load_golden
+from conftest import load_golden
 from ava_amd import _lib
 from ava_amd import mixture as M
 
@@ -246,26 +243,6 @@ def test_n_parameters_matches_sklearn():
 
 
 # ---- the C ABI ---------------------------------------------------------------------------------------------------------
-def test_header_mirror():
-    """every ava_gm_* declaration of include/ava_hip.h has its ctypes mirror, argument by argument"""
-    header = open(os.path.join(ROOT, "include", "ava_hip.h")).read()
-    decls = re.findall(r"^(int|size_t) (ava_gm_[a-z_]+)\(([^;]*)\);", header, flags=re.M)
-    assert sorted(d[1] for d in decls) == sorted(n for n in _lib.SIGNATURES if n.startswith("ava_gm_"))
-    assert len(decls) == 9
-
-    def ctype(arg):
-        arg = " ".join(arg.split())
-        if "*" in arg or arg.startswith("ava_stream_t"):
-            return ctypes.c_void_p
-        return {"int": ctypes.c_int, "double": ctypes.c_double, "size_t": ctypes.c_size_t}[arg.rsplit(" ", 1)[0]]
-
-    for res, name, args in decls:
-        want = [] if args.strip() == "void" else [ctype(a) for a in args.split(",")]
-        got_res, got_args = _lib.SIGNATURES[name]
-        assert got_res is (ctypes.c_int if res == "int" else ctypes.c_size_t), name
-        assert got_args == want, name
-
-
 def up256(x):
     return (x + 255) // 256 * 256
 

@@ -7,7 +7,6 @@ Labels, edges and linkage matrices compare with ``==``: the inputs are exact (hd
 is decided.  Probabilities are one square root, one reciprocal and one division away from exact keys: 4 * 2^-53."""
 import ctypes
 import os
-import re
 
 import numpy as np
 import pytest
@@ -284,26 +283,6 @@ def test_constructor_keeps_its_parameters():
 
 
 # ---- the C ABI ---------------------------------------------------------------------------------------------------------
-def test_header_mirror():
-    """every ava_hd_* declaration of include/ava_hip.h has its ctypes mirror, argument by argument"""
-    header = open(os.path.join(ROOT, "include", "ava_hip.h")).read()
-    decls = re.findall(r"^(int|size_t) (ava_hd_[a-z_]+)\(([^;]*)\);", header, flags=re.M)
-    assert sorted(d[1] for d in decls) == sorted(n for n in _lib.SIGNATURES if n.startswith("ava_hd_"))
-    assert len(decls) == 7
-
-    def ctype(arg):
-        arg = " ".join(arg.split())
-        if "*" in arg or arg.startswith("ava_stream_t"):
-            return ctypes.c_void_p
-        return {"int": ctypes.c_int, "double": ctypes.c_double, "size_t": ctypes.c_size_t}[arg.rsplit(" ", 1)[0]]
-
-    for res, name, args in decls:
-        want = [] if args.strip() == "void" else [ctype(a) for a in args.split(",")]
-        got_res, got_args = _lib.SIGNATURES[name]
-        assert got_res is (ctypes.c_int if res == "int" else ctypes.c_size_t), name
-        assert got_args == want, name
-
-
 def up256(x):
     return (x + 255) // 256 * 256
 

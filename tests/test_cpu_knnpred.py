@@ -5,16 +5,13 @@ kfold against KFold, the argument checks that need no device and the C ABI's mir
 
 Classes compare with ``==`` (the margins of knnpred_cases.py decide every comparison); regression values within the
 per-element bound of knnpred_cases.py."""
-import ctypes
-import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
 import knnpred_cases as KC
-from conftest import ROOT, load_golden
+from conftest import load_golden
 from ava_amd import _lib
 from ava_amd import knn_predict as KP
 
@@ -241,26 +238,6 @@ def test_constructors_keep_their_parameters():
 
 
 # ---- the C ABI -------------------------------------------------------------------------------------------------------
-def test_header_mirror():
-    """every ava_kp_* declaration of include/ava_hip.h has its ctypes mirror, argument by argument"""
-    header = open(os.path.join(ROOT, "include", "ava_hip.h")).read()
-    decls = re.findall(r"^(int|size_t) (ava_kp_[a-z_]+)\(([^;]*)\);", header, flags=re.M)
-    assert sorted(d[1] for d in decls) == sorted(n for n in _lib.SIGNATURES if n.startswith("ava_kp_"))
-    assert len(decls) == 7
-
-    def ctype(arg):
-        arg = " ".join(arg.split())
-        if "*" in arg or arg.startswith("ava_stream_t"):
-            return ctypes.c_void_p
-        return {"int": ctypes.c_int, "double": ctypes.c_double, "size_t": ctypes.c_size_t}[arg.rsplit(" ", 1)[0]]
-
-    for res, name, args in decls:
-        want = [] if args.strip() == "void" else [ctype(a) for a in args.split(",")]
-        got_res, got_args = _lib.SIGNATURES[name]
-        assert got_res is ctypes.c_int, name
-        assert got_args == want, name
-
-
 def test_library_argument_checks():
     """ava_kp_* return their limits / AVA_EINVAL before any HIP call (the test runs without a device, where a HIP call
     would return AVA_ELAUNCH instead)"""
