@@ -215,6 +215,21 @@ SIGNATURES = {
     "ava_kp_regress": (_i, [_p, _p, _i, _i, _p, _i, _p, _i, _i, _p, _p]),
 }
 
+# the k-means entry points (row f25); mirrors include/ava_kmeans.h one to one
+KM_SIGNATURES = {
+    "ava_km_max_d": (_i, []),
+    "ava_km_max_k": (_i, []),
+    "ava_km_chunk_rows": (_i, []),
+    "ava_km_workspace_bytes": (_sz, [_i, _i, _i]),
+    "ava_km_assign": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _p, _p, _sz, _p]),
+    "ava_km_update": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _p, _sz, _p]),
+    "ava_km_fit": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _d, _p, _i, _i, _p, _p, _p, _sz, _p]),
+    "ava_km_pp_start": (_i, [_p, _i, _i, _i, _i, _p, _p]),
+    "ava_km_pp_step": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _p, _p, _sz, _p]),
+    "ava_km_variance": (_i, [_p, _i, _i, _i, _p, _p, _sz, _p]),
+    "ava_km_transform": (_i, [_p, _i, _i, _i, _i, _p, _p, _p]),
+}
+
 _lib = None
 
 
@@ -229,7 +244,7 @@ def load():
             "`python -c 'import __graft_entry__ as g; g.build()'` or `make -C %s`." % (LIB_PATH, CSRC))
     import torch  # noqa: F401  (loads torch's libamdhip64.so first; same SONAME as ROCm's)
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in list(SIGNATURES.items()) + list(KM_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError if a declared symbol is missing
         fn.restype = res
         fn.argtypes = args

@@ -988,6 +988,10 @@ int ava_kp_proba(const int64_t* idx, const double* dist, int nq, int k, const in
 int ava_kp_regress(const int64_t* idx, const double* dist, int nq, int kmax, const double* Y, int n_out, const int* ks,
                    int n_k, int weighted, double* out, ava_stream_t s);
 
+/* ---- Lloyd k-means with k-means++ seeding (row f25; csrc/kmeans.hip): the ava_km_ entry points are declared, with their
+ * comment block, in a header of their own, mirrored by _lib.KM_SIGNATURES ----------------------------------------------- */
+#include "ava_kmeans.h"
+
 #ifdef __cplusplus
 }
 #endif
