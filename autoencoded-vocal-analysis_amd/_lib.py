@@ -98,9 +98,6 @@ SIGNATURES = {
     "ava_cast_to_f32": (_i, [_p, _i, _i64, _p, _p]),
     "ava_host_gather_rows": (_i, [_p, _p, _p, _i64, _i64, _sz, _i]),
     "ava_gather_rows_f32": (_i, [_p, _i, _i64, _i64, _p, _i64, _p, _p]),
-    "ava_mmd2_workspace_bytes": (_sz, [_i, _i]),
-    "ava_mmd2": (_i, [_p, _i, _p, _i, _p, _i, _d, _p, _p, _sz, _p]),
-    "ava_mmd2_linear": (_i, [_p, _i, _p, _p, _i, _d, _p, _p, _sz, _p]),
     "ava_mmd2_matrix_workspace_bytes": (_sz, [_p, _i, _i]),
     "ava_mmd2_matrix": (_i, [_p, _i, _p, _p, _p, _i, _p, _i64, _d, _p, _p, _p, _sz, _p]),
     "ava_mmd2_matrix_linear": (_i, [_p, _i, _p, _p, _p, _i, _p, _i64, _d, _p, _p, _sz, _p]),
@@ -213,10 +210,6 @@ SIGNATURES = {
     "ava_kp_vote": (_i, [_p, _p, _i, _i, _p, _p, _i, _i, _p, _p]),
     "ava_kp_proba": (_i, [_p, _p, _i, _i, _p, _i, _i, _p, _p]),
     "ava_kp_regress": (_i, [_p, _p, _i, _i, _p, _i, _p, _i, _i, _p, _p]),
-}
-
-# the k-means entry points (row f25); mirrors include/ava_kmeans.h one to one
-KM_SIGNATURES = {
     "ava_km_max_d": (_i, []),
     "ava_km_max_k": (_i, []),
     "ava_km_chunk_rows": (_i, []),
@@ -244,7 +237,7 @@ def load():
             "`python -c 'import __graft_entry__ as g; g.build()'` or `make -C %s`." % (LIB_PATH, CSRC))
     import torch  # noqa: F401  (loads torch's libamdhip64.so first; same SONAME as ROCm's)
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(SIGNATURES.items()) + list(KM_SIGNATURES.items()):
+    for name, (res, args) in SIGNATURES.items():
         fn = getattr(lib, name)          # AttributeError if a declared symbol is missing
         fn.restype = res
         fn.argtypes = args

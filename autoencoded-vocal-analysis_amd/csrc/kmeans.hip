@@ -1,7 +1,7 @@
 // Lloyd k-means with k-means++ seeding of latent means: the device counterpart of
 // scikit-learn 1.7's KMeans(algorithm='lloyd') (sklearn/cluster/_kmeans.py: _kmeans_plusplus, _init_centroids,
 // _tolerance, _kmeans_single_lloyd; _k_means_common.pyx: _relocate_empty_clusters_dense, _inertia_dense).  X is [N][d]
-// float32 or float64 and is converted on load; the C ABI is include/ava_kmeans.h.
+// float32 or float64 and is converted on load; the C ABI is the ava_km_ block of include/ava_hip.h.
 //
 // The model (ava_amd/kmeans.py states the same; tests/kmeans_cases.py restates it in numpy):
 //   arithmetic   all fp64, also for float32 rows.  Every distance is the tile of sqdist_tile.h or a scalar loop in its

@@ -13,10 +13,15 @@
 // block of squared distances in registers while sweeping the z latent dimensions, then adds exp(A * dist) of the
 // pairs that exist (and, for the within-set terms, lie above the diagonal: i < j).
 //
-// The condition-by-condition matrix of `_calculate_mmd2` (:337-447, row f16) is one launch sequence over the index lists
-// of all conditions, sorted by condition: the same tile body and the same reduction order, a workgroup per tile of
-// every block of condition pairs (mmd_matrix_pair_kernel), one workgroup per block for the second stage
-// (mmd_matrix_finalize_kernel), so every term has the bits the per-pair entry points give.
+// There is one implementation of the sums.  The condition-by-condition matrix of `_calculate_mmd2` (:337-447, row f16)
+// is one launch sequence over the index lists of all conditions, sorted by condition: a workgroup per tile of every
+// block of condition pairs (mmd_matrix_pair_kernel; mmd_matrix_linear_kernel for the linear-time estimator), then one
+// workgroup per block for the second stage (mmd_matrix_finalize_kernel).  One pair of index lists is that matrix with
+// two conditions, which is how ava_amd.mmd serves `_estimate_mmd2` and `_estimate_mmd2_linear_time`.  A block's bits
+// depend on its own two lists, z and sigma alone -- not on the other conditions of the launch sequence, nor on where
+// its workgroups fall in it.  The order of every sum is stated once, on the functions below:
+//   first stage   mmd_tile_sum (a tile), mmd_linear_sum and mmd_matrix_linear_kernel (a workgroup's quadruples)
+//   second stage  mmd_matrix_finalize_kernel
 #include "common.h"
 #include "sqdist_tile.h"
 
@@ -24,8 +29,9 @@
 
 // One 64 x 64 tile of (i, j) pairs of the index lists ia (rows i0 ..) and ib (rows j0 ..): gathers the rows into LDS,
 // accumulates the squared distances and returns, in thread 0, the sum of exp(A * dist) over the pairs that exist (and,
-// with sym, lie above the diagonal), reduced per wave and then as (r0 + r1) + (r2 + r3).  sm: 2 * 64 * (z | 1) doubles
-// of LDS, red: 4 doubles of LDS.  Shared by mmd_pair_kernel and mmd_matrix_pair_kernel: same bits for the same tile.
+// with sym, lie above the diagonal).  Order: a thread adds its 4 x 4 pairs row by row (r outer, c inner), then the wave
+// sums of wave_sum_d, then (r0 + r1) + (r2 + r3) over the four waves.  sm: 2 * 64 * (z | 1) doubles of LDS, red: 4
+// doubles of LDS.
 __device__ __forceinline__ double mmd_tile_sum(double* sm, double* red, const double* __restrict__ L, int z,
                                                const int64_t* __restrict__ ia, int na,
                                                const int64_t* __restrict__ ib, int nb, double A, int sym, int i0,
@@ -63,48 +69,6 @@ __device__ __forceinline__ double mmd_tile_sum(double* sm, double* red, const do
   return (red[0] + red[1]) + (red[2] + red[3]);
 }
 
-__global__ __launch_bounds__(256) void mmd_pair_kernel(const double* __restrict__ L, int z,
-                                                       const int64_t* __restrict__ ia, int na,
-                                                       const int64_t* __restrict__ ib, int nb, double A, int sym,
-                                                       int tiles_j, double* __restrict__ partials) {
-  extern __shared__ __align__(16) double sm[];
-  __shared__ double red[4];
-  const int t = threadIdx.x;
-  const int ti = blockIdx.x / tiles_j, tj = blockIdx.x - ti * tiles_j;
-  if (sym && tj < ti) {                  // below the diagonal: nothing to add
-    if (t == 0) partials[blockIdx.x] = 0.0;
-    return;
-  }
-  const double s = mmd_tile_sum(sm, red, L, z, ia, na, ib, nb, A, sym, ti * MMD_T, tj * MMD_T);
-  if (t == 0) partials[blockIdx.x] = s;
-}
-
-// out[0..2] = the three normalised terms of mmd_plots.py:276-295, out[3] = term_1 + term_2 - term_3
-__global__ __launch_bounds__(256) void mmd_finalize_kernel(const double* __restrict__ p1, int n_p1,
-                                                           const double* __restrict__ p2, int n_p2,
-                                                           const double* __restrict__ p3, int n_p3, double c1,
-                                                           double c2, double c3, double* __restrict__ out) {
-  __shared__ double red[3][4];
-  const int t = threadIdx.x;
-  double s[3] = {0.0, 0.0, 0.0};
-  for (int i = t; i < n_p1; i += 256) s[0] += p1[i];
-  for (int i = t; i < n_p2; i += 256) s[1] += p2[i];
-  for (int i = t; i < n_p3; i += 256) s[2] += p3[i];
-#pragma unroll
-  for (int q = 0; q < 3; ++q) {
-    const double r = wave_sum_d(s[q]);
-    if ((t & 63) == 0) red[q][t >> 6] = r;
-  }
-  __syncthreads();
-  if (t == 0) {
-    const double t1 = ((red[0][0] + red[0][1]) + (red[0][2] + red[0][3])) * c1;
-    const double t2 = ((red[1][0] + red[1][1]) + (red[1][2] + red[1][3])) * c2;
-    const double t3 = ((red[2][0] + red[2][1]) + (red[2][2] + red[2][3])) * c3;
-    out[0] = t1; out[1] = t2; out[2] = t3;
-    out[3] = t1 + t2 - t3;
-  }
-}
-
 // out[p] = sum_k (L[a[p]][k] - L[b[p]][k])^2   (estimate_median_sigma's sampled pairs, mmd_plots.py:468-471)
 __global__ __launch_bounds__(256) void pair_sqdist_kernel(const double* __restrict__ L, int z,
                                                           const int64_t* __restrict__ a,
@@ -123,7 +87,8 @@ __global__ __launch_bounds__(256) void pair_sqdist_kernel(const double* __restri
 }
 
 // linear-time estimator (mmd_plots.py:299-312): one thread per i < m, h(x1,y1,x2,y2) = k(x1,x2)+k(y1,y2)-k(x1,y2)-k(x2,y1).
-// This thread's sum over i = first, first + stride, ... < m; shared by mmd_linear_kernel and mmd_matrix_linear_kernel.
+// This thread's sum over i = first, first + stride, ... < m, in that order; a quadruple's four kernel values are added
+// left to right.
 __device__ __forceinline__ double mmd_linear_sum(const double* __restrict__ L, int z, const int64_t* __restrict__ i1,
                                                  const int64_t* __restrict__ i2, int m, double A, int first,
                                                  int stride) {
@@ -146,19 +111,6 @@ __device__ __forceinline__ double mmd_linear_sum(const double* __restrict__ L, i
   return s;
 }
 
-__global__ __launch_bounds__(256) void mmd_linear_kernel(const double* __restrict__ L, int z,
-                                                         const int64_t* __restrict__ i1,
-                                                         const int64_t* __restrict__ i2, int m, double A,
-                                                         double* __restrict__ partials) {
-  __shared__ double red[4];
-  const int t = threadIdx.x;
-  double s = mmd_linear_sum(L, z, i1, i2, m, A, blockIdx.x * 256 + t, gridDim.x * 256);
-  s = wave_sum_d(s);
-  if ((t & 63) == 0) red[t >> 6] = s;
-  __syncthreads();
-  if (t == 0) partials[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
-}
-
 // ---- all condition pairs in one launch sequence (the loop of _calculate_mmd2, mmd_plots.py:395-418) -------------------
 // idx: the index lists of all C conditions, concatenated in condition order; off[c] .. off[c + 1]: the list of
 // condition c.  A table row is 4 int64: {first workgroup of the launch, first workspace slot, a, b}; row n_rows is the
@@ -179,8 +131,8 @@ __device__ __forceinline__ int mmd_find_row(const int64_t* __restrict__ table, i
 
 // Quadratic estimator: a row is a block (a, b), a <= b, in row-major order.  A block with a < b launches its whole
 // ti x tj tile grid; a block with a = b is symmetric (i < j only) and launches the tiles with tj >= ti, row by row.
-// Either way the tile's sum lands at slot ti * tiles_j + tj of the block's row-major grid in the workspace -- where the
-// per-pair path puts it -- and the slots below the diagonal of a symmetric block are never written nor read.
+// Either way the tile's sum (mmd_tile_sum) lands at slot ti * tiles_j + tj of the block's row-major grid in the
+// workspace, and the slots below the diagonal of a symmetric block are never written nor read.
 __global__ __launch_bounds__(256) void mmd_matrix_pair_kernel(const double* __restrict__ L, int z,
                                                               const int64_t* __restrict__ idx,
                                                               const int64_t* __restrict__ off,
@@ -215,7 +167,8 @@ __global__ __launch_bounds__(256) void mmd_matrix_pair_kernel(const double* __re
 }
 
 // Linear estimator: a row is a pair (a, b), a < b, with m = min(n_a, n_b) / 2 quadruples and min(ceil(m / 256), 1024)
-// workgroups, which stride over the quadruples as the workgroups of mmd_linear_kernel do.
+// workgroups.  Thread t of the pair's workgroup wg takes the quadruples wg * 256 + t, + 256 * (the pair's workgroups),
+// ... (mmd_linear_sum); then the wave sums, then (r0 + r1) + (r2 + r3) over the four waves, into slot wg of the pair.
 __global__ __launch_bounds__(256) void mmd_matrix_linear_kernel(const double* __restrict__ L, int z,
                                                                 const int64_t* __restrict__ idx,
                                                                 const int64_t* __restrict__ off,
@@ -238,11 +191,12 @@ __global__ __launch_bounds__(256) void mmd_matrix_linear_kernel(const double* __
   if (t == 0) partials[row[1] + wg] = (red[0] + red[1]) + (red[2] + red[3]);
 }
 
-// One workgroup per table row reduces the row's slots in the order of mmd_finalize_kernel: thread t takes the slots
-// t, t + 256, ... of the row-major grid, then the wave sums, then (r0 + r1) + (r2 + r3), then one multiply.  The slots
-// below the diagonal of a symmetric block hold +0.0 on the per-pair path, and a sum of exp() values is never -0.0, so
-// skipping them gives the same bits.  linear = 0: within[a] = 2 / (n_a (n_a - 1)) * sum for a = b (and cross[a][a] = 0),
-// cross[a][b] = cross[b][a] = 2 / (n_a n_b) * sum otherwise.  linear = 1: cross[a][b] = cross[b][a] = sum / m.
+// Second stage: one workgroup per table row reduces the row's slots.  Thread t adds the slots t, t + 256, ... of the
+// row-major grid in that order (passing over the slots below the diagonal of a symmetric block, which stand for +0.0:
+// a sum of exp() values is never -0.0, so adding them would change no bit), then the wave sums, then (r0 + r1) +
+// (r2 + r3) over the four waves, then one multiply by c.  linear = 0: within[a] = sum * c, c = 2 / (n_a (n_a - 1)), for
+// a = b (and cross[a][a] = 0); cross[a][b] = cross[b][a] = sum * c, c = 2 / (n_a n_b), otherwise.  linear = 1:
+// cross[a][b] = cross[b][a] = sum * c, c = 1 / m.
 __global__ __launch_bounds__(256) void mmd_matrix_finalize_kernel(const double* __restrict__ partials,
                                                                   const int64_t* __restrict__ off,
                                                                   const int64_t* __restrict__ table, int C, int linear,
@@ -283,72 +237,6 @@ __global__ __launch_bounds__(256) void mmd_matrix_finalize_kernel(const double* 
       cross[(size_t)b * C + a] = v;
     }
   }
-}
-
-static inline int mmd_tiles(int n) { return (n + MMD_T - 1) / MMD_T; }
-
-extern "C" size_t ava_mmd2_workspace_bytes(int n1, int n2) {
-  if (n1 < 0 || n2 < 0) return 0;
-  const size_t t1 = mmd_tiles(n1), t2 = mmd_tiles(n2);
-  return (t1 * t1 + t2 * t2 + t1 * t2 + 8) * sizeof(double);
-}
-
-static int launch_pairs(const double* L, int z, const int64_t* ia, int na, const int64_t* ib, int nb, double A, int sym,
-                        double* partials, hipStream_t st) {
-  const int ti = mmd_tiles(na), tj = mmd_tiles(nb);
-  if (ti * tj == 0) return AVA_OK;
-  const size_t lds = (size_t)2 * MMD_T * (z | 1) * sizeof(double);
-  static bool attr = false;
-  if (!attr) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&mmd_pair_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)((size_t)2 * MMD_T * 129 * sizeof(double))) != hipSuccess)
-      return AVA_ELAUNCH;
-    attr = true;
-  }
-  hipLaunchKernelGGL(mmd_pair_kernel, dim3(ti * tj), dim3(256), lds, st, L, z, ia, na, ib, nb, A, sym, tj, partials);
-  AVA_CHECK_LAUNCH();
-  return AVA_OK;
-}
-
-extern "C" int ava_mmd2(const double* latent, int z, const int64_t* i1, int n1, const int64_t* i2, int n2, double sigma,
-                        double* out4, void* ws, size_t ws_bytes, ava_stream_t s) {
-  if (latent == nullptr || i1 == nullptr || i2 == nullptr || out4 == nullptr || ws == nullptr || z < 1 || z > 128 ||
-      n1 < 2 || n2 < 2 || !(sigma > 0.0))
-    return AVA_EINVAL;
-  if (ws_bytes < ava_mmd2_workspace_bytes(n1, n2)) return AVA_EWORKSPACE;
-  hipStream_t st = to_stream(s);
-  const double A = -0.5 / (sigma * sigma);
-  const int t1 = mmd_tiles(n1), t2 = mmd_tiles(n2);
-  double* p1 = reinterpret_cast<double*>(ws);
-  double* p2 = p1 + (size_t)t1 * t1;
-  double* p3 = p2 + (size_t)t2 * t2;
-  int rc = launch_pairs(latent, z, i1, n1, i1, n1, A, 1, p1, st);
-  if (rc == AVA_OK) rc = launch_pairs(latent, z, i2, n2, i2, n2, A, 1, p2, st);
-  if (rc == AVA_OK) rc = launch_pairs(latent, z, i1, n1, i2, n2, A, 0, p3, st);
-  if (rc != AVA_OK) return rc;
-  hipLaunchKernelGGL(mmd_finalize_kernel, dim3(1), dim3(256), 0, st, p1, t1 * t1, p2, t2 * t2, p3, t1 * t2,
-                     2.0 / ((double)n1 * (n1 - 1)), 2.0 / ((double)n2 * (n2 - 1)), 2.0 / ((double)n1 * n2), out4);
-  AVA_CHECK_LAUNCH();
-  return AVA_OK;
-}
-
-extern "C" int ava_mmd2_linear(const double* latent, int z, const int64_t* i1, const int64_t* i2, int m, double sigma,
-                               double* out, void* ws, size_t ws_bytes, ava_stream_t s) {
-  if (latent == nullptr || i1 == nullptr || i2 == nullptr || out == nullptr || ws == nullptr || z < 1 || m < 1 ||
-      !(sigma > 0.0))
-    return AVA_EINVAL;
-  int grid = (m + 255) / 256;
-  if (grid > 1024) grid = 1024;
-  if (ws_bytes < (size_t)(grid + 8) * sizeof(double)) return AVA_EWORKSPACE;
-  hipStream_t st = to_stream(s);
-  double* p = reinterpret_cast<double*>(ws);
-  hipLaunchKernelGGL(mmd_linear_kernel, dim3(grid), dim3(256), 0, st, latent, z, i1, i2, m, -0.5 / (sigma * sigma), p);
-  AVA_CHECK_LAUNCH();
-  // term / m through the same finalise kernel: out[0] = sum / m (out[1..3] scratch)
-  hipLaunchKernelGGL(mmd_finalize_kernel, dim3(1), dim3(256), 0, st, p, grid, p, 0, p, 0, 1.0 / (double)m, 0.0, 0.0, p + grid);
-  AVA_CHECK_LAUNCH();
-  if (hipMemcpyAsync(out, p + grid, sizeof(double), hipMemcpyDeviceToDevice, st) != hipSuccess) return AVA_ELAUNCH;
-  return AVA_OK;
 }
 
 // ---- host side of the one-pass matrix ----------------------------------------------------------------------------------

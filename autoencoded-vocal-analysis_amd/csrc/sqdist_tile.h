@@ -6,14 +6,14 @@
 //   sqd_pair_tile   the tile of one matrix of rows against itself, or the entries of a precomputed matrix: db_count_kernel,
 //                   db_union_kernel, db_border_kernel (dbscan.hip), hd_rowmin_kernel (hdbscan.hip)
 //   sqd_stage, sqd_stage_rows, sqd_accumulate      the halves of a stage, for the kernels that stage whole rows at a
-//                   stride of their own or through row lists: mmd_tile_sum of mmd_pair_kernel and
-//                   mmd_matrix_pair_kernel (mmd.hip), mmd_perm_stat_kernel (mmd_perm.hip)
+//                   stride of their own or through row lists: mmd_tile_sum of mmd_matrix_pair_kernel (mmd.hip),
+//                   mmd_perm_stat_kernel (mmd_perm.hip)
 //
 // Order contract: every pair's sum starts at 0 and takes one fma(x_k - y_k, x_k - y_k, sum) per k, k ascending from 0
 // to d - 1, whatever tile, stage or kernel the pair falls in.  So all these kernels give the same bits for the same
 // pair of rows (and the bits of the scalar loops of pair_sqdist_kernel and hd_core_kernel), d2(i, j) and d2(j, i) have
 // the same bits, and no result depends on the tiling.  mmd_perm_stat_kernel forms its tiles of exp(A d^2) from the same
-// pieces, so its kernel values have the bits of mmd_pair_kernel's; what it adds to the contract -- a column of K0 S
+// pieces, so its kernel values have the bits of mmd_tile_sum's; what it adds to the contract -- a column of K0 S
 // depends on the latent rows, sigma and its membership vector only -- is stated in the header of mmd_perm.hip.
 //
 // Barrier contract of sqd_tile (and of sqd_pair_tile<T, false>): every stage is "barrier, write xs / ys, barrier,

@@ -8,10 +8,10 @@ kernels of ``csrc/mmd.hip`` (fp64, like the reference's numpy arithmetic):
 reference (mmd_plots.py)       here                                        C entry point
 =============================  ==========================================  =============================
 ``estimate_median_sigma``      :func:`estimate_median_sigma`  (:450-474)   ``ava_pair_sqdist``
-``_estimate_mmd2``             :func:`_estimate_mmd2`         (:255-296)   ``ava_mmd2``
-``_estimate_mmd2_linear_time`` :func:`_estimate_mmd2_linear_time` (:299-312) ``ava_mmd2_linear``
-loop of ``_calculate_mmd2``    :func:`mmd2_matrix`            (:395-418)   the above per condition pair
-the same loop, in one pass     :func:`mmd2_matrix_one_pass`                ``ava_mmd2_matrix`` / ``_linear``
+``_estimate_mmd2``             :func:`_estimate_mmd2`         (:255-296)   ``ava_mmd2_matrix``, two conditions
+``_estimate_mmd2_linear_time`` :func:`_estimate_mmd2_linear_time` (:299-312) ``ava_mmd2_matrix_linear``, two conditions
+loop of ``_calculate_mmd2``    :func:`mmd2_matrix`            (:395-418)   ``ava_mmd2_matrix`` / ``_linear`` per pair
+the same loop, in one pass     :func:`mmd2_matrix_one_pass`                ``ava_mmd2_matrix`` / ``_linear``, all at once
 ``_calculate_mmd2``            :func:`_calculate_mmd2`        (:337-434)   the one-pass matrix
 (none: Gretton et al. 2012)    :func:`mmd2_permutation_test`, ``_matrix``  ``ava_mmd2_perm`` (row f18)
 =============================  ==========================================  =============================
@@ -54,12 +54,12 @@ def _latent_dev(latent):
     return t
 
 
-def _index_dev(idx, n_rows):
-    a = np.ascontiguousarray(np.asarray(idx), dtype=np.int64)
+def _pair_index(i1, i2, n_rows):
+    """the index list ``i1`` followed by ``i2``, int64 on the host, as rows 0 .. n_rows - 1 (negative ones wrapped)"""
+    a = np.concatenate([np.asarray(i1, dtype=np.int64), np.asarray(i2, dtype=np.int64)])
     if a.size and (a.min() < -n_rows or a.max() >= n_rows):
         raise IndexError("index out of bounds for latent with %d rows" % n_rows)      # numpy would raise the same
-    a = np.where(a < 0, a + n_rows, a)
-    return torch.from_numpy(a).to(_device())
+    return np.where(a < 0, a + n_rows, a)
 
 
 def estimate_median_sigma(latent, n=10000, seed=42):
@@ -78,17 +78,13 @@ def estimate_median_sigma(latent, n=10000, seed=42):
 
 
 def _terms(L, i1, i2, sigma):
+    """float64 ``[term_1, term_2, term_3, term_1 + term_2 - term_3]`` of mmd_plots.py:276-295 for two index lists (in any
+    order, rows may repeat or be in both): the one-pass matrix of two conditions, the last entry formed on the host"""
     n1, n2 = len(i1), len(i2)
     if n1 * (n1 - 1) == 0 or n2 * (n2 - 1) == 0:
         raise ZeroDivisionError("division by zero")                       # the reference's 2/(n*(n-1))
-    lib = _lib.load()
-    d1, d2 = _index_dev(i1, len(L)), _index_dev(i2, len(L))
-    nbytes = lib.ava_mmd2_workspace_bytes(n1, n2)
-    ws = _lib.workspace(nbytes, L.device, "%d and %d rows" % (n1, n2))
-    out = torch.empty(4, dtype=torch.float64, device=L.device)
-    _lib.check(lib.ava_mmd2(L.data_ptr(), L.shape[1], d1.data_ptr(), n1, d2.data_ptr(), n2, float(sigma),
-                            out.data_ptr(), ws.data_ptr(), nbytes, _lib.stream()), "ava_mmd2")
-    return out.cpu().numpy()
+    within, cross = _launch_pair(L, i1, i2, sigma, False)
+    return np.array([within[0], within[1], cross[0, 1], within[0] + within[1] - cross[0, 1]])
 
 
 def _estimate_mmd2(latent, i1, i2, sigma=None, max_n=None, seed=None):
@@ -117,14 +113,7 @@ def _estimate_mmd2_linear_time(latent, i1, i2, sigma=None):
     n = min(len(i1), len(i2))
     m = n // 2
     assert m > 0
-    L = _latent_dev(latent)
-    lib = _lib.load()
-    d1, d2 = _index_dev(i1[:2 * m], len(L)), _index_dev(i2[:2 * m], len(L))
-    ws = torch.empty((min((m + 255) // 256, 1024) + 8) * 8, dtype=torch.uint8, device=L.device)
-    out = torch.empty(1, dtype=torch.float64, device=L.device)
-    _lib.check(lib.ava_mmd2_linear(L.data_ptr(), L.shape[1], d1.data_ptr(), d2.data_ptr(), m, float(sigma), out.data_ptr(),
-                                   ws.data_ptr(), ws.numel(), _lib.stream()), "ava_mmd2_linear")
-    return float(out.item())
+    return float(_launch_pair(_latent_dev(latent), i1[:2 * m], i2[:2 * m], sigma, True)[1][0, 1])
 
 
 def mmd2_matrix(latent, condition, alg='quadratic', sigma=None, max_n=None):
@@ -153,53 +142,71 @@ def mmd2_matrix(latent, condition, alg='quadratic', sigma=None, max_n=None):
     return result, all_conditions
 
 
+def _count_plan(counts):
+    """What the launches need to know about conditions of ``counts`` rows each, in numpy (no GPU): a dict with
+
+    ``counts``, ``tiles``  int64 ``[C]``: rows and ``ceil(rows / 64)`` tiles per condition
+    ``offsets``         int64 ``[C + 1]``: condition ``c`` owns ``index[offsets[c]:offsets[c + 1]]`` of the index list
+    ``blocks``          int64 ``[C (C + 1) / 2 + 1, 4]``: a row ``{first workgroup, first workspace slot, a, b}`` per
+                        block ``a <= b`` in row-major order, then the totals (the table of ``ava_mmd2_matrix``)
+    ``pairs``           the same for the pairs ``a < b`` of the linear estimator (``ava_mmd2_matrix_linear``)
+    """
+    counts = np.asarray(counts, dtype=np.int64).reshape(-1)
+    offsets = np.zeros(len(counts) + 1, dtype=np.int64)
+    np.cumsum(counts, out=offsets[1:])
+    tiles = (counts + TILE - 1) // TILE
+
+    def table(a, b, workgroups, slots):
+        out = np.zeros((len(a) + 1, 4), dtype=np.int64)
+        np.cumsum(workgroups, out=out[1:, 0])
+        np.cumsum(slots, out=out[1:, 1])
+        out[:-1, 2], out[:-1, 3] = a, b
+        return out
+    r = np.arange(len(counts))
+    a, b = np.nonzero(r[:, None] <= r)                     # row-major; a two-condition call builds this per estimate
+    full = tiles[a] * tiles[b]
+    blocks = table(a, b, np.where(a == b, tiles[a] * (tiles[a] + 1) // 2, full), full)
+    a, b = a[a < b], b[a < b]
+    groups = np.minimum((np.minimum(counts[a], counts[b]) // 2 + 255) // 256, 1024)
+    return {"offsets": offsets, "counts": counts, "tiles": tiles, "blocks": blocks, "pairs": table(a, b, groups, groups)}
+
+
 def _group_plan(condition):
-    """Everything the one-pass launches need to know about the grouping, in numpy (no GPU): a dict with
+    """The grouping of a condition array: :func:`_count_plan` of the rows per condition, and
 
     ``all_conditions``  ``np.unique(condition)`` (sorted), ``C`` of them
     ``index``           int64 ``[N]``: the rows of condition 0, then of condition 1, ...; within a condition ascending,
                         i.e. ``np.argwhere(condition == c).flatten()`` (one stable argsort)
-    ``offsets``         int64 ``[C + 1]``: condition ``c`` owns ``index[offsets[c]:offsets[c + 1]]``
-    ``counts``, ``tiles``  rows and ``ceil(rows / 64)`` tiles per condition
-    ``blocks``          int64 ``[C (C + 1) / 2 + 1, 4]``: a row ``{first workgroup, first workspace slot, a, b}`` per
-                        block ``a <= b`` in row-major order, then the totals (the table of ``ava_mmd2_matrix``)
-    ``pairs``           the same for the pairs ``a < b`` of the linear estimator (``ava_mmd2_matrix_linear``)
     """
     condition = np.asarray(condition).reshape(-1)
     order = np.argsort(condition, kind='stable').astype(np.int64)
     ordered = condition[order]
     starts = np.concatenate([[0], np.flatnonzero(ordered[1:] != ordered[:-1]) + 1]) if len(ordered) else np.zeros(0)
     starts = starts.astype(np.int64)
-    offsets = np.concatenate([starts, [len(ordered)]]).astype(np.int64)
-    counts = np.diff(offsets)
-    tiles = (counts + TILE - 1) // TILE
-
-    def table(a, b, workgroups, slots):
-        out = np.zeros((len(a) + 1, 4), dtype=np.int64)
-        out[1:, 0], out[1:, 1] = np.cumsum(workgroups), np.cumsum(slots)
-        out[:-1, 2], out[:-1, 3] = a, b
-        return out
-    a, b = np.triu_indices(len(counts))
-    full = tiles[a] * tiles[b]
-    blocks = table(a, b, np.where(a == b, tiles[a] * (tiles[a] + 1) // 2, full), full)
-    a, b = np.triu_indices(len(counts), 1)
-    groups = np.minimum((np.minimum(counts[a], counts[b]) // 2 + 255) // 256, 1024)
-    return {"all_conditions": ordered[starts], "index": order, "offsets": offsets, "counts": counts, "tiles": tiles,
-            "blocks": blocks, "pairs": table(a, b, groups, groups)}
+    plan = _count_plan(np.diff(np.concatenate([starts, [len(ordered)]])))
+    plan.update(all_conditions=ordered[starts], index=order)
+    return plan
 
 
-def _launch_matrix(latent, plan, sigma, linear):
-    """One upload of the plan, one launch sequence, one download: ``(within [C] or None, cross / linear [C, C])``."""
+def _condition_latent(latent, plan):
+    """the device latent of a condition array's callers: one row per entry of the array"""
     L = _latent_dev(latent)
-    C = len(plan["counts"])
     if len(L) != len(plan["index"]):
         raise ValueError("latent has %d rows, condition %d" % (len(L), len(plan["index"])))
+    return L
+
+
+def _launch_matrix(L, index, plan, sigma, linear):
+    """One upload (``index``, the offsets and the table of ``plan`` in one tensor), one launch sequence, one download:
+    ``(within [C] or None, cross / linear [C, C])``.  ``index``: int64 rows of the device latent ``L``, the lists of the
+    plan's conditions one after the other."""
+    C, n = len(plan["counts"]), len(index)
     lib = _lib.load()
     offsets = np.ascontiguousarray(plan["offsets"])
     table = plan["pairs"] if linear else plan["blocks"]
-    host = np.concatenate([plan["index"], offsets, table.reshape(-1)])
+    host = np.concatenate([index, offsets, table.reshape(-1)])
     dev = torch.from_numpy(host).to(L.device)
-    idx, off, tab = dev[:len(L)], dev[len(L):len(L) + C + 1], dev[len(L) + C + 1:]
+    idx, off, tab = dev[:n], dev[n:n + C + 1], dev[n + C + 1:]
     nbytes = lib.ava_mmd2_matrix_workspace_bytes(offsets.ctypes.data, C, int(linear))
     if nbytes == 0:
         raise _lib.AvaHipError("ava_mmd2_matrix_workspace_bytes: unsupported grouping (%d conditions)" % C)
@@ -218,6 +225,11 @@ def _launch_matrix(latent, plan, sigma, linear):
     return (None if linear else host_out[C * C:]), host_out[:C * C].reshape(C, C)
 
 
+def _launch_pair(L, i1, i2, sigma, linear):
+    """:func:`_launch_matrix` of two conditions, the rows ``i1`` and the rows ``i2`` of the device latent ``L``"""
+    return _launch_matrix(L, _pair_index(i1, i2, len(L)), _count_plan([len(i1), len(i2)]), sigma, linear)
+
+
 def mmd2_block_terms(latent, condition, sigma=None):
     """The normalised block sums behind the whole MMD^2 matrix, from one launch sequence: ``(within [C], cross [C, C],
     all_conditions)`` with ``within[a]`` the within-set term of condition ``a`` (``term_1`` / ``term_2`` of
@@ -231,7 +243,7 @@ def mmd2_block_terms(latent, condition, sigma=None):
         raise ZeroDivisionError("division by zero")
     if sigma is None:
         sigma = estimate_median_sigma(latent)
-    within, cross = _launch_matrix(latent, plan, sigma, False)
+    within, cross = _launch_matrix(_condition_latent(latent, plan), plan["index"], plan, sigma, False)
     return within, cross, plan["all_conditions"]
 
 
@@ -264,7 +276,7 @@ def mmd2_matrix_one_pass(latent, condition, alg='quadratic', sigma=None, max_n=N
         return mmd2_matrix(latent, condition, alg=alg, sigma=sigma, max_n=max_n)
     if sigma is None:
         sigma = estimate_median_sigma(latent)
-    within, cross = _launch_matrix(latent, plan, sigma, alg == 'linear')
+    within, cross = _launch_matrix(_condition_latent(latent, plan), plan["index"], plan, sigma, alg == 'linear')
     i, j = np.triu_indices(n, 1)
     upper = cross[i, j] if alg == 'linear' else within[i] + within[j] - cross[i, j]
     result[i, j] = upper
@@ -386,7 +398,7 @@ def _perm_terms(latent, i1, i2, n_perm, seed, sigma, max_bytes=None, pair=0):
     0 .. n_perm, and ``#{p >= 1 : stat_p >= stat_0}`` as the device counted it."""
     n1, n2 = len(i1), len(i2)
     L = _latent_dev(latent)
-    idx = torch.cat([_index_dev(i1, len(L)), _index_dev(i2, len(L))])
+    idx = torch.from_numpy(_pair_index(i1, i2, len(L))).to(L.device)
     _, counts, null = _run_perm(L, idx, _perm_table(0, n1, n1, n2, pair), n_perm, seed, sigma, max_bytes, True)
     return null[0], int(counts[0])
 
@@ -408,7 +420,7 @@ def mmd2_permutation_test(latent, i1, i2, n_perm=1000, seed=0, sigma=None, retur
     if sigma is None:
         sigma = estimate_median_sigma(latent)
     L = _latent_dev(latent)
-    idx = torch.cat([_index_dev(i1, len(L)), _index_dev(i2, len(L))])
+    idx = torch.from_numpy(_pair_index(i1, i2, len(L))).to(L.device)
     stat0, counts, null = _run_perm(L, idx, _perm_table(0, n1, n1, n2, 0), n_perm, seed, sigma, max_bytes, return_null)
     out = (float(stat0[0]), (1 + int(counts[0])) / (n_perm + 1))
     return out + (null[0, 1:, 3].copy(),) if return_null else out
@@ -429,9 +441,7 @@ def mmd2_permutation_matrix(latent, condition, n_perm=1000, seed=0, sigma=None, 
         return mmd2, pvalue, all_conditions
     if sigma is None:
         sigma = estimate_median_sigma(latent)
-    L = _latent_dev(latent)
-    if len(L) != len(plan["index"]):
-        raise ValueError("latent has %d rows, condition %d" % (len(L), len(plan["index"])))
+    L = _condition_latent(latent, plan)
     a, b = np.triu_indices(C, 1)
     table = _perm_table(plan["offsets"][a], plan["offsets"][b], counts[a], counts[b], np.arange(len(a)))
     idx = torch.from_numpy(plan["index"]).to(L.device)

@@ -292,22 +292,15 @@ int ava_gather_rows_f32(const void* src, int src_dtype, int64_t n_rows, int64_t 
                         float* dst, ava_stream_t s);
 
 /* ---- MMD^2 between sets of latent means (downstream consumer of get_latent) ------------ */
-/* _estimate_mmd2 (ava/plotting/mmd_plots.py:255-296, Gretton et al. 2012, unbiased quadratic-time estimator with a
- * Gaussian kernel of bandwidth sigma).  latent: [N][z] float64 row-major on the device (what VAE.get_latent returns,
- * vae.py:538); i1 / i2: device int64 index lists of the two conditions (already subsampled if the caller wants max_n).
- * out4 (device, 4 doubles) = {term_1, term_2, term_3, term_1 + term_2 - term_3}.  n1, n2 >= 2 (the reference divides
- * by n*(n-1)); z <= 128.  ws: ava_mmd2_workspace_bytes(n1, n2) bytes of device scratch. */
-size_t ava_mmd2_workspace_bytes(int n1, int n2);
-int ava_mmd2(const double* latent, int z, const int64_t* i1, int n1, const int64_t* i2, int n2, double sigma,
-             double* out4, void* ws, size_t ws_bytes, ava_stream_t s);
-/* _estimate_mmd2_linear_time (mmd_plots.py:299-312): m = min(len(i1), len(i2)) / 2 quadruples (i1[2i], i2[2i],
- * i1[2i+1], i2[2i+1]); out (device double) = sum h / m.  ws: (min(ceil(m/256), 1024) + 8) doubles. */
-int ava_mmd2_linear(const double* latent, int z, const int64_t* i1, const int64_t* i2, int m, double sigma,
-                    double* out, void* ws, size_t ws_bytes, ava_stream_t s);
-/* The condition-by-condition loop of _calculate_mmd2 (mmd_plots.py:395-418) in one launch sequence (row f16).
- * idx (device): the int64 index lists of the C conditions, concatenated in condition order; offsets (HOST) and
- * offsets_dev (device): the same C + 1 int64 list starts, offsets[C] = len(idx).  2 <= C <= 4096, every condition has
- * 2 .. 2^31 - 1 rows, 1 <= z <= 128, sigma > 0 (AVA_EINVAL otherwise).
+/* The Gaussian-kernel estimators of ava/plotting/mmd_plots.py (Gretton et al. 2012), bandwidth sigma: the unbiased
+ * quadratic-time one of _estimate_mmd2 (:255-296) and the linear-time one of _estimate_mmd2_linear_time (:299-312),
+ * for every pair of C conditions in one launch sequence -- the condition-by-condition loop of _calculate_mmd2
+ * (:395-418, row f16).  One pair of index lists is the call with C = 2.
+ * latent: [N][z] float64 row-major on the device (what VAE.get_latent returns, vae.py:538).  idx (device): the int64
+ * index lists of the C conditions (already subsampled if the caller wants max_n), concatenated in condition order;
+ * offsets (HOST) and offsets_dev (device): the same C + 1 int64 list starts, offsets[C] = len(idx).  2 <= C <= 4096,
+ * every condition has 2 .. 2^31 - 1 rows (the reference divides by n (n - 1)), 1 <= z <= 128, sigma > 0 (AVA_EINVAL
+ * otherwise).  k(x, y) = exp(-|x - y|^2 / (2 sigma^2)).
  * A table row is 4 int64 {first workgroup, first workspace slot, a, b}, followed by one sentinel row {total
  * workgroups, total slots, 0, 0}; with t_c = ceil(n_c / 64):
  *   blocks (ava_mmd2_matrix): the C (C + 1) / 2 blocks a <= b, row-major; block (a, b) has t_a t_b slots (its whole
@@ -318,10 +311,19 @@ int ava_mmd2_linear(const double* latent, int z, const int64_t* i1, const int64_
  * total_tiles / total_workgroups: column 0 of the sentinel row; it is checked against the host offsets and must be
  * below 2^31.  ws: ava_mmd2_matrix_workspace_bytes(offsets, C, linear) = (total slots + 8) doubles; returns 0 for
  * arguments the entry points reject.
- * ava_mmd2_matrix: within[a] (device, C doubles) = 2 / (n_a (n_a - 1)) sum_{i<j} k, cross (device, C x C doubles)
- * [a][b] = [b][a] = 2 / (n_a n_b) sum k, cross[a][a] = 0: the terms ava_mmd2 gives pair by pair, bit for bit.
- * ava_mmd2_matrix_linear: out (device, C x C doubles) [a][b] = [b][a] = what ava_mmd2_linear gives for the first 2 m
- * indices of both lists, bit for bit; the diagonal is not written.  Neither allocates nor synchronises. */
+ * ava_mmd2_matrix: within[a] (device, C doubles) = 2 / (n_a (n_a - 1)) sum_{i<j} k (term_1 / term_2 of :276-288),
+ * cross (device, C x C doubles) [a][b] = [b][a] = 2 / (n_a n_b) sum k (term_3, :289-294), cross[a][a] = 0; the
+ * estimate of a pair is within[a] + within[b] - cross[a][b], which the caller forms.
+ * ava_mmd2_matrix_linear: out (device, C x C doubles) [a][b] = [b][a] = 1 / m sum_{i<m} h over the quadruples (x1, y1,
+ * x2, y2) = rows (ia[2i], ib[2i], ia[2i+1], ib[2i+1]) of the two lists, h = k(x1,x2) + k(y1,y2) - k(x1,y2) - k(x2,y1):
+ * the first 2 m indices of both lists; the diagonal is not written.  Neither allocates nor synchronises.
+ * Every sum has one fixed order (no atomics), so a block's bits depend on its two lists, z and sigma alone, not on the
+ * other conditions of the call.  First stage, one slot per workgroup of 256 threads = 4 waves: a tile's thread adds
+ * its 4 x 4 pairs row by row (a pair's |x - y|^2 in the order of csrc/sqdist_tile.h), a pair's thread t of workgroup w
+ * of W its quadruples w 256 + t, + 256 W, ...; then the wave sums r0 .. r3, then (r0 + r1) + (r2 + r3).  Second stage,
+ * one workgroup per block or pair: thread t adds the slots t, t + 256, ... of the row-major grid (those below the
+ * diagonal of a symmetric block left out), then the wave sums, then (r0 + r1) + (r2 + r3), then ONE multiply by
+ * 2 / (n (n - 1)), 2 / (n_a n_b) or 1 / m. */
 size_t ava_mmd2_matrix_workspace_bytes(const int64_t* offsets, int C, int linear);
 int ava_mmd2_matrix(const double* latent, int z, const int64_t* idx, const int64_t* offsets, const int64_t* offsets_dev,
                     int C, const int64_t* blocks, int64_t total_tiles, double sigma, double* within, double* cross,
@@ -988,9 +990,59 @@ int ava_kp_proba(const int64_t* idx, const double* dist, int nq, int k, const in
 int ava_kp_regress(const int64_t* idx, const double* dist, int nq, int kmax, const double* Y, int n_out, const int* ks,
                    int n_k, int weighted, double* out, ava_stream_t s);
 
-/* ---- Lloyd k-means with k-means++ seeding (row f25; csrc/kmeans.hip): the ava_km_ entry points are declared, with their
- * comment block, in a header of their own, mirrored by _lib.KM_SIGNATURES ----------------------------------------------- */
-#include "ava_kmeans.h"
+/* ---- Lloyd k-means with k-means++ seeding (row f25; csrc/kmeans.hip; scikit-learn 1.7 cluster/_kmeans.py:
+ * _kmeans_plusplus, _tolerance, _kmeans_single_lloyd; _k_means_common.pyx: _relocate_empty_clusters_dense,
+ * _inertia_dense) -----------------------------------------------------------------------------------------------------
+ * x [n][d] (dtype 0 = float32, 1 = float64; device) is converted on load; everything else is fp64.  Every (row, centre)
+ * and (row, row) distance has the bits ava_pair_sqdist gives the pair.  Nothing uses floating-point atomics: every sum
+ * over rows is taken inside chunks of ava_km_chunk_rows() = 2048 rows in ascending row order and the chunk partials are
+ * added in ascending chunk order, so the same inputs give the same bits on every run, for float32 and float64 copies of
+ * the same values.  1 <= n <= 2^31 - 64, 1 <= d <= ava_km_max_d() = 128, 1 <= k <= ava_km_max_k() = 256; a fit also
+ * needs k <= n.  Nothing allocates or synchronises; every pointer is a device pointer.
+ * ws: ava_km_workspace_bytes(n, d, k) bytes (0 for an unsupported shape); ava_km_pp_step and ava_km_variance accept the
+ *   size for k = 1.
+ *
+ * ava_km_assign: labels [n] int = the nearest of the centres [k][d] of every row, the lowest index on a tie; d2 [n] the
+ *   squared distance to it; inertia [1] (may be null) = sum d2 in the chunk order.
+ * ava_km_update: one M-step from labels [n] int (a label outside [0, k) is in no cluster): counts [k] int64 and
+ *   centres [k][d] = the sum of the rows of the cluster in the chunk order / its count, zeros for an empty cluster.
+ * ava_km_fit: iterations [it0, it0 + n_iters) of sklearn's Lloyd loop on centres [k][d] (in and out): assign, new centres
+ *   (an empty cluster takes the row farthest from its own centre; several empty clusters in ascending id take the rows in
+ *   the order (d2 descending, row ascending); the row leaves its old cluster's sum and count), shift = sum_k |c_new -
+ *   c_old|^2; the loop stops when no label changed (strict), else when shift <= tol * mean_var[0].  labels [n] int must
+ *   hold -1 before iteration 0; labels and d2 [n] are those of the last assignment that ran, made at the centres BEFORE
+ *   that iteration's update.  ctl [>= 3 + it0 + n_iters] int, zeroed before iteration 0: ctl[0] = 1 after a strict stop,
+ *   ctl[1] the number of iterations that ran, ctl[2 + it] whether the loop had stopped before iteration it: the launches
+ *   of a stopped iteration return at once, so iterations are enqueued in blocks between reads of ctl.  shift [1] (may be
+ *   null): the shift of the last iteration that ran.  mean_var [1]: ava_km_variance's out[0].
+ * ava_km_pp_start: closest [n] = the squared distance of every row to row `first` (sklearn's first centre).
+ * ava_km_pp_step: one further centre of sklearn's _kmeans_plusplus.  rand [n_trials] are the caller's uniform draws,
+ *   1 <= n_trials <= 8.  The candidates are searchsorted(scan, rand * potential) clipped to n - 1, scan the inclusive
+ *   sums of closest (sequential inside the chunks, the ascending chunk offsets added), potential its last entry; the
+ *   candidate whose min(closest, d2(candidate, .)) has the least sum (chunk order; the first on a tie) is written to
+ *   out_idx [1] int, its sum to out_pot [1], and closest becomes that minimum.
+ * ava_km_variance: out [1 + d]: out[1 + j] = mean_n (x_nj - mean_j)^2 with both means in the chunk order, out[0] their
+ *   ascending sum / d (np.mean(np.var(x, axis=0)), the factor of sklearn's _tolerance).
+ * ava_km_transform: out [n][k] = the euclidean distance of every row to every centre (the square root of the tile).
+ *
+ * All return AVA_EINVAL before any launch for null pointers, an unknown dtype or an unsupported shape, AVA_EWORKSPACE
+ * for a workspace that is too small. */
+int ava_km_max_d(void);
+int ava_km_max_k(void);
+int ava_km_chunk_rows(void);
+size_t ava_km_workspace_bytes(int n, int d, int k);
+int ava_km_assign(const void* x, int dtype, int n, int d, int k, const double* centres, int* labels, double* d2,
+                  double* inertia, void* ws, size_t ws_bytes, ava_stream_t s);
+int ava_km_update(const void* x, int dtype, int n, int d, int k, const int* labels, double* centres, int64_t* counts,
+                  void* ws, size_t ws_bytes, ava_stream_t s);
+int ava_km_fit(const void* x, int dtype, int n, int d, int k, double* centres, int* labels, double* d2, double tol,
+               const double* mean_var, int it0, int n_iters, int* ctl, double* shift, void* ws, size_t ws_bytes,
+               ava_stream_t s);
+int ava_km_pp_start(const void* x, int dtype, int n, int d, int first, double* closest, ava_stream_t s);
+int ava_km_pp_step(const void* x, int dtype, int n, int d, int n_trials, const double* rand, double* closest, int* out_idx,
+                   double* out_pot, void* ws, size_t ws_bytes, ava_stream_t s);
+int ava_km_variance(const void* x, int dtype, int n, int d, double* out, void* ws, size_t ws_bytes, ava_stream_t s);
+int ava_km_transform(const void* x, int dtype, int n, int d, int k, const double* centres, double* out, ava_stream_t s);
 
 #ifdef __cplusplus
 }

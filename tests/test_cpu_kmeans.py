@@ -1,12 +1,9 @@
 """ava_amd.kmeans without a GPU: the restatement of tests/kmeans_cases.py against scikit-learn's own KMeans and
 kmeans_plusplus, the margin of every golden case to the model's discontinuous rules, the content of
-tests/golden/kmeans.npz, the argument checks that need no device and the C ABI's mirror and refusals.
+tests/golden/kmeans.npz, the argument checks that need no device and the C ABI's refusals.
 
 Label and index comparisons are exact on every row; floats are held to max(1e-11, 4 x floor) with the floors of
 make_golden_kmeans.py (the reference's own noise)."""
-import ctypes
-import os
-import re
 import warnings
 
 import numpy as np
@@ -14,7 +11,7 @@ import pytest
 import torch
 
 import kmeans_cases as KC
-from conftest import ROOT, load_golden
+from conftest import load_golden
 from ava_amd import _lib
 from ava_amd import kmeans as KM
 
@@ -210,38 +207,6 @@ def test_no_cpu_fallback(monkeypatch):
 
 
 # ---- the C ABI -------------------------------------------------------------------------------------------------------
-def test_header_mirror_of_the_kmeans_entry_points():
-    """every declaration of include/ava_kmeans.h has its ctypes mirror in _lib.KM_SIGNATURES (the rule of
-    test_cpu_boundary.py::test_header_mirror), the library exports each, and ava_hip.h includes the header"""
-    scalar = {"int": ctypes.c_int, "float": ctypes.c_float, "double": ctypes.c_double, "size_t": ctypes.c_size_t,
-              "int64_t": ctypes.c_int64, "uint64_t": ctypes.c_uint64}
-    header = open(os.path.join(ROOT, "include", "ava_kmeans.h")).read()
-    assert '#include "ava_kmeans.h"' in open(os.path.join(ROOT, "include", "ava_hip.h")).read()
-    decls = re.findall(r"^((?:const )?\w+\s*\*?)\s*(ava_[a-z0-9_]+)\(([^;{]*)\);", header, flags=re.M)
-    assert sorted(d[1] for d in decls) == sorted(_lib.KM_SIGNATURES) and len(decls) == 11
-    assert all(d[1].startswith("ava_km_") for d in decls) and not set(_lib.KM_SIGNATURES) & set(_lib.SIGNATURES)
-    assert set(re.findall(r"\b(ava_km_[a-z0-9_]+)\s*\(", header)) == set(_lib.KM_SIGNATURES)
-
-    def mirrors(ctype, got):
-        ctype = ctype.replace("const ", "").strip()
-        if ctype == "ava_stream_t":
-            return got is ctypes.c_void_p
-        if ctype.endswith("*"):
-            return got is ctypes.c_void_p
-        return got is (None if ctype == "void" else scalar[ctype])
-
-    lib = _lib.load()
-    for res, name, args in decls:
-        got_res, got_args = _lib.KM_SIGNATURES[name]
-        assert mirrors(" ".join(res.split()), got_res), name
-        want = [] if args.strip() == "void" else [" ".join(a.split()) for a in args.split(",")]
-        assert len(got_args) == len(want), name
-        for arg, got in zip(want, got_args):
-            m = re.fullmatch(r"(.*?)\s*\b\w+(\[\d*\])?", arg)
-            assert mirrors(m.group(1) + ("*" if m.group(2) else ""), got), (name, arg)
-        assert hasattr(lib, name)
-
-
 def test_limits_and_refusals_without_a_launch():
     """the constants, the workspace sizes, and AVA_EINVAL / AVA_EWORKSPACE for bad arguments: every refusal comes before
     any HIP call, so it needs no device (the pointers are never dereferenced)"""

@@ -1,11 +1,14 @@
 """The one-pass MMD^2 matrix on the device: ``_calculate_mmd2`` against the golden of the reference's own
-function, and the one-pass kernels of csrc/mmd.hip bit for bit against the per-pair entry points they restate."""
+function, and the kernels of csrc/mmd.hip bit for bit between a launch sequence over all conditions and the two-condition
+calls that serve the per-pair estimators -- and against tests/golden/mmd_pair_gpu.npz, the results of the per-pair
+kernels those calls replaced."""
 import types
 
 import numpy as np
 import pytest
 
 import mmd_matrix_cases as MC
+import test_mmd as TM
 from conftest import load_golden
 from oracle import mmd_oracle as MO
 
@@ -150,3 +153,42 @@ def test_sigma_none_uses_the_median_heuristic_of_the_whole_latent_set():
     sigma = mmd.estimate_median_sigma(latent)
     assert np.array_equal(mmd.mmd2_matrix_one_pass(latent, condition)[0],
                           mmd.mmd2_matrix_one_pass(latent, condition, sigma=sigma)[0])
+
+
+def test_bits_of_the_retired_per_pair_kernels():
+    """tests/golden/mmd_pair_gpu.npz (tests/golden/make_golden_mmd_pair.py) was recorded on the MI355X at the last commit
+    whose ``_terms`` and ``_estimate_mmd2_linear_time`` ran kernels of their own.  The estimators, the block terms and
+    the one-pass matrices must reproduce it bit for bit: 2 and 3 rows in one tile, 64, 65, a 129-row symmetric block with
+    tiles below the diagonal, 260 quadruples over two workgroups.  A pin for this toolchain's ``exp``; the portable check
+    is the 1e-11 comparison with oracle/mmd_oracle.py of the tests above."""
+    from ava_amd import mmd, synthetic as syn
+    G = load_golden("mmd_pair_gpu.npz")
+    pairs = lambda C: [(a, b) for a in range(C - 1) for b in range(a + 1, C)]
+    for z in (1, 32, 128):
+        latent, condition = MC.edge_case(z)
+        sigma = MC.edge_sigma(z)
+        _, terms = _pairwise_terms(mmd, latent, condition, sigma)
+        within, cross, _ = mmd.mmd2_block_terms(latent, condition, sigma=sigma)
+        M, _ = mmd.mmd2_matrix_one_pass(latent, condition, sigma=sigma)
+        want = G["terms_z%d" % z]
+        assert want.shape == (15, 4) and len(terms) == 15
+        for (a, b), w in zip(pairs(len(MC.EDGE_COUNTS)), want):
+            assert terms[a, b].dtype == np.float64 and np.array_equal(terms[a, b], w), (z, a, b)
+            assert np.array_equal([within[a], within[b], cross[a, b], M[a, b]], w), (z, a, b)
+    sigma = MC.edge_sigma(32)
+    for key, (latent, condition) in (("linear_edge", MC.edge_case(32)), ("linear_two_workgroups", MC.linear_case())):
+        _, idx = MC.pair_indices(condition)
+        L = mmd._latent_dev(latent)
+        M, _ = mmd.mmd2_matrix_one_pass(latent, condition, alg='linear', sigma=sigma)
+        assert G[key].shape == (len(pairs(len(idx))),)
+        for (a, b), w in zip(pairs(len(idx)), G[key]):
+            assert mmd._estimate_mmd2_linear_time(L, idx[a], idx[b], sigma=sigma) == w == M[a, b], (key, a, b)
+    # the quadratic calls of test_mmd.py::test_hip_matches_reference_golden_and_oracle that name their sigma
+    latent, idx = TM._sets()
+    sigma = float(load_golden("mmd.npz")["sigma_default_seed"])
+    quad = [mmd._estimate_mmd2(latent, idx[a].copy(), idx[b].copy(), sigma=sigma) for a, b in pairs(3)]
+    quad.append(mmd._estimate_mmd2(latent, idx[0].copy(), idx[2].copy(), sigma=sigma, max_n=40, seed=3))
+    quad.append(mmd._estimate_mmd2(latent, idx[1][:26].copy(), idx[1][26:].copy(), sigma=0.5 * sigma))
+    assert np.array_equal(quad, G["quad"])
+    M, _ = mmd.mmd2_matrix_one_pass(latent, syn.latent_conditions()[1], sigma=sigma)
+    assert [M[0, 1], M[0, 2], M[1, 2]] == G["quad"][:3].tolist()
