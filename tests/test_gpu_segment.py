@@ -1,5 +1,6 @@
 """Amplitude segmentation on the MI355X (ava_amd.segment) against the reference's outputs
-stored in tests/golden/segment.npz (tests/golden/make_golden_segment.py)."""
+stored in tests/golden/segment.npz (tests/golden/make_golden_segment.py), and every kernel of csrc/segment.hip against
+the numpy restatement of tests/segment_cases.py on seeded cases at the kernels' tile, grid and file edges."""
 import ctypes as C
 import os
 
@@ -199,6 +200,157 @@ def test_c_abi_argument_checks():
         args[i] = v
         assert lib.ava_amp_decide(*args) == -1, i
     torch.cuda.synchronize()
+
+
+# ---- the kernels against the numpy restatement of tests/segment_cases.py, at their own edges -------------------------
+LD = np.longdouble
+
+
+def _triples(trace, fo, files):
+    """ava_amp_decide's (count, [maxima, left, right] sorted by maximum) through the C ABI"""
+    lib = _lib.load()
+    frames = trace.numel()
+    f64 = trace.dtype == torch.float64
+    th1, th2, th3 = S.decide_thresholds(SC.TH, np.float64 if f64 else np.float32)
+    cnt = torch.full((1,), 77, dtype=torch.int64, device=trace.device)          # the entry point zeroes it
+    buf = torch.full((3, frames), -7, dtype=torch.int64, device=trace.device)
+    rc = lib.ava_amp_decide(trace.data_ptr(), 1 if f64 else 0, fo.data_ptr(), files, frames, th1, th2, th3,
+                            cnt.data_ptr(), buf[0].data_ptr(), buf[1].data_ptr(), buf[2].data_ptr(), frames,
+                            _lib.stream())
+    assert rc == 0
+    torch.cuda.synchronize()
+    n = int(cnt.item())
+    assert 0 <= n <= frames
+    t = buf[:, :n].cpu().numpy()
+    return n, t[:, np.argsort(t[0], kind='stable')]
+
+
+@pytest.mark.parametrize("dtype", ["float32", "float64"])
+@pytest.mark.parametrize("name", sorted(SC.DECISION_CASES))
+def test_decisions_against_the_restatement(name, dtype):
+    a, frame_off = SC.decision_case(name)
+    want = SC.decision_want(name, dtype)
+    files = len(frame_off) - 1
+    trace = torch.from_numpy(a.astype(dtype)).cuda()
+    fo = torch.from_numpy(np.array(frame_off)).cuda()
+    n, (mx, left, right) = _triples(trace, fo, files)
+    assert n == sum(len(w[0]) for w in want)
+    cut = np.searchsorted(mx, frame_off)
+    for f in range(files):
+        s = slice(cut[f], cut[f + 1])
+        assert (mx[s] - frame_off[f]).tolist() == want[f][0], (f, "maxima")
+        assert left[s].tolist() == want[f][1], (f, "left")
+        assert right[s].tolist() == want[f][2], (f, "right")
+    assert S._decide(trace, np.array(frame_off), fo, SC.TH) == [S.chain(*w) for w in want]
+    n2, again = _triples(trace, fo, files)
+    assert n2 == n and np.array_equal(again, np.stack([mx, left, right]))
+
+
+def test_decisions_of_a_batch_equal_each_file_alone():
+    a, frame_off = SC.decision_case("boundaries")
+    p = dict(SC.TH, min_dur=0.0, max_dur=1e9)
+    dt = np.float64(1.0)
+    for dtype in ("float32", "float64"):
+        want = SC.decision_want("boundaries", dtype)
+        trace = torch.from_numpy(a.astype(dtype)).cuda()
+        fo = torch.from_numpy(np.array(frame_off)).cuda()
+        batch = S._decide(trace, np.array(frame_off), fo, p)
+        alone = 0
+        for f in range(len(frame_off) - 1):
+            one = a[frame_off[f]:frame_off[f + 1]].astype(dtype)
+            chain = S.duration_filter(*S.chain(*want[f]), dt, p)
+            assert S.duration_filter(*batch[f], dt, p) == chain
+            if len(one) >= 3:
+                assert S.onsets_offsets_from_trace(one, dt, p) == chain, f
+                alone += 1
+        assert alone >= 7
+
+
+def _ratio(err, bound):
+    return float((np.abs(err) / bound).max())
+
+
+def _band_run(audio, p):
+    """(trace, spec) of S._trace as host arrays, the frame offsets checked against frame_count"""
+    N, noverlap = p['nperseg'], p['noverlap']
+    dev = DeviceAudio(list(audio))
+    T = S.frame_count([len(a) for a in audio], N, noverlap)
+    frame_off = np.concatenate([[0], np.cumsum(T)]).astype(np.int64)
+    dt = S.frame_step(p['fs'], N, noverlap)
+    trace, fo, spec = S._trace(dev, frame_off, p, dt, want_spec=True)
+    torch.cuda.synchronize()
+    i1, i2, _ = S.band_indices(p)
+    assert trace.shape == (frame_off[-1],) and spec.shape == (i2 - i1, frame_off[-1]) and spec.dtype == torch.float64
+    np.testing.assert_array_equal(fo.cpu().numpy(), frame_off)
+    return dev, trace, spec, frame_off
+
+
+def _check_band(tag, trace, spec, frame_off, want, p, float32):
+    np.testing.assert_array_equal(frame_off, want['frame_off'])
+    got_v, got = spec.cpu().numpy(), trace.cpu().numpy()
+    assert got.dtype == (np.float32 if float32 else np.float64)
+    vb, fb = SC.v_bound(want, p), SC.value_bound(want, p)
+    if float32:
+        fb = fb + 2.0 ** -24 * np.abs(want['value'])
+    r_v, r_value = _ratio(got_v.astype(LD) - want['v'], vb), _ratio(got.astype(LD) - want['value'], fb)
+    print("%s: device / bound: v %.3f value %.3f (%d x %d elements)" % ((tag, r_v, r_value) + got_v.shape))
+    assert np.isfinite(got_v).all() and np.isfinite(got).all()
+    assert r_v <= 1.0, tag                                                        # every element, none left out
+    assert r_value <= 1.0, tag
+    low, high = want['u'] < -vb, want['u'] > 1 + vb
+    assert low.any() and high.any()
+    assert (got_v[low] == 0.0).all() and (got_v[high] == 1.0).all()
+
+
+@pytest.mark.parametrize("row,mode", SC.BAND_MODES)
+def test_band_values_against_the_restatement(row, mode):
+    p, want = SC.band_params(row, mode), SC.band_want(row, mode)
+    dev, trace, spec, frame_off = _band_run(SC.band_audio(row), p)
+    _check_band("%s %s" % (row, mode), trace, spec, frame_off, want, p, False)
+    if mode == "sum":                                       # the template segmenter's band stage: the same bits
+        from ava_amd import template_segmentation as TS
+        tspec, fsum, tfo, tfo_host, _ = TS._band(dev, p)
+        np.testing.assert_array_equal(tfo_host, frame_off)
+        assert torch.equal(tspec, spec) and torch.equal(fsum, trace)
+
+
+@pytest.mark.parametrize("dtype", SC.DTYPES)
+@pytest.mark.parametrize("row", sorted(SC.DTYPE_ROWS))
+def test_band_values_of_integer_and_float32_audio(row, dtype):
+    mode = SC.DTYPE_ROWS[row]
+    p, want = SC.band_params(row, mode, dtype), SC.band_want(row, mode, dtype)
+    audio = SC.band_audio(row, dtype)
+    assert audio[0].dtype == np.dtype(dtype)
+    _, trace, spec, frame_off = _band_run(audio, p)
+    _check_band("%s %s %s" % (row, mode, dtype), trace, spec, frame_off, want, p, dtype != "int32")
+
+
+@pytest.mark.parametrize("dtype", ["float64", "int16"])
+def test_smoothing_against_the_restatement(dtype):
+    audio = SC.smooth_audio(dtype)
+    same = [np.asarray(a, dtype=np.float64) for a in audio]                      # the same samples: the same fp64 raw trace
+    p = dict(SC.SMOOTH_P)
+    _, raw_t, _, frame_off = _band_run(same, p)                                  # radius 0: one fma with the weight 1
+    raw = raw_t.cpu().numpy()
+    assert np.diff(frame_off).tolist() == list(SC.SMOOTH_FRAMES) and raw.dtype == np.float64
+    want_raw = SC.band_values(same, p)
+    assert _ratio(raw.astype(LD) - want_raw['value'], SC.value_bound(want_raw, p)) <= 1.0
+    assert raw.min() > 0.5 and raw.max() - raw.min() > 1.0
+    dt = S.frame_step(p['fs'], p['nperseg'], p['noverlap'])
+    worst = 0.0
+    for radius in SC.SMOOTH_RADII:
+        q = dict(p, smoothing_timescale=SC.smooth_timescale(radius))
+        w, r = S.gaussian_weights(q['smoothing_timescale'] / dt)
+        assert r == radius
+        _, trace, _, _ = _band_run(audio, q)
+        got = trace.cpu().numpy()
+        assert got.dtype == (np.float32 if dtype == "int16" else np.float64)
+        want = SC.smoothed(raw, frame_off, w, r)
+        bound = SC.smooth_bound(raw, frame_off, w, r, want, float32=dtype == "int16")
+        ratio = _ratio(got.astype(LD) - want, bound)
+        worst = max(worst, ratio)
+        assert ratio <= 1.0, radius
+    print("smoothing %s: device / bound %.3f" % (dtype, worst))
 
 
 def test_unsupported_nperseg_raises():
