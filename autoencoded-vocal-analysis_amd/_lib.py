@@ -88,6 +88,13 @@ SIGNATURES = {
     "ava_bn_stats": (_i, [_p, _i64, _i, _p, C.POINTER(_i), _p]),
     "ava_bn_finalize": (_i, [_p, _i, _i64, _i, _p, _p, _p, _p, _p, _i, _p, _p, _p, _p, _p]),
     "ava_bn_finalize_bwd": (_i, [_p, _i, _i64, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "ava_acc_shards": (_i, []),
+    "ava_acc_shard_ll": (_i, []),
+    "ava_layout_nchw_to_nhwc_stats": (_i, [_p, _p, _p, _i, _p, _p, _p, _p, _i, _i, _i, C.POINTER(_i), _p]),
+    "ava_layout_nhwc_to_nchw": (_i, [_p, _p, _i, _i, _p]),
+    "ava_layout_relu_mask_to_nhwc": (_i, [_p, _p, _p, _p, _i, _i, _p]),
+    "ava_layout_bn_bwd_apply_to_nchw": (_i, [_p] * 6 + [_i, _i, _i] + [_p] * 7 + [_d, _i, _i, _p]),
+    "ava_layout_scale_backward_roots": (_i, [_p, _i64, _p, _i64, _p, _p, _p]),
     "ava_gemm_workspace_bytes": (_sz, [_i, _i, _i]),
     "ava_gemm": (_i, [_p, _i, _p, _i, _p, _p, _i, _p, _p, _i, _i, _i, _i, _i, _i, _p, _sz, _p]),
     "ava_gemm_path": (_i, [_p, _i, _p, _i, _p, _p, _i, _p, _p, _i, _i, _i, _i, _i, _i, C.POINTER(_i)]),

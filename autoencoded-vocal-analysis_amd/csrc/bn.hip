@@ -448,3 +448,49 @@ int ava_bn_bwd_apply_to_nchw(const float* g, const float* f8, const float* A, co
   AVA_CHECK_LAUNCH();
   return AVA_OK;
 }
+
+// ---- test entry points (include/ava_hip.h): the launchers above on caller-owned buffers, arguments checked before any launch ----
+static inline bool layout_shape_ok(int B, int P, int act_bf16) {
+  return B >= 1 && P >= QPIX && P % QPIX == 0 && (act_bf16 == 0 || act_bf16 == 1);
+}
+extern "C" int ava_acc_shards(void) { return AVA_ACC_SHARDS; }
+extern "C" int ava_acc_shard_ll(void) { return AVA_ACC_SHARD_LL; }
+extern "C" int ava_layout_nchw_to_nhwc_stats(const float* in, const float* slab1, const float* bias, int relu, float* full,
+                                             float* out, float* partials, long long* acc_out, int B, int P, int act_bf16,
+                                             int* nparts, ava_stream_t s) {
+  if (in == nullptr || out == nullptr || nparts == nullptr || !layout_shape_ok(B, P, act_bf16)) return AVA_EINVAL;
+  if (partials == nullptr && acc_out == nullptr) return AVA_EINVAL;
+  if (relu != 0 && relu != 1) return AVA_EINVAL;
+  if (slab1 == nullptr) {
+    if (bias != nullptr || relu != 0 || full != nullptr) return AVA_EINVAL;      // only the two-slab form completes a product
+    return ava_nchw_to_nhwc_stats(in, out, partials, B, P, act_bf16, acc_out, nparts, to_stream(s));
+  }
+  return ava_nchw_to_nhwc_stats_slabs(in, slab1, bias, relu, full, out, partials, B, P, act_bf16, acc_out, nparts, to_stream(s));
+}
+extern "C" int ava_layout_nhwc_to_nchw(const float* in, float* out, int B, int P, ava_stream_t s) {
+  if (in == nullptr || out == nullptr || !layout_shape_ok(B, P, 0)) return AVA_EINVAL;
+  return ava_nhwc_to_nchw(in, out, B, P, to_stream(s));
+}
+extern "C" int ava_layout_relu_mask_to_nhwc(const float* dy_nchw, const float* slab1, const float* y_nhwc, float* du, int B,
+                                            int P, ava_stream_t s) {
+  if (dy_nchw == nullptr || y_nhwc == nullptr || du == nullptr || !layout_shape_ok(B, P, 0)) return AVA_EINVAL;
+  return ava_relu_mask_to_nhwc(dy_nchw, slab1, y_nhwc, du, B, P, to_stream(s));
+}
+extern "C" int ava_layout_bn_bwd_apply_to_nchw(const float* g, const float* f8, const float* A, const float* Bc, const float* Cc,
+                                               float* out, int B, int P, int act_bf16, const long long* acc,
+                                               const float* gamma, const float* mean, const float* invstd, float* dgamma,
+                                               float* dbeta, float* abc, double n, int C, int eval, ava_stream_t s) {
+  if (g == nullptr || f8 == nullptr || out == nullptr || !layout_shape_ok(B, P, act_bf16)) return AVA_EINVAL;
+  if (acc == nullptr) {
+    if (A == nullptr || Bc == nullptr || Cc == nullptr) return AVA_EINVAL;
+    return ava_bn_bwd_apply_to_nchw(g, f8, A, Bc, Cc, out, B, P, act_bf16, nullptr, to_stream(s));
+  }
+  if (gamma == nullptr || mean == nullptr || invstd == nullptr || dgamma == nullptr || dbeta == nullptr || abc == nullptr)
+    return AVA_EINVAL;
+  if (!(n >= 1.0) || C < 1 || C > 32 || (eval != 0 && eval != 1)) return AVA_EINVAL;
+  BnFin fin = {};
+  fin.acc = acc; fin.gamma = gamma; fin.mean = mean; fin.invstd = invstd;
+  fin.dgamma = dgamma; fin.dbeta = dbeta; fin.abc = abc;
+  fin.n = n; fin.C = C; fin.backward = 1; fin.eval = eval;
+  return ava_bn_bwd_apply_to_nchw(g, f8, nullptr, nullptr, nullptr, out, B, P, act_bf16, &fin, to_stream(s));
+}

@@ -224,6 +224,12 @@ int ava_scale_backward_roots(float* seed, int64_t n, float* wg, int64_t nwg, lon
   AVA_CHECK_LAUNCH();
   return AVA_OK;
 }
+// test entry point (include/ava_hip.h): the launcher above on caller-owned buffers
+extern "C" int ava_layout_scale_backward_roots(float* seed, int64_t n, float* wg, int64_t nwg, long long* slot,
+                                               const float* scale, ava_stream_t s) {
+  if (seed == nullptr || scale == nullptr || n < 4 || n % 4 != 0 || nwg < 0 || (wg != nullptr && nwg < 1)) return AVA_EINVAL;
+  return ava_scale_backward_roots(seed, n, wg, nwg, slot, scale, to_stream(s));
+}
 int ava_elbo_finalize_strided(const float* latent_sums, int B, const float* sse_partials, int nparts, int stride,
                               int zdim, float prec, int xdim, float* loss_out, double* loss_accum, hipStream_t st) {
   hipLaunchKernelGGL(elbo_finalize_kernel, dim3(1), dim3(256), 0, st, latent_sums, B, sse_partials, nparts, stride, zdim,

@@ -230,6 +230,47 @@ int ava_bn_finalize_bwd(const float* partials, int nparts, int64_t n, int C, con
                         const float* mean, const float* invstd, float* dgamma, float* dbeta,
                         float* A, float* Bc, float* Cc, ava_stream_t s);
 
+/* ---- test entry points of the training step's layout hand-offs and its BatchNorm accumulator ---------------------------
+ * The launchers the model driver calls between the convolutional and the fully connected part, on caller-owned device
+ * buffers (the ava_gemm_path precedent: nothing but tests calls these).  Tensors are [B][32][P] floats, P = pixels per
+ * sample; "NCHW" is element b*32*P + c*P + p, "NHWC" element b*32*P + p*32 + c.  One workgroup moves tiles of 32 channels
+ * x 64 pixels; tile w = b*(P/64) + q goes to workgroup w mod grid, grid = min((P/64)*B, 1024) for the statistics kernel
+ * and min(.., 2048) for the others.  Every call returns AVA_EINVAL before any launch for a null pointer that is not
+ * marked optional, B < 1, P < 64, P % 64 != 0 or act_bf16 outside {0, 1}.
+ *
+ * An accumulator slot is ava_acc_shards() shards of ava_acc_shard_ll() int64 words: [3 limbs][64 values] and a flag word
+ * at 192.  Value idx of the slot is sum over shards of (limb0 + limb1 * 2^32 + limb2 * 2^64) * 2^-48, NaN when any flag
+ * word is non-zero; a producer adds trunc(|p| * 2^48) of its fp32 partial p, split into three 32-bit limbs that carry the
+ * sign of p, to shard (workgroup index mod shards), and sets the flag for a NaN, an Inf or |p| >= 2^47. */
+int ava_acc_shards(void);
+int ava_acc_shard_ll(void);
+/* NCHW `in` -> NHWC `out` (stored as float, or as bfloat16 bits in the low half of the buffer when act_bf16) and the
+ * per-channel {sum, sum of squares} of what was stored: to slot acc_out when it is not NULL (which = 0: sums at values
+ * 0..31, squares at 32..63), else to partials [nparts][64].  slab1 != NULL: `in` is slab 0 of a two-slab product and the
+ * element is 0 + in + slab1 (+ bias [32*P], optional), ReLU when relu = 1, also written to `full` (NCHW, optional).
+ * slab1 == NULL requires bias = full = NULL and relu = 0.  nparts receives the grid. */
+int ava_layout_nchw_to_nhwc_stats(const float* in, const float* slab1, const float* bias, int relu, float* full,
+                                  float* out, float* partials, long long* acc_out, int B, int P, int act_bf16,
+                                  int* nparts, ava_stream_t s);
+/* NHWC `in` -> NCHW `out` */
+int ava_layout_nhwc_to_nchw(const float* in, float* out, int B, int P, ava_stream_t s);
+/* du (NHWC) = y_nhwc > 0 ? dy : 0 with dy the NCHW tensor dy_nchw, or 0 + dy_nchw + slab1 when slab1 (optional) is given */
+int ava_layout_relu_mask_to_nhwc(const float* dy_nchw, const float* slab1, const float* y_nhwc, float* du, int B,
+                                 int P, ava_stream_t s);
+/* out (NCHW) = f > 0 ? fma(A[c], g, fma(Bc[c], f, Cc[c])) : 0 with g NHWC and f the stored value of f8 (NCHW; rounded to
+ * bfloat16 when act_bf16).  acc == NULL: the coefficients are the arrays A, Bc, Cc [32].  acc != NULL: they are finalised
+ * from slot acc ({sum g, sum g*xhat}) as ava_bn_finalize_bwd does from its partials, with Bc = Cc = 0 when eval = 1, zero
+ * beyond C; workgroup 0 publishes dgamma [C], dbeta [C] and abc [3][32]; A, Bc, Cc are not read.  1 <= C <= 32, n >= 1. */
+int ava_layout_bn_bwd_apply_to_nchw(const float* g, const float* f8, const float* A, const float* Bc, const float* Cc,
+                                    float* out, int B, int P, int act_bf16, const long long* acc, const float* gamma,
+                                    const float* mean, const float* invstd, float* dgamma, float* dbeta, float* abc,
+                                    double n, int C, int eval, ava_stream_t s);
+/* seed [n] (n >= 4, n % 4 == 0), wg [nwg] (optional; nwg >= 1 with it, nwg >= 0 without) and the 64 values of slot
+ * (optional) times scale[0] (device), in place; the slot is rewritten as exact limbs in shard 0, a poisoned one as the flag
+ * of shard 0.  scale[0] == 1 touches nothing. */
+int ava_layout_scale_backward_roots(float* seed, int64_t n, float* wg, int64_t nwg, long long* slot,
+                                    const float* scale, ava_stream_t s);
+
 /* C[M,N] = relu_mask(act(A*B + bias)) on the fp32 matrix cores (nn.Linear and its two backward products).
  *   a_kmajor: 1 = A stored [M,K] (K contiguous), 0 = A stored [K,M] ; lda = stored leading dimension (0: dense)
  *   b_kmajor: 1 = B stored [N,K] (K contiguous), 0 = B stored [K,N] ; ldb likewise ; ldc: row stride of C (0: N)
