@@ -1,5 +1,7 @@
 """CPU-side tests of the shotgun-movie search (row f7): the golden against an fp64 numpy restatement of both metrics,
-the window schedule against the reference's loop, argument validation and ``install``."""
+the conditions of the edge cases that test_gpu_neighbors_edges.py runs on the device (clear winners, exact planted ties,
+every tile position deciding, the restatement's own floor on near-constant rows, the grid.y boundary), the window
+schedule against the reference's loop, argument validation and ``install``."""
 import types
 
 import numpy as np
@@ -41,6 +43,125 @@ def test_restatement_tie_and_nan_rules():
     assert np.isnan(dist[2])
     idx, _ = NC.nearest_from_distances(D, "euclidean")
     np.testing.assert_array_equal(idx, [1, 0, 0])
+
+
+# ---- the edge cases (neighbor_cases.EDGE_CASES): the conditions under which the device tests compare with == --------
+
+def test_edge_cases_cover_the_listed_sizes():
+    shapes = {m: {(len(NC.edge_case(n)["q"]), len(NC.edge_case(n)["r"]), NC.edge_case(n)["q"].shape[1],
+                   str(NC.edge_case(n)["q"].dtype)) for n, c in NC.EDGE_CASES.items() if c[0] == "tile" and c[1] == m}
+              for m in NC.TILE}
+    for metric, sizes, ds, corner in [("euclidean", (63, 64, 65), (1, 31, 32, 33, 65), (65, 65, 33)),
+                                      ("correlation", (127, 128, 129), (2, 15, 16, 17, 33), (129, 129, 17))]:
+        got = shapes[metric]
+        assert {s[:2] for s in got} >= {(a, b) for a in sizes for b in sizes} | {(1, sizes[2]), (sizes[2], 1)}
+        assert {s[2] for s in got} == set(ds)
+        assert {corner + ("float32",), corner + ("float64",)} <= got
+    groups = {c[0] for c in NC.EDGE_CASES.values()}
+    assert groups == {"tile", "d1", "position", "tie", "reduce", "near_constant", "clip"}
+
+
+@pytest.mark.parametrize("name", sorted(NC.EDGE_CASES))
+def test_edge_case_decides(name):
+    """no tie but the planted ones: gap > 1e-9 on every query (between bit-identical rows exactly 0, and then > 1e-9
+    to the third best), and the planted winner is the restatement's"""
+    case = NC.edge_case(name)
+    tied = sorted({t[0] for t in case["ties"]})
+    clear = np.setdiff1d(np.arange(len(case["q"])), tied)
+    assert (case["gap"][clear] > 1e-9).all(), case["gap"][clear].min()
+    for query, low, high in case["ties"]:
+        assert low < high and np.array_equal(case["r"][low], case["r"][high])
+        assert case["D"][query, low] == case["D"][query, high] == case["dist"][query]
+        assert case["gap"][query] == 0.0 and case["idx"][query] == low
+    assert (NC.third_gap(case["D"])[tied] > 1e-9).all()
+    if case["winners"] is not None:
+        np.testing.assert_array_equal(case["idx"], case["winners"])
+    for query in case["same"]:
+        assert np.array_equal(case["q"][query], case["r"][case["idx"][query]])
+    if case["group"] == "d1" or name == "edge_corr_nan_query":
+        rows = slice(None) if case["group"] == "d1" else 1
+        assert np.isnan(case["D"][rows]).all() and (case["idx"][rows] == 0).all()
+
+
+@pytest.mark.parametrize("name", sorted(n for n, c in NC.EDGE_CASES.items() if c[0] == "reduce"))
+def test_reduce_cases_reach_the_later_passes(name):
+    """more than 64 tiles, and winners planted in tile 0, tile 63, tile 64 and the last row (plain runs) or a pair of
+    bit-identical rows in tiles j and j + 64 (dup runs); a spoilt row in tile 64 and one in tile 2"""
+    case = NC.edge_case(name)
+    metric, nr = case["metric"], len(case["r"])
+    tile = NC.TILE[metric]
+    assert len(case["q"]) == 5 and -(-nr // tile) in (65, 129) and case["q"].shape[1] == (5 if tile == 128 else 3)
+    args = NC.EDGE_CASES[name][3]
+    rows, dup, spoil = args[2], args[3], args[4]
+    tiles = {row // tile for row in rows}
+    if dup is None or nr == 8193 and tile == 64:
+        assert {0, 63, 64} <= tiles and nr - 1 in rows
+    if dup is not None:
+        assert dup[0] // tile == 0 and dup[1] // tile == 64 and dup[0] in rows
+    if spoil:
+        assert {row // tile for row in spoil} in ({64, 2}, {64})
+    if metric == "correlation" and spoil:
+        assert np.isnan(case["D"][:, spoil]).all() and not np.isin(case["idx"], spoil).any()
+
+
+@pytest.mark.parametrize("name", sorted(n for n, c in NC.EDGE_CASES.items() if c[0] == "position"))
+def test_every_position_of_a_tile_decides(name):
+    """each reference is the clear winner of exactly one query, and within the first full tile every query position
+    has its winner in the tile and every reference position is a winner"""
+    case = NC.edge_case(name)
+    idx, tile = case["idx"], NC.TILE[case["metric"]]
+    assert NC.QTILE[case["metric"]] == tile
+    np.testing.assert_array_equal(np.sort(idx), np.arange(len(case["r"])))
+    pairs = {(i % tile, int(idx[i]) % tile) for i in range(tile) if idx[i] < tile}
+    assert {p[0] for p in pairs} == set(range(tile)) and {p[1] for p in pairs} == set(range(tile))
+    # neighbouring queries do not share a winner's 16-row block: the lanes that hold the winners differ too
+    assert len({int(idx[i]) // 16 for i in range(4)}) > 1
+
+
+def test_near_constant_floor():
+    """the fp64 restatement's own error on rows of a large mean and a small variation, against np.longdouble; far
+    below the 1e-9 by which the winners are clear, so the indices of this case compare with == as well"""
+    case = NC.edge_case(NC.NEAR_CONSTANT)
+    assert case["q"].shape == (9, 4096) and case["r"].shape == (130, 4096) and case["q"].dtype == np.float64
+    for x in (case["q"], case["r"]):
+        assert np.abs(x.mean(axis=1) - 1e6).max() < 1e-2 and x.std(axis=1).max() < 1e-3
+    floor, DL = NC.near_constant_floor()
+    print("near-constant rows: floor of the fp64 restatement against longdouble %.3e" % floor)
+    assert DL.dtype == np.longdouble and DL.shape == case["D"].shape
+    assert 0.0 <= floor < 1e-10
+    idx_l, _ = NC.nearest_from_distances(DL, "correlation")
+    np.testing.assert_array_equal(idx_l, case["idx"])
+
+
+def test_workspace_bytes_at_the_grid_y_boundary():
+    """ceil_div(nq, query tile) <= 65535; a host-only query, nothing is launched"""
+    lib = _lib.load()
+    for metric, tile in [(0, 128), (1, 64)]:
+        assert lib.ava_nn_workspace_bytes(65535 * tile, 1, 1, metric) > 0
+        assert lib.ava_nn_workspace_bytes(65535 * tile + 1, 1, 1, metric) == 0
+        assert lib.ava_nn_workspace_bytes(65535 * tile - 1, 1, 1, metric) > 0
+
+
+def test_nn_better_restatement():
+    nan = np.nan
+    B = NC.nn_better
+    for nan_wins in (0, 1):
+        assert B(1.0, 3, 2.0, 1, nan_wins) and not B(2.0, 1, 1.0, 3, nan_wins)
+        assert B(1.0, 1, 1.0, 3, nan_wins) and not B(1.0, 3, 1.0, 1, nan_wins) and not B(1.0, 3, 1.0, 3, nan_wins)
+        assert B(-0.0, 1, 0.0, 3, nan_wins) and not B(-0.0, 3, 0.0, 1, nan_wins)      # -0.0 == 0.0: the index decides
+        assert B(nan, 1, nan, 3, nan_wins) and not B(nan, 3, nan, 1, nan_wins)
+        assert B(5.0, 0, 0.0, -1, nan_wins) and not B(0.0, -1, 5.0, 0, nan_wins) and not B(0.0, -1, 0.0, -1, nan_wins)
+    assert B(nan, 9, 0.0, 1, 1) and not B(0.0, 1, nan, 9, 1)
+    assert B(0.0, 9, nan, 1, 0) and not B(nan, 1, 0.0, 9, 0)
+    # the restated merge on the rows of test_restatement_tie_and_nan_rules, one reference per chunk
+    D = np.array([[0.5, 0.25, 0.25], [np.nan, 0.7, np.nan], [np.nan, np.nan, np.nan]])
+    for metric, nan_wins in (("correlation", 0), ("euclidean", 1)):
+        bi, bd = np.zeros(3, dtype=np.int64), D[:, 0].copy()
+        for j in (1, 2):
+            bi, bd = NC.merge(bi, bd, np.zeros(3, dtype=np.int64), D[:, j], j, nan_wins)
+        want_i, want_d = NC.nearest_from_distances(D, metric)
+        np.testing.assert_array_equal(bi, want_i)
+        np.testing.assert_array_equal(bd, want_d)
 
 
 def _reference_schedule(n_samples, fs, window_length, fps, shoulder):
