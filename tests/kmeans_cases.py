@@ -249,3 +249,174 @@ def empty_three_case():
     X = np.concatenate([X, X + np.array([40.0, 0.0])])
     init = np.array([[0.0, 0.0], [40.0, 0.0], [500.0, 500.0], [600.0, 600.0], [700.0, 700.0]])
     return X, init
+
+
+# ---- the edge cases (test_gpu_kmeans_edges.py; test_cpu_kmeans.py proves that each decides what it claims) -------------
+INT32_MAX, INT32_MIN = 2 ** 31 - 1, -2 ** 31
+# (n, d, K): K on both sides of the 16 | 17, 32 | 33 and 48 | 49 boundaries of the sums dispatch, d around the 16-feature slab,
+# one chunk and two.  n = 2115 is a second chunk of one 64-row stage and three rows: a second chunk of one row (n = 2049)
+# cannot hold rows of the four clusters 15, 16, K - 16 and K - 1.
+EDGE_DISPATCH = [(130, 16, 16), (200, 17, 17), (130, 15, 32), (2115, 17, 33), (300, 2, 48), (2115, 16, 49)]
+EDGE_BOUNDARIES = [(16, 17), (32, 33), (48, 49), (64, 65)]
+EDGE_FOREIGN_K = [16, 20, 64, 65]
+EDGE_FOREIGN_ROWS = (63, 64, 2047, 2048, 1, 2110)           # stage edges, chunk edges, both chunks
+EDGE_RELOCATION_M = [5, 66]
+EDGE_TRANSFORM = [(63, 31, 63), (65, 33, 64), (65, 1, 65), (130, 32, 129), (2049, 8, 256)]
+EDGE_VARIANCE = [(1, 1), (2, 3), (2047, 1), (2048, 128), (2049, 17), (4097, 33)]
+EDGE_SCAN_RAND = [0.0, 2047 / 4096, 2047.5 / 4096, 2048 / 4096, 4095 / 4096, 4095.5 / 4096, 1.0, 1.5]
+EDGE_SCAN_ROWS = [0, 2047, 2048, 2048, 4095, 4096, 4096, 4096]
+# (fit case, tol or None for the case's own): two strict stops, and the rows of tol0 stopped by a tolerance of 1e-3
+EDGE_CONTROL = [("n300_d5_k4_sep6", None), ("tol0", None), ("tol0", 1e-3)]
+
+
+def dispatch_case(n, d, k):
+    """(float32 rows, centres float64 [k, d]): row r lies around mean r % k, the means 6 apart on a lattice in the first two
+    features, the centres near the means; so every cluster has rows in every stretch of k rows"""
+    rng = np.random.RandomState(1000 + n + d + k)
+    j = np.arange(k)
+    means = 2.0 * rng.standard_normal((k, d))
+    means[:, 0] = 6.0 * (j % 8)
+    means[:, min(1, d - 1)] = 6.0 * (j // 8) if d > 1 else means[:, 0] + 48.0 * (j // 8)
+    X32 = (means[np.arange(n) % k] + 0.5 * rng.standard_normal((n, d))).astype(np.float32)
+    return X32, means + 0.1 * rng.standard_normal((k, d))
+
+
+def boundary_case(k):
+    """(float32 rows [2115, 17], labels int32 r % k): one label vector to run at k and at k + 1"""
+    X32 = np.random.RandomState(2000 + k).standard_normal((2115, 17)).astype(np.float32)
+    return X32, (np.arange(2115) % k).astype(np.int32)
+
+
+def foreign_case(k, rot):
+    """(float32 rows [2115, 17], labels int32, the foreign rows): labels r % k, and at EDGE_FOREIGN_ROWS the values -1, k,
+    k + 15, -16, INT32_MAX, INT32_MIN rotated by ``rot``"""
+    X32 = (1.0 + np.random.RandomState(3000 + k).standard_normal((2115, 17))).astype(np.float32)
+    labels = np.arange(2115) % k
+    rows = np.array(EDGE_FOREIGN_ROWS)
+    labels[rows] = np.roll([-1, k, k + 15, -16, INT32_MAX, INT32_MIN], rot)
+    return X32, labels.astype(np.int32), rows
+
+
+def relocation_case(m, reverse=False):
+    """(rows float64 [2314, 2], init [4 + m, 2]), all integers: the lattice g x g, g = -8 .. 8, and its copy shifted by
+    (64, 0), the pair four times (2312 rows, across row 2048), then (1000, 0) and (0, 1000); centres at (0, 0), (64, 0),
+    (900, 0), (0, 900) and m far away, empty.  ``reverse`` turns the rows round."""
+    g = np.arange(-8.0, 9.0)
+    L = np.stack(np.meshgrid(g, g, indexing='ij'), axis=-1).reshape(-1, 2)
+    pair = np.concatenate([L, L + np.array([64.0, 0.0])])
+    X = np.concatenate([np.tile(pair, (4, 1)), np.array([[1000.0, 0.0], [0.0, 1000.0]])])
+    init = np.array([[0.0, 0.0], [64.0, 0.0], [900.0, 0.0], [0.0, 900.0]] + [[5000.0 + 100.0 * i, 5000.0] for i in range(m)])
+    return (X[::-1].copy() if reverse else X), init
+
+
+def relocation_picks(d2, m):
+    """the first m rows in the order (d2 descending, row ascending)"""
+    return np.lexsort((np.arange(len(d2)), -d2))[:m]
+
+
+def many_tiles_case():
+    """(float32 rows [16449, 2], init [2, 2]): 258 assign tiles.  Rows 0 .. 16383 alternate around -10 and +10 in feature 0;
+    the rows 16384 .. 16448 (tiles 256 and 257) lie between, at 0.001 j, and are the only ones that change their label after
+    the first iteration."""
+    x0 = np.where(np.arange(16384) % 2 == 0, -10.0, 10.0) + 0.1 * np.random.RandomState(0).standard_normal(16384)
+    X = np.zeros((16449, 2))
+    X[:, 0] = np.concatenate([x0, 0.001 * np.arange(1, 66)])
+    return X.astype(np.float32), np.array([[-10.0, 0.0], [10.5, 0.0]])
+
+
+def transform_case(n, d, k):
+    """(float32 rows, centres float64 [k, d]) as test_assign_and_update_against_the_restatement draws them"""
+    X32 = np.random.RandomState(100 + n + d + k).standard_normal((n, d)).astype(np.float32)
+    rng = np.random.RandomState(k)
+    return X32, X32.astype(np.float64)[rng.choice(n, size=k, replace=k > n)] + 0.25 * rng.standard_normal((k, d))
+
+
+def variance_case(n, d):
+    """float32 rows around 3 with a spread of 2; for d >= 2 the column d // 2 is the constant 3"""
+    X32 = (3.0 + 2.0 * np.random.RandomState(4000 + n + d).standard_normal((n, d))).astype(np.float32)
+    if d >= 2:
+        X32[:, d // 2] = 3.0
+    return X32
+
+
+def column_variances(X):
+    """(the column means, the column variances) in the chunk order"""
+    X = np.asarray(X, dtype=np.float64)
+    mean = chunk_sum(X) / len(X)
+    return mean, chunk_sum((X - mean) ** 2) / len(X)
+
+
+def scan_case():
+    """rows float64 [4097, 2]: row 0 at the origin, the odd rows at (-1, 0), the even rows from 2 at (1, 0).  From row 0
+    closest is 0, 1, 1, ..., scan[r] = r and the potential 4096, all exact; from row 2047 closest is 1, 0, 4, 0, 4, ...: a
+    scan of plateaus that run over both chunk boundaries, 1 + 4 j, the potential 8193."""
+    X = np.zeros((4097, 2))
+    X[1::2, 0] = -1.0
+    X[2::2, 0] = 1.0
+    return X
+
+
+def plateau_thresholds():
+    """(rand [T], the thresholds rand * 8193 [T]) for scan_case from row 2047.  The first are dyadic, so their products are
+    exact and lie between two plateaus; the others are fitted so that the fp64 product is exactly a plateau value or the
+    integer after it (8193 is odd: no dyadic number below 1 gives an integer)."""
+    pot = 8193.0
+    rand = [j / 2048.0 for j in (0, 1, 512, 1023, 1024, 1025, 2047, 2048)]
+    for target in (1.0, 2.0, 5.0, 6.0, 4093.0, 4094.0, 4097.0, 4098.0, 8189.0, 8190.0):
+        r = target / pot
+        for _ in range(8):
+            if r * pot == target:
+                break
+            r = np.nextafter(r, np.inf if r * pot < target else -np.inf)
+        rand.append(float(r))
+    rand = np.array(rand)
+    return rand, rand * pot
+
+
+def plusplus_trial(X, closest, rand):
+    """one step of ``plusplus_steps`` from ``closest``: (the candidates [L], their potentials [L], the position of the
+    chosen one, the new closest)"""
+    X = np.asarray(X, dtype=np.float64)
+    scan = chunk_scan(closest)
+    cand = np.minimum(np.searchsorted(scan, np.asarray(rand) * scan[-1]), len(X) - 1)
+    dc = np.minimum(closest[None, :], sqd(X[cand], X))
+    pots = np.array([chunk_sum(row) for row in dc])
+    b = int(np.argmin(pots))
+    return cand, pots, b, dc[b]
+
+
+def lloyd_steps(X, centres, tol_abs, max_iter, trace=None):
+    """the iterations of ``lloyd`` one by one, up to and with the one that stops: dicts of labels, d2 (the assignment at
+    the centres before), centres (after), shift, changed (the rows whose label changed), strict, stopped"""
+    X = np.asarray(X, dtype=np.float64)
+    C = np.array(centres, dtype=np.float64)
+    old = np.full(len(X), -1, dtype=np.int64)
+    steps = []
+    for _ in range(max_iter):
+        labels, d2 = assign(X, C, trace)
+        C, shift = update(X, labels, d2, C)
+        strict = bool(np.array_equal(labels, old))
+        if not strict and tol_abs > 0:
+            _note(trace, 'shift', abs(shift - tol_abs) / tol_abs)
+        steps.append(dict(labels=labels.astype(np.int32), d2=d2, centres=C.copy(), shift=shift,
+                          changed=np.flatnonzero(labels != old), strict=strict, stopped=strict or shift <= tol_abs))
+        if steps[-1]['stopped']:
+            break
+        old = labels
+    return steps
+
+
+def control_case(name, tol=None):
+    """(rows, the k-means++ start of the fit case, tol, the absolute tolerance)"""
+    X, kw = fit_case(name)
+    start = X[plusplus(X, kw['n_clusters'], np.random.RandomState(kw['random_state']))]
+    tol = kw.get('tol', 1e-4) if tol is None else tol
+    return X, start, tol, mean_variance(X) * tol
+
+
+def permuted_lattice_case():
+    """(the 256 rows of a 16 x 16 lattice, the same rows permuted as init, the permutation)"""
+    g = np.arange(16.0)
+    X = np.stack(np.meshgrid(g, g, indexing='ij'), axis=-1).reshape(-1, 2)
+    perm = np.random.RandomState(3).permutation(256)
+    return X, X[perm].copy(), perm
