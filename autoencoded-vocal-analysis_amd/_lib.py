@@ -230,6 +230,16 @@ SIGNATURES = {
     "ava_km_transform": (_i, [_p, _i, _i, _i, _i, _p, _p, _p]),
 }
 
+# the embedding-quality entry points (row f26); mirrors include/ava_embed_quality.h one to one
+EQ_SIGNATURES = {
+    "ava_eq_max_targets": (_i, []),
+    "ava_eq_max_sweep": (_i, []),
+    "ava_eq_workspace_bytes": (_sz, [_i, _i]),
+    "ava_eq_ranks": (_i, [_p, _i, _i, _i, _p, _i, _i, _p, _p, _sz, _p]),
+    "ava_eq_penalties": (_i, [_p, _i, _i, C.POINTER(_i), _i, _p, _p, _p]),
+    "ava_eq_overlap": (_i, [_p, _p, _i, _i, C.POINTER(_i), _i, _p, _p, _p]),
+}
+
 _lib = None
 
 
@@ -244,7 +254,7 @@ def load():
             "`python -c 'import __graft_entry__ as g; g.build()'` or `make -C %s`." % (LIB_PATH, CSRC))
     import torch  # noqa: F401  (loads torch's libamdhip64.so first; same SONAME as ROCm's)
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in list(SIGNATURES.items()) + list(EQ_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError if a declared symbol is missing
         fn.restype = res
         fn.argtypes = args

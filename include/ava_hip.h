@@ -1085,6 +1085,10 @@ int ava_km_pp_step(const void* x, int dtype, int n, int d, int n_trials, const d
 int ava_km_variance(const void* x, int dtype, int n, int d, double* out, void* ws, size_t ws_bytes, ava_stream_t s);
 int ava_km_transform(const void* x, int dtype, int n, int d, int k, const double* centres, double* out, ava_stream_t s);
 
+/* ---- Trustworthiness, continuity and preserved neighbours of an embedding (row f26; csrc/embed_quality.hip): the ava_eq_
+ * entry points are declared, with their comment block, in a header of their own, mirrored by _lib.EQ_SIGNATURES -------- */
+#include "ava_embed_quality.h"
+
 #ifdef __cplusplus
 }
 #endif
