@@ -240,6 +240,22 @@ EQ_SIGNATURES = {
     "ava_eq_overlap": (_i, [_p, _p, _i, _i, C.POINTER(_i), _i, _p, _p, _p]),
 }
 
+# the sparse-graph components and eigensolver entry points (row f27); mirrors include/ava_spectral.h one to one
+SP_SIGNATURES = {
+    "ava_sp_max_n": (_i, []),
+    "ava_sp_max_basis": (_i, []),
+    "ava_sp_chunk_rows": (_i, []),
+    "ava_sp_rotate_tile": (_i, []),
+    "ava_sp_workspace_bytes": (_sz, [_i, _i]),
+    "ava_sp_components": (_i, [_p, _p, _p, _i, _i64, _p, C.POINTER(_i), _p, _sz, _p]),
+    "ava_sp_degrees": (_i, [_p, _p, _p, _i, _i64, _p, _p, _p, _sz, _p]),
+    "ava_sp_apply": (_i, [_p, _p, _p, _p, _i, _i64, _p, _p, _p, _sz, _p]),
+    "ava_sp_null_vectors": (_i, [_p, _p, _i, _i, _p, _i, _p, _sz, _p]),
+    "ava_sp_start": (_i, [_p, _i, _i, _i, C.c_uint64, _d, _p, _p, _sz, _p]),
+    "ava_sp_lanczos": (_i, [_p, _p, _p, _p, _i, _i64, _p, _i, _i, _i, _i, _d, _p, _p, _p, _sz, _p]),
+    "ava_sp_rotate": (_i, [_p, _i, _i, _i, _i, _p, _p, _sz, _p]),
+}
+
 _lib = None
 
 
@@ -254,7 +270,7 @@ def load():
             "`python -c 'import __graft_entry__ as g; g.build()'` or `make -C %s`." % (LIB_PATH, CSRC))
     import torch  # noqa: F401  (loads torch's libamdhip64.so first; same SONAME as ROCm's)
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(SIGNATURES.items()) + list(EQ_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(EQ_SIGNATURES.items()) + list(SP_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError if a declared symbol is missing
         fn.restype = res
         fn.argtypes = args

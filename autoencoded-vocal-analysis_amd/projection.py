@@ -281,12 +281,31 @@ def _spectral(graph):
     return vecs[:, order]
 
 
-def init_embedding(graph, init, rs):
+def _spectral_device(graph, tol=1e-4, maxiter=None):
+    """``_spectral`` with the components and the eigensolver of ``ava_amd.spectral`` on the device: the same result
+    up to ``tol`` and the sign of each vector, None (with the same warnings) in the same cases"""
+    from . import spectral as _sp
+    try:
+        n_comp, Y = _sp.umap_eigenvectors(graph, tol=tol, maxiter=maxiter)
+    except _sp.SpectralConvergenceError as e:
+        warnings.warn("the spectral init failed (%s): using the random init" % e)
+        return None
+    if Y is None:
+        warnings.warn("the graph has %d connected components: using the random init" % n_comp)
+    return Y
+
+
+def init_embedding(graph, init, rs, eigen_solver='scipy', tol=1e-4, maxiter=None):
     """The initial positions (float64 ``[n, 2]``) drawn from ``rs`` (a ``np.random.RandomState``): ``'spectral'``
     (max |.| scaled to 10, plus ``rs.normal(scale=1e-4)``; the random init if that is impossible) or ``'random'``
-    (``rs.uniform(-10, 10)``), then every column rescaled to [0, 10]."""
+    (``rs.uniform(-10, 10)``), then every column rescaled to [0, 10].  ``eigen_solver``: ``'scipy'`` (ARPACK on the host)
+    or ``'device'`` (``ava_amd.spectral``, residual at most ``tol`` within ``maxiter`` operator applications)."""
+    if eigen_solver not in ('scipy', 'device'):
+        raise ValueError("eigen_solver must be 'scipy' or 'device', got %r" % (eigen_solver,))
     n = graph.shape[0]
-    Y = _spectral(graph) if init == 'spectral' else None
+    Y = None
+    if init == 'spectral':
+        Y = _spectral(graph) if eigen_solver == 'scipy' else _spectral_device(graph, tol, maxiter)
     if Y is not None:
         Y = Y * (10.0 / np.abs(Y).max()) + rs.normal(scale=0.0001, size=[n, 2])
     else:
@@ -424,7 +443,7 @@ class UMAP:
 
     def __init__(self, n_components=2, n_neighbors=20, min_dist=0.1, metric='euclidean', random_state=42,
                  n_epochs=None, init='spectral', spread=1.0, learning_rate=1.0, repulsion_strength=1.0,
-                 negative_sample_rate=5, set_op_mix_ratio=1.0, local_connectivity=1.0):
+                 negative_sample_rate=5, set_op_mix_ratio=1.0, local_connectivity=1.0, eigen_solver='scipy'):
         self.n_components = n_components
         self.n_neighbors = n_neighbors
         self.min_dist = min_dist
@@ -438,6 +457,7 @@ class UMAP:
         self.negative_sample_rate = negative_sample_rate
         self.set_op_mix_ratio = set_op_mix_ratio
         self.local_connectivity = local_connectivity
+        self.eigen_solver = eigen_solver     # of the spectral init: 'scipy' (host ARPACK) or 'device' (ava_amd.spectral)
 
     METRICS = ('euclidean',)                # the metrics _validate accepts
 
@@ -451,6 +471,8 @@ class UMAP:
             raise ValueError("n_neighbors must be an integer in [2, %d], got %r" % (MAX_K, self.n_neighbors))
         if self.init not in ('spectral', 'random'):
             raise ValueError("init must be 'spectral' or 'random', got %r" % (self.init,))
+        if getattr(self, 'eigen_solver', 'scipy') not in ('scipy', 'device'):
+            raise ValueError("eigen_solver must be 'scipy' or 'device', got %r" % (self.eigen_solver,))
         if self.n_epochs is not None and (int(self.n_epochs) != self.n_epochs or self.n_epochs < 1):
             raise ValueError("n_epochs must be a positive integer or None, got %r" % (self.n_epochs,))
         if (int(self.negative_sample_rate) != self.negative_sample_rate or
@@ -492,7 +514,7 @@ class UMAP:
             graph.eliminate_zeros()
         rs = self.random_state if isinstance(self.random_state, np.random.RandomState) else \
             np.random.RandomState(self.random_state)
-        Y0 = init_embedding(graph, self.init, rs)
+        Y0 = init_embedding(graph, self.init, rs, getattr(self, 'eigen_solver', 'scipy'))
         salt = rs.randint(2 ** 31 - 1)
         lay = Layout(graph, Y0, n_epochs, self.a_, self.b_, self.repulsion_strength, self.learning_rate,
                      self.negative_sample_rate, salt)
@@ -526,9 +548,11 @@ class TransformableUMAP(UMAP):
 
     def __init__(self, n_components=2, n_neighbors=20, min_dist=0.1, metric='euclidean', random_state=42,
                  n_epochs=None, init='spectral', spread=1.0, learning_rate=1.0, repulsion_strength=1.0,
-                 negative_sample_rate=5, set_op_mix_ratio=1.0, local_connectivity=1.0, transform_seed=42):
+                 negative_sample_rate=5, set_op_mix_ratio=1.0, local_connectivity=1.0, transform_seed=42,
+                 eigen_solver='scipy'):
         super().__init__(n_components, n_neighbors, min_dist, metric, random_state, n_epochs, init, spread,
-                         learning_rate, repulsion_strength, negative_sample_rate, set_op_mix_ratio, local_connectivity)
+                         learning_rate, repulsion_strength, negative_sample_rate, set_op_mix_ratio, local_connectivity,
+                         eigen_solver)
         self.transform_seed = transform_seed
         self._train_rows = None          # float32 [N, d] on the device
         self._train_stats = None         # float64 [N, 2] on the device: the rows' statistics (metric='correlation')

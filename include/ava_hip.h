@@ -1089,6 +1089,10 @@ int ava_km_transform(const void* x, int dtype, int n, int d, int k, const double
  * entry points are declared, with their comment block, in a header of their own, mirrored by _lib.EQ_SIGNATURES -------- */
 #include "ava_embed_quality.h"
 
+/* ---- Connected components and the symmetric eigensolver of a sparse graph (row f27; csrc/spectral.hip): the ava_sp_
+ * entry points are declared, with their comment block, in a header of their own, mirrored by _lib.SP_SIGNATURES -------- */
+#include "ava_spectral.h"
+
 #ifdef __cplusplus
 }
 #endif

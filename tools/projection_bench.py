@@ -5,7 +5,7 @@ wall-clock total of one call -- the achieved fp64 GFLOP/s of the kNN pass (3 N^2
 the device moments and projection times beside sklearn's CPU ``PCA(n_components=2).fit_transform`` (when sklearn is
 installed).  There is no umap-learn CPU time to compare with.
 
-    python tools/projection_bench.py [--sizes 20000 200000] [--z 32] [--reps 3]
+    python tools/projection_bench.py [--sizes 20000 200000] [--z 32] [--reps 3] [--quality-n 20000]
 """
 import argparse
 import json
@@ -33,7 +33,7 @@ def _events_ms(fn, reps):
     return float(np.median(ms))
 
 
-def bench(n, z, reps):
+def bench(n, z, reps, quality_n=20000):
     import torch
     from ava_amd import _lib, projection as P, synthetic as syn
     X = syn.gauss(n * z, 7100 + n).reshape(n, z).astype(np.float32)
@@ -58,6 +58,11 @@ def bench(n, z, reps):
     t0 = time.perf_counter()
     Y0 = P.init_embedding(Gp, 'spectral', rs)
     out["init_host_s"] = round(time.perf_counter() - t0, 3)
+    P.init_embedding(Gp, 'spectral', np.random.RandomState(42), eigen_solver='device')        # warm-up
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    P.init_embedding(Gp, 'spectral', np.random.RandomState(42), eigen_solver='device')
+    out["init_device_s"] = round(time.perf_counter() - t0, 4)
     salt = rs.randint(2 ** 31 - 1)
     a, b = P.find_ab_params(1.0, 0.1)
     out["graph_nnz"] = int(Gp.nnz)
@@ -68,6 +73,16 @@ def bench(n, z, reps):
     Y = P.UMAP().fit_transform(X)
     out["umap_total_s"] = round(time.perf_counter() - t0, 3)
     assert Y.shape == (n, 2) and np.all(np.isfinite(Y))
+    t0 = time.perf_counter()
+    Yd = P.UMAP(eigen_solver='device').fit_transform(X)
+    out["umap_total_device_s"] = round(time.perf_counter() - t0, 3)
+    assert Yd.shape == (n, 2) and np.all(np.isfinite(Yd))
+    if n <= quality_n:
+        from ava_amd import embedding_quality as EQ
+        ks = [5, 15, 30]
+        for name, pic in (("quality_scipy_init", Y), ("quality_device_init", Yd)):
+            out[name] = {key: [round(float(v), 4) for v in val] for key, val in EQ.quality_curve(X, pic, ks).items()}
+        out["quality_ks"] = ks
 
     lib = _lib.load()
     nbytes = lib.ava_pj_gram_workspace_bytes(n, z)
@@ -101,9 +116,10 @@ def main():
     ap.add_argument("--sizes", type=int, nargs="+", default=[20000, 200000])
     ap.add_argument("--z", type=int, default=32)
     ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--quality-n", type=int, default=20000)
     args = ap.parse_args()
     for n in args.sizes:
-        print(json.dumps(bench(n, args.z, args.reps)), flush=True)
+        print(json.dumps(bench(n, args.z, args.reps, args.quality_n)), flush=True)
 
 
 if __name__ == "__main__":
